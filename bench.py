@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N > 1 under torch.distributed.run (WORLD_SIZE set): this process is one rank.
         N > 1 started plainly: the parent starts N rank processes itself (one per GPU, RCCL rendezvous on 127.0.0.1) BEFORE it
         touches the GPU, relays rank 0's JSON line and exits with the worst child code.
@@ -12,10 +12,14 @@ BASELINE.json configs[2]: 3M synthetic Gaussians (synth-v1), SH degree 3, the in
 autograd Function, inputs resident in HBM.  The raster path does not shard a single view ("replicas
 only"), so with --gpus N every rank renders its own replica and `value` is the whole-job views/s (weak scaling).
 
-Extra objects on the same JSON line:
+A plain run sets up, warms up, times exactly K steps and prints the headline line (`value`, `ms_per_step` = ms of one timed
+step, no event pair inside the timed region).  --dump-outputs DIR then also writes what the last timed step returned to its
+caller (dump_outputs).  Everything below is measured only with --full.
+
+Extra objects on the same JSON line (--full):
   roofline      dominant kernel: algorithmic bytes per launch (SURVEY.md 8(d) formula) / live HIP-event duration; `traffic` = HBM
                 bytes per launch from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) that THIS invocation runs on a child
-                copy of itself (N = 1, default flags; otherwise the committed profiles/traffic_latest.json), `traffic_source` says which
+                copy of itself (N = 1, no --no-* option; otherwise the committed profiles/traffic_latest.json), `traffic_source` says which
   cpu_baseline  the oracle (CPU restatement, OpenMP) timed on this box's host cores on a bounded sample
   stages        per-stage mean ms from the same HIP events (all kernels of the view)
   parity        HIP vs oracle on THIS workload at full size (integers equal, PSNR, gradient rel-inf; tests/fullsize.py),
@@ -180,6 +184,11 @@ def main():
     ap.add_argument("--vq-steps", type=int, default=30)
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not run the two rocprofv3 --pmc passes (about 30 s); roofline.traffic then comes from profiles/traffic_latest.json")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline (stages, roofline, live PMC traffic, other sizes, extras, "
+                         "VQ, CPU baselines, parity); the --no-* options select among them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; seeded row samples of the large ones)")
     ap.add_argument("--selftest-launch", default=None, metavar="BACKEND", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -230,7 +239,7 @@ def main():
                             sh_indices=t["sh_indices"], g_indices=t["g_indices"], shs=leaves["shs"], scales=leaves["scales"],
                             scale_factors=leaves["scale_factors"], rotations=leaves["rotations"], extrinsic_vector=evd)
         torch.autograd.backward(color, dL)
-        state["radii"], state["visible"] = radii, visible
+        state["color"], state["radii"], state["visible"] = color, radii, visible
 
     def barrier():
         if world > 1:
@@ -249,24 +258,29 @@ def main():
         if k >= 5 and prev is not None and abs(cur - prev) <= 0.05 * min(cur, prev):
             break
         prev = cur
-    # every stage bracketed by HIP events: per-stage means and the dominant kernel (untimed pass; an event pair costs
-    # ~10 us of queue time, x11 stages, which does not belong in `value`)
-    _lib.profile_enable(True)
-    _lib.profile_read()
-    for _ in range(max(args.warmup, 3)):
-        step()
-    torch.cuda.synchronize()
-    stages = _lib.profile_read()
-    _lib.profile_enable(False)
-    raster_names = ("preprocess", "scan", "duplicate_with_keys", "sort", "identify_ranges", "render_forward", "zero_partials",
-                    "render_backward", "backward_preprocess", "mark_visible", "depth_sort")
-    # the dominant kernel among the stages SURVEY 8(d) gives a byte formula for (the depth sort is part of its one "sort" term)
-    dom = max((k for k in stages if k in raster_names and k != "depth_sort"), key=lambda k: stages[k][0] / max(stages[k][1], 1))
+    if args.full:
+        # every stage bracketed by HIP events: per-stage means and the dominant kernel (untimed pass; an event pair costs
+        # ~10 us of queue time, x11 stages, which does not belong in `value`)
+        _lib.profile_enable(True)
+        _lib.profile_read()
+        for _ in range(max(args.warmup, 3)):
+            step()
+        torch.cuda.synchronize()
+        stages = _lib.profile_read()
+        _lib.profile_enable(False)
+        raster_names = ("preprocess", "scan", "duplicate_with_keys", "sort", "identify_ranges", "render_forward", "zero_partials",
+                        "render_backward", "backward_preprocess", "mark_visible", "depth_sort")
+        # the dominant kernel among the stages SURVEY 8(d) gives a byte formula for (the depth sort is part of its one "sort" term)
+        dom = max((k for k in stages if k in raster_names and k != "depth_sort"), key=lambda k: stages[k][0] / max(stages[k][1], 1))
+    else:
+        for _ in range(args.warmup):
+            step()
     barrier()
-    # timed region: exactly K steps; only the dominant kernel carries an event pair (roofline.achieved is its live
-    # average over these same K launches)
-    _lib.profile_enable(True, only=dom)
-    _lib.profile_read()
+    # timed region: exactly K steps; with --full only the dominant kernel carries an event pair (roofline.achieved is its
+    # live average over these same K launches)
+    if args.full:
+        _lib.profile_enable(True, only=dom)
+        _lib.profile_read()
     n_alloc = torch.cuda.memory_stats(dev)["num_device_alloc"]
     gc_ms = _quiesce()
     t0 = time.perf_counter()
@@ -276,13 +290,41 @@ def main():
     elapsed = time.perf_counter() - t0
     gc_ms = _GC["ms"] - gc_ms
     n_alloc = torch.cuda.memory_stats(dev)["num_device_alloc"] - n_alloc
-    dom_live = _lib.profile_read()
-    _lib.profile_enable(False)
+    if args.full:
+        dom_live = _lib.profile_read()
+        _lib.profile_enable(False)
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
     barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state, leaves, means2D)
+
+    out = {
+        "metric": "raster views/sec fwd+bwd @1920x1080",
+        "value": world * args.steps / elapsed,
+        "unit": "views/s",
+        "n_gpus": world,
+        "ranks_seen": ranks_seen,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE.json configs[2]: synth-v1 3M Gaussians, SH deg 3, indexed-camera rasterizer "
+                               "(QAT inner loop), mark_visible+fwd+bwd, 1 view/step/GPU",
+                   "gaussians": P, "width": W, "height": H,
+                   "sh_codebook": int(t["shs"].shape[0]), "gaussian_codebook": int(t["scales"].shape[0]),
+                   "parallelism": f"replicas x{world}"},
+        "device_allocs_in_timed_region": n_alloc,     # hipMalloc calls of the caching allocator (expected: 0)
+        "host_gc_ms": round(gc_ms, 3),                # time of Python's cyclic collector inside the timed region (expected: ~0)
+    }
+    if not args.full:
+        return emit(out, rank, world)
 
     # workload statistics for the roofline
     radii = state["radii"]
@@ -309,7 +351,7 @@ def main():
         if P == 3_000_000 and (W, H) == (1920, 1080):
             with open(os.path.join(ROOT, "profiles", "traffic_latest.json")) as f:
                 traffic_all = json.load(f)
-            traffic_src = "profiles/traffic_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `python bench.py --no-vq " \
+            traffic_src = "profiles/traffic_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `python bench.py --full --no-vq " \
                           "--no-cpu-baseline --no-extras` (tools/pmc_traffic.sh; counters cannot be read inside the timed process)"
     except Exception:
         traffic_all = {}
@@ -334,36 +376,17 @@ def main():
                 "alg_bytes_per_launch": b, "avg_launch_ms": stage_ms[k]}
     view_bytes = sum(alg_bytes(k, P, V, R, T, N, 16, bit, True) for k in raster_stages)
 
-    out = {
-        "metric": "raster views/sec fwd+bwd @1920x1080",
-        "value": world * args.steps / elapsed,
-        "unit": "views/s",
-        "n_gpus": world,
-        "ranks_seen": ranks_seen,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "BASELINE.json configs[2]: synth-v1 3M Gaussians, SH deg 3, indexed-camera rasterizer "
-                               "(QAT inner loop), mark_visible+fwd+bwd, 1 view/step/GPU",
-                   "gaussians": P, "visible": V, "tile_instances": R, "width": W, "height": H,
-                   "sh_codebook": int(t["shs"].shape[0]), "gaussian_codebook": int(t["scales"].shape[0]),
-                   "parallelism": f"replicas x{world}"},
+    out["config"].update(visible=V, tile_instances=R)
+    out.update({
         "roofline": dict(roofline_of(dom), traffic_source=traffic_src),
         "roofline_blend": {k: roofline_of(k) for k in ("render_forward", "render_backward") if k in stage_ms},
         "stages_ms": {k: round(v, 4) for k, v in sorted(stage_ms.items(), key=lambda kv: -kv[1])},
         # informational: kernels of one step (untimed profiling pass) vs the timed step. A ratio far above 1 means the
         # GPU sat idle waiting for the host during the timed region (seen once on a heavily loaded box: profiles/README.md)
-        "device_allocs_in_timed_region": n_alloc,     # hipMalloc calls of the caching allocator (expected: 0)
-        "host_gc_ms": round(gc_ms, 3),                # time of Python's cyclic collector inside the timed region (expected: ~0)
         "step_over_kernel_time": (1e3 * elapsed / args.steps) / max(sum(v for k, v in stage_ms.items() if k in raster_names), 1e-9),
         "view_alg_bytes": view_bytes,
         "view_hbm_frac": view_bytes * (args.steps / elapsed) / 1e9 / HBM_PEAK_GBS,
-    }
+    })
 
     # ---- the same step with the fused L1+SSIM loss producing dL/dimage (QAT inner loop of finetune.py:40-49 without the
     # optimizer / FakeQuantize glue): extra, not the headline
@@ -455,10 +478,53 @@ def main():
         except Exception as e:
             out["cpu_baseline"] = {"error": repr(e)}
 
+    emit(out, rank, world)
+
+
+def emit(out, rank, world):
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_ROWS = 2 ** 17          # rows kept of a larger per-Gaussian / codebook output
+DUMP_SH_ROWS = 2 ** 15       # SH codebook gradient rows are 16 x 3 floats each
+DUMP_PIXELS = 2 ** 21        # pixels kept of an image larger than DUMP_IMAGE_BYTES
+DUMP_IMAGE_BYTES = 32 * 2 ** 20
+DUMP_BUDGET = 64 * 2 ** 20   # bytes of all files together
+
+
+def _sample_rows(x, n, seed):
+    """x, or a fixed seeded sample of n of its rows kept in row order: the same rows for the same shape, whatever the build."""
+    if x.shape[0] <= n:
+        return x
+    import numpy as np
+    idx = np.sort(np.random.default_rng(seed).choice(x.shape[0], n, replace=False))
+    return x[torch.from_numpy(idx).to(x.device)]
+
+
+def dump_outputs(d, state, leaves, means2D):
+    """--dump-outputs: what the caller of the timed step holds after its last timed step, one float32 DIR/<name>.npy each --
+    the image (3 x H x W; a seeded sample of pixel rows [n, 3] when larger than DUMP_IMAGE_BYTES), radii, the visibility flags,
+    and the gradient of every input. Outputs longer than DUMP_ROWS rows keep a seeded sample of rows; all per-Gaussian outputs
+    share one sample, so their rows line up."""
+    import numpy as np
+    color = state["color"].detach()
+    if color.numel() * 4 > DUMP_IMAGE_BYTES:
+        color = _sample_rows(color.reshape(color.shape[0], -1).t(), DUMP_PIXELS, 1)
+    arrays = {"color": color, "radii": state["radii"], "visible": state["visible"], "grad_means2D": means2D.grad}
+    arrays.update({"grad_" + k: v.grad for k, v in leaves.items()})
+    seeds = {"grad_shs": 3, "grad_scales": 4, "grad_rotations": 4}     # codebooks: rows of their own; per-Gaussian outputs: 2
+    for k, v in arrays.items():
+        if k != "color":
+            arrays[k] = _sample_rows(v, DUMP_SH_ROWS if k == "grad_shs" else DUMP_ROWS, seeds.get(k, 2))
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET, f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget"
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
 
 
 def _scene_step(c3dgs_amd, intr, evd, t, dL, dev, indexed, backward):
@@ -608,7 +674,7 @@ def live_pmc_traffic(P, W, H):
         files = {}
         for counter, tag in (("FETCH_SIZE", "f"), ("WRITE_SIZE", "w")):
             cmd = ["rocprofv3", "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", os.path.join(out, tag), "-o", tag, "--",
-                   sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-vq", "--no-cpu-baseline",
+                   sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-vq", "--no-cpu-baseline",
                    "--no-extras", "--gaussians", str(P), "--width", str(W), "--height", str(H)]
             subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=150, check=True)
             import glob

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
 OUT=$R/gpurun_out/pmc_traffic
 rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch" -o f -- python3 bench.py --steps 3 --warmup 1 --no-vq --no-cpu-baseline --no-extras > "$OUT/fetch.log" 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/write" -o w -- python3 bench.py --steps 3 --warmup 1 --no-vq --no-cpu-baseline --no-extras > "$OUT/write.log" 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch" -o f -- python3 bench.py --full --steps 3 --warmup 1 --no-vq --no-cpu-baseline --no-extras > "$OUT/fetch.log" 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/write" -o w -- python3 bench.py --full --steps 3 --warmup 1 --no-vq --no-cpu-baseline --no-extras > "$OUT/write.log" 2>&1
 python3 tools/pmc_summarize.py "$OUT/fetch/f_counter_collection.csv" "$OUT/write/w_counter_collection.csv" > "$OUT/traffic.json"
 cat "$OUT/traffic.json"
