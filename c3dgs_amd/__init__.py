@@ -6,6 +6,7 @@ Drop-in for the reference's two native extensions and the Python directly around
     c3dgs_amd.rasterizer_matrix <-> diff_gaussian_rasterization / diff_gaussian_rasterization_camera (4x4 `extrinsic` API)
     c3dgs_amd.vq          <->  weighted_distance._C.weightedDistance + compression/vq.py
     c3dgs_amd.loss        <->  utils/loss_utils.py (l1_loss, ssim) + the fused QAT loss of finetune.py:48
+    c3dgs_amd.metrics     <->  utils/image_utils.py:psnr + 4-D ssim + compress.py:render_and_eval (no gradient)
     c3dgs_amd.sensitivity <->  compress.py:calc_importance_experimental (camera-sharded)
     c3dgs_amd.encode      <->  GaussianModel._sort_morton / mortonEncode
     c3dgs_amd.model       <->  GaussianModel getters + FakeQuantize modules + render() glue (scene/gaussian_model.py)
@@ -17,7 +18,7 @@ The numeric work runs in c3dgs_amd/libc3dgs_hip.so (include/c3dgs_hip.h); build 
 import sys
 import types
 
-from . import encode, loss, model, optim, rasterizer, rasterizer_matrix, sensitivity, vq  # noqa: F401
+from . import encode, loss, metrics, model, optim, rasterizer, rasterizer_matrix, sensitivity, vq  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,  # noqa: F401
                          getProjectionMatrix, mat_to_quat, quat_to_mat, rasterize_gaussians,
                          rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera)

@@ -113,6 +113,8 @@ PROTOTYPES = {
     "c3dgs_l1_ssim_value": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "c3dgs_l1_ssim_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "c3dgs_image_metrics_ws_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "c3dgs_image_metrics": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "c3dgs_qat_workspace_bytes": (C.c_size_t, []),
     "c3dgs_qat_scan_bytes": (C.c_size_t, [C.c_int32]),
     "c3dgs_qat_observe": (C.c_int, [C.POINTER(QatParams), _vp, _vp]),

@@ -31,6 +31,7 @@ SOURCES = {
     "vq.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + os.environ.get("C3DGS_VQ_FLAGS", "").split(),
     "draws.hip": [],
     "loss.hip": [],
+    "metrics.hip": [],
     "encode.hip": [],
     "adam.hip": ["-ffp-contract=off"],
     "qat.hip": ["-ffp-contract=off"],

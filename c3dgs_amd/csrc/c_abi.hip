@@ -723,6 +723,26 @@ int c3dgs_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float* img, co
     return C3DGS_OK;
 }
 
+// ---- image metrics of the evaluation pass (metrics.hip) ----
+size_t c3dgs_image_metrics_ws_bytes(int32_t N, int32_t C, int32_t H, int32_t W) { return image_metrics_ws_bytes(N, C, H, W); }
+
+int c3dgs_image_metrics(int32_t N, int32_t C, int32_t H, int32_t W, const float* img, const float* gt, void* ws, size_t ws_bytes,
+                        double* out, void* stream)
+{
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(C3DGS_E_INVALID, "image_metrics: N, C, H and W must be positive");
+    if (image_metrics_workgroups(N, C, H, W) > IMAGE_METRICS_MAX_WORKGROUPS)
+        return fail(C3DGS_E_INVALID, "image_metrics: size overflow (N * C * H * W too large for one call; split the batch)");
+    if (!img || !gt || !ws || !out) return fail(C3DGS_E_INVALID, "image_metrics: img, gt, ws and out are required");
+    if (reinterpret_cast<uintptr_t>(ws) & 7) return fail(C3DGS_E_INVALID, "image_metrics: ws must be 8-byte aligned");
+    const size_t need = image_metrics_ws_bytes(N, C, H, W);
+    if (ws_bytes < need)
+        return fail(C3DGS_E_INVALID, "image_metrics: ws too small (" + std::to_string(ws_bytes) + " bytes, need " +
+                                         std::to_string(need) + ")");
+    launch_image_metrics(N, C, H, W, img, gt, (double*)ws, out, (hipStream_t)stream);
+    C3DGS_STAGE("image_metrics", 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
 // ---- QAT getters ----
 static int qat_validate(const c3dgs_qat_params* q, const char* who)
 {

@@ -235,6 +235,12 @@ void launch_l1_ssim_forward(int C, int H, int W, const float* img, const float* 
 void launch_l1_ssim_backward(int C, int H, int W, const float* img, const float* gt, const float* Dmu, const float* Ds1,
                              const float* Ds12, const float* grad_loss, float l1_coeff, float ssim_coeff, float* dL_dimg,
                              hipStream_t s);
+// metrics.hip: one launch of the tile kernel is at most 2^24 - 1 workgroups (2^32 work-items of 256 threads)
+constexpr int64_t IMAGE_METRICS_MAX_WORKGROUPS = (int64_t(1) << 24) - 1;
+int64_t image_metrics_workgroups(int N, int C, int H, int W);
+size_t image_metrics_ws_bytes(int N, int C, int H, int W);
+void launch_image_metrics(int N, int C, int H, int W, const float* img, const float* gt, double* partials, double* out,
+                          hipStream_t s);
 
 // qat.hip
 size_t qat_workspace_bytes();

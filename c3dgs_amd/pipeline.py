@@ -1,7 +1,7 @@
 """The drivers either side of the hot path: the QAT fine-tuning loop and the compression run.
 
     finetune(...)            <- finetune.py:10-66        (hot loop C of SURVEY.md section 3)
-    run_vq(...)              <- compress.py:202-290      (sensitivity -> prune + VQ -> fine-tune -> npz)
+    run_vq(...)              <- compress.py:202-303      (sensitivity -> prune + VQ -> fine-tune -> npz [-> evaluation])
     OptimizationParams / CompressionParams               <- arguments/__init__.py:85-136 (defaults only, no argparse)
 
 The reference's `Scene` (COLMAP / Blender loaders, camera JSON) is outside the path: here `scene` is anything with
@@ -19,6 +19,7 @@ from typing import Optional
 import torch
 
 from . import loss as _loss
+from . import metrics as _metrics
 from . import sensitivity as _sensitivity
 from .vq import CompressionSettings, compress_gaussians
 
@@ -135,11 +136,14 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None):
 
 
 def run_vq(gaussians, scene, optim_params, pipeline_params, comp_params, dataset=None, group=None, silent=True,
-           out_file: Optional[str] = None):
-    """compress.py:202-290 on an already constructed model and camera set: sensitivity (use_gt) -> prune + colour /
-    covariance VQ -> QAT fine-tuning -> Morton-sorted npz. Returns (timings dict, npz path). The reference's
-    evaluation pass (`render_and_eval`: PSNR / SSIM / LPIPS over the test set) is not part of the path.
-    `group`: process group for the camera-sharded sensitivity pass and the sharded Lloyd steps (None = one GPU)."""
+           out_file: Optional[str] = None, eval_cameras=None, eval_name="test", background=None):
+    """compress.py:202-303 on an already constructed model and camera set: sensitivity (use_gt) -> prune + colour /
+    covariance VQ -> QAT fine-tuning -> Morton-sorted npz. Returns (timings dict, npz path).
+    `group`: process group for the camera-sharded sensitivity pass and the sharded Lloyd steps (None = one GPU).
+    With `eval_cameras` (views carrying `original_image`), the evaluation pass follows the npz as in compress.py:293-303:
+    metrics.render_and_eval (SSIM / PSNR; LPIPS is not bundled and reported as None) against `background` (default: that
+    of `dataset`, black without one), PNGs under output_vq/<eval_name>/ours_<iteration>/, and output_vq/results.json =
+    {"ours_<iteration>": {SSIM, PSNR, LPIPS, size}} with size the npz size in MB."""
     timings = {}
     dev = gaussians.device
 
@@ -196,6 +200,16 @@ def run_vq(gaussians, scene, optim_params, pipeline_params, comp_params, dataset
     timings["total"] = sum(timings.values())
     with open(os.path.join(comp_params.output_vq, "times.json"), "w") as f:
         json.dump(timings, f)
+
+    if eval_cameras is not None:
+        if background is None:
+            white = getattr(dataset, "white_background", False) if dataset is not None else False
+            background = torch.tensor([1, 1, 1] if white else [0, 0, 0], dtype=torch.float32, device=dev)
+        metrics = _metrics.render_and_eval(gaussians, eval_cameras, pipeline_params, background,
+                                           out_dir=os.path.join(comp_params.output_vq, eval_name, f"ours_{iteration}"))
+        metrics["size"] = os.path.getsize(out_file) / 1024 ** 2
+        with open(os.path.join(comp_params.output_vq, "results.json"), "w") as f:
+            json.dump({f"ours_{iteration}": metrics}, f, indent=4)
     return timings, out_file
 
 

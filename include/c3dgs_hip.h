@@ -240,6 +240,19 @@ int c3dgs_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float* img, co
                            const float* grad_loss /*device [1]*/, float l1_coeff, float ssim_coeff, float* dL_dimg,
                            void* stream);
 
+/* ---- image metrics of the evaluation pass (reference compress.py:121-163: psnr of utils/image_utils.py:17-19 and ssim of
+ * utils/loss_utils.py:33-63, forward only) ----
+ * img, gt: [N, C, H, W] fp32 contiguous (device). out (device, float64) receives N rows of 3:
+ *   out[3n] = mean (img - gt)^2,  out[3n+1] = mean ssim_map,  out[3n+2] = mean |img - gt|   (means over C * H * W)
+ * out may point into a larger caller table (row v of an evaluation loop at out + 3 * v). ws: device scratch of
+ * c3dgs_image_metrics_ws_bytes(N, C, H, W) bytes (8-byte aligned; 0 = sizes not served), owned by the caller and busy until
+ * the stream passes the call. Deterministic: no float atomics, so rows are bit-identical from run to run and row n equals
+ * the row of image n passed alone. Any H, W >= 1 (zero padding 5 as the reference's conv2d); one call serves at most
+ * 2^24 - 1 tiles of 32 x 22 pixels over all planes (about 1860 images of 3 x 1080 x 1920). */
+size_t c3dgs_image_metrics_ws_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int c3dgs_image_metrics(int32_t N, int32_t C, int32_t H, int32_t W, const float* img, const float* gt, void* ws, size_t ws_bytes,
+                        double* out /*device [N][3]*/, void* stream);
+
 /* ---- Morton ordering (reference GaussianModel._sort_morton, scene/gaussian_model.py:997-1003,
  * mortonEncode :1417-1432).  codes[i] = 63-bit Morton code of xyz[i] (21 bits per axis, axes in ascending-extent order),
  * order = ids sorted stably by code (int64, usable as a torch index). workspace: c3dgs_morton_workspace_bytes(P). */
