@@ -129,7 +129,7 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
     if (!indexed) { p.sh_indices = nullptr; p.g_indices = nullptr; p.scale_factors = nullptr; }
     hipStream_t s = (hipStream_t)stream_;
     const int P = p.P, W = p.W, H = p.H;
-    const int gx = tiles_x(W), gy = tiles_y(H), T = gx * gy;
+    const int gx = tiles_x(W), gy = tiles_y(H);
     *num_rendered = 0;
 
     c3dgs_image_layout IL; image_layout(W, H, &IL);
@@ -225,7 +225,7 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
     const BinPtrs b = bin_ptrs(bin_base, R, W, H);
 
     if (R > 0) {
-        const int end_bit = (int)higher_msb((uint32_t)T);                           // tile bits only (rasterizer_impl.cu:298)
+        const int end_bit = tile_sort_end_bit(W, H);                                // tile bits only (rasterizer_impl.cu:298)
         // the tile sort's control words are cleared by the pair emission's workgroups (0 bytes: that sort clears its own)
         size_t tclear = tile_sort_clear_bytes(R, end_bit, b.key_bytes);
         if (tclear > b.sort_temp_bytes) tclear = 0;
@@ -425,6 +425,36 @@ int c3dgs_debug_sort_pairs(int32_t key_bytes, int64_t n, int32_t end_bit, const 
                                           nullptr, nullptr, s));
     C3DGS_STAGE("debug_sort_pairs", 1, s);
     if (onesweep_timed_out(s)) return fail(C3DGS_E_HIP, "debug_sort_pairs: look-back timed out");
+    return C3DGS_OK;
+}
+
+// the forward's tile sort for a grid of `tiles` tiles: key width and end_bit as forward_impl / binning_layout choose them.
+// Largest grid validate() admits: 256 x 65,535 tiles (tiles_x^2 x tiles_y < 2^32, tiles_y <= 65,535)
+static bool debug_tile_sort_args_ok(int32_t tiles, int64_t n)
+{
+    return tiles >= 1 && (long long)tiles <= 256LL * 65535 && n >= 0 && n <= 0x3fffffff;
+}
+
+size_t c3dgs_debug_tile_sort_temp_bytes(int32_t tiles, int64_t n)
+{
+    if (!debug_tile_sort_args_ok(tiles, n)) { set_error("debug_tile_sort_temp_bytes: bad arguments"); return 0; }
+    return sort_temp_bytes((int)n, tile_sort_end_bit_for(tiles), tile_key_bytes_for(tiles));
+}
+
+int c3dgs_debug_tile_sort_pairs(int32_t tiles, int64_t n, const void* keys_in, void* keys_out, const uint32_t* values_in,
+                                uint32_t* values_out, void* temp, size_t temp_bytes, void* stream)
+{
+    if (!debug_tile_sort_args_ok(tiles, n)) return fail(C3DGS_E_INVALID, "debug_tile_sort_pairs: bad arguments");
+    if (n == 0) return C3DGS_OK;
+    if (!keys_in || !keys_out || !values_in || !values_out || !temp)
+        return fail(C3DGS_E_INVALID, "debug_tile_sort_pairs: NULL buffer");
+    const int kb = tile_key_bytes_for(tiles), end_bit = tile_sort_end_bit_for(tiles);
+    if (temp_bytes < sort_temp_bytes((int)n, end_bit, kb))
+        return fail(C3DGS_E_INVALID, "debug_tile_sort_pairs: temp smaller than c3dgs_debug_tile_sort_temp_bytes()");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_HIP_TRY(run_tile_sort(temp, temp_bytes, keys_in, keys_out, kb, values_in, values_out, (int)n, end_bit, s, false));
+    C3DGS_STAGE("debug_tile_sort_pairs", 1, s);
+    if (onesweep_timed_out(s)) return fail(C3DGS_E_HIP, "debug_tile_sort_pairs: look-back timed out");
     return C3DGS_OK;
 }
 

@@ -85,12 +85,22 @@ inline size_t geom_gtab_bytes(const c3dgs_raster_params& p) { return (p.g_indice
 // Tile keys are 16-bit up to 65,536 tiles (4096 x 4096 pixels) and 32-bit above (e.g. 7680 x 4320 = 129,600 tiles): the
 // reference's 64-bit keys (rasterizer_impl.cu:98-108) have no tile limit, and neither has this path; the common case keeps
 // its 6-byte instances and two digit passes.
-inline int tile_key_bytes(int W, int H) { return (long long)tiles_x(W) * tiles_y(H) > 65536 ? 4 : 2; }
+inline int tile_key_bytes_for(long long T) { return T > 65536 ? 4 : 2; }
+inline int tile_key_bytes(int W, int H) { return tile_key_bytes_for((long long)tiles_x(W) * tiles_y(H)); }
+// Bits the tile sort orders on: the reference's higher_msb(T) (rasterizer_impl.cu:298), clamped to the key width. They differ
+// only at exactly 65,536 tiles (4096 x 4096 pixels): 17 bits, but every tile id < 2^16 fits the 16-bit key, and the 16-bit sort
+// has no third digit pass. The scratch sizing (binning_layout) and the sort (forward_impl) both take it from here.
+inline int tile_sort_end_bit_for(long long T)
+{
+    const int msb = (int)higher_msb((uint32_t)T), kbits = 8 * tile_key_bytes_for(T);
+    return msb < kbits ? msb : kbits;
+}
+inline int tile_sort_end_bit(int W, int H) { return tile_sort_end_bit_for((long long)tiles_x(W) * tiles_y(H)); }
 
 inline void binning_layout(int R, int W, int H, c3dgs_binning_layout* L)
 {
     size_t o = 0, r = (size_t)(R > 0 ? R : 1);
-    int end_bit = (int)higher_msb((uint32_t)(tiles_x(W) * tiles_y(H)));
+    const int end_bit = tile_sort_end_bit(W, H);
     const size_t kb = (size_t)tile_key_bytes(W, H);
     L->keys_unsorted = o;   o = align_up(o + r * kb);
     L->values_unsorted = o; o = align_up(o + r * 4);

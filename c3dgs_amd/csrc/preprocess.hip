@@ -526,7 +526,7 @@ duplicate_with_keys_kernel(int P, const uint32_t* __restrict__ order, const uint
                 const int x0 = rc.x & 0xffff, y0 = rc.x >> 16, x1 = rc.y & 0xffff;
                 const uint32_t local = o - first, w = (uint32_t)(x1 - x0), inv = s_inv[g];
                 // local / w as a multiply-high by ceil(2^32 / w): exact while local * w < 2^32, and local < rectangle area <=
-                // number of tiles (<= 2^16 with 16-bit tile keys; the C ABI admits at most 2^22 tiles), w <= 2^10 of them per row
+                // tiles_x * tiles_y, w <= tiles_x, so local * w < tiles_x^2 * tiles_y, which validate() (c_abi.hip) keeps < 2^32
                 const uint32_t ry = inv ? __umulhi(local, inv) : local, rx = local - ry * w;   // emission order: y outer, x inner (:98-108)
                 kq[e] = (K)((y0 + ry) * grid_x + (x0 + rx));
                 vq[e] = s_id[g];

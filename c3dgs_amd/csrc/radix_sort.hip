@@ -426,6 +426,9 @@ static hipError_t os_sort(void* temp, size_t temp_bytes, const K* kin, K* kout, 
         pay2 = false;
     if (n >= ((size_t)1 << 30) || os_temp_bytes<K>(n, total_bits) > temp_bytes) return hipErrorInvalidValue;
     const OsPlan plan = os_plan(total_bits);
+    // the look-back-free first pass's table holds the global histograms of passes 0 and 1 only (OS_TABLE_ROW): a third pass
+    // would scatter with zero digit offsets, so more than 16 bits on u16 keys is refused instead of sorted wrong
+    if (os_pre_pass0<K>() && plan.passes > 2) return hipErrorInvalidValue;
     const size_t blocks = os_blocks<K>(n);
     char* base = (char*)temp;
     const size_t ctrl = os_ctrl_bytes<K>(n, plan.passes);

@@ -408,6 +408,14 @@ size_t c3dgs_debug_sort_temp_bytes(int32_t key_bytes, int64_t n, int32_t end_bit
 int c3dgs_debug_sort_pairs(int32_t key_bytes, int64_t n, int32_t end_bit, const void* keys_in, void* keys_out,
                            const uint32_t* values_in, uint32_t* values_out, void* temp, size_t temp_bytes, void* stream);
 
+/* tests only: the forward's tile-key sort for a grid of `tiles` tiles (1 .. 256 x 65535), taking the forward's own route: keys
+ * are uint16 up to 65,536 tiles and uint32 above, sorted on min(higher_msb(tiles), key bits) bits, through the same dispatch
+ * (hand-written sort, or rocPRIM with C3DGS_SORT_ROCPRIM=1). Ties keep input order. temp >= c3dgs_debug_tile_sort_temp_bytes(),
+ * which is the forward's own sizing of that scratch (0 = bad arguments, see c3dgs_last_error). */
+size_t c3dgs_debug_tile_sort_temp_bytes(int32_t tiles, int64_t n);
+int c3dgs_debug_tile_sort_pairs(int32_t tiles, int64_t n, const void* keys_in, void* keys_out, const uint32_t* values_in,
+                                uint32_t* values_out, void* temp, size_t temp_bytes, void* stream);
+
 /* experiment builds only (radix_sort.hip compiled with -DC3DGS_OS_TIMING): phase time stamps of the last digit pass, 64 tiles x 8
  * stamps of the shader clock; fails in the product build. */
 int c3dgs_debug_sort_times(uint64_t* out /*[512], host*/);

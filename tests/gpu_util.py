@@ -86,6 +86,7 @@ def unpack(fw):
         out["depths"] = _view(geom, gl.depth_keys, P, torch.float32).cpu().numpy()
         rects = _view(geom, gl.rects, 4 * P, torch.int16).cpu().numpy().view(np.uint16).reshape(P, 4).astype(np.int64)
         out["tiles_touched"] = ((rects[:, 2] - rects[:, 0]) * (rects[:, 3] - rects[:, 1])).astype(np.uint32)
+        out["rects"] = rects                                # tile rectangles [x0, y0, x1, y1), x1 / y1 exclusive
         out["depth_order"] = _view(geom, gl.depth_order, P, torch.int32).cpu().numpy().view(np.uint32)
         out["inst_offset"] = _view(geom, gl.inst_offset, P, torch.int32).cpu().numpy().view(np.uint32)
         cl = _view(geom, gl.clamped, P, torch.uint8).cpu().numpy()

@@ -109,3 +109,45 @@ def test_image_size_limits(L):
     L.c3dgs_get_binning_layout(1000, 4096, 4096, C.byref(b2))        # 65,536 tiles: 16-bit keys
     L.c3dgs_get_binning_layout(1000, 4112, 4096, C.byref(b4))        # 65,792 tiles: 32-bit keys
     assert b2.values_unsorted - b2.keys_unsorted < b4.values_unsorted - b4.keys_unsorted
+
+
+def test_tile_sort_at_65536_tiles_is_sized_as_a_two_pass_16_bit_sort(L):
+    """Exactly 65,536 tiles (4096 x 4096 pixels): higher_msb(65536) = 17, but the keys are 16-bit and every tile id fits them.
+    The forward's tile sort (and its scratch) must use 16 bits -- two digit passes -- not the three-pass 17-bit plan the 16-bit
+    sort cannot carry out (its look-back-free first pass holds global histograms for two passes only)."""
+    from c3dgs_amd import _lib
+    for n in (1, 8191, 8192, 8193, 1_000_000, 16_000_000):
+        t = L.c3dgs_debug_tile_sort_temp_bytes(65536, n)
+        assert t == L.c3dgs_debug_sort_temp_bytes(2, n, 16), n
+        assert t < L.c3dgs_debug_sort_temp_bytes(2, n, 17), n
+        assert t == L.c3dgs_debug_tile_sort_temp_bytes(65535, n), n       # same key width, same 16 bits
+        assert L.c3dgs_debug_tile_sort_temp_bytes(65537, n) > t, n        # 32-bit keys from 65,537 tiles on
+        b = _lib.BinningLayout()
+        assert L.c3dgs_get_binning_layout(n, 4096, 4096, C.byref(b)) == 0
+        assert b.sort_temp_bytes == t, n                                   # the forward sizes what the sort entry sorts with
+        b17 = _lib.BinningLayout()
+        assert L.c3dgs_get_binning_layout(n, 4112, 4096, C.byref(b17)) == 0
+        assert b17.sort_temp_bytes == L.c3dgs_debug_tile_sort_temp_bytes(257 * 256, n), n
+
+
+def test_tile_sort_debug_entries_validate_their_arguments(L):
+    """Grids of 1 .. 256 x 65,535 tiles (the largest validate() accepts); n in [0, 2^30); NULL buffers and a short temp are
+    refused before any device work (so this runs without a GPU)."""
+    fake = C.c_void_p(16)
+    big = 256 * 65535
+    assert L.c3dgs_debug_tile_sort_temp_bytes(big, 1000) > 0
+    for tiles, n in ((0, 10), (-1, 10), (big + 1, 10), (2, -1), (2, 1 << 30)):
+        assert L.c3dgs_debug_tile_sort_temp_bytes(tiles, n) == 0, (tiles, n)
+        assert b"bad arguments" in L.c3dgs_last_error()
+        assert L.c3dgs_debug_tile_sort_pairs(tiles, n, fake, fake, fake, fake, fake, 1 << 40, None) == 1, (tiles, n)
+        assert b"bad arguments" in L.c3dgs_last_error()
+    assert L.c3dgs_debug_tile_sort_pairs(65536, 0, None, None, None, None, None, 0, None) == 0      # nothing to sort
+    for i in range(5):
+        ptrs = [fake] * 5
+        ptrs[i] = None
+        assert L.c3dgs_debug_tile_sort_pairs(65536, 100, *ptrs, 1 << 40, None) == 1, i
+        assert b"NULL buffer" in L.c3dgs_last_error()
+    for tiles in (2, 65536, 65537, big):
+        need = L.c3dgs_debug_tile_sort_temp_bytes(tiles, 100_000)
+        assert L.c3dgs_debug_tile_sort_pairs(tiles, 100_000, fake, fake, fake, fake, fake, need - 1, None) == 1, tiles
+        assert b"temp smaller" in L.c3dgs_last_error()

@@ -71,7 +71,7 @@ def test_rocprim_fallback_gives_the_same_sorted_lists():
     env = dict(os.environ, C3DGS_SORT_ROCPRIM="1")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_raster_gpu.py", "tests/test_sort_gpu.py", "-q", "-m", "gpu", "-x",
-                        "-k", "(forward_parity and (base or wide_depth or p8193 or equal_depth or indexed)) or ragged or stable_sort"],
+                        "-k", "(forward_parity and (base or wide_depth or p8193 or equal_depth or indexed)) or ragged or stable_sort or grid_limit"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
@@ -142,3 +142,103 @@ def test_sort_timeout_is_not_silent():
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "RAISED" in r.stdout and "DEBUG_RAISED" in r.stdout, r.stdout
+
+
+# ------------------------------------------------------------------ the forward's tile sort at tile-grid limits
+# c3dgs_debug_tile_sort_pairs takes the forward's own route: 16-bit keys up to 65,536 tiles and 32-bit above, sorted on
+# min(higher_msb(T), key bits) bits. The grids: the smallest, the packed-rectangle limit (255 / 256 tiles a side), the 1080p
+# headline (8160), both sides of the key-width switch (65,535 .. 65,537: 16 bits on 16-bit keys at exactly 65,536), the 32-bit
+# key sort at 17 .. 24 bits (three passes of 6 .. 8 bits), and the largest grid the ABI admits (256 x 65,535 tiles).
+GRID_TILES = [2, 255, 256, 8160, 65535, 65536, 65537, 1 << 17, (1 << 18) - 1, 1 << 18, 1 << 20, 1 << 22, 256 * 65535]
+GRID_N = [1, 8191, 8192, 8193, 12287, 12288, 12289, 1_000_003]
+
+
+def _tile_sort(T, keys, values):
+    from c3dgs_amd import _lib
+    L = _lib.lib()
+    n = keys.numel()
+    assert keys.element_size() == (2 if T <= 65536 else 4)
+    tb = int(L.c3dgs_debug_tile_sort_temp_bytes(T, n))
+    assert tb > 0, L.c3dgs_last_error()
+    temp = torch.empty(tb, dtype=torch.uint8, device="cuda")
+    ko, vo = torch.empty_like(keys), torch.empty_like(values)
+    _lib.check(L.c3dgs_debug_tile_sort_pairs(T, n, keys.data_ptr(), ko.data_ptr(), values.data_ptr(), vo.data_ptr(),
+                                             temp.data_ptr(), tb, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return ko, vo
+
+
+def _grid_shape(T):
+    """a tiles_x x tiles_y factorisation of T, as square as its divisors allow"""
+    tx = 1
+    d = 1
+    while d * d <= T:
+        if T % d == 0:
+            tx = d
+        d += 1
+    return T // tx, tx
+
+
+def _emission_keys(T, n, g):
+    """the pair emission's shape: per Gaussian, the tile ids of a rectangle (y outer, x inner), Gaussians one after the other
+    (depth-major); a few rectangles span whole rows / the whole grid, like screen-filling splats"""
+    tx, ty = _grid_shape(T)
+    parts, total = [], 0
+    while total < n:
+        m = 4096
+        x0 = torch.randint(0, tx, (m,), device="cuda", generator=g)
+        y0 = torch.randint(0, ty, (m,), device="cuda", generator=g)
+        w = torch.minimum(tx - x0, torch.randint(1, 24, (m,), device="cuda", generator=g))
+        h = torch.minimum(ty - y0, torch.randint(1, 24, (m,), device="cuda", generator=g))
+        if not parts:                                   # the first Gaussians cover a full row and, if small enough, the grid
+            x0[:2], w[:2], h[0] = 0, tx, 1
+            y0[1], h[1] = 0, min(ty, max(1, 200_000 // tx))
+        cnt = w * h
+        start = torch.cumsum(cnt, 0) - cnt
+        own = torch.repeat_interleave(torch.arange(m, device="cuda"), cnt)
+        local = torch.arange(int(cnt.sum()), device="cuda") - start[own]
+        ry, rx = local // w[own], local % w[own]
+        parts.append((y0[own] + ry) * tx + x0[own] + rx)
+        total += parts[-1].numel()
+    return torch.cat(parts)[:n]
+
+
+def _grid_keys(T, n, pattern, g):
+    if pattern == "uniform":
+        k = torch.randint(0, T, (n,), device="cuda", generator=g)
+    elif pattern == "top":                              # every key in the top digit of every pass
+        k = torch.full((n,), T - 1, device="cuda", dtype=torch.int64)
+    elif pattern == "ties":                             # four ids, one of them the largest
+        pick = torch.tensor([0, T - 1, T // 2, (T * 2) // 3], device="cuda")
+        k = pick[torch.randint(0, 4, (n,), device="cuda", generator=g)]
+    else:
+        k = _emission_keys(T, n, g)
+    assert int(k.min()) >= 0 and int(k.max()) < T
+    return k
+
+
+def _check_tile_sort(T, k64, g, what):
+    n = k64.numel()
+    keys = (k64.to(torch.int32).to(torch.int16) if T <= 65536 else k64.to(torch.int32))   # 16-bit keys: same bits, wrapped
+    vals = torch.randperm(n, device="cuda", generator=g).to(torch.int32)                # distinct payloads pin stability
+    ko, vo = _tile_sort(T, keys, vals)
+    want = torch.sort(k64, stable=True)
+    mask = 0xffff if T <= 65536 else 0xffffffff
+    assert torch.equal(ko.to(torch.int64) & mask, want.values), what
+    assert torch.equal(vo, vals[want.indices]), what
+
+
+@pytest.mark.parametrize("T", GRID_TILES)
+def test_tile_sort_at_grid_limit_matches_stable_sort(T):
+    g = torch.Generator(device="cuda").manual_seed(T)
+    for n in GRID_N:
+        for pattern in ("uniform", "top", "ties", "emission"):
+            _check_tile_sort(T, _grid_keys(T, n, pattern, g), g, (T, n, pattern))
+
+
+@pytest.mark.parametrize("T", [65536, 1 << 20])
+def test_tile_sort_at_grid_limit_of_16m_pairs(T):
+    """~16.4 M pairs (the bench view's instance count): thousands of sort tiles per pass, with the emission's shape."""
+    g = torch.Generator(device="cuda").manual_seed(T + 1)
+    n = 16_400_001
+    for pattern in ("uniform", "emission"):
+        _check_tile_sort(T, _grid_keys(T, n, pattern, g), g, (T, n, pattern))
