@@ -9,6 +9,8 @@ Drop-in for the reference's two native extensions and the Python directly around
     c3dgs_amd.metrics     <->  utils/image_utils.py:psnr + 4-D ssim + compress.py:render_and_eval (no gradient)
     c3dgs_amd.sensitivity <->  compress.py:calc_importance_experimental (camera-sharded)
     c3dgs_amd.encode      <->  GaussianModel._sort_morton / mortonEncode
+    c3dgs_amd.knn         <->  simple_knn._C.distCUDA2 (initial scales of a point cloud in load_ply)
+    c3dgs_amd.ply         <->  the plyfile reads / writes of GaussianModel.load_ply / save_ply
     c3dgs_amd.model       <->  GaussianModel getters + FakeQuantize modules + render() glue (scene/gaussian_model.py)
     c3dgs_amd.optim       <->  the torch.optim.Adam step of the QAT loop (finetune.py:65-66), one fused launch
 
@@ -18,7 +20,7 @@ The numeric work runs in c3dgs_amd/libc3dgs_hip.so (include/c3dgs_hip.h); build 
 import sys
 import types
 
-from . import encode, loss, metrics, model, optim, rasterizer, rasterizer_matrix, sensitivity, vq  # noqa: F401
+from . import encode, knn, loss, metrics, model, optim, ply, rasterizer, rasterizer_matrix, sensitivity, vq  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,  # noqa: F401
                          getProjectionMatrix, mat_to_quat, quat_to_mat, rasterize_gaussians,
                          rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera)
@@ -27,13 +29,14 @@ from .vq import (CompressionSettings, VectorQuantize, compress_color, compress_c
 
 from .loss import l1_loss, l1_ssim_loss, ssim  # noqa: F401,E402
 from .encode import morton_codes, morton_order  # noqa: F401,E402
+from .knn import distCUDA2  # noqa: F401,E402
 
 __version__ = "0.1.0"
 
 
 def install_as_reference_modules():
     """Register this package under the module names the reference imports
-    (scene/gaussian_model.py:43-44, compression/vq.py:12), so the reference's Python runs unmodified."""
+    (scene/gaussian_model.py:39,43-44, compression/vq.py:12), so the reference's Python runs unmodified."""
     sys.modules["diff_gaussian_rasterization_no_camera"] = rasterizer
     for name in ("diff_gaussian_rasterization", "diff_gaussian_rasterization_camera"):   # the matrix-`extrinsic` siblings
         sys.modules[name] = rasterizer_matrix
@@ -43,3 +46,9 @@ def install_as_reference_modules():
     wd._C = wdc
     sys.modules["weighted_distance"] = wd
     sys.modules["weighted_distance._C"] = wdc
+    sk = types.ModuleType("simple_knn")
+    skc = types.ModuleType("simple_knn._C")
+    skc.distCUDA2 = distCUDA2
+    sk._C = skc
+    sys.modules["simple_knn"] = sk
+    sys.modules["simple_knn._C"] = skc

@@ -106,6 +106,8 @@ PROTOTYPES = {
     "c3dgs_draws_upload": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "c3dgs_morton_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "c3dgs_morton_order": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "c3dgs_knn_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "c3dgs_knn_mean_dist2": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
     "c3dgs_adam_step": (C.c_int, [C.c_int32, C.POINTER(AdamTensor), C.c_double, C.c_double, C.c_double, _vp]),
     "c3dgs_extract_rot_scale": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
     "c3dgs_l1_ssim_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

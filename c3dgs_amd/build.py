@@ -3,7 +3,8 @@
     python -m c3dgs_amd.build [--force] [--verbose]
 
 Per-file flags matter: preprocess.hip / backward_preprocess.hip are compiled with -ffp-contract=off
-because radii, tile rectangles and depth bits feed bit-exact integer tile keys (see csrc/gsmath.hpp).
+because radii, tile rectangles and depth bits feed bit-exact integer tile keys (see csrc/gsmath.hpp); knn.hip
+because its distances are a bit-exact contract.
 """
 import os
 import subprocess
@@ -33,6 +34,7 @@ SOURCES = {
     "loss.hip": [],
     "metrics.hip": [],
     "encode.hip": [],
+    "knn.hip": ["-ffp-contract=off"],       # the distances and box bounds are bit-exact fp32 expressions (csrc/knn.hip)
     "adam.hip": ["-ffp-contract=off"],
     "qat.hip": ["-ffp-contract=off"],
     "probe.hip": [],            # measurement-only kernels (PMC calibration), see csrc/probe.hip

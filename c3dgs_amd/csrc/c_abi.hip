@@ -17,12 +17,14 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 // synchronises until c3dgs_profile_read().
 enum Stage { ST_MARK_VISIBLE, ST_PREPROCESS, ST_DEPTH_SORT, ST_SCAN, ST_DUPLICATE, ST_SORT, ST_RANGES, ST_RENDER_FWD, ST_ZERO_PARTIALS,
              ST_RENDER_BWD, ST_BWD_PREPROCESS, ST_WDIST, ST_VQ_ACC, ST_VQ_APPLY, ST_LOSS_FWD, ST_LOSS_BWD,
-             ST_QAT_OBSERVE, ST_QAT_CODEBOOKS, ST_QAT_VISIBLE, ST_QAT_POINTS, ST_QAT_POINTS_BWD, ST_QAT_CODEBOOKS_BWD, ST_ADAM, ST_COUNT };
+             ST_QAT_OBSERVE, ST_QAT_CODEBOOKS, ST_QAT_VISIBLE, ST_QAT_POINTS, ST_QAT_POINTS_BWD, ST_QAT_CODEBOOKS_BWD, ST_ADAM,
+             ST_KNN_SORT, ST_KNN_BOUNDS, ST_KNN_QUERY, ST_COUNT };
 static const char* kStageNames[ST_COUNT] = { "mark_visible", "preprocess", "depth_sort", "scan", "duplicate_with_keys", "sort",
                                              "identify_ranges", "render_forward", "zero_partials", "render_backward",
                                              "backward_preprocess", "weighted_distance", "vq_accumulate", "vq_apply", "l1_ssim_forward",
                                              "l1_ssim_backward", "qat_observe", "qat_codebooks", "qat_visible", "qat_points",
-                                             "qat_points_backward", "qat_codebooks_backward", "adam_step" };
+                                             "qat_points_backward", "qat_codebooks_backward", "adam_step",
+                                             "knn_sort", "knn_bounds", "knn_query" };
 struct ProfRec { int stage; hipEvent_t a, b; };
 static std::mutex g_prof_mu;
 static bool g_prof_on = false;
@@ -681,6 +683,24 @@ int c3dgs_morton_order(int32_t P, const float* xyz, int64_t* codes, int64_t* ord
     if (!xyz || !codes || !order || !workspace) return fail(C3DGS_E_INVALID, "morton_order: bad arguments");
     if (run_morton_order(P, xyz, codes, order, workspace, (hipStream_t)stream)) return fail(C3DGS_E_HIP, "morton_order failed");
     C3DGS_STAGE("morton_order", 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
+size_t c3dgs_knn_workspace_bytes(int32_t P) { return knn_workspace_bytes(P); }
+
+int c3dgs_knn_mean_dist2(int32_t P, const float* xyz, float* out, void* workspace, void* stream)
+{
+    if (P < 0) return fail(C3DGS_E_INVALID, "knn_mean_dist2: P must be >= 0");
+    if (P == 0) return C3DGS_OK;
+    if (!xyz || !out || !workspace) return fail(C3DGS_E_INVALID, "knn_mean_dist2: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    { StageTimer t_(ST_KNN_SORT, s);
+      if (run_knn_sort(P, xyz, workspace, s)) return fail(C3DGS_E_HIP, "knn_mean_dist2: sort failed"); }
+    C3DGS_STAGE("knn_sort", 0, s);
+    { StageTimer t_(ST_KNN_BOUNDS, s); launch_knn_bounds(P, workspace, s); }
+    C3DGS_STAGE("knn_bounds", 0, s);
+    { StageTimer t_(ST_KNN_QUERY, s); launch_knn_query(P, workspace, out, s); }
+    C3DGS_STAGE("knn_query", 0, s);
     return C3DGS_OK;
 }
 

@@ -37,6 +37,21 @@ inline int fail(int code, const std::string& msg) { set_error(msg); return code;
             return ::c3dgs::fail(C3DGS_E_HIP, std::string("stage ") + name + ": " + hipGetErrorString(e__)); \
     } while (0)
 
+// ---------------------------------------------------------------- order-preserving float <-> uint mapping
+// atomicMin / atomicMax on the mapped words order the floats (bounding boxes of encode.hip and knn.hip)
+__device__ __forceinline__ uint32_t f2ord(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __host__ __forceinline__ float ord2f(uint32_t o)
+{
+    const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
 // ---------------------------------------------------------------- scratch layouts
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
@@ -235,6 +250,11 @@ int launch_gather_probe(int kind, size_t n, void* table, const uint32_t* index, 
 size_t morton_workspace_bytes(int P);
 int run_morton_order(int P, const float* xyz, int64_t* codes_out, int64_t* order_out, void* workspace, hipStream_t s);
 void launch_extract_rot_scale(int n, const float* cov6, float* rot, float* scale, hipStream_t s);
+// knn.hip (3-nearest-neighbour mean squared distance): sort, then bounds, then query, on one workspace
+size_t knn_workspace_bytes(int P);
+int run_knn_sort(int P, const float* xyz, void* workspace, hipStream_t s);
+void launch_knn_bounds(int P, void* workspace, hipStream_t s);
+void launch_knn_query(int P, const void* workspace, float* out, hipStream_t s);
 // adam.hip
 void launch_adam(int n_tensors, const c3dgs_adam_tensor* tensors, double beta1, double beta2, double eps, hipStream_t s);
 void launch_abs_accumulate(int64_t n, const float* g, float* acc, hipStream_t s);

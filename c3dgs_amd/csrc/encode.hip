@@ -12,20 +12,6 @@
 
 namespace c3dgs {
 
-// order-preserving float <-> uint mapping so that atomicMin/atomicMax on uint order floats
-__device__ __forceinline__ uint32_t f2ord(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __host__ __forceinline__ float ord2f(uint32_t o)
-{
-    const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
 __global__ void __launch_bounds__(256)
 bbox_kernel(int P, const float* __restrict__ xyz, uint32_t* __restrict__ box /*[6]: min xyz, max xyz (ordered ints)*/)
 {

@@ -6,7 +6,8 @@ Mirrors, for the render path only, scene/gaussian_model.py:
     get_scaling ... get_opacity                   :213-267
     GaussianModel.render                          :766-886
     FakeQuantizationHalf                          :1405-1414
-Densification and ply IO of the reference class are outside the hot path and not mirrored.
+    save_ply / load / load_ply                    :324-503  (PLY IO in ply.py; distCUDA2 scales in knn.py)
+Densification of the reference class is outside the hot path and not mirrored.
 
 The reference evaluates every getter with torch ops and seven torch.ao FakeQuantize modules: about a hundred small
 launches and twenty host syncs per view (aminmax + float(scale) / int(zero_point) per module, one nonzero per
@@ -319,7 +320,8 @@ class PipelineParams:
 
 class GaussianModel:
     """Render-path mirror of scene/gaussian_model.py:GaussianModel (same constructor arguments, parameter attribute
-    names, getters and render()). Parameters are plain tensors the caller assigns (`set_tensors`)."""
+    names, getters and render()). Parameters come from `load` (a trained .ply, a point cloud .ply, or a compressed .npz)
+    or are plain tensors the caller assigns (`set_tensors`)."""
 
     def __init__(self, sh_degree, quantization=True, use_factor_scaling=True, device="cuda", is_splitted=True):
         self.is_splitted = is_splitted
@@ -593,6 +595,119 @@ class GaussianModel:
         self._gaussian_indices = torch.from_numpy(sd["gaussian_indices"]).long().to(dev) if "gaussian_indices" in sd else None
         self.color_index_mode = ColorMode.ALL_INDEXED if self._feature_indices is not None else ColorMode.NOT_INDEXED
         self.active_sh_degree = self.max_sh_degree
+        return self
+
+    # ---- PLY files (gaussian_model.py:324-387 save_ply, :389-396 load, :398-503 load_ply)
+    def _ply_attributes(self):                                  # construct_list_of_attributes, :324-337
+        names = ["x", "y", "z", "nx", "ny", "nz"]
+        names += [f"f_dc_{i}" for i in range(self._features_dc.shape[1] * self._features_dc.shape[2])]
+        names += [f"f_rest_{i}" for i in range(self._features_rest.shape[1] * self._features_rest.shape[2])]
+        names.append("opacity")
+        names += [f"scale_{i}" for i in range(self._scaling.shape[1])]
+        names += [f"rot_{i}" for i in range(self._rotation.shape[1])]
+        return names
+
+    def save_ply(self, path):
+        """The standard 3DGS PLY every viewer reads: dense per-Gaussian attributes (an indexed model is expanded),
+        raw opacity, log of the activated scale (scale factor folded in), activated rotation, zero normals."""
+        import os
+        import numpy as np
+        from . import ply
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        if self.is_gaussian_indexed or self.is_color_indexed:
+            print("WARNING: indexed colors/gaussians are not supported for ply files and are converted to dense attributes")
+        with torch.no_grad():
+            color = self.get_features.detach()                 # getter order of the reference: features, scaling, rotation
+            xyz = self._xyz.detach().cpu().numpy()
+            f_dc = color[:, :1].transpose(1, 2).flatten(start_dim=1).contiguous().cpu().numpy()
+            f_rest = color[:, 1:].transpose(1, 2).flatten(start_dim=1).contiguous().cpu().numpy()
+            opacities = self._opacity.detach().cpu().numpy()
+            scale = torch.log(self.get_scaling.detach()).cpu().numpy()   # scaling_factor_inverse / scaling_inverse = log
+            rotation = self.get_rotation.detach().cpu().numpy()
+        attributes = np.concatenate((xyz, np.zeros_like(xyz), f_dc, f_rest, opacities, scale, rotation), axis=1)
+        ply.write_ply(path, {name: attributes[:, k] for k, name in enumerate(self._ply_attributes())})
+
+    def load(self, path, override_quantization=False):
+        import os
+        ext = os.path.splitext(path)[1]
+        if ext == ".ply":
+            return self.load_ply(path)
+        if ext == ".npz":
+            return self.load_npz(path, override_quantization)
+        raise NotImplementedError(f"file ending '{ext}' not supported")
+
+    def load_ply(self, path):
+        """A trained 3DGS PLY, or a point cloud (x y z [nx ny nz] red green blue): missing opacity -> logit(0.1), missing
+        scales -> log(sqrt(max(distCUDA2(xyz), 1e-7))) per axis, missing rotation -> identity (gaussian_model.py:398-503)."""
+        import numpy as np
+        from . import ply
+        from .knn import distCUDA2
+        v = ply.read_ply(path)
+        keys = list(v)
+        dev = self.device
+        xyz = np.stack((v["x"], v["y"], v["z"]), axis=1)
+        n = xyz.shape[0]
+        if "opacity" in keys:
+            opacities = v["opacity"][..., None]
+        else:
+            x = 0.1 * np.ones((n, 1))
+            opacities = np.log(x / (1 - x))
+        features_dc = np.zeros((n, 3, 1))
+        color_codes = ["red", "green", "blue"] if "red" in keys else ["f_dc_0", "f_dc_1", "f_dc_2"]
+        for i, name in enumerate(color_codes):
+            if name not in v:
+                raise ValueError(f"{path}: vertex element has no '{name}' property")
+            features_dc[:, i, 0] = v[name]
+        if "red" in keys:
+            features_dc = (features_dc / 255.0 - 0.5) / 0.28209479177387814      # RGB2SH, in float64 as numpy does
+        rest = sorted((k for k in keys if k.startswith("f_rest_")), key=lambda k: int(k.split("_")[-1]))
+        if rest:
+            degree = {3 * ((d + 1) ** 2 - 1): d for d in range(self.max_sh_degree + 1)}
+            if degree.get(len(rest)) is None:
+                raise ValueError(f"{path}: {len(rest)} f_rest_* properties match no SH degree <= {self.max_sh_degree}")
+            self.active_sh_degree = degree[len(rest)]
+            features_extra = np.zeros((n, len(rest)))
+            for i, name in enumerate(rest):
+                features_extra[:, i] = v[name]
+            features_extra = features_extra.reshape((n, 3, len(rest) // 3))
+        else:
+            self.active_sh_degree = 0
+            features_extra = np.zeros((n, 3, (self.max_sh_degree + 1) ** 2 - 1))
+        scale_names = sorted((k for k in keys if k.startswith("scale_") and not k.startswith("scale_factor")),
+                             key=lambda k: int(k.split("_")[-1]))
+        if scale_names:
+            scales = np.zeros((n, len(scale_names)))
+            for i, name in enumerate(scale_names):
+                scales[:, i] = v[name]
+            scaling = torch.tensor(scales, dtype=torch.float, device=dev)
+        else:
+            dist2 = torch.clamp_min(distCUDA2(torch.from_numpy(xyz).float().to(dev)), 0.0000001)
+            scaling = torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3)
+        rot_names = sorted((k for k in keys if k.startswith("rot")), key=lambda k: int(k.split("_")[-1]))
+        if rot_names:
+            rots = np.zeros((n, len(rot_names)))
+            for i, name in enumerate(rot_names):
+                rots[:, i] = v[name]
+        else:
+            rots = np.zeros((n, 4))
+            rots[:, 0] = 1
+        par = lambda t: t.detach().contiguous().requires_grad_(True)
+        self._xyz = par(torch.tensor(xyz, dtype=torch.float, device=dev))
+        self._features_dc = par(torch.tensor(features_dc, dtype=torch.float, device=dev).transpose(1, 2))
+        self._features_rest = par(torch.tensor(features_extra, dtype=torch.float, device=dev).transpose(1, 2))
+        self._opacity = par(torch.tensor(opacities, dtype=torch.float, device=dev))
+        if self.use_factor_scaling:
+            scaling = torch.exp(scaling)
+            norm = scaling.norm(2, -1, keepdim=True)
+            self._scaling = par(scaling / norm)
+            self._scaling_factor = par(torch.log(norm))
+        else:
+            self._scaling = par(scaling)
+            self._scaling_factor = None
+        self._rotation = par(torch.tensor(rots, dtype=torch.float, device=dev))
+        self._feature_indices = self._gaussian_indices = None
+        self.color_index_mode = ColorMode.NOT_INDEXED
+        self.max_radii2D = torch.zeros(n, device=dev)
         return self
 
     # ---- optimizer plumbing of the fine-tuning loop (gaussian_model.py:292-322)

@@ -260,6 +260,14 @@ size_t c3dgs_morton_workspace_bytes(int32_t P);
 int c3dgs_morton_order(int32_t P, const float* xyz /*[P,3]*/, int64_t* codes /*[P]*/, int64_t* order /*[P]*/,
                        void* workspace, void* stream);
 
+/* ---- 3-nearest-neighbour scale initialiser (simple_knn's distCUDA2, called by GaussianModel.load_ply for a point cloud
+ * without scale_* properties, scene/gaussian_model.py:459).  out[i] = ((d0 + d1) + d2) / 3 where d0 <= d1 <= d2 are the
+ * three smallest fp32 squared distances dx*dx + dy*dy + dz*dz (dx = x[j] - x[i], no FMA contraction) over j != i; for
+ * P <= 3 the missing slots are FLT_MAX. Exact: the same bits as a brute force. xyz must be finite.
+ * workspace: c3dgs_knn_workspace_bytes(P) bytes. P == 0 is a no-op that touches no pointer. */
+size_t c3dgs_knn_workspace_bytes(int32_t P);
+int c3dgs_knn_mean_dist2(int32_t P, const float* xyz /*[P,3]*/, float* out /*[P]*/, void* workspace, void* stream);
+
 /* ---- fused Adam step (the optimizer.step() that closes the QAT inner loop, finetune.py:65-66; optimizer set-up
  * scene/gaussian_model.py:296-308: torch.optim.Adam(param groups, lr=0.0, eps=1e-15), no weight decay, no amsgrad).
  * ONE launch updates up to C3DGS_ADAM_MAX_TENSORS tensors with torch's _single_tensor_adam arithmetic; the caller passes
