@@ -53,6 +53,10 @@ class ImageLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "final_T", "n_contrib", "ranges", "tile_used", "tile_order")]
 
 
+class CompactLayout(C.Structure):     # c3dgs_get_compact_layout: the compact per-tile lists the backward walks
+    _fields_ = [(n, C.c_size_t) for n in ("cqm", "cid", "tile_used_c", "n_contrib_c")]
+
+
 class QatParams(C.Structure):
     _fields_ = [("P", C.c_int32), ("GS", C.c_int32), ("SHS", C.c_int32), ("M", C.c_int32),
                 ("xyz", C.c_void_p), ("opacity", C.c_void_p), ("scaling_factor", C.c_void_p), ("scaling", C.c_void_p),
@@ -138,6 +142,7 @@ PROTOTYPES = {
     "c3dgs_get_geom_layout": (C.c_int, [C.c_int32, C.POINTER(GeomLayout)]),
     "c3dgs_get_binning_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(BinningLayout)]),
     "c3dgs_get_image_layout": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(ImageLayout)]),
+    "c3dgs_get_compact_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(CompactLayout)]),
     "c3dgs_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "c3dgs_profile_enable": (C.c_int, [C.c_int]),
     "c3dgs_profile_only": (C.c_int, [C.c_char_p]),

@@ -242,8 +242,9 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
         C3DGS_STAGE("identify_ranges", p.debug, s);
     }
     { StageTimer t_(ST_RENDER_FWD, s);
-      // per-instance quadrant masks go to the (now idle) sort scratch: R bytes the backward reads instead of recomputing
-      launch_render_forward(W, H, img, b.point_list, g.splat, p.background, out_color, (uint8_t*)b.sort_temp, sort_err, s); } // K9
+      // the tiles' compact lists (ids + quadrant masks of the entries that can reach their tile) go to the now idle sort scratch:
+      // 5 R bytes, what the backward walks instead of the point list
+      launch_render_forward(W, H, img, b.point_list, g.splat, p.background, out_color, compact_ptrs(b, R, W, H), sort_err, s); } // K9
     C3DGS_STAGE("render_forward", p.debug, s);
     return C3DGS_OK;
 }
@@ -312,8 +313,8 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
     if (R > 0) {
         const BinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), R, W, H);
         { StageTimer t_(ST_RENDER_BWD, s);
-          launch_render_backward(W, H, img, b.point_list, g.splat, g.block_base, p.background, dL_dout_color, partials, touched,
-                                 (const uint8_t*)b.sort_temp, tile_order, cb_zero, cb_zero16, s); } // K10
+          launch_render_backward(W, H, img, g.splat, g.block_base, p.background, dL_dout_color, partials, touched,
+                                 compact_ptrs(b, R, W, H), tile_order, cb_zero, cb_zero16, s); } // K10
         C3DGS_STAGE("render_backward", p.debug, s);
     }
     { StageTimer t_(ST_BWD_PREPROCESS, s);
@@ -476,6 +477,15 @@ int c3dgs_get_image_layout(int32_t W, int32_t H, c3dgs_image_layout* out)
 {
     if (!out || W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, "bad arguments");
     image_layout(W, H, out);
+    return C3DGS_OK;
+}
+int c3dgs_get_compact_layout(int32_t R, int32_t W, int32_t H, c3dgs_compact_layout* out)
+{
+    if (!out || R < 0 || W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, "bad arguments");
+    c3dgs_binning_layout BL; binning_layout(R, W, H, &BL);
+    const CompactLayout C = compact_layout(R, W, H);
+    out->cqm = BL.sort_temp + C.cqm; out->cid = BL.sort_temp + C.cid;
+    out->tile_used_c = C.tile_used_c; out->n_contrib_c = C.n_contrib_c;
     return C3DGS_OK;
 }
 size_t c3dgs_backward_workspace_bytes(int32_t P, int32_t R)

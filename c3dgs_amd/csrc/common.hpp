@@ -126,6 +126,10 @@ inline void binning_layout(int R, int W, int H, c3dgs_binning_layout* L)
     L->total_bytes = o;
 }
 
+inline size_t compact_image_bytes(int W, int H)
+{
+    return align_up((size_t)tiles_x(W) * tiles_y(H) * 4) + align_up((size_t)W * H * 4);
+}
 inline void image_layout(int W, int H, c3dgs_image_layout* L)
 {
     size_t o = 0, n = (size_t)W * H, t = (size_t)tiles_x(W) * tiles_y(H);
@@ -134,7 +138,24 @@ inline void image_layout(int W, int H, c3dgs_image_layout* L)
     L->ranges = o;    o = align_up(o + t * 8);
     L->tile_used = o; o = align_up(o + t * 4);
     L->tile_order = o; o = align_up(o + t * 4);
-    L->total_bytes = o;
+    L->total_bytes = o + compact_image_bytes(W, H);   // tile_used_c | n_contrib_c behind it (compact_layout below)
+}
+
+// Compact per-tile lists (render.hip): of a tile's visited list entries only those whose quadrant mask is non-zero ("live") can
+// touch a pixel of the tile. The forward writes their Gaussian ids (cid) and masks (cqm) densely from the start of the tile's
+// own segment [range.x, ...) of two arrays in the idle sort scratch, and per pixel / per tile the 1-based COMPACT index of the last
+// contributor (n_contrib_c, tile_used_c) behind the public part of the image buffer; the backward walks only those. Offsets are
+// private to the library (tests: c3dgs_get_compact_layout); the public layout structs do not change.
+struct CompactLayout { size_t cqm, cid, bin_bytes; size_t tile_used_c, n_contrib_c; };
+inline CompactLayout compact_layout(int R, int W, int H)
+{
+    const size_t r = (size_t)(R > 0 ? R : 1), t = (size_t)tiles_x(W) * tiles_y(H);
+    c3dgs_image_layout IL; image_layout(W, H, &IL);
+    CompactLayout C;
+    C.cqm = 0; C.cid = align_up(r); C.bin_bytes = C.cid + align_up(r * 4);          // relative to sort_temp
+    C.tile_used_c = IL.tile_order + align_up(t * 4);
+    C.n_contrib_c = C.tile_used_c + align_up(t * 4);
+    return C;
 }
 
 // ---------------------------------------------------------------- kernel launchers (one per .hip file)
@@ -148,7 +169,9 @@ struct BinPtrs {
     void* keys_unsorted; uint32_t* values_unsorted; void* keys_sorted; uint32_t* point_list;   // keys: u16, or u32 above 65,536 tiles
     void* sort_temp; size_t sort_temp_bytes; int key_bytes;
 };
-struct ImgPtrs { float* final_T; uint32_t* n_contrib; uint2* ranges; uint32_t* tile_used; uint32_t* tile_order; };
+struct ImgPtrs { float* final_T; uint32_t* n_contrib; uint2* ranges; uint32_t* tile_used; uint32_t* tile_order;
+                 uint32_t* tile_used_c; uint32_t* n_contrib_c; };
+struct CompactPtrs { uint8_t* cqm; uint32_t* cid; };   // inside BinPtrs::sort_temp, valid once the tile sort has run
 
 inline GeomPtrs geom_ptrs(void* base, int P)
 {
@@ -169,9 +192,15 @@ inline BinPtrs bin_ptrs(void* base, int R, int W, int H)
 inline ImgPtrs img_ptrs(void* base, int W, int H)
 {
     c3dgs_image_layout L; image_layout(W, H, &L);
+    const CompactLayout C = compact_layout(0, W, H);
     char* b = (char*)base;
     return { (float*)(b + L.final_T), (uint32_t*)(b + L.n_contrib), (uint2*)(b + L.ranges), (uint32_t*)(b + L.tile_used),
-             (uint32_t*)(b + L.tile_order) };
+             (uint32_t*)(b + L.tile_order), (uint32_t*)(b + C.tile_used_c), (uint32_t*)(b + C.n_contrib_c) };
+}
+inline CompactPtrs compact_ptrs(const BinPtrs& bp, int R, int W, int H)
+{
+    const CompactLayout C = compact_layout(R, W, H);
+    return { (uint8_t*)bp.sort_temp + C.cqm, (uint32_t*)((char*)bp.sort_temp + C.cid) };
 }
 
 // preprocess.hip
@@ -217,12 +246,12 @@ hipError_t onesweep_tile_sort(void* temp, size_t temp_bytes, const uint16_t* kin
 int os_read_times(unsigned long long* out512);   // radix_sort.hip, experiment builds with -DC3DGS_OS_TIMING only
 int read_lane_counters(unsigned long long* out16, hipStream_t s);   // render.hip; all zero unless built with -DC3DGS_COUNT_LANES
 void launch_render_forward(int W, int H, const ImgPtrs& img, const uint32_t* point_list, const float4* splat,
-                           const float* bg, float* out_color, uint8_t* qmask, const uint32_t* sort_err, hipStream_t s);
+                           const float* bg, float* out_color, const CompactPtrs& cl, const uint32_t* sort_err, hipStream_t s);
 void launch_backward_prep(int W, int H, const ImgPtrs& img, uint32_t* tile_order, void* zero_a, size_t n16_a, void* zero_b,
                           size_t n16_b, hipStream_t s);
-void launch_render_backward(int W, int H, const ImgPtrs& img, const uint32_t* point_list, const float4* splat,
+void launch_render_backward(int W, int H, const ImgPtrs& img, const float4* splat,
                             const uint32_t* block_base, const float* bg, const float* dL_dpix, float* partials,
-                            uint8_t* touched, const uint8_t* qmask, const uint32_t* tile_order, void* zero_span, size_t zero_n16,
+                            uint8_t* touched, const CompactPtrs& cl, const uint32_t* tile_order, void* zero_span, size_t zero_n16,
                             hipStream_t s);
 // backward_preprocess.hip
 void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g,

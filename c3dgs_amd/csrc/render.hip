@@ -13,6 +13,10 @@
 //    the current batch is blended; the forward blend is branch-free (selects), early-out is a per-wave ballot plus
 //    four LDS flags read after the batch barrier;
 //  * workgroup ids are remapped so that each XCD (own L2) gets a contiguous band of tiles;
+//  * the forward also writes each tile's COMPACT list: ids and masks of the visited entries whose mask is non-zero (half of them
+//    on the bench scene: a splat's 3-sigma rectangle is far larger than its alpha >= 1/255 footprint), in list order, plus every
+//    pixel's last contributor as an index into it; the backward walks that list, not the point list, so an entry that reaches
+//    no pixel of the tile costs it no record gather, no staging, no partial-sum slot;
 //  * backward: NO global atomics. Per pixel only 9 raw sums (3 colour terms + 6 moments of w = G*dL/dalpha about the
 //    mean) are formed; 7 Gaussians x 9 sums are reduced over the wave together by a transposing DPP / permlane-swap
 //    network, the 4 waves are combined through LDS, and one plain 36-byte store (+ a flag byte) per (Gaussian, tile)
@@ -36,8 +40,7 @@ __device__ unsigned long long g_lane_counters[16];
 
 #ifndef C3DGS_BWD_ABLATE
 #define C3DGS_BWD_ABLATE 0      // timing-only experiment builds (WRONG gradients): bit 0 = no partial-sum stores, bit 1 = cache-resident
-                                // record gathers, bit 2 = without the two in-bank reduction levels, bit 3 = without any reduction, bit 4 = records read
-                                // coalesced by list position (what parking the forward's staged records would give)
+                                // record gathers, bit 2 = without the two in-bank reduction levels, bit 3 = without any reduction
 #endif
 #ifdef C3DGS_BWD_TIMING
 // phase clocks of render_backward (experiment build variant "bwdtime"): shader-clock ticks summed over all waves:
@@ -201,7 +204,8 @@ __global__ void __launch_bounds__(256)
 render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
                       const float4* __restrict__ splat, const float* __restrict__ bg, float* __restrict__ out_color,
                       float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, uint32_t* __restrict__ tile_used,
-                      uint8_t* __restrict__ qmask, const uint32_t* __restrict__ sort_err)
+                      uint32_t* __restrict__ n_contrib_c, uint32_t* __restrict__ tile_used_c, uint8_t* __restrict__ cqm,
+                      uint32_t* __restrict__ cid, const uint32_t* __restrict__ sort_err)
 {
     const int tile = tile_of_block(blockIdx.x, T);
     if (tile >= T || (blockIdx.x >> 3) >= ((T + 7) >> 3)) return;
@@ -215,7 +219,13 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
     __shared__ uint32_t s_list[4][BATCH + 8];        // per wave: its candidates of the batch, padded to a multiple of 8
     __shared__ int s_wdone[2][4];
     __shared__ unsigned long long s_mask[2][4][4];   // [buf][quadrant][staging wave]: which staged Gaussians reach it
-    __shared__ uint32_t s_used;
+    // Compact list of the tile (what the backward walks): the entries whose mask is non-zero ("live"), in list order.
+    // s_live = how many of a staging wave's 64 entries are live. (12 bytes: the kernel's LDS must stay within 18 allocation
+    // granules of 1280 bytes = 23,040, or a CU holds six workgroups instead of seven.)
+    __shared__ __attribute__((aligned(4))) uint8_t s_live[2][4];
+    __shared__ uint32_t s_used, s_used_c;
+    static_assert(sizeof(s_ab) + sizeof(s_c) + sizeof(s_list) + sizeof(s_wdone) + sizeof(s_mask) + sizeof(s_live) + 2 * sizeof(uint32_t)
+                      <= 18 * 1280, "render_forward: more than 18 LDS granules = six workgroups per CU instead of seven");
     constexpr uint32_t REC_BYTES = 32, BUF_BYTES = (BATCH + 1) * REC_BYTES;
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -225,7 +235,7 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
     const bool inside = px < W && py < H;
     const float pxf = (float)px, pyf = (float)py;
     bool done = !inside;
-    if (tid == 0) s_used = 0;
+    if (tid == 0) { s_used = 0; s_used_c = 0; }
     if (tid < 2) { s_ab[tid][BATCH][0] = make_float4(0, 0, 0, 0); s_ab[tid][BATCH][1] = make_float4(0, 0, 0, 0); s_c[tid][BATCH] = 0.f; }
     const float tile_x0 = (float)(tx * TILE), tile_y0 = (float)(ty * TILE);
 
@@ -239,7 +249,8 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
     const int rounds = (n + BATCH - 1) / BATCH;
 
     float Tr = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
-    uint32_t last_contributor = 0;
+    uint32_t last_contributor = 0, last_contributor_c = 0;   // 1-based: position in the tile's list / index in its compact list
+    uint32_t n_live = 0;                                      // live entries of the batches in front of this one (all waves agree)
     constexpr uint32_t NO_ENTRY = 0xffffffffu;
 #ifdef C3DGS_COUNT_LANES
     LaneCount lc;
@@ -248,8 +259,9 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
     const char* blue_base = reinterpret_cast<const char*>(&s_c[0][0]);
 
     float4 ra = make_float4(0, 0, 0, 0), rb = ra, rc = ra;
+    uint32_t id = 0u;                                         // Gaussian of the entry this thread stages
     if (tid < n) {
-        const uint32_t id = point_list[range.x + tid];
+        id = point_list[range.x + tid];
         ra = splat[3 * (size_t)id]; rb = splat[3 * (size_t)id + 1]; rc = splat[3 * (size_t)id + 2];
     }
     for (int r = 0; r < rounds; r++) {
@@ -257,21 +269,40 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
         const uint32_t qm = (r * BATCH + tid < n) ? quadrant_mask(ra, rb, tile_x0, tile_y0) : 0u;
         prescale_conic(ra, rb);
         s_ab[buf][tid][0] = ra; s_ab[buf][tid][1] = rb; s_c[buf][tid] = rc.x;
-        if (r * BATCH + tid < n) qmask[range.x + r * BATCH + tid] = (uint8_t)qm;   // the backward reuses it (same test, ~100 VALU ops)
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const unsigned long long bm = __ballot((qm >> q) & 1u);
             if (lane == 0) s_mask[buf][q][wave] = bm;
         }
+        const unsigned long long live = __ballot(qm != 0u);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(live >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)live, 0u));
+        if (lane == 0) s_live[buf][wave] = (uint8_t)__popcll(live);                 // 64 is the most
         const bool wave_done = __all(done);
         if (lane == 0) s_wdone[buf][wave] = wave_done;
         __syncthreads();
         if (s_wdone[buf][0] & s_wdone[buf][1] & s_wdone[buf][2] & s_wdone[buf][3]) break; // forward.cu:318-320
+        const uint32_t cur_id = id;
         const int nxt = (r + 1) * BATCH + tid;
         if (nxt < n) {                           // prefetch the next batch behind this batch's blending
-            const uint32_t id = point_list[range.x + nxt];
+            id = point_list[range.x + nxt];
             ra = splat[3 * (size_t)id]; rb = splat[3 * (size_t)id + 1]; rc = splat[3 * (size_t)id + 2];
         }
+        // The batch's live entries go to the tile's compact list: Gaussian id and mask (the backward reuses the mask: same test,
+        // ~100 VALU ops) at index n_live + live entries of the staging waves in front + rank. A compact index never exceeds the
+        // entry's position, so the tile stays inside its own segment of cid / cqm. Every wave passes here for every batch the tile
+        // blends (the exit above is taken by all four together), so all four keep the same n_live. Issued behind the prefetch,
+        // so that no store sits in front of the loads the next batch waits for.
+        // (the four counts of a buffer as ONE word: relies on s_live's [2][4] shape and its aligned(4) attribute)
+        const uint32_t lv = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const uint32_t*>(&s_live[buf][0]));   // scalar register
+        const uint32_t lv0 = lv & 0xffu, lv1 = (lv >> 8) & 0xffu, lv2 = (lv >> 16) & 0xffu, lv3 = lv >> 24;
+        const uint32_t wb1 = n_live + lv0, wb2 = wb1 + lv1, wb3 = wb2 + lv2;                               // wave-uniform
+        const uint32_t wb0 = n_live;
+        auto wave_base = [&](uint32_t w) { return w == 0 ? wb0 : w == 1 ? wb1 : w == 2 ? wb2 : wb3; };
+        if (qm != 0u) {
+            const uint32_t ci = range.x + wave_base((uint32_t)wave) + rank;
+            cid[ci] = cur_id; cqm[ci] = (uint8_t)qm;
+        }
+        n_live = wb3 + lv3;
         if (wave_done) continue;
         // This wave's candidates of the batch, compacted into LDS once (record offsets, padded with the sentinel's to a
         // multiple of 8): the blend loop then needs no bit scanning and no per-Gaussian scalar control flow.
@@ -326,12 +357,21 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
         lc.end_list();
 #endif
         // offset -> 1-based position in the tile's list (once per batch, not per Gaussian)
-        if (last_off != NO_ENTRY) last_contributor = (uint32_t)(r * BATCH) + ((last_off - (uint32_t)buf * BUF_BYTES) >> 5) + 1u;
+        if (last_off != NO_ENTRY) {
+            const uint32_t j = (last_off - (uint32_t)buf * BUF_BYTES) >> 5;       // batch entry; it blended, so it is live
+            last_contributor = (uint32_t)(r * BATCH) + j + 1u;
+            // its compact index: live entries of the staging waves in front + its rank in its own staging wave, from the
+            // quadrant ballots (per lane, once per batch)
+            const uint32_t c = j >> 6;
+            const unsigned long long lv_c = s_mask[buf][0][c] | s_mask[buf][1][c] | s_mask[buf][2][c] | s_mask[buf][3][c];
+            last_contributor_c = wave_base(c) + (uint32_t)__popcll(lv_c & ((1ull << (j & 63u)) - 1ull)) + 1u;
+        }
     }
     if (inside) {
         const size_t pix = (size_t)W * py + px, HW = (size_t)H * W;
         final_T[pix] = Tr;
         n_contrib[pix] = last_contributor;
+        n_contrib_c[pix] = last_contributor_c;
         const float poison = poisoned ? __uint_as_float(0x7fc00000u) : 0.f;
         out_color[pix] = fmaf(Tr, bg[0], C0) + poison;
         out_color[HW + pix] = fmaf(Tr, bg[1], C1) + poison;
@@ -341,18 +381,20 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
     lc.flush(0, lane);
 #endif
     // tile_used = max over the tile's pixels of n_contrib: the backward never looks past it
+    // (tile_used_c: the same in compact indices = the entries the backward walks)
     atomicMax(&s_used, last_contributor);
+    atomicMax(&s_used_c, last_contributor_c);
     __syncthreads();
-    if (tid == 0) tile_used[tile] = s_used;
+    if (tid == 0) { tile_used[tile] = s_used; tile_used_c[tile] = s_used_c; }
 }
 
 void launch_render_forward(int W, int H, const ImgPtrs& img, const uint32_t* point_list, const float4* splat,
-                           const float* bg, float* out_color, uint8_t* qmask, const uint32_t* sort_err, hipStream_t s)
+                           const float* bg, float* out_color, const CompactPtrs& cl, const uint32_t* sort_err, hipStream_t s)
 {
     const int gx = tiles_x(W), T = gx * tiles_y(H);
     const int grid = ((T + 7) / 8) * 8;
     render_forward_kernel<<<grid, 256, 0, s>>>(W, H, gx, T, img.ranges, point_list, splat, bg, out_color, img.final_T,
-                                               img.n_contrib, img.tile_used, qmask, sort_err);
+                                               img.n_contrib, img.tile_used, img.n_contrib_c, img.tile_used_c, cl.cqm, cl.cid, sort_err);
 }
 
 // ---------------------------------------------------------------- backward
@@ -454,11 +496,11 @@ __device__ __forceinline__ void reduce_rows_9(const float* n, float& total, floa
 #define C3DGS_BWD_WPE 5   // waves per SIMD the register allocator must reach (102 VGPRs); measured 3: 0.85 ms, 4: 0.745, 5: 0.707
 #endif
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(C3DGS_BWD_WPE, C3DGS_BWD_WPE)))
-render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ranges, const uint32_t* __restrict__ tile_used,
-                       const uint32_t* __restrict__ point_list, const float4* __restrict__ splat,
+render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ranges, const uint32_t* __restrict__ tile_used_c,
+                       const uint32_t* __restrict__ cid, const float4* __restrict__ splat,
                        const uint32_t* __restrict__ block_base, const float* __restrict__ bg, const float* __restrict__ final_Ts,
-                       const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpixels,
-                       float* __restrict__ partials, uint8_t* __restrict__ touched, const uint8_t* __restrict__ qmask,
+                       const uint32_t* __restrict__ n_contrib_c, const float* __restrict__ dL_dpixels,
+                       float* __restrict__ partials, uint8_t* __restrict__ touched, const uint8_t* __restrict__ cqm,
                        const uint32_t* __restrict__ tile_order, uint4* __restrict__ zero_span, size_t zero_n16)
 {
     // every workgroup of the grid first clears its slice of `zero_span` (the scatter-added codebook gradients of the indexed
@@ -467,7 +509,10 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
         const size_t per = (zero_n16 + gridDim.x - 1) / gridDim.x, z0 = (size_t)blockIdx.x * per, z1 = min(z0 + per, zero_n16);
         for (size_t i = z0 + threadIdx.x; i < z1; i += 256) zero_span[i] = make_uint4(0u, 0u, 0u, 0u);
     }
-    // longest tiles first (tile_order: descending tile_used), so that the last workgroups to start are the short ones
+    // The kernel walks the tile's COMPACT list (cid / cqm, written by the forward): the visited entries whose quadrant mask is
+    // non-zero, in list order. `used`, every position and both depth cuts below are compact indices; because they are ordered like
+    // list positions, all thresholds keep the form they have in position space.
+    // longest tiles first (tile_order: descending tile_used_c), so that the last workgroups to start are the short ones
     if ((int)blockIdx.x >= T) return;
     BT_STAMP(bt_begin)
 #ifdef C3DGS_BWD_TIMING
@@ -499,7 +544,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
 
     const uint2 range = ranges[tile];
     const int n = (int)(range.y - range.x);
-    const int used = min(n, (int)tile_used[tile]);
+    const int used = min(n, (int)tile_used_c[tile]);
     if (used <= 0) return;
     const int rounds = (used + BATCH - 1) / BATCH;
     if (tid == 0) { s_ab[BATCH][0] = make_float4(0, 0, 0, 0); s_ab[BATCH][1] = make_float4(0, 0, 0, 0); s_c[BATCH] = 0.f; }
@@ -508,7 +553,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
 
     const float T_final = inside ? final_Ts[pix] : 0.f;         // backward.cu:441-447
     float Tr = T_final;
-    const int last_contributor = inside ? (int)n_contrib[pix] : 0;
+    const int last_contributor = inside ? (int)n_contrib_c[pix] : 0;
     float dpx0 = 0.f, dpx1 = 0.f, dpx2 = 0.f;
     if (inside) { dpx0 = dL_dpixels[pix]; dpx1 = dL_dpixels[HW + pix]; dpx2 = dL_dpixels[2 * HW + pix]; }
     // Running "what lies behind" term. The reference keeps the blended colour behind the current Gaussian as a
@@ -532,7 +577,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
     uint32_t next_id = 0u, next_qm = 0u;
     {
         const int p0 = used - 1 - tid;
-        if (p0 >= 0) { next_id = point_list[range.x + p0]; next_qm = qmask[range.x + p0]; }
+        if (p0 >= 0) { next_id = cid[range.x + p0]; next_qm = cqm[range.x + p0]; }
     }
     BT_STAMP(bt_pro)
     for (int r = 0; r < rounds; r++) {
@@ -545,9 +590,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
             // the entry's Gaussian id and quadrant mask were requested one round ago (below): the record gather is the only
             // memory round trip left in front of this round's blending (measured with the "bwdtime" variant: the dependent chain
             // point list -> record was 31 % of a wave's lifetime, more than its group loop)
-#if C3DGS_BWD_ABLATE & 16
-            const uint32_t id = (range.x + (uint32_t)mypos) & 0x1fffffu;   // timing-only build: coalesced records, no dependence on the point list
-#elif C3DGS_BWD_ABLATE & 2
+#if C3DGS_BWD_ABLATE & 2
             const uint32_t id = next_id & 4095u;                  // timing-only build: records from a cache-resident corner of the array
 #else
             const uint32_t id = next_id;
@@ -558,7 +601,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
             prescale_conic(a, b);
             const uint32_t off = __float_as_uint(c.y), lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
             const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
-#if C3DGS_BWD_ABLATE & 18
+#if C3DGS_BWD_ABLATE & 2
             s_slot[tid] = range.x + (uint32_t)mypos;              // timing-only build: a slot that exists (the record is not this entry's)
             (void)off; (void)x0; (void)y0; (void)x1;
 #else
@@ -568,7 +611,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
         }
         {   // next round's ids / masks: in flight behind this round's blending (two registers)
             const int npos = mypos - BATCH;
-            if (npos >= 0) { next_id = point_list[range.x + npos]; next_qm = qmask[range.x + npos]; }   // qmask: written by the forward for every entry it staged
+            if (npos >= 0) { next_id = cid[range.x + npos]; next_qm = cqm[range.x + npos]; }
         }
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -783,18 +826,18 @@ void launch_backward_prep(int W, int H, const ImgPtrs& img, uint32_t* tile_order
     if (T <= 0 && n16 == 0) return;
     // fill workgroups: 16 KB each per sweep, at most four per CU
     const unsigned fill = n16 ? (unsigned)std::min<size_t>((n16 + 1023) / 1024, 1024) : 0u;
-    backward_prep_kernel<<<1 + fill, 1024, 0, s>>>(T, img.tile_used, tile_order, (uint4*)zero_a, n16_a, (uint4*)zero_b, n16_b);
+    backward_prep_kernel<<<1 + fill, 1024, 0, s>>>(T, img.tile_used_c, tile_order, (uint4*)zero_a, n16_a, (uint4*)zero_b, n16_b);
 }
 
-void launch_render_backward(int W, int H, const ImgPtrs& img, const uint32_t* point_list, const float4* splat,
+void launch_render_backward(int W, int H, const ImgPtrs& img, const float4* splat,
                             const uint32_t* block_base, const float* bg, const float* dL_dpix, float* partials,
-                            uint8_t* touched, const uint8_t* qmask, const uint32_t* tile_order, void* zero_span, size_t zero_n16,
+                            uint8_t* touched, const CompactPtrs& cl, const uint32_t* tile_order, void* zero_span, size_t zero_n16,
                             hipStream_t s)
 {
     const int gx = tiles_x(W), T = gx * tiles_y(H);
     const int grid = ((T + 7) / 8) * 8;
-    render_backward_kernel<<<grid, 256, 0, s>>>(W, H, gx, T, img.ranges, img.tile_used, point_list, splat, block_base, bg, img.final_T,
-                                                img.n_contrib, dL_dpix, partials, touched, qmask, tile_order, (uint4*)zero_span,
+    render_backward_kernel<<<grid, 256, 0, s>>>(W, H, gx, T, img.ranges, img.tile_used_c, cl.cid, splat, block_base, bg, img.final_T,
+                                                img.n_contrib_c, dL_dpix, partials, touched, cl.cqm, tile_order, (uint4*)zero_span,
                                                 zero_span ? zero_n16 : 0);
 }
 

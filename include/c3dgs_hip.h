@@ -446,6 +446,18 @@ int c3dgs_get_binning_layout(int32_t R, int32_t W, int32_t H, c3dgs_binning_layo
 int c3dgs_get_image_layout(int32_t W, int32_t H, c3dgs_image_layout* out);
 size_t c3dgs_backward_workspace_bytes(int32_t P, int32_t R);
 
+/* tests / tools only: where the forward leaves the tiles' COMPACT lists -- of the list entries a tile visits, those that can reach
+ * a pixel of it (non-zero quadrant mask), in list order, densely from the start of the tile's own segment [ranges[tile].x, ...).
+ * The backward walks these instead of the point list. Not part of the public buffer layouts (the structs above do not change).
+ * Valid after a forward with R > 0, until the binning / image buffers are reused. */
+typedef struct c3dgs_compact_layout {
+    size_t cqm;         /* binning buffer: uint8[R]  quadrant mask (bit qy*2+qx, never 0) of compact entry ranges[tile].x + k  */
+    size_t cid;         /* binning buffer: uint32[R] its Gaussian id; the entries k < tile_used_c[tile] are written            */
+    size_t tile_used_c; /* image buffer: uint32[T]   max n_contrib_c over the tile's pixels = compact entries the tile uses    */
+    size_t n_contrib_c; /* image buffer: uint32[W*H] 1-based compact index of the pixel's last contributor (0: none)           */
+} c3dgs_compact_layout;
+int c3dgs_get_compact_layout(int32_t R, int32_t W, int32_t H, c3dgs_compact_layout* out);
+
 /* ---- optional per-stage timing (HIP events on the caller's stream; used by bench.py's roofline leg) ----
  * c3dgs_profile_enable(1) makes every stage launch record a start/stop event pair; c3dgs_profile_read()
  * synchronises those events, returns one record per stage seen since the last read (count returned, at

@@ -30,7 +30,7 @@ txt = [f"render_backward on configs[2] (3M, 1920x1080, R={o[0]}): shader-clock t
 for name, x in (("prologue (pixel state, wave_last)", pro), ("staging of a batch incl. its two barriers", stage), ("candidate-list compaction", lst),
                 ("group loop (alpha, body, reduction, LDS adds)", loop), ("flush incl. barrier (LDS planes -> partial-sum slots)", flush)):
     txt.append(f"  {name:52s} {100.0 * x / total:5.1f} %")
-for name, x in (("  staging: barrier at the top of the round", fine[0]), ("  staging: point list -> splat record -> LDS (dependent loads)", fine[1]),
+for name, x in (("  staging: barrier at the top of the round", fine[0]), ("  staging: compact list -> splat record -> LDS (dependent loads)", fine[1]),
                 ("  staging: clearing the LDS planes", fine[2]), ("  staging: closing barrier", fine[3]), ("  flush: its barrier (slowest wave's group loop)", fine[4])):
     txt.append(f"  {name:60s} {100.0 * x / total:5.1f} %")
 txt.append(f"  unaccounted (loop control between the stamps)        {100.0 * (total - stage - lst - loop - flush - pro) / total:5.1f} %")
