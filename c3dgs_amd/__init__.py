@@ -11,7 +11,9 @@ Drop-in for the reference's two native extensions and the Python directly around
     c3dgs_amd.encode      <->  GaussianModel._sort_morton / mortonEncode
     c3dgs_amd.knn         <->  simple_knn._C.distCUDA2 (initial scales of a point cloud in load_ply)
     c3dgs_amd.ply         <->  the plyfile reads / writes of GaussianModel.load_ply / save_ply
-    c3dgs_amd.model       <->  GaussianModel getters + FakeQuantize modules + render() glue (scene/gaussian_model.py)
+    c3dgs_amd.model       <->  GaussianModel getters + FakeQuantize modules + render() glue + adaptive density control
+                               (scene/gaussian_model.py)
+    c3dgs_amd.pipeline    <->  train.py / finetune.py / compress.py drivers
     c3dgs_amd.optim       <->  the torch.optim.Adam step of the QAT loop (finetune.py:65-66), one fused launch
 
 The numeric work runs in c3dgs_amd/libc3dgs_hip.so (include/c3dgs_hip.h); build it with

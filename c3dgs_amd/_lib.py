@@ -70,6 +70,14 @@ class AdamTensor(C.Structure):
                 ("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float)]
 
 
+class RowsTensor(C.Structure):          # c3dgs_rows_tensor
+    _fields_ = [("in_param", C.c_void_p), ("in_exp_avg", C.c_void_p), ("in_exp_avg_sq", C.c_void_p), ("out_param", C.c_void_p),
+                ("out_exp_avg", C.c_void_p), ("out_exp_avg_sq", C.c_void_p), ("row_floats", C.c_int32), ("role", C.c_int32)]
+
+
+ROLE_COPY, ROLE_XYZ, ROLE_SCALING = 0, 1, 2
+ROW_KEEP, ROW_CLONE, ROW_SPLIT, ROW_CHILD_KEPT = 1, 2, 4, 8
+
 _vp = C.c_void_p
 # name -> (restype, argtypes); every symbol include/c3dgs_hip.h declares
 PROTOTYPES = {
@@ -113,6 +121,12 @@ PROTOTYPES = {
     "c3dgs_knn_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "c3dgs_knn_mean_dist2": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
     "c3dgs_adam_step": (C.c_int, [C.c_int32, C.POINTER(AdamTensor), C.c_double, C.c_double, C.c_double, _vp]),
+    "c3dgs_densify_classify": (C.c_int, [C.c_int32] + [_vp] * 7 + [C.c_float] * 4 + [_vp, _vp]),
+    "c3dgs_rows_plan_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "c3dgs_rows_plan": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c3dgs_rows_apply": (C.c_int, [C.c_int32, C.c_int64, _vp, _vp, _vp, C.c_int32, C.POINTER(RowsTensor), C.c_int32, C.c_int64,
+                                   _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
+    "c3dgs_densify_stats": (C.c_int, [C.c_int32] + [_vp] * 7),
     "c3dgs_extract_rot_scale": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
     "c3dgs_l1_ssim_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),

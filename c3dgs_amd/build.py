@@ -37,6 +37,7 @@ SOURCES = {
     "knn.hip": ["-ffp-contract=off"],       # the distances and box bounds are bit-exact fp32 expressions (csrc/knn.hip)
     "adam.hip": ["-ffp-contract=off"],
     "qat.hip": ["-ffp-contract=off"],
+    "densify.hip": ["-ffp-contract=off"],   # sqrt(gx*gx + gy*gy) of the densification stats is torch's two-rounding sum
     "probe.hip": [],            # measurement-only kernels (PMC calibration), see csrc/probe.hip
 }
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"),

@@ -735,6 +735,85 @@ int c3dgs_adam_step(int32_t n_tensors, const c3dgs_adam_tensor* tensors, double 
     return C3DGS_OK;
 }
 
+// ---- adaptive density control (densify.hip)
+static const int kRowsMaxCopies = 250;     // kind is a byte: 2 + k
+
+int c3dgs_densify_classify(int32_t P, const float* accum, const float* denom, const float* scale_clone, const float* scale_split,
+                           const float* scale_prune_self, const float* scale_prune_child, const float* opacity, float max_grad,
+                           float dense_extent, float min_opacity, float big_extent, uint8_t* code, void* stream)
+{
+    if (P < 0) return fail(C3DGS_E_INVALID, "densify_classify: P must be >= 0");
+    if (!(max_grad > 0.f)) return fail(C3DGS_E_INVALID, "densify_classify: max_grad must be > 0 (see include/c3dgs_hip.h)");
+    if (P == 0) return C3DGS_OK;
+    if (!accum || !denom || !scale_clone || !scale_split || !opacity || !code)
+        return fail(C3DGS_E_INVALID, "densify_classify: NULL buffer");
+    if ((scale_prune_self == nullptr) != (scale_prune_child == nullptr))
+        return fail(C3DGS_E_INVALID, "densify_classify: scale_prune_self and scale_prune_child go together");
+    launch_densify_classify(P, accum, denom, scale_clone, scale_split, scale_prune_self, scale_prune_child, opacity, max_grad,
+                            dense_extent, min_opacity, big_extent, code, (hipStream_t)stream);
+    C3DGS_STAGE("densify_classify", 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
+size_t c3dgs_rows_plan_workspace_bytes(int32_t P) { return rows_plan_workspace_bytes(P); }
+
+int c3dgs_rows_plan(int32_t P, const uint8_t* code, int32_t N, int64_t capacity, int32_t* src, uint8_t* kind, int32_t* draw_row,
+                    int32_t* totals, void* workspace, void* stream)
+{
+    if (P < 0) return fail(C3DGS_E_INVALID, "rows_plan: P must be >= 0");
+    if (N < 1 || N > kRowsMaxCopies) return fail(C3DGS_E_INVALID, "rows_plan: N must be between 1 and 250");
+    if (capacity < 0) return fail(C3DGS_E_INVALID, "rows_plan: capacity must be >= 0");
+    if ((int64_t)P * (2 + N) >= ((int64_t)1 << 31)) return fail(C3DGS_E_INVALID, "rows_plan: P * (2 + N) must fit 31 bits");
+    if (!totals) return fail(C3DGS_E_INVALID, "rows_plan: totals is required");
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0) { C3DGS_HIP_TRY(hipMemsetAsync(totals, 0, 4 * sizeof(int32_t), s)); return C3DGS_OK; }
+    if (!code || !workspace) return fail(C3DGS_E_INVALID, "rows_plan: NULL buffer");
+    if (src && (!kind || !draw_row)) return fail(C3DGS_E_INVALID, "rows_plan: src, kind and draw_row go together");
+    C3DGS_HIP_TRY(run_rows_plan(P, code, N, capacity, src, kind, draw_row, totals, workspace, s));
+    C3DGS_STAGE("rows_plan", 0, s);
+    return C3DGS_OK;
+}
+
+int c3dgs_rows_apply(int32_t P, int64_t P_new, const int32_t* src, const uint8_t* kind, const int32_t* draw_row, int32_t n_tensors,
+                     const c3dgs_rows_tensor* tensors, int32_t N, int64_t n_draws, const float* rotation_raw, const float* std,
+                     const float* z, int32_t log_scaling, int32_t half_xyz, void* stream)
+{
+    if (P < 0 || P_new < 0 || n_draws < 0) return fail(C3DGS_E_INVALID, "rows_apply: sizes must be >= 0");
+    if (N < 1 || N > kRowsMaxCopies) return fail(C3DGS_E_INVALID, "rows_apply: N must be between 1 and 250");
+    if (n_tensors < 0 || n_tensors > C3DGS_ROWS_MAX_TENSORS) return fail(C3DGS_E_INVALID, "rows_apply: between 0 and 16 tensors per call");
+    if (P_new >= ((int64_t)1 << 31)) return fail(C3DGS_E_INVALID, "rows_apply: P_new must fit 31 bits");
+    if (P_new == 0 || n_tensors == 0) return C3DGS_OK;
+    if (P == 0) return fail(C3DGS_E_INVALID, "rows_apply: P_new > 0 rows cannot come from P = 0");
+    if (!src || !kind || !draw_row || !tensors) return fail(C3DGS_E_INVALID, "rows_apply: NULL buffer");
+    for (int k = 0; k < n_tensors; k++) {
+        const c3dgs_rows_tensor& t = tensors[k];
+        if (t.row_floats < 1 || t.row_floats > 4096) return fail(C3DGS_E_INVALID, "rows_apply: row_floats must be between 1 and 4096");
+        if (!t.in_param || !t.out_param) return fail(C3DGS_E_INVALID, "rows_apply: NULL tensor pointer");
+        const int nm = (t.in_exp_avg != nullptr) + (t.in_exp_avg_sq != nullptr) + (t.out_exp_avg != nullptr) + (t.out_exp_avg_sq != nullptr);
+        if (nm != 0 && nm != 4) return fail(C3DGS_E_INVALID, "rows_apply: the four moment pointers go together");
+        if (t.role != C3DGS_ROLE_COPY && t.role != C3DGS_ROLE_XYZ && t.role != C3DGS_ROLE_SCALING)
+            return fail(C3DGS_E_INVALID, "rows_apply: unknown role");
+        if (t.role != C3DGS_ROLE_COPY && t.row_floats != 3) return fail(C3DGS_E_INVALID, "rows_apply: xyz / scaling rows have 3 floats");
+        if (t.role != C3DGS_ROLE_COPY && n_draws > 0 && (!std || !z || (t.role == C3DGS_ROLE_XYZ && !rotation_raw)))
+            return fail(C3DGS_E_INVALID, "rows_apply: children need rotation_raw, std and z");
+    }
+    launch_rows_apply(P, P_new, src, kind, draw_row, n_tensors, tensors, N, n_draws, rotation_raw, std, z, log_scaling, half_xyz, (hipStream_t)stream);
+    C3DGS_STAGE("rows_apply", 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
+int c3dgs_densify_stats(int32_t P, const float* grad, const uint8_t* filter, const int32_t* radii, float* accum, float* denom,
+                        float* max_radii, void* stream)
+{
+    if (P < 0) return fail(C3DGS_E_INVALID, "densify_stats: P must be >= 0");
+    if (P == 0) return C3DGS_OK;
+    if (!grad || !filter || !accum || !denom) return fail(C3DGS_E_INVALID, "densify_stats: NULL buffer");
+    if ((radii == nullptr) != (max_radii == nullptr)) return fail(C3DGS_E_INVALID, "densify_stats: radii and max_radii go together");
+    launch_densify_stats(P, grad, filter, radii, accum, denom, max_radii, (hipStream_t)stream);
+    C3DGS_STAGE("densify_stats", 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
 int c3dgs_extract_rot_scale(int32_t n, const float* cov6, float* rot, float* scale, void* stream)
 {
     if (n < 0) return fail(C3DGS_E_INVALID, "extract_rot_scale: n must be >= 0");

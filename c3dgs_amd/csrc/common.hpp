@@ -287,6 +287,18 @@ void launch_knn_query(int P, const void* workspace, float* out, hipStream_t s);
 // adam.hip
 void launch_adam(int n_tensors, const c3dgs_adam_tensor* tensors, double beta1, double beta2, double eps, hipStream_t s);
 void launch_abs_accumulate(int64_t n, const float* g, float* acc, hipStream_t s);
+// densify.hip (adaptive density control): classify -> plan (scan + emit) -> apply, and the per-iteration stats
+void launch_densify_classify(int P, const float* accum, const float* denom, const float* scale_clone, const float* scale_split,
+                             const float* scale_prune_self, const float* scale_prune_child, const float* opacity, float max_grad,
+                             float dense_extent, float min_opacity, float big_extent, uint8_t* code, hipStream_t s);
+size_t rows_plan_workspace_bytes(int P);
+hipError_t run_rows_plan(int P, const uint8_t* code, int N, long long capacity, int32_t* src, uint8_t* kind, int32_t* draw_row,
+                         int32_t* totals, void* workspace, hipStream_t s);
+void launch_rows_apply(int P, long long P_new, const int32_t* src, const uint8_t* kind, const int32_t* draw_row, int n_tensors,
+                       const c3dgs_rows_tensor* tensors, int N, long long n_draws, const float* rotation_raw, const float* std,
+                       const float* z, int log_scaling, int half_xyz, hipStream_t s);
+void launch_densify_stats(int P, const float* grad, const uint8_t* filter, const int32_t* radii, float* accum, float* denom,
+                          float* max_radii, hipStream_t s);
 // loss.hip
 void launch_l1_ssim_value(const double* sums, double l1_scale, double ssim_scale, double constant, float* out, hipStream_t s);
 void launch_l1_ssim_forward(int C, int H, int W, const float* img, const float* gt, float* Dmu, float* Ds1, float* Ds12,

@@ -1,13 +1,13 @@
 """The QAT getters and render glue of the reference's GaussianModel, fused on the device.
 
-Mirrors, for the render path only, scene/gaussian_model.py:
+Mirrors of scene/gaussian_model.py:
     setup_functions / activations                 :54-77
     the FakeQuantize(dtype=qint8) module set      :109-134
     get_scaling ... get_opacity                   :213-267
     GaussianModel.render                          :766-886
     FakeQuantizationHalf                          :1405-1414
     save_ply / load / load_ply                    :324-503  (PLY IO in ply.py; distCUDA2 scales in knn.py)
-Densification of the reference class is outside the hot path and not mirrored.
+    adaptive density control (non-indexed)        :288-290, :1061-1403  (csrc/densify.hip)
 
 The reference evaluates every getter with torch ops and seven torch.ao FakeQuantize modules: about a hundred small
 launches and twenty host syncs per view (aminmax + float(scale) / int(zero_point) per module, one nonzero per
@@ -741,6 +741,261 @@ class GaussianModel:
                 lr = self.xyz_scheduler_args(iteration)
                 param_group["lr"] = lr
                 return lr
+
+    # ---- adaptive density control (gaussian_model.py:288-290, :1061-1403), non-indexed models; csrc/densify.hip
+    _GROUPS = (("xyz", "_xyz", _lib.ROLE_XYZ), ("f_dc", "_features_dc", 0), ("f_rest", "_features_rest", 0),
+               ("opacity", "_opacity", 0), ("scaling", "_scaling", _lib.ROLE_SCALING), ("rotation", "_rotation", 0),
+               ("scaling_factor", "_scaling_factor", 0))
+
+    def oneupSHdegree(self):
+        if self.active_sh_degree < self.max_sh_degree:
+            self.active_sh_degree += 1
+
+    def _dense_only(self, what):
+        if self._feature_indices is not None or self._gaussian_indices is not None:
+            raise NotImplementedError(f"c3dgs_amd: {what} supports non-indexed models only (the reference's index remapping in "
+                                      "prune_points is not mirrored)")
+
+    def _density_stats(self):
+        """xyz_gradient_accum / denom / max_radii2D of the current length (training_setup and load_ply create them; a model
+        filled with set_tensors gets them here)."""
+        n = self._xyz.shape[0]
+        for name, shape in (("xyz_gradient_accum", (n, 1)), ("denom", (n, 1)), ("max_radii2D", (n,))):
+            t = getattr(self, name, None)
+            if t is None or tuple(t.shape) != shape or t.device != self._xyz.device:
+                setattr(self, name, torch.zeros(shape, device=self.device))
+        return self.xyz_gradient_accum, self.denom, self.max_radii2D
+
+    def add_densification_stats(self, viewspace_point_tensor, update_filter, radii=None):
+        """:1399-1402, and with `radii` the max_radii2D update of train.py:105, in one launch that neither allocates nor
+        synchronises. `update_filter`: bool [P]; `radii`: int32 [P] (per Gaussian, like the filter)."""
+        self._dense_only("add_densification_stats")
+        accum, denom, max_radii = self._density_stats()
+        grad = viewspace_point_tensor.grad
+        P = self._xyz.shape[0]
+        if grad is None or tuple(grad.shape) != (P, 3) or update_filter.shape[0] != P:
+            raise RuntimeError("add_densification_stats: viewspace gradient [P,3] and filter [P] of the model's length are needed")
+        grad = _need_gpu(grad, "viewspace gradient")
+        flt = update_filter.contiguous()
+        if flt.dtype == torch.bool:
+            flt = flt.view(torch.uint8)
+        elif flt.dtype != torch.uint8:
+            raise RuntimeError("update_filter must be a bool (or uint8) tensor")
+        if radii is not None:
+            if radii.dtype != torch.int32 or radii.shape[0] != P:
+                raise RuntimeError("radii must be the rasterizer's int32 [P] tensor")
+            radii = radii.contiguous()
+        _lib.check(_lib.lib().c3dgs_densify_stats(P, grad.data_ptr(), flt.data_ptr(), _ptr(radii), accum.data_ptr(),
+                                                  denom.data_ptr(), max_radii.data_ptr() if radii is not None else None,
+                                                  _stream(self.device)))
+
+    def _activated_scaling(self, raw, factor):
+        """get_scaling (:214-222) on explicit raw rows: one observer access per module, as the property."""
+        if self.use_factor_scaling:
+            scaling_n = self._get(scaling=raw)[4]
+            return self._get(scaling_factor=factor)[3] * scaling_n
+        return self.scaling_qa(self.scaling_activation(raw))
+
+    def _read_totals(self, totals):
+        """The one device->host read of a rebuild: four int32 through pinned memory and an event."""
+        host = getattr(self, "_totals_host", None)
+        if host is None:
+            host = self._totals_host = torch.empty(4, dtype=torch.int32).pin_memory()
+        host.copy_(totals, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        ev.synchronize()
+        return host.tolist()
+
+    def plan_rows(self, code, N=2):
+        """code uint8[P] (bits: include/c3dgs_hip.h C3DGS_ROW_*) -> (src int32[P_new], kind uint8[P_new], draw_row int32[P_new],
+        (kept, clones, S, parents with surviving children)). One host read."""
+        lib = _lib.lib()
+        dev = self.device
+        P = int(code.shape[0])
+        s = _stream(dev)
+        ws = torch.empty(max(int(lib.c3dgs_rows_plan_workspace_bytes(P)), 256), dtype=torch.uint8, device=dev)
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        _lib.check(lib.c3dgs_rows_plan(P, _ptr(code), N, 0, None, None, None, totals.data_ptr(), ws.data_ptr(), s))
+        K, Cn, S, CK = self._read_totals(totals)
+        P_new = K + Cn + N * CK
+        src = torch.empty(P_new, dtype=torch.int32, device=dev)
+        kind = torch.empty(P_new, dtype=torch.uint8, device=dev)
+        draw_row = torch.empty(P_new, dtype=torch.int32, device=dev)
+        if P_new > 0:
+            _lib.check(lib.c3dgs_rows_plan(P, _ptr(code), N, P_new, src.data_ptr(), kind.data_ptr(), draw_row.data_ptr(),
+                                           totals.data_ptr(), ws.data_ptr(), s))
+        return src, kind, draw_row, (K, Cn, S, CK)
+
+    def _rebuild(self, code, N=2, std=None, draws=None, carry_stats=False):
+        """plan -> one host read -> allocate every new tensor once -> ONE apply launch -> install parameters and optimizer
+        state (cat_tensors_to_optimizer / _prune_optimizer, :1081-1099, :1161-1185: `step` kept, moments of surviving originals
+        copied, zero for new rows). Returns (src, kind, draw_row, totals)."""
+        lib = _lib.lib()
+        dev = self.device
+        P = self._xyz.shape[0]
+        accum, denom, max_radii = self._density_stats()
+        src, kind, draw_row, tot = self.plan_rows(code, N)
+        K, Cn, S, CK = tot
+        P_new = K + Cn + N * CK
+        if S > 0 and std is None:
+            raise RuntimeError("split rows need their activated scales")
+        if draws is None:
+            draws = torch.randn((N * S, 3), device=dev)     # torch.normal(mean, std) is randn * std + mean (:1242)
+        if tuple(draws.shape) != (N * S, 3):
+            raise RuntimeError(f"draws must be [N*S, 3] = [{N * S}, 3] unit normals, got {tuple(draws.shape)}")
+        draws = _need_gpu(draws, "draws")
+        std = None if std is None else _need_gpu(std, "std")
+        rotation = _need_gpu(self._rotation.detach(), "rotation")
+        table, new, moments = [], {}, {}
+        for name, attr, role in self._GROUPS:
+            old = getattr(self, attr)
+            if old is None:
+                continue
+            old_c = _need_gpu(old.detach(), attr)
+            out = torch.empty((P_new,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
+            st = self.optimizer.state.get(old) if self.optimizer is not None else None
+            t = _lib.RowsTensor()
+            t.in_param, t.out_param = old_c.data_ptr(), out.data_ptr()
+            t.row_floats, t.role = int(torch.Size(old.shape[1:]).numel()), role
+            keep = [old_c]
+            if st is not None and "exp_avg" in st:
+                m, v = st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous()
+                om, ov = torch.empty_like(out), torch.empty_like(out)
+                t.in_exp_avg, t.in_exp_avg_sq, t.out_exp_avg, t.out_exp_avg_sq = m.data_ptr(), v.data_ptr(), om.data_ptr(), ov.data_ptr()
+                moments[attr] = (om, ov)
+                keep += [m, v]
+            table.append((t, keep))
+            new[attr] = out
+        stats_new = None
+        if carry_stats:                                       # prune_points gathers the accumulators (:1150-1152)
+            stats_new = []
+            for old in (accum, denom, max_radii):
+                out = torch.empty((P_new,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
+                t = _lib.RowsTensor()
+                t.in_param, t.out_param, t.row_floats, t.role = old.data_ptr(), out.data_ptr(), 1, 0
+                table.append((t, [old]))
+                stats_new.append(out)
+        if P_new > 0 and P > 0:
+            arr = (_lib.RowsTensor * len(table))(*[t for t, _ in table])
+            _lib.check(lib.c3dgs_rows_apply(P, P_new, src.data_ptr(), kind.data_ptr(), draw_row.data_ptr(), len(table), arr, N,
+                                            N * S, rotation.data_ptr(), _ptr(std),
+                                            draws.data_ptr() if draws.numel() else None,
+                                            int(not self.use_factor_scaling), int(self.quantization), _stream(dev)))
+        for name, attr, _ in self._GROUPS:
+            if attr not in new:
+                continue
+            old, param = getattr(self, attr), new[attr].requires_grad_(True)
+            if self.optimizer is not None:
+                for group in self.optimizer.param_groups:
+                    if group.get("name") == name:
+                        st = self.optimizer.state.pop(old, None)
+                        group["params"][0] = param
+                        if st is not None:
+                            if attr in moments:
+                                st["exp_avg"], st["exp_avg_sq"] = moments[attr]
+                            self.optimizer.state[param] = st
+            setattr(self, attr, param)
+        if stats_new is not None:
+            self.xyz_gradient_accum, self.denom, self.max_radii2D = stats_new
+        else:                                                 # densification_postfix, :1209-1211
+            self.xyz_gradient_accum = torch.zeros((P_new, 1), device=dev)
+            self.denom = torch.zeros((P_new, 1), device=dev)
+            self.max_radii2D = torch.zeros((P_new,), device=dev)
+        return src, kind, draw_row, tot
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, draws=None, N=2):
+        """:1336-1349 fused: the reference's clone stage, split stage and final prune decided per row in one classification
+        pass, the scene rebuilt in one pass. Every decision is taken on the values the staged sequence would have seen and the
+        three observers (scaling, scaling_factor, opacity) are left as it leaves them (DESIGN.md "Density control").
+        `draws`: [N*S,3] unit normals for the S split parents (default torch.randn). Returns the plan (src, kind, draw_row,
+        (kept, clones, S, parents with surviving children))."""
+        self._dense_only("densify_and_prune")
+        lib = _lib.lib()
+        dev = self.device
+        with torch.no_grad():
+            P = self._xyz.shape[0]
+            accum, denom, _ = self._density_stats()
+            raw_s = self._scaling.detach()
+            raw_f = self._scaling_factor.detach() if self._scaling_factor is not None else None
+            dense_extent, big_extent = self.percent_dense * extent, 0.1 * extent
+            s1 = self._activated_scaling(raw_s, raw_f).contiguous()             # get_scaling of the clone stage, :1284
+            s2 = self._activated_scaling(raw_s, raw_f).contiguous()             # get_scaling of the split stage, :1225; children's std
+            opacity = self._get(opacity=self._opacity.detach())[2].contiguous()  # get_opacity on the post-split scene, :1344
+            code = torch.empty(P, dtype=torch.uint8, device=dev)
+            sp_self = sp_child = None
+
+            def classify(min_op):
+                _lib.check(lib.c3dgs_densify_classify(P, accum.data_ptr(), denom.data_ptr(), s1.data_ptr(), s2.data_ptr(),
+                                                      _ptr(sp_self), _ptr(sp_child), opacity.data_ptr(), max_grad, dense_extent,
+                                                      min_op, big_extent, code.data_ptr(), _stream(dev)))
+            if max_screen_size and P > 0:
+                # get_scaling on the post-split scene (:1347): its value set is every non-parent original, every clone (raw rows)
+                # and the children (std / (0.8 N)); a [2P,3] batch holds exactly that set with duplicates, which leaves the
+                # min / max the observers see unchanged
+                classify(float("-inf"))                                           # nothing pruned: the raw clone and split bits
+                split = (code & _lib.ROW_SPLIT).bool()[:, None]
+                pure_parent = split & ((code & _lib.ROW_CLONE) == 0)[:, None]
+                child_raw = s2 / torch.full((1,), 0.8 * N, device=dev)
+                if not self.use_factor_scaling:
+                    child_raw = torch.log(child_raw)
+                batch = torch.empty(2 * P, 3, device=dev)
+                torch.where(pure_parent, child_raw, raw_s, out=batch[:P])
+                torch.where(split, child_raw, raw_s, out=batch[P:])
+                factors = raw_f.expand(2, P, 1).reshape(2 * P, 1) if raw_f is not None else None
+                s3 = self._activated_scaling(batch, factors).contiguous()
+                sp_self, sp_child = s3[:P], s3[P:]
+            if P > 0:
+                classify(min_opacity)
+            return self._rebuild(code, N, std=s2, draws=draws)
+
+    def densify_and_clone(self, grads, grad_threshold, scene_extent):
+        """:1279-1330 (the gradient-mask form). Row order: every original, then the clones."""
+        self._dense_only("densify_and_clone")
+        with torch.no_grad():
+            mask = torch.norm(grads, dim=-1) >= grad_threshold
+            mask &= self.get_scaling.detach().amax(dim=1) <= self.percent_dense * scene_extent
+            code = mask.to(torch.uint8) * _lib.ROW_CLONE + _lib.ROW_KEEP
+            return self._rebuild(code.contiguous())
+
+    def densify_and_split(self, grads, grad_threshold, scene_extent, N=2, draws=None):
+        """:1213-1277. Row order: the originals that are not selected, then child copy 0 .. N-1 of the selected ones."""
+        self._dense_only("densify_and_split")
+        with torch.no_grad():
+            P = self._xyz.shape[0]
+            scaling = self.get_scaling.detach().contiguous()
+            padded = torch.zeros(P, device=self.device)
+            padded[:grads.shape[0]] = grads.squeeze()
+            mask = (padded >= grad_threshold) & (scaling.amax(dim=1) > self.percent_dense * scene_extent)
+            code = torch.where(mask, _lib.ROW_SPLIT | _lib.ROW_CHILD_KEPT, _lib.ROW_KEEP).to(torch.uint8)
+            return self._rebuild(code.contiguous(), N, std=scaling, draws=draws)
+
+    def prune_points(self, mask):
+        """:1101-1158 for a non-indexed model: rows with mask are removed; the accumulators are gathered like the parameters."""
+        self._dense_only("prune_points")
+        with torch.no_grad():
+            code = (~mask.to(self.device).bool()).to(torch.uint8).contiguous()
+            return self._rebuild(code, carry_stats=True)
+
+    def reset_opacity(self):
+        """:1391-1397 with replace_tensor_to_optimizer (:1061-1079): opacity <- inverse_sigmoid(min(get_opacity, 0.01)), its
+        moments zeroed, `step` kept."""
+        with torch.no_grad():
+            # the reference writes torch.min(self.get_opacity, torch.ones_like(self.get_opacity) * 0.01): two accesses, so the
+            # opacity observer moves twice; the value is the first one's
+            m = torch.min(self.get_opacity.detach(), torch.ones_like(self.get_opacity) * 0.01)
+            new = torch.log(m / (1 - m)).contiguous().requires_grad_(True)
+        old = self._opacity
+        if self.optimizer is not None:
+            for group in self.optimizer.param_groups:
+                if group.get("name") == "opacity":
+                    st = self.optimizer.state.pop(old, None)
+                    group["params"][0] = new
+                    if st is not None:
+                        if "exp_avg" in st:
+                            st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(new), torch.zeros_like(new)
+                        self.optimizer.state[new] = st
+        self._opacity = new
 
     # ---- render (gaussian_model.py:766-886)
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, clamp_color=True,

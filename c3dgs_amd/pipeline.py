@@ -1,5 +1,6 @@
 """The drivers either side of the hot path: the QAT fine-tuning loop and the compression run.
 
+    train(...)               <- train.py:15-173          (optimise a scene from a point cloud, with adaptive density control)
     finetune(...)            <- finetune.py:10-66        (hot loop C of SURVEY.md section 3)
     run_vq(...)              <- compress.py:202-303      (sensitivity -> prune + VQ -> fine-tune -> npz [-> evaluation])
     OptimizationParams / CompressionParams               <- arguments/__init__.py:85-136 (defaults only, no argparse)
@@ -133,6 +134,84 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None):
             gaussians.optimizer.step()
             gaussians.optimizer.zero_grad(set_to_none=True)
     return ema_loss_for_log
+
+
+def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, degree_up_iter=1000):
+    """train.py:15-173 without its disabled compression-statistics branch: optimise a non-indexed model (usually
+    GaussianModel.load_ply of a point cloud) with adaptive density control.
+
+    The schedule is the reference's, counted in epochs: epoch_count = iterations // len(cameras) and every `*_iter` /
+    `*_interval` of `opt` is converted with calc_epoch(i) = max(1, i * epoch_count // iterations); one epoch visits
+    cameras[::camera_stride] in order (the reference's stride is 10 while its epoch count is over all cameras), SH degree up
+    every calc_epoch(degree_up_iter) epochs. Per view: learning-rate update, render of the precomputed covariance exactly as
+    train.py:62-67 (the covariance is a detached leaf: in this loop scale and rotation move through densification only, as
+    in the reference), fused L1 + SSIM loss, Adam step, densification statistics while epoch < densify_until_epoch. After an
+    epoch: densify_and_prune (screen-size threshold 20 once past the opacity-reset interval) and reset_opacity on the
+    reference's conditions (train.py:160-173).
+
+    `scene`: as for finetune(), plus `cameras_extent` (or pass `extent`). The model's `spatial_lr_scale` is the caller's to set
+    (the reference's scene loader sets it to the camera extent). `log(epoch, info)` is called after every epoch with
+    {"iteration", "ema_loss", "N", "densified": None | (rows before, (kept, clones, S, parents with children)), "reset_opacity"}.
+    Returns the number of iterations run."""
+    gaussians = scene.gaussians if hasattr(scene, "gaussians") else dataset.gaussians
+    cameras = _train_cameras(scene)
+    if extent is None:
+        extent = scene.cameras_extent
+    gaussians.training_setup(opt)
+    gaussians.update_learning_rate(0)
+    dev = gaussians.device
+    bg = torch.rand(3, device=dev) if opt.random_background else torch.tensor([0, 0, 0], dtype=torch.float32, device=dev)
+    ema_loss_for_log = 0.0
+    epoch_count = opt.iterations // len(cameras)
+    calc_epoch = lambda i: max(1, i * epoch_count // opt.iterations)        # noqa: E731
+    densify_until_epoch = calc_epoch(opt.densify_until_iter)
+    densify_from_epoch = calc_epoch(opt.densify_from_iter)
+    densification_interval = calc_epoch(opt.densification_interval)
+    opacity_reset_interval = calc_epoch(opt.opacity_reset_interval)
+    degree_up = calc_epoch(degree_up_iter)
+
+    iteration = 0
+    for epoch in range(epoch_count):
+        pending = []
+        for viewpoint_cam in cameras[::camera_stride]:
+            gaussians.update_learning_rate(iteration)
+            cov3d_scaled = gaussians.get_covariance().detach()
+            scaling_factor = gaussians.get_scaling_factor
+            coeff = scaling_factor.detach().square() if torch.is_tensor(scaling_factor) else 1.0
+            cov3d = (cov3d_scaled / coeff).requires_grad_(True)
+            # every row goes to the rasterizer (it culls them itself): radii and the screen-space gradient are then indexed
+            # by Gaussian, which is what the reference scatters them back to (train.py:103-105)
+            render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False)
+            image, viewspace_point_tensor, radii = render_pkg["render"], render_pkg["viewspace_points"], render_pkg["radii"]
+            gt_image = viewpoint_cam.original_image.to(image.device)
+            loss = _loss.l1_ssim_loss(image, gt_image, opt.lambda_dssim)
+            loss.backward()
+            pending.append(loss.detach())
+            gaussians.optimizer.step()
+            gaussians.optimizer.zero_grad(set_to_none=True)
+            if epoch < densify_until_epoch:
+                with torch.no_grad():
+                    gaussians.add_densification_stats(viewspace_point_tensor, render_pkg["visibility_filter"], radii)
+            iteration += 1
+        for v in torch.stack(pending).tolist():                   # one host read per epoch
+            ema_loss_for_log = 0.4 * v + 0.6 * ema_loss_for_log
+        info = {"iteration": iteration, "ema_loss": ema_loss_for_log, "densified": None, "reset_opacity": False}
+        with torch.no_grad():
+            if epoch < densify_until_epoch:
+                if epoch > densify_from_epoch and epoch % densification_interval == 0:
+                    size_threshold = 20 if epoch > opacity_reset_interval else None
+                    rows = gaussians._xyz.shape[0]
+                    plan = gaussians.densify_and_prune(opt.densify_grad_threshold, 0.005, extent, size_threshold)
+                    info["densified"] = (rows, plan[3])
+                if epoch > 0 and epoch % opacity_reset_interval == 0:
+                    gaussians.reset_opacity()
+                    info["reset_opacity"] = True
+        if epoch % degree_up == 0:
+            gaussians.oneupSHdegree()
+        info["N"] = gaussians._xyz.shape[0]
+        if log is not None:
+            log(epoch, info)
+    return iteration
 
 
 def run_vq(gaussians, scene, optim_params, pipeline_params, comp_params, dataset=None, group=None, silent=True,

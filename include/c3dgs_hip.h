@@ -284,6 +284,74 @@ typedef struct c3dgs_adam_tensor {
 } c3dgs_adam_tensor;
 int c3dgs_adam_step(int32_t n_tensors, const c3dgs_adam_tensor* tensors /*host*/, double beta1, double beta2, double eps, void* stream);
 
+/* ---- adaptive density control (scene/gaussian_model.py:1187-1403: densify_and_clone / densify_and_split / prune_points /
+ * densify_and_prune / add_densification_stats), non-indexed models. The reference rebuilds the scene in four passes (clone
+ * cat, split cat, the split's prune, the final prune); here: classify (one code byte per row) -> plan (one scan, the source
+ * map of the new scene in the reference's row order, four totals) -> apply (ONE launch writes every row of every parameter
+ * tensor and both Adam moments once). Added without an ABI version bump: new entry points only.
+ *
+ * code bits */
+#define C3DGS_ROW_KEEP 1u        /* the original row survives                                              */
+#define C3DGS_ROW_CLONE 2u       /* its clone survives                                                     */
+#define C3DGS_ROW_SPLIT 4u       /* selected as a split parent (counts towards S whether or not its children survive) */
+#define C3DGS_ROW_CHILD_KEPT 8u  /* its N children survive (implies C3DGS_ROW_SPLIT)                        */
+/* row kinds of the plan: 0 original, 1 clone, 2 + k child copy k */
+#define C3DGS_KIND_ORIGINAL 0
+#define C3DGS_KIND_CLONE 1
+#define C3DGS_KIND_CHILD 2
+/* classify: one thread per row, on the ACTIVATED quantities the reference's masks are made of (the caller runs the getters
+ * in the reference's order, see DESIGN.md "Density control"):
+ *   g = accum / denom, NaN -> 0 (0/0; x/0 = inf stays and selects)                                   :1337-1338
+ *   clone  = sqrt(g*g) >= max_grad && max(scale_clone) <= dense_extent                               :1282-1284
+ *   split  = g >= max_grad && max(scale_split) > dense_extent                                        :1232-1236
+ *   pruned = opacity < min_opacity || max(scale_prune_*) > big_extent   (second term only when both scale_prune_self and
+ *            scale_prune_child are given: _self for the original and its clone, _child for the N children)   :1344-1349
+ *   code   = (!split && !pruned_self) | (clone && !pruned_self) << 1 | split << 2 | (split && !pruned_child) << 3
+ * The reference's max_radii2D test is dead inside densify_and_prune (the postfix has zeroed it) and is not mirrored.
+ * max_grad must be > 0: with max_grad <= 0 the reference's zero-padded gradients would make every clone a split parent
+ * too, a corner the training loop never reaches; it is rejected with C3DGS_E_INVALID. Thresholds are the Python doubles
+ * rounded to float, as torch's tensor-vs-scalar comparison rounds them. */
+int c3dgs_densify_classify(int32_t P, const float* accum /*[P]*/, const float* denom /*[P]*/, const float* scale_clone /*[P,3]*/,
+                           const float* scale_split /*[P,3]*/, const float* scale_prune_self /*[P,3] or NULL*/,
+                           const float* scale_prune_child /*[P,3] or NULL*/, const float* opacity /*[P]*/, float max_grad,
+                           float dense_extent, float min_opacity, float big_extent, uint8_t* code /*[P]*/, void* stream);
+/* plan: exclusive scans of the four per-row counts and the source map in the reference's row order: surviving originals
+ * in source order, surviving clones in source order, then child copy 0 of every parent whose children survive in source
+ * order, copy 1, ... copy N-1. totals (device int32[4]) = {kept, clones, S, parents whose children survive}; the new
+ * scene has P_new = kept + clones + N * totals[3] rows. With src == NULL only the totals are computed (the caller reads
+ * them, allocates and calls again); otherwise rows j < capacity of src (source row), kind and draw_row (for a child:
+ * k * S + rank of its parent among ALL S selected parents = the row of the [N*S,3] draws it consumes; -1 otherwise) are
+ * written and rows beyond capacity are not touched. workspace >= c3dgs_rows_plan_workspace_bytes(P). */
+size_t c3dgs_rows_plan_workspace_bytes(int32_t P);
+int c3dgs_rows_plan(int32_t P, const uint8_t* code /*[P]*/, int32_t N, int64_t capacity, int32_t* src, uint8_t* kind,
+                    int32_t* draw_row, int32_t* totals /*device [4]*/, void* workspace, void* stream);
+/* apply: out[j] = in[src[j]] for every tensor of the table; moments copied for kind == original and zero otherwise
+ * (cat_tensors_to_optimizer, :1169-1172); NULL moment pointers = no optimizer state. role 1 (xyz) and 2 (scaling) rewrite
+ * child rows: xyz = R(rotation_raw[src]) (z[draw_row] * std[src]) + get_xyz[src] with R = build_rotation of the raw quaternion
+ * (utils/general_utils.py:84-107) and get_xyz the parent position, rounded through fp16 when half_xyz (the reference adds
+ * get_xyz, which is xyz_qa(_xyz), :1245), and scaling = std[src] / (0.8 N), or its log when log_scaling (:1247). */
+#define C3DGS_ROWS_MAX_TENSORS 16
+enum { C3DGS_ROLE_COPY = 0, C3DGS_ROLE_XYZ = 1, C3DGS_ROLE_SCALING = 2 };
+typedef struct c3dgs_rows_tensor {
+    const float* in_param;
+    const float* in_exp_avg;     /* NULL together with the other three moment pointers */
+    const float* in_exp_avg_sq;
+    float* out_param;
+    float* out_exp_avg;
+    float* out_exp_avg_sq;
+    int32_t row_floats;          /* 1 .. 4096 */
+    int32_t role;
+} c3dgs_rows_tensor;
+int c3dgs_rows_apply(int32_t P, int64_t P_new, const int32_t* src /*[P_new]*/, const uint8_t* kind /*[P_new]*/,
+                     const int32_t* draw_row /*[P_new]*/, int32_t n_tensors, const c3dgs_rows_tensor* tensors /*host*/,
+                     int32_t N, int64_t n_draws, const float* rotation_raw /*[P,4]*/, const float* std /*[P,3]*/,
+                     const float* z /*[n_draws,3]*/, int32_t log_scaling, int32_t half_xyz, void* stream);
+/* stats: the per-iteration bookkeeping (train.py:101-106, :1399-1402) in one launch, no allocation, no synchronisation:
+ * for rows with filter: accum += sqrt(gx*gx + gy*gy) of grad[p, 0:2] (row stride 3), denom += 1 and, with radii,
+ * max_radii = max(max_radii, radii). */
+int c3dgs_densify_stats(int32_t P, const float* grad /*[P,3]*/, const uint8_t* filter /*[P]*/, const int32_t* radii /*[P] or NULL*/,
+                        float* accum /*[P]*/, float* denom /*[P]*/, float* max_radii /*[P] or NULL*/, void* stream);
+
 /* ---- sensitivity pass (compress.py:110-113): acc[i] += |g[i]| for n floats, one launch */
 int c3dgs_abs_accumulate(int64_t n, const float* g, float* acc, void* stream);
 

@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""Optimises the synthetic point-cloud scene of tests/train_scene.py with c3dgs_amd.pipeline.train, once with adaptive density
+control and once with densify_until_iter = 0, and prints one JSON line: Gaussian counts, mean PSNR over the training views
+before / after, and seconds per phase.
+
+    python tools/run_train.py [--iterations 400] [--out profiles/r06_train_synth.json]"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tests import train_scene  # noqa: E402
+
+
+def run(iterations, densify):
+    from c3dgs_amd import pipeline
+    from c3dgs_amd.model import PipelineParams
+    with tempfile.TemporaryDirectory() as tmp:
+        t0 = time.perf_counter()
+        student, cams, extent = train_scene.make(tmp)
+        torch.cuda.synchronize()
+        t_setup = time.perf_counter() - t0
+    rows0, before = student._xyz.shape[0], train_scene.mean_psnr(student, cams)
+    events = []
+
+    class Scene:
+        gaussians = student
+        cameras_extent = extent
+
+        def getTrainCameras(self):
+            return cams
+
+    torch.manual_seed(0)
+    t0 = time.perf_counter()
+    n = pipeline.train(Scene(), None, train_scene.schedule(iterations, densify), PipelineParams(), camera_stride=1, degree_up_iter=80,
+                       log=lambda epoch, info: events.append((epoch, info)))
+    torch.cuda.synchronize()
+    t_train = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    after = train_scene.mean_psnr(student, cams)
+    t_eval = time.perf_counter() - t0
+    return {"iterations": n, "gaussians_before": rows0, "gaussians_after": student._xyz.shape[0], "psnr_before": before,
+            "psnr_after": after, "densifications": [[e, i["densified"][0], list(i["densified"][1])] for e, i in events if i["densified"]],
+            "opacity_resets": [e for e, i in events if i["reset_opacity"]],
+            "seconds": {"setup": t_setup, "train": t_train, "eval": t_eval}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iterations", type=int, default=400)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("run_train.py needs the GPU; there is no CPU path")
+    out = {"scene": "tests/train_scene.py: 4000-Gaussian synth-v1 teacher, 8 views 160x112, student = every 8th position as a point cloud",
+           "with_density_control": run(args.iterations, True), "densify_until_iter_0": run(args.iterations, False)}
+    print(json.dumps(out))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
