@@ -1,5 +1,19 @@
 """-m gpu: fused L1 + SSIM loss (row N3) against the oracle and the committed reference-generated golden vectors.
-Tolerances: scalar values 2e-6 absolute (fp32 separable window vs float64 direct sums), gradient rel-inf 1e-4."""
+Tolerances: scalar values 2e-6 absolute (fp32 separable window vs float64 direct sums), gradient rel-inf 1e-4.
+
+Content classes (flat regions, img == gt, values outside [0, 1]): there sigma = E[x^2] - mu^2 cancels in fp32 and the
+reference's own fp32 evaluation leaves those bars, so the kernel is held to max(project bar, 4 x the reference's own fp32
+deviation d_ref from the float64 truth), both measured at run time (test_loss_content_classes_...). Observed on an MI355X,
+kernel deviation / d_ref (value | gradient, absolute inf-norm), 3 x 131 x 203 and 3 x 1080 x 1920:
+    a  flat gt, noise rectangle in img      0.74 | 0.44      0.69 | 0.44
+    b  flat background, different rects     0.72 | 0.36      0.68 | 0.37
+    c  near-constant pair 0.7 +- 1e-3       0.05 | 0.41      0.01 | 0.36
+    d  img == gt, noise                     d_ref = 0, kernel 4e-10 (bar 2e-6) | 0.94      same | 1.02
+    d  img == gt, constant 0.7              d_ref = 0, kernel 7e-10 / 8e-11 | 2.58         same | 1.24
+    e  zeros vs zeros                       0 | 0 (every deviation exactly 0)
+    f  img in [-0.5, 1.5]                   1.00 | 0.43      1.00 | 0.40
+The separable FMA kernel is never further from the truth than 2.6 x the 121-tap fp32 sum, usually closer (the FMA keeps the
+products unrounded). Nothing in csrc/loss.hip had to change."""
 import os
 
 import numpy as np
@@ -53,3 +67,165 @@ def test_ssim_is_differentiable_and_errors(hip):
         L.l1_ssim_loss(x.cpu(), gt.cpu())
     with pytest.raises(RuntimeError, match="same shape"):
         L.l1_ssim_loss(x, gt[:, :20])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Shapes around the 11 x 11 window and the 32 x 22 tile, C != 3, and the content real training produces (flat regions,
+# img == gt, values outside [0, 1]) where sigma = E[x^2] - mu^2 cancels in fp32.
+from tests import loss_ref          # noqa: E402
+
+EDGE_SHAPES = [(3, 1, 1), (3, 5, 7), (3, 11, 11), (3, 22, 32), (3, 23, 33), (3, 21, 31), (3, 1, 500), (3, 500, 1), (1, 40, 40),
+               (4, 40, 40), (3, 22 * 3, 32 * 3)]
+
+
+def _noise_pair(shape, seed):
+    g = torch.Generator().manual_seed(seed)
+    gt = torch.rand(*shape, generator=g)
+    return (gt + 0.1 * torch.randn(*shape, generator=g)).clamp(0, 1), gt
+
+
+def _truth(orc, img, gt, kind):
+    """float64 direct sums: (value, gradient) of l1_ssim_loss(0.2) / ssim / l1_loss."""
+    lam = {"loss": 0.2, "ssim": 1.0, "l1": 0.0}[kind]
+    lo, l1, ss, gr = orc.l1_ssim(img.numpy(), gt.numpy(), lam)
+    gr = gr.astype(np.float64)
+    return {"loss": (lo, gr), "ssim": (ss, -gr), "l1": (l1, gr)}[kind]                 # lam = 1: loss = 1 - ssim
+
+
+def _kernel(L, img, gt, kind, upstream=1.0):
+    x = img.cuda().requires_grad_()
+    fn = {"loss": lambda a, b: L.l1_ssim_loss(a, b, 0.2), "ssim": L.ssim, "l1": L.l1_loss}[kind]
+    val = fn(x, gt.cuda())
+    (val * upstream).backward()
+    return float(val.item()), x.grad.cpu().numpy().astype(np.float64) / upstream
+
+
+@pytest.mark.parametrize("kind", ["loss", "ssim", "l1"])
+@pytest.mark.parametrize("shape", EDGE_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_loss_shapes_around_window_and_tile(hip, orc, shape, kind):
+    """Images smaller than the window (zero padding on every side of every pixel), smaller than / equal to / one past the
+    32 x 22 tile, one-pixel rows and columns, one and four channels, an exact 3 x 3 grid of tiles."""
+    from c3dgs_amd import loss as L
+    img, gt = _noise_pair(shape, seed=shape[1] * 1000 + shape[2])
+    want, want_grad = _truth(orc, img, gt, kind)
+    val, grad = _kernel(L, img, gt, kind)
+    print(f"loss {kind} {shape}: value dev {abs(val - want):.2e}, grad rel-inf {np.abs(grad - want_grad).max() / np.abs(want_grad).max():.2e}")
+    assert abs(val - want) < (1e-6 if kind == "l1" else 2e-6)
+    assert np.abs(want_grad).max() > 0
+    assert np.abs(grad - want_grad).max() / np.abs(want_grad).max() < 1e-4
+
+
+@pytest.mark.parametrize("kind", ["loss", "ssim", "l1"])
+def test_loss_non_unit_upstream_gradient_on_a_ragged_shape(hip, orc, kind):
+    from c3dgs_amd import loss as L
+    img, gt = _noise_pair((3, 23, 33), seed=5)
+    want, want_grad = _truth(orc, img, gt, kind)
+    val, grad = _kernel(L, img, gt, kind, upstream=-2.5)
+    assert abs(val - want) < (1e-6 if kind == "l1" else 2e-6)
+    assert np.abs(want_grad).max() > 0 and np.abs(grad - want_grad).max() / np.abs(want_grad).max() < 1e-4
+
+
+def _content(name, shape, seed):
+    """-> (img, gt) of one content class."""
+    C, H, W = shape
+    g = torch.Generator().manual_seed(seed)
+    rect = lambda t, y0, y1, x0, x1: t[:, H * y0 // 100:H * y1 // 100, W * x0 // 100:W * x1 // 100]
+    if name == "a_flat_gt_noise_rect_in_img":
+        gt = torch.ones(shape)
+        img = gt.clone()
+        r = rect(img, 30, 60, 25, 60)
+        r.copy_(torch.rand(r.shape, generator=g))
+    elif name == "b_flat_background_different_rects":
+        gt, img = torch.ones(shape), torch.ones(shape)
+        r = rect(img, 30, 60, 25, 60)
+        r.copy_(torch.rand(r.shape, generator=g))
+        r = rect(gt, 45, 80, 40, 90)
+        r.copy_(torch.rand(r.shape, generator=g))
+    elif name == "c_near_constant_pair":
+        gt = 0.7 + 1e-3 * (2 * torch.rand(shape, generator=g) - 1)
+        img = 0.7 + 1e-3 * (2 * torch.rand(shape, generator=g) - 1)
+    elif name == "d_identical_noise":
+        gt = torch.rand(shape, generator=g)
+        img = gt.clone()
+    elif name == "d_identical_constant":
+        gt = torch.full(shape, 0.7)
+        img = gt.clone()
+    elif name == "e_zeros":
+        gt, img = torch.zeros(shape), torch.zeros(shape)
+    elif name == "f_outside_unit_range":
+        gt = torch.rand(shape, generator=g)
+        img = 2 * torch.rand(shape, generator=g) - 0.5
+    else:
+        raise KeyError(name)
+    return img, gt
+
+
+CONTENT = ["a_flat_gt_noise_rect_in_img", "b_flat_background_different_rects", "c_near_constant_pair", "d_identical_noise",
+           "d_identical_constant", "e_zeros", "f_outside_unit_range"]
+
+
+@pytest.mark.parametrize("shape", [(3, 131, 203), (3, 1080, 1920)], ids=["131x203", "1080p"])
+@pytest.mark.parametrize("name", CONTENT)
+def test_loss_content_classes_against_the_references_own_fp32_error(hip, orc, name, shape):
+    """T = float64 truth (oracle). d_ref = distance of the reference's formula evaluated in fp32 as the reference runs it
+    (conv2d + autograd on the CPU, tests/loss_ref.py) from T. The kernel must be within max(project bar, 4 d_ref) of T, for the
+    value (project bar 2e-6) and for the gradient (absolute inf-norm; project bar 1e-4 |T|_inf, which is 0 where the true
+    gradient is). 4 = 2 (two fp32 orders of one cancelling expression may err in opposite directions) x 2 (the separable
+    11 + 11 FMA pass rounds elsewhere than the 121-tap sum)."""
+    from c3dgs_amd import loss as L
+    img, gt = _content(name, shape, seed=shape[1])
+    T, T_grad = _truth(orc, img, gt, "loss")
+    ref, ref_grad = loss_ref.torch_loss(img, gt, *loss_ref.coeffs("loss"))
+    val, grad = _kernel(L, img, gt, "loss")
+    assert np.isfinite(val) and np.isfinite(grad).all()
+    d_ref, d_k = abs(ref - T), abs(val - T)
+    g_ref, g_k = np.abs(ref_grad - T_grad).max(), np.abs(grad - T_grad).max()
+    ratio = lambda a, b: a / b if b > 0 else (0.0 if a == 0 else float("inf"))
+    print(f"loss content {name} {shape[1]}x{shape[2]}: value d_ref {d_ref:.2e} kernel {d_k:.2e} ratio {ratio(d_k, d_ref):.2f} | "
+          f"grad d_ref {g_ref:.2e} kernel {g_k:.2e} ratio {ratio(g_k, g_ref):.2f} (|T_grad|_inf {np.abs(T_grad).max():.2e})")
+    assert d_k <= max(2e-6, 4 * d_ref), (name, d_k, d_ref)
+    assert g_k <= max(1e-4 * np.abs(T_grad).max(), 4 * g_ref), (name, g_k, g_ref)
+    if name.startswith("d_") or name == "e_zeros":
+        x = img.cuda().requires_grad_()
+        L.l1_loss(x, gt.cuda()).backward()
+        assert not x.grad.view(torch.int32).any().item(), "sign(0) = 0: the L1 gradient of identical images is exactly +0"
+    if name == "e_zeros":
+        assert val == 0.0 and not grad.any()                       # mu = sigma = 0: map = 1 exactly, every derivative times 0
+
+
+@pytest.mark.parametrize("shape", [(3, 5, 7), (3, 44, 64), (1, 22, 32)], ids=lambda s: "x".join(map(str, s)))
+def test_forward_without_derivative_maps_returns_the_same_bits(hip, shape):
+    """The dmaps == NULL launch (an input that does not require grad: `plain`) vs the differentiable call, and the call under
+    torch.no_grad(): that one still sees needs_input_grad[0] == True for a requires_grad input and takes the with-maps launch,
+    only its result carries no graph. These shapes have at most one workgroup per accumulation slot, so the float64 sums and
+    hence the value are reproducible bit for bit."""
+    from c3dgs_amd import loss as L
+    img, gt = _noise_pair(shape, seed=3)
+    x, y = img.cuda(), gt.cuda()
+    for fn in (lambda a, b: L.l1_ssim_loss(a, b, 0.2), L.ssim, L.l1_loss):
+        with_maps = fn(x.clone().requires_grad_(), y)
+        assert with_maps.requires_grad
+        plain = fn(x, y)
+        with torch.no_grad():
+            nograd = fn(x.clone().requires_grad_(), y)
+        assert not plain.requires_grad and not nograd.requires_grad
+        bits = lambda t: t.detach().view(torch.int32).item()
+        assert bits(with_maps) == bits(plain) == bits(nograd)
+
+
+@pytest.mark.parametrize("tile", [(0, 0, 0), (37, 25, 1), (59, 49, 2), (59, 0, 0), (0, 49, 2)])
+def test_every_tiles_partial_sum_reaches_an_accumulator(hip, tile):
+    """1080p: 60 x 50 x 3 workgroups add into 64 slots. All L1 mass sits in ONE 32 x 22 tile (row 49 is the partial one, two
+    pixel rows high); everywhere else img == gt. l1_loss must equal that tile's float64 sum / N."""
+    from c3dgs_amd import loss as L
+    C, H, W = 3, 1080, 1920
+    bx, by, c = tile
+    g = torch.Generator().manual_seed(bx + 100 * by)
+    gt = torch.rand(C, H, W, generator=g)
+    img = gt.clone()
+    ys, xs = slice(by * 22, min(H, by * 22 + 22)), slice(bx * 32, bx * 32 + 32)
+    img[c, ys, xs] = torch.rand(img[c, ys, xs].shape, generator=g)
+    want = float((img[c, ys, xs].double() - gt[c, ys, xs].double()).abs().sum()) / (C * H * W)
+    assert want > 0
+    got = float(L.l1_loss(img.cuda(), gt.cuda()).item())
+    assert abs(got - want) <= 1e-6 * want, (tile, got, want)
