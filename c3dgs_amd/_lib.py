@@ -4,7 +4,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# C3DGS_LIB_PATH: test hook only -- loads a variant build of the SAME library (c3dgs_amd/build.py VARIANTS)
+# C3DGS_LIB_PATH: test hook only -- loads a variant build of the SAME library (c3dgs_amd/build.py VARIANTS, DIAG_VARIANTS)
 LIB_PATH = os.environ.get("C3DGS_LIB_PATH") or os.path.join(_HERE, "libc3dgs_hip.so")
 
 _f32p = C.POINTER(C.c_float)
@@ -79,7 +79,7 @@ ROLE_COPY, ROLE_XYZ, ROLE_SCALING = 0, 1, 2
 ROW_KEEP, ROW_CLONE, ROW_SPLIT, ROW_CHILD_KEPT = 1, 2, 4, 8
 
 _vp = C.c_void_p
-# name -> (restype, argtypes); every symbol include/c3dgs_hip.h declares
+# name -> (restype, argtypes); every symbol include/c3dgs_hip.h declares, and the test hooks of include/c3dgs_hip_debug.h
 PROTOTYPES = {
     "c3dgs_camera_from_pose": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "c3dgs_mark_visible": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -146,9 +146,6 @@ PROTOTYPES = {
     "c3dgs_qat_quantize": (C.c_int, [C.POINTER(QatParams), C.c_int32] + [_vp] * 7),
     "c3dgs_fake_quantize": (C.c_int, [C.c_int64, _vp, _vp, C.c_int32, C.c_int32, C.c_float, _vp, _vp, _vp]),
     "c3dgs_fake_quantize_backward": (C.c_int, [C.c_int64, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
-    "c3dgs_debug_lane_counters": (C.c_int, [C.POINTER(C.c_uint64), _vp]),
-    "c3dgs_debug_sort_times": (C.c_int, [C.POINTER(C.c_uint64)]),
-    "c3dgs_debug_gather_probe": (C.c_int, [C.c_int32, C.c_int64, _vp, _vp, _vp, _vp]),
     "c3dgs_debug_sort_temp_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32]),
     "c3dgs_debug_sort_pairs": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "c3dgs_debug_tile_sort_temp_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
@@ -164,6 +161,12 @@ PROTOTYPES = {
     "c3dgs_last_error": (C.c_char_p, []),
     "c3dgs_abi_version": (C.c_int, []),
     "c3dgs_abs_accumulate": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+# the measurement entries of include/c3dgs_hip_debug.h: only the diag variants of the library export them (build.py DIAG_VARIANTS)
+DIAG_PROTOTYPES = {
+    "c3dgs_debug_lane_counters": (C.c_int, [C.POINTER(C.c_uint64), _vp]),
+    "c3dgs_debug_sort_times": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "c3dgs_debug_gather_probe": (C.c_int, [C.c_int32, C.c_int64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
@@ -181,7 +184,8 @@ def lib():
             handle = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise RuntimeError(f"c3dgs_amd: cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in PROTOTYPES.items():
+        diag = {n: p for n, p in DIAG_PROTOTYPES.items() if hasattr(handle, n)}
+        for name, (res, args) in {**PROTOTYPES, **diag}.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

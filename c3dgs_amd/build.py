@@ -1,6 +1,6 @@
 """Build c3dgs_amd/libc3dgs_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-    python -m c3dgs_amd.build [--force] [--verbose]
+    python -m c3dgs_amd.build [--force] [--verbose] [--variants] [--diag]
 
 Per-file flags matter: preprocess.hip / backward_preprocess.hip are compiled with -ffp-contract=off
 because radii, tile rectangles and depth bits feed bit-exact integer tile keys (see csrc/gsmath.hpp); knn.hip
@@ -22,6 +22,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno
           "-fno-gpu-rdc", "-DNDEBUG"]
 SOURCES = {
     "c_abi.hip": [],
+    "c_abi_debug.hip": [],      # test hooks (include/c3dgs_hip_debug.h)
     "preprocess.hip": ["-ffp-contract=off"],
     "backward_preprocess.hip": ["-ffp-contract=off"] + os.environ.get("C3DGS_BWDPRE_FLAGS", "").split(),
     "binning.hip": [],
@@ -38,10 +39,9 @@ SOURCES = {
     "adam.hip": ["-ffp-contract=off"],
     "qat.hip": ["-ffp-contract=off"],
     "densify.hip": ["-ffp-contract=off"],   # sqrt(gx*gx + gy*gy) of the densification stats is torch's two-rounding sum
-    "probe.hip": [],            # measurement-only kernels (PMC calibration), see csrc/probe.hip
 }
-HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"),
-           os.path.join(HERE, "..", "include", "c3dgs_hip.h")]
+HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), os.path.join(CSRC, "render_diag.hpp"),
+           os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h")]
 
 
 def _stale(target, deps):
@@ -61,32 +61,37 @@ def _compile(name, extra, verbose):
     return obj
 
 
-# Test-only variants of the library: same sources, extra flags for some files; objects of untouched files are shared with
-# the product build. "spin1": every look-back of the radix sorts gives up after ONE poll, which forces the time-out path
-# that tests/test_sort_gpu.py::test_sort_timeout_is_not_silent exercises (loaded through C3DGS_LIB_PATH in a child process).
-# "lanes": the blend kernels count how many pixel lanes use each (wave, Gaussian) pair (tools/lane_efficiency.py).
-VARIANTS = {"spin1": {"radix_sort.hip": ["-DC3DGS_OS_SPIN_LIMIT=1u"]},
-            "lanes": {"render.hip": ["-DC3DGS_COUNT_LANES", "-fno-slp-vectorize"]},
-            # "bwdtime": render_backward sums the shader clock per phase (staging / list compaction / group loop / flush)
-            "bwdtime": {"render.hip": ["-DC3DGS_BWD_TIMING", "-fno-slp-vectorize"]},
-            # (timing-only ablations of render_backward, WRONG gradients, are built by hand: C3DGS_RENDER_FLAGS="-fno-slp-vectorize
-            #  -DC3DGS_BWD_ABLATE=1|2|3" python -m c3dgs_amd.build; bit 0 = no partial-sum stores, bit 1 = cache-resident record gathers)
-            # "ostime": the digit passes of the onesweep sorts stamp the shader clock at their phase boundaries (tools/sort_phases.py)
-            "ostime": {"radix_sort.hip": ["-DC3DGS_OS_TIMING"]}}
+# Variants of the library: same sources, extra flags for some files; objects of untouched files are shared with the product build.
+# VARIANTS are what tests need. "spin1": every look-back of the radix sorts gives up after ONE poll, which forces the time-out
+# path that tests/test_sort_gpu.py::test_sort_timeout_is_not_silent exercises (loaded through C3DGS_LIB_PATH in a child process).
+VARIANTS = {"spin1": {"radix_sort.hip": ["-DC3DGS_OS_SPIN_LIMIT=1u"]}}
+# DIAG_VARIANTS are measurement builds (python -m c3dgs_amd.build --diag): the two instrumented files are compiled with
+# -DC3DGS_DIAG plus the variant's mode flag and diag.hip, which is no product source, is linked in, so every one of them exports
+# the measurement entries of include/c3dgs_hip_debug.h (zeros for the kinds of data its mode does not collect).
+#   "lanes":   the blend kernels count how many pixel lanes use each (wave, Gaussian) pair (tools/lane_efficiency.py)
+#   "bwdtime": render_backward sums the shader clock per phase (tools/bwd_phases.py)
+#   "ostime":  the digit passes of the onesweep sorts stamp the shader clock at their phase boundaries (tools/sort_phases.py)
+def _diag(mode):
+    return {src: ["-DC3DGS_DIAG", mode] for src in ("render.hip", "radix_sort.hip", "diag.hip")}
+
+
+DIAG_VARIANTS = {"lanes": _diag("-DC3DGS_COUNT_LANES"), "bwdtime": _diag("-DC3DGS_BWD_TIMING"), "ostime": _diag("-DC3DGS_OS_TIMING")}
 
 
 def build_variant(name, verbose=False):
     build(verbose=verbose)
+    flags = {**VARIANTS, **DIAG_VARIANTS}[name]
     odir = os.path.join(HERE, "build", "variant_" + name)
     os.makedirs(odir, exist_ok=True)
     lib = os.path.join(HERE, f"libc3dgs_hip_{name}.so")
     objs, rebuilt = [], False
-    for src, extra in SOURCES.items():
+    for src in list(SOURCES) + [f for f in flags if f not in SOURCES]:
+        extra = SOURCES.get(src, [])
         obj = os.path.join(OBJ, src.replace(".hip", ".o"))
-        if src in VARIANTS[name]:
+        if src in flags:
             obj = os.path.join(odir, src.replace(".hip", ".o"))
             if _stale(obj, [os.path.join(CSRC, src)] + HEADERS + [os.path.abspath(__file__)]):
-                cmd = [HIPCC] + COMMON + extra + VARIANTS[name][src] + ["-c", os.path.join(CSRC, src), "-o", obj]
+                cmd = [HIPCC] + COMMON + extra + flags[src] + ["-c", os.path.join(CSRC, src), "-o", obj]
                 if verbose:
                     print(" ".join(cmd), flush=True)
                 subprocess.check_call(cmd)
@@ -119,6 +124,6 @@ def build(force=False, verbose=False):
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv or "-v" in sys.argv))
-    if "--variants" in sys.argv:
-        for v in VARIANTS:
+    for flag, table in (("--variants", VARIANTS), ("--diag", DIAG_VARIANTS)):
+        for v in table if flag in sys.argv else ():
             print(build_variant(v, verbose="--verbose" in sys.argv or "-v" in sys.argv))

@@ -243,8 +243,6 @@ hipError_t onesweep_tile_sort32(void* temp, size_t temp_bytes, const uint32_t* k
 hipError_t onesweep_tile_sort(void* temp, size_t temp_bytes, const uint16_t* kin, uint16_t* kout, const uint32_t* vin, uint32_t* vout,
                               int R, int end_bit, hipStream_t s, bool ctrl_cleared = false);
 // render.hip
-int os_read_times(unsigned long long* out512);   // radix_sort.hip, experiment builds with -DC3DGS_OS_TIMING only
-int read_lane_counters(unsigned long long* out16, hipStream_t s);   // render.hip; all zero unless built with -DC3DGS_COUNT_LANES
 void launch_render_forward(int W, int H, const ImgPtrs& img, const uint32_t* point_list, const float4* splat,
                            const float* bg, float* out_color, const CompactPtrs& cl, const uint32_t* sort_err, hipStream_t s);
 void launch_backward_prep(int W, int H, const ImgPtrs& img, uint32_t* tile_order, void* zero_a, size_t n16_a, void* zero_b,
@@ -273,8 +271,6 @@ void launch_vq_accumulate(int64_t B, int K, int D, const float* x, const float* 
 void launch_vq_apply(int K, int D, const float* S, float* codebook, float* entry_importance, float decay, float alpha,
                      float eps, int scale_normalize, hipStream_t s);
 
-// probe.hip (measurement only)
-int launch_gather_probe(int kind, size_t n, void* table, const uint32_t* index, uint32_t* out, hipStream_t s);
 // encode.hip
 size_t morton_workspace_bytes(int P);
 int run_morton_order(int P, const float* xyz, int64_t* codes_out, int64_t* order_out, void* workspace, hipStream_t s);

@@ -1,10 +1,18 @@
-// probe.hip -- measurement-only kernels (c3dgs_debug_gather_probe): known access patterns with a known byte count, run under
-// the same two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) as the product kernels, to calibrate what those counters report
-// for GATHERS on gfx950 (MI355X_MICROARCH.md only calibrates wide coalesced streams: FETCH_SIZE = 1/2 of the bytes).
-// tools/pmc_calibrate.py drives them; nothing in the product path calls them.
+// diag.hip -- the measurement entries of include/c3dgs_hip_debug.h. Linked ONLY into the diag variants of the library
+// (c3dgs_amd/build.py DIAG_VARIANTS); the product library holds none of this.
+//   c3dgs_debug_lane_counters  reads the counters of the blend kernels' instruments (render_diag.hpp, in render.hip's translation unit)
+//   c3dgs_debug_sort_times     reads the phase stamps of the onesweep digit passes (radix_sort.hip)
+//   c3dgs_debug_gather_probe   the kernels below: known access patterns with a known byte count, run under the same two
+//       rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) as the product kernels, to calibrate what those counters report for
+//       GATHERS on gfx950 (MI355X_MICROARCH.md only calibrates wide coalesced streams: FETCH_SIZE = 1/2 of the bytes).
+//       tools/pmc_calibrate.py drives them.
 #include "common.hpp"
+#include "../../include/c3dgs_hip_debug.h"
 
 namespace c3dgs {
+
+int read_lane_counters(unsigned long long* out16, hipStream_t s);   // render_diag.hpp; reads and clears
+int os_read_times(unsigned long long* out512);                      // radix_sort.hip
 
 // kind 0: coalesced stream, 16 bytes per lane (the calibrated case: the control)
 __global__ void __launch_bounds__(256) probe_stream_kernel(size_t n16, const uint4* __restrict__ src, uint32_t* __restrict__ out)
@@ -45,7 +53,7 @@ __global__ void __launch_bounds__(256) probe_scatter36_kernel(size_t n, float* _
     for (int k = 0; k < 9; k++) dst[k] = (float)k;
 }
 
-int launch_gather_probe(int kind, size_t n, void* table, const uint32_t* index, uint32_t* out, hipStream_t s)
+static int launch_gather_probe(int kind, size_t n, void* table, const uint32_t* index, uint32_t* out, hipStream_t s)
 {
     if (n == 0) return 0;
     const unsigned g = (unsigned)((n + 255) / 256);
@@ -59,3 +67,34 @@ int launch_gather_probe(int kind, size_t n, void* table, const uint32_t* index, 
 }
 
 } // namespace c3dgs
+
+using namespace c3dgs;
+
+extern "C" {
+
+int c3dgs_debug_sort_times(uint64_t* out /*[512]*/)
+{
+    unsigned long long v[512];
+    if (!out) return fail(C3DGS_E_INVALID, "debug_sort_times: NULL buffer");
+    if (os_read_times(v)) return fail(C3DGS_E_HIP, "debug_sort_times: copy failed");
+    for (int i = 0; i < 512; i++) out[i] = (uint64_t)v[i];
+    return C3DGS_OK;
+}
+
+int c3dgs_debug_gather_probe(int32_t kind, int64_t n, void* table, const uint32_t* index, uint32_t* out, void* stream)
+{
+    if (n < 0 || !table || !out || (kind != 0 && !index)) return fail(C3DGS_E_INVALID, "debug_gather_probe: bad arguments");
+    if (launch_gather_probe(kind, (size_t)n, table, index, out, (hipStream_t)stream)) return fail(C3DGS_E_INVALID, "debug_gather_probe: kind must be 0..3");
+    return C3DGS_OK;
+}
+
+int c3dgs_debug_lane_counters(uint64_t* out, void* stream)
+{
+    if (!out) return fail(C3DGS_E_INVALID, "debug_lane_counters: NULL buffer");
+    unsigned long long v[16];
+    if (read_lane_counters(v, (hipStream_t)stream)) return fail(C3DGS_E_HIP, "debug_lane_counters: copy failed");
+    for (int i = 0; i < 16; i++) out[i] = (uint64_t)v[i];
+    return C3DGS_OK;
+}
+
+} // extern "C"

@@ -56,11 +56,22 @@ constexpr int OS_MAX_PASSES = 4;
 #endif
 constexpr uint32_t OS_SPIN_LIMIT = C3DGS_OS_SPIN_LIMIT;
 __device__ uint32_t g_os_error;           // zero-initialised at module load; bit 0 = tile-key sort, bit 1 = depth-key sort
+// Phase stamps of os_pass_kernel (diag variant "ostime": -DC3DGS_DIAG -DC3DGS_OS_TIMING, tools/sort_phases.py): every fourth of the
+// first 256 tiles stamps the shader clock at eight phase boundaries. OS_T_LOADS_DONE / OS_T_DRAIN make the memory operations in front
+// of a stamp complete before it (the first through a store that never happens but needs the loaded values). All empty in the product.
+#ifdef C3DGS_DIAG
+__device__ unsigned long long g_os_times[64 * 8];   // stays zero in a diag variant without C3DGS_OS_TIMING
+#endif
 #ifdef C3DGS_OS_TIMING
-__device__ unsigned long long g_os_times[64 * 8];
 #define OS_T(slot) if (tid == 0 && (bid & 3) == 0 && (bid >> 2) < 64) g_os_times[(bid >> 2) * 8 + (slot)] = __builtin_readcyclecounter();
+#define OS_T_DRAIN() asm volatile("s_waitcnt vmcnt(0)");
+#define OS_T_LOADS_DONE()                                                                                    \
+    if (key[0] == (K)0x12345678 && val[OS_IPT - 1] == 0x87654321u) kout[0] = key[OS_IPT - 1];                \
+    OS_T_DRAIN()
 #else
 #define OS_T(slot)
+#define OS_T_DRAIN()
+#define OS_T_LOADS_DONE()
 #endif
 
 struct OsPlan { int passes; int bits[OS_MAX_PASSES]; };
@@ -259,10 +270,7 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
     // `volatile` pointer made them FLAT loads / stores with system-scope cache bits and a full vmcnt(0) wait each -- two memory
     // round trips per item, which was most of this loop's time (tools/sort_phases.py: rank loop 47 % of a depth-key pass).
     const uint32_t lt_lo = lane < 32 ? (1u << lane) - 1u : 0xffffffffu, lt_hi = lane < 32 ? 0u : (1u << (lane - 32)) - 1u;
-#ifdef C3DGS_OS_TIMING
-    if (key[0] == (K)0x12345678 && val[OS_IPT - 1] == 0x87654321u) kout[0] = key[OS_IPT - 1];   // force the loads to complete here
-    asm volatile("s_waitcnt vmcnt(0)");
-#endif
+    OS_T_LOADS_DONE()
     OS_T(1)
     uint32_t* wc = s_cnt[wave];                       // other lanes of the wave update these between iterations
 #pragma unroll
@@ -371,9 +379,7 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
             } else if (gather_src) gather_dst[g] = gather_src[vv]; // last pass of the depth sort: per-Gaussian data in sorted order
         }
     }
-#ifdef C3DGS_OS_TIMING
-    asm volatile("s_waitcnt vmcnt(0)");
-#endif
+    OS_T_DRAIN()
     OS_T(7)
 }
 
@@ -488,13 +494,11 @@ static hipError_t os_sort(void* temp, size_t temp_bytes, const K* kin, K* kout, 
     return hipGetLastError();
 }
 
-#ifdef C3DGS_OS_TIMING
+#ifdef C3DGS_DIAG
 int os_read_times(unsigned long long* out512)
 {
     return hipMemcpyFromSymbol(out512, HIP_SYMBOL(g_os_times), sizeof(unsigned long long) * 512) != hipSuccess;
 }
-#else
-int os_read_times(unsigned long long*) { return 1; }
 #endif
 
 // address of the current device's sticky error word (cached per device; one process per GPU is the normal case)

@@ -24,65 +24,12 @@
 //    then sums a contiguous run of slots. Plain stores run ~4-5x the chip-wide float-atomic rate on MI355X and the
 //    result is bitwise reproducible (the reference's 9 atomics per pixel-Gaussian pair, backward.cu:523-554, are not).
 #include "common.hpp"
+#include "render_diag.hpp"   // LaneCount, PhaseClock: the instruments the kernels call; empty bodies in the product build
 #include <algorithm>
 
 namespace c3dgs {
 
 constexpr int BATCH = 256;
-
-// Lane-efficiency counters of the blend kernels (test-only build variant "lanes": -DC3DGS_COUNT_LANES, c3dgs_amd/build.py).
-// [fwd = 0 | bwd = 8] + { 0: (wave, Gaussian) pairs the blend loop ran (real list entries), 1: slots incl. the sentinel padding,
-// 2: lanes whose pixel used the pair (forward: blended it; backward: hit), 3: pairs with at least one such lane,
-// 4: sum over (wave, list) of max(pairs touching pixel rows 0-3, pairs touching rows 4-7) = iterations of a half-wave
-//    (8x4-pixel) scheduling unit, 5: the same for four 4x4-pixel blocks, 6: lists walked, 7: lanes hit (forward, incl. finished pixels) }
-// The product build never touches them; c3dgs_debug_lane_counters() reads and clears them.
-__device__ unsigned long long g_lane_counters[16];
-
-#ifndef C3DGS_BWD_ABLATE
-#define C3DGS_BWD_ABLATE 0      // timing-only experiment builds (WRONG gradients): bit 0 = no partial-sum stores, bit 1 = cache-resident
-                                // record gathers, bit 2 = without the two in-bank reduction levels, bit 3 = without any reduction
-#endif
-#ifdef C3DGS_BWD_TIMING
-// phase clocks of render_backward (experiment build variant "bwdtime"): shader-clock ticks summed over all waves:
-// g_lane_counters[8 + {0: staging incl. its two barriers, 1: list compaction, 2: group loop, 3: flush incl. barrier, 4: prologue, 5: waves}]
-#define BT_STAMP(var) const unsigned long long var = __builtin_readcyclecounter();
-#else
-#define BT_STAMP(var)
-#endif
-#ifdef C3DGS_COUNT_LANES
-struct LaneCount {
-    unsigned long long pairs = 0, slots = 0, lanes = 0, live = 0, half = 0, blk = 0, lists = 0, aux = 0;
-    int nA = 0, nB = 0, nb[4] = { 0, 0, 0, 0 };
-    __device__ void pair(bool real, unsigned long long used, unsigned long long aux_mask)
-    {
-        slots++;
-        if (!real) return;
-        pairs++;
-        lanes += __popcll(used);
-        aux += __popcll(aux_mask);
-        live += used != 0;
-        nA += (used & 0x00000000ffffffffull) != 0;
-        nB += (used & 0xffffffff00000000ull) != 0;
-        nb[0] += (used & 0x000000000f0f0f0full) != 0;
-        nb[1] += (used & 0x00000000f0f0f0f0ull) != 0;
-        nb[2] += (used & 0x0f0f0f0f00000000ull) != 0;
-        nb[3] += (used & 0xf0f0f0f000000000ull) != 0;
-    }
-    __device__ void end_list()
-    {
-        lists++;
-        half += max(nA, nB);
-        blk += max(max(nb[0], nb[1]), max(nb[2], nb[3]));
-        nA = nB = nb[0] = nb[1] = nb[2] = nb[3] = 0;
-    }
-    __device__ void flush(int base, int lane)
-    {
-        if (lane != 0) return;
-        const unsigned long long v[8] = { pairs, slots, lanes, live, half, blk, lists, aux };
-        for (int q = 0; q < 8; q++) atomicAdd(&g_lane_counters[base + q], v[q]);
-    }
-};
-#endif
 
 // The staged LDS records carry the conic PRE-SCALED for the blend loops: {-0.5 a, -b, -0.5 c} x log2(e), so that the
 // exponent of  G = exp(-0.5 (a dx^2 + c dy^2) - b dx dy)  is three multiplies and three multiply-adds feeding v_exp_f32
@@ -252,9 +199,7 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
     uint32_t last_contributor = 0, last_contributor_c = 0;   // 1-based: position in the tile's list / index in its compact list
     uint32_t n_live = 0;                                      // live entries of the batches in front of this one (all waves agree)
     constexpr uint32_t NO_ENTRY = 0xffffffffu;
-#ifdef C3DGS_COUNT_LANES
     LaneCount lc;
-#endif
     const char* rec_base = reinterpret_cast<const char*>(&s_ab[0][0][0]);
     const char* blue_base = reinterpret_cast<const char*>(&s_c[0][0]);
 
@@ -348,14 +293,10 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
                 Tr = blend ? test_T : Tr;
                 last_off = blend ? e[g] : last_off;
                 done = done || stop;
-#ifdef C3DGS_COUNT_LANES
                 lc.pair(k + g < nw, __ballot(blend), __ballot(hit));
-#endif
             }
         }
-#ifdef C3DGS_COUNT_LANES
         lc.end_list();
-#endif
         // offset -> 1-based position in the tile's list (once per batch, not per Gaussian)
         if (last_off != NO_ENTRY) {
             const uint32_t j = (last_off - (uint32_t)buf * BUF_BYTES) >> 5;       // batch entry; it blended, so it is live
@@ -377,9 +318,7 @@ render_forward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ran
         out_color[HW + pix] = fmaf(Tr, bg[1], C1) + poison;
         out_color[2 * HW + pix] = fmaf(Tr, bg[2], C2) + poison;
     }
-#ifdef C3DGS_COUNT_LANES
     lc.flush(0, lane);
-#endif
     // tile_used = max over the tile's pixels of n_contrib: the backward never looks past it
     // (tile_used_c: the same in compact indices = the entries the backward walks)
     atomicMax(&s_used, last_contributor);
@@ -514,10 +453,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
     // list positions, all thresholds keep the form they have in position space.
     // longest tiles first (tile_order: descending tile_used_c), so that the last workgroups to start are the short ones
     if ((int)blockIdx.x >= T) return;
-    BT_STAMP(bt_begin)
-#ifdef C3DGS_BWD_TIMING
-    unsigned long long bt_stage = 0, bt_list = 0, bt_loop = 0, bt_flush = 0, bt_s0 = 0, bt_s1 = 0, bt_s2 = 0, bt_s3 = 0, bt_f0 = 0;
-#endif
+    PhaseClock clk;
     const int tile = (int)tile_order[blockIdx.x];
     // staged entries as in the forward: 32-byte records {x, y, conic a, b | conic c, opacity, r, g}, blue and the instance's
     // backward slot in arrays of their own; the candidate lists hold record BYTE OFFSETS that feed the LDS reads directly
@@ -570,43 +506,31 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
     // where this lane's reduced values belong: Gaussian slot beta of the group, term my_m of the nine (see the network above)
     const int beta = ((lane >> 2) & 1) * 4 + (lane & 1) * 2 + ((lane >> 1) & 1);
     const int my_m = ((lane >> 3) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 5) & 1);
-#ifdef C3DGS_COUNT_LANES
     LaneCount lc;
-#endif
 
     uint32_t next_id = 0u, next_qm = 0u;
     {
         const int p0 = used - 1 - tid;
         if (p0 >= 0) { next_id = cid[range.x + p0]; next_qm = cqm[range.x + p0]; }
     }
-    BT_STAMP(bt_pro)
+    clk.mark(PhaseClock::PROLOGUE);
     for (int r = 0; r < rounds; r++) {
-        BT_STAMP(bt0)
         __syncthreads();                                         // previous flush has read s_part / s_slot
-        BT_STAMP(btA)
+        clk.mark(PhaseClock::TOP_BARRIER);
         const int mypos = used - 1 - (r * BATCH + tid);          // back to front (backward.cu:466-479)
         uint32_t qm = 0u;
         if (mypos >= 0) {
             // the entry's Gaussian id and quadrant mask were requested one round ago (below): the record gather is the only
             // memory round trip left in front of this round's blending (measured with the "bwdtime" variant: the dependent chain
             // point list -> record was 31 % of a wave's lifetime, more than its group loop)
-#if C3DGS_BWD_ABLATE & 2
-            const uint32_t id = next_id & 4095u;                  // timing-only build: records from a cache-resident corner of the array
-#else
             const uint32_t id = next_id;
-#endif
             qm = next_qm;
             float4 a = splat[3 * (size_t)id], b = splat[3 * (size_t)id + 1];
             const float4 c = splat[3 * (size_t)id + 2];
             prescale_conic(a, b);
             const uint32_t off = __float_as_uint(c.y), lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
             const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
-#if C3DGS_BWD_ABLATE & 2
-            s_slot[tid] = range.x + (uint32_t)mypos;              // timing-only build: a slot that exists (the record is not this entry's)
-            (void)off; (void)x0; (void)y0; (void)x1;
-#else
             s_slot[tid] = block_base[id >> 8] + off + (uint32_t)((ty - y0) * (x1 - x0) + (tx - x0));
-#endif
             s_ab[tid][0] = a; s_ab[tid][1] = b; s_c[tid] = c.x;
         }
         {   // next round's ids / masks: in flight behind this round's blending (two registers)
@@ -618,18 +542,14 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
             const unsigned long long bm = __ballot((qm >> q) & 1u);
             if (lane == 0) s_mask[q][wave] = bm;
         }
-        BT_STAMP(btB)
+        clk.mark(PhaseClock::GATHER);
 #pragma unroll
         for (int w = 0; w < 2; w++)
 #pragma unroll
             for (int q = 0; q < NPART; q++) s_part[w][tid][q] = 0.f;
-        BT_STAMP(btC)
+        clk.mark(PhaseClock::CLEAR);
         __syncthreads();
-        BT_STAMP(bt1)
-#ifdef C3DGS_BWD_TIMING
-        bt_stage += bt1 - bt0;
-        bt_s0 += btA - bt0; bt_s1 += btB - btA; bt_s2 += btC - btB; bt_s3 += bt1 - btC;
-#endif
+        clk.mark(PhaseClock::CLOSE_BARRIER);
 
         const int cnt = min(BATCH, used - r * BATCH);
         const int pos0 = used - 1 - r * BATCH;                   // position of batch entry j is pos0 - j
@@ -641,7 +561,6 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
         // bench scene -- adds zeros; testing for it per Gaussian cost more than it saved.)
 #pragma unroll 1
         for (int half = 0; half < 2; half++) {
-        BT_STAMP(bt2)
         int nw = 0;
         {
             const unsigned long long lt = (1ull << lane) - 1ull;
@@ -660,7 +579,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-        BT_STAMP(bt3)
+        clk.mark(PhaseClock::COMPACT);
         // Software pipeline, two levels: inside a group, record g + 1 is requested from LDS before Gaussian g is blended; across
         // groups, the NEXT group's list row and first record are requested behind this group's reduction (the list is padded, so
         // the row behind the last group exists; it is not used). Left to the compiler, a group started with two dependent LDS
@@ -691,9 +610,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
                 float dx, dy, G, alpha;
                 bool hit = gaussian_alpha(a.x, a.y, a.z, a.w, b.x, b.y, pxf, pyf, dx, dy, G, alpha);
                 hit = hit && ((int)e[g] > thr);                  // backward.cu:486-488
-#ifdef C3DGS_COUNT_LANES
                 lc.pair(k + g < nw, __ballot(hit), 0ull);
-#endif
                 // branch-free: a pixel that does not blend this Gaussian runs the same instructions with
                 // alpha = G = 0, which leaves T and Sd untouched and makes all six terms exactly 0
                 const float a_eff = hit ? alpha : 0.f, G_eff = hit ? G : 0.f;
@@ -717,21 +634,14 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
                 // which leaves the register allocator room (96 registers = five waves per SIMD) to request the NEXT Gaussian's
                 // record from LDS while this one is blended; with all 48 live every record read sat directly in front of its
                 // first use (three LDS latencies per Gaussian and wave, exposed).
-#if C3DGS_BWD_ABLATE & 8      // timing-only build: no reduction at all (the six values are merely kept alive)
-#pragma unroll
-                for (int q = 0; q < NCOL; q++) asm volatile("" : : "v"(v[g * NCOL + q]));
-#else
                 if (g == 4) { C3DGS_TR4("row_half_mirror", "0x5", "0xa", u, v, v, 0, 24); }
                 if (g == 5) { C3DGS_TR4("row_half_mirror", "0x5", "0xa", u, v, v, 4, 24); C3DGS_TR4("row_half_mirror", "0x5", "0xa", u, v, v, 8, 24); }
                 if (g == 6) { C3DGS_TR4("row_half_mirror", "0x5", "0xa", u, v, v, 12, 24); }
                 if (g == 7) { C3DGS_TR4("row_half_mirror", "0x5", "0xa", u, v, v, 16, 24); C3DGS_TR4("row_half_mirror", "0x5", "0xa", u, v, v, 20, 24); }
-#endif
             }
             row0 = *reinterpret_cast<const uint4*>(lrow + GROUP_G);          // next group's row (in bounds: the list is padded)
             row1 = *reinterpret_cast<const uint4*>(lrow + GROUP_G + 4);
-#if !(C3DGS_BWD_ABLATE & 12)  // timing-only builds: bit 2 = without the two in-bank column levels, bit 3 = without any reduction
             reduce_columns_24(u, lane);
-#endif
             a_n = *reinterpret_cast<const float4*>(rec_base + row0.x);          // ... and its first record, behind the row levels
             b_n = *reinterpret_cast<const float4*>(rec_base + row0.x + 16);
             c_n = *reinterpret_cast<const float*>(blue_base + (row0.x >> 3));
@@ -741,14 +651,8 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
             const float dyb = *reinterpret_cast<const float*>(rec_base + my_off + 4) - pyf;
             // row sums {c0, c1, c2, S0, Sx, Sxx} of Gaussian slot beta -> the nine terms {.., Sy, Sxy | Syy}
             float total, ninth;
-#if !(C3DGS_BWD_ABLATE & 8)
             const float nine[NPART] = { u[0], u[1], u[2], u[3], u[4], u[5], dyb * u[3], dyb * u[4], (dyb * dyb) * u[3] };
-#endif
-#if C3DGS_BWD_ABLATE & 8
-            total = v[0]; ninth = dyb;
-#else
             reduce_rows_9(nine, total, ninth);
-#endif
             // LDS float add into the plane this wave shares with ONE other wave: every (entry, term) receives at most
             // one add per wave, and a + b == b + a, so the result does not depend on which wave arrives first
             if (myj < BATCH) {
@@ -756,22 +660,13 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
                 if (lane < 8) __hip_atomic_fetch_add(&s_part[wave >> 1][myj][8], ninth, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
-#ifdef C3DGS_COUNT_LANES
         lc.end_list();
-#endif
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the list is rebuilt for the second half
         __builtin_amdgcn_wave_barrier();
-        BT_STAMP(bt4)
-#ifdef C3DGS_BWD_TIMING
-        bt_list += bt3 - bt2; bt_loop += bt4 - bt3;
-#endif
+        clk.mark(PhaseClock::GROUPS);
         }
-        BT_STAMP(bt5)
         __syncthreads();
-        BT_STAMP(bt5b)
-#ifdef C3DGS_BWD_TIMING
-        bt_f0 += bt5b - bt5;
-#endif
+        clk.mark(PhaseClock::FLUSH_BARRIER);
         if (tid < cnt) {
             const uint32_t slot = s_slot[tid];
             float* dst = partials + (size_t)slot * NPART;
@@ -781,40 +676,15 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
             // network order {c0, c1, c2, S0, Sx, Sxx, Sy, Sxy, Syy} -> what backward_preprocess.hip expects
             // (writing a slot cooperatively -- consecutive lanes on consecutive floats, 7 slots per store instruction -- measured
             // SLOWER: the flush went from 13 % to 19 % of a wave's lifetime, "bwdtime" variant)
-#if !(C3DGS_BWD_ABLATE & 1)
             dst[0] = t[0]; dst[1] = t[1]; dst[2] = t[2];
             dst[3] = t[3]; dst[4] = t[4]; dst[5] = t[6];
             dst[6] = t[5]; dst[7] = t[7]; dst[8] = t[8];
-#else
-            if (t[0] == 123.456f) dst[0] = t[1] + t[2] + t[3] + t[4] + t[5] + t[6] + t[7] + t[8];     // timing-only build: no slot stores
-#endif
             touched[slot] = 1;
         }
-        BT_STAMP(bt6)
-#ifdef C3DGS_BWD_TIMING
-        bt_flush += bt6 - bt5;
-#endif
+        clk.mark(PhaseClock::FLUSH_STORES);
     }
-#ifdef C3DGS_COUNT_LANES
     lc.flush(8, lane);
-#endif
-#ifdef C3DGS_BWD_TIMING
-    if (lane == 0) {
-        atomicAdd(&g_lane_counters[8], bt_stage); atomicAdd(&g_lane_counters[9], bt_list); atomicAdd(&g_lane_counters[10], bt_loop);
-        atomicAdd(&g_lane_counters[11], bt_flush); atomicAdd(&g_lane_counters[12], bt_pro - bt_begin); atomicAdd(&g_lane_counters[13], 1ull);
-        atomicAdd(&g_lane_counters[14], (unsigned long long)__builtin_readcyclecounter() - bt_begin);
-        atomicAdd(&g_lane_counters[0], bt_s0); atomicAdd(&g_lane_counters[1], bt_s1); atomicAdd(&g_lane_counters[2], bt_s2);
-        atomicAdd(&g_lane_counters[3], bt_s3); atomicAdd(&g_lane_counters[4], bt_f0);
-    }
-#endif
-}
-
-int read_lane_counters(unsigned long long* out16, hipStream_t s)
-{
-    static const unsigned long long zeros[16] = { 0 };
-    if (hipStreamSynchronize(s) != hipSuccess) return 1;
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_lane_counters), sizeof(zeros)) != hipSuccess) return 1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_lane_counters), zeros, sizeof(zeros)) != hipSuccess;
+    clk.flush(lane);
 }
 
 // tile schedule + the backward's fills in one launch; zero_a / zero_b: 16-byte aligned spans of n16 x 16 bytes (or null / 0)

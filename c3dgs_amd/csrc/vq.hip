@@ -844,12 +844,9 @@ static void launch_wd_mfma(int64_t N, int C, const float* coefs, const int64_t* 
     // fewer than one 4-wave workgroup per CU (256 CUs): let the 4 waves share 64 points and split the codebook instead
     // (measured, K = 4096 x 48: N = 32,768: 267 -> 158 us; N = 65,536: 271 vs 283 us, so the plain kernel from there on;
     // profiles/r02a_vq_slices.txt)
-    static const int split_env = []() { const char* e = getenv("C3DGS_VQ_SPLIT"); return e ? atoi(e) : -1; }();   // A/B switch for tests
-    static const bool force_f32 = getenv("C3DGS_VQ_F32_MFMA") != nullptr;                                          // A/B switch
-    static const float margin_env = []() { const char* e = getenv("C3DGS_VQ_SPLIT_MARGIN"); return e ? (float)atof(e) : WD_SPLIT_MARGIN; }();
-    const bool split = split_env >= 0 ? split_env != 0 : g1 < 256;
+    const bool split = g1 < 256;
     const size_t sb = wd_split_bytes(C, K);
-    const bool f16 = ws && ws_bytes >= sb && (((uintptr_t)ws) & 15) == 0 && !force_f32;
+    const bool f16 = ws && ws_bytes >= sb && (((uintptr_t)ws) & 15) == 0;
     char* rest = (char*)ws + (f16 ? sb : 0);
     const size_t rest_bytes = ws ? ws_bytes - (f16 ? sb : 0) : 0;
     int* flag_list = rest_bytes >= 2 * sizeof(int) && N < ((int64_t)1 << 31) ? (int*)rest : nullptr;
@@ -864,8 +861,8 @@ static void launch_wd_mfma(int64_t N, int C, const float* coefs, const int64_t* 
         const uint32_t* absmax_true = nullptr;
         if (presplit >= 0) { wd_split_pointers<K>(C, ws, frag, norms, absmax); absmax_true = absmax + 1 + (presplit & 1); }
         else launch_wd_split_codebook<K>(C, codebook, ws, frag, norms, absmax, s);
-        if (split) wd_f16_kernel<K, true, false><<<g2, 256, 0, s>>>(N, C, coefs, gather, codebook, frag, norms, absmax, out_dist, out_idx, flag_list, flag_cap, margin_env, nullptr, absmax_true);
-        else wd_f16_kernel<K, false, false><<<g1, 256, 0, s>>>(N, C, coefs, gather, codebook, frag, norms, absmax, out_dist, out_idx, flag_list, flag_cap, margin_env, nullptr, absmax_true);
+        if (split) wd_f16_kernel<K, true, false><<<g2, 256, 0, s>>>(N, C, coefs, gather, codebook, frag, norms, absmax, out_dist, out_idx, flag_list, flag_cap, WD_SPLIT_MARGIN, nullptr, absmax_true);
+        else wd_f16_kernel<K, false, false><<<g1, 256, 0, s>>>(N, C, coefs, gather, codebook, frag, norms, absmax, out_dist, out_idx, flag_list, flag_cap, WD_SPLIT_MARGIN, nullptr, absmax_true);
     } else if (split) wd_mfma_kernel<K, true><<<g2, 256, 0, s>>>(N, C, coefs, gather, codebook, out_dist, out_idx, flag_list, flag_cap);
     else wd_mfma_kernel<K, false><<<g1, 256, 0, s>>>(N, C, coefs, gather, codebook, out_dist, out_idx, flag_list, flag_cap);
     if (listed) {
@@ -886,8 +883,7 @@ size_t wd_ws_bytes(int64_t N, int C, int K)
 // can the fused Lloyd step (vq_apply_split_kernel + pre-split search) serve this shape with this scratch?
 bool wd_presplit_supported(int C, int K, const float* coefs, const float* codebook, const void* ws, size_t ws_bytes)
 {
-    static const bool off = getenv("C3DGS_VQ_EXACT_VALU") != nullptr || getenv("C3DGS_VQ_F32_MFMA") != nullptr || getenv("C3DGS_VQ_NO_FUSED_STEP") != nullptr;
-    if (off || !(K == 48 || K == 12 || K == 6) || C < 32 || !ws || (((uintptr_t)ws) & 15)) return false;
+    if (!(K == 48 || K == 12 || K == 6) || C < 32 || !ws || (((uintptr_t)ws) & 15)) return false;
     if ((((uintptr_t)coefs | (uintptr_t)codebook) & (K == 48 ? 15 : 7)) != 0) return false;
     return ws_bytes >= wd_split_bytes(C, K) + 2 * sizeof(int);
 }
@@ -907,10 +903,9 @@ int launch_weighted_distance(int64_t N, int C, int K, const float* coefs, const 
     const unsigned grid = (unsigned)((N + per_block - 1) / per_block);
     const bool al16 = (((uintptr_t)coefs | (uintptr_t)codebook) & 15) == 0;
     const bool al8 = (((uintptr_t)coefs | (uintptr_t)codebook) & 7) == 0;
-    static const bool force_exact = getenv("C3DGS_VQ_EXACT_VALU") != nullptr;   // A/B switch for tests and profiling
-    if (K == 48 && al16 && C >= 32 && !force_exact) launch_wd_mfma<48>(N, C, coefs, gather, codebook, out_dist, out_idx, ws, ws_bytes, s);
-    else if (K == 12 && al8 && C >= 32 && !force_exact) launch_wd_mfma<12>(N, C, coefs, gather, codebook, out_dist, out_idx, ws, ws_bytes, s);
-    else if (K == 6 && al8 && C >= 32 && !force_exact) launch_wd_mfma<6>(N, C, coefs, gather, codebook, out_dist, out_idx, ws, ws_bytes, s);
+    if (K == 48 && al16 && C >= 32) launch_wd_mfma<48>(N, C, coefs, gather, codebook, out_dist, out_idx, ws, ws_bytes, s);
+    else if (K == 12 && al8 && C >= 32) launch_wd_mfma<12>(N, C, coefs, gather, codebook, out_dist, out_idx, ws, ws_bytes, s);
+    else if (K == 6 && al8 && C >= 32) launch_wd_mfma<6>(N, C, coefs, gather, codebook, out_dist, out_idx, ws, ws_bytes, s);
     else if (K == 48 && al16) weighted_distance_kernel<48, 128><<<grid, WD_BLOCK, 0, s>>>(N, C, coefs, gather, codebook, out_dist, out_idx);
     else if (K == 12 && al16) weighted_distance_kernel<12, 512><<<grid, WD_BLOCK, 0, s>>>(N, C, coefs, gather, codebook, out_dist, out_idx);
     else if (K == 6 && al8) weighted_distance_kernel<6, 1024><<<grid, WD_BLOCK, 0, s>>>(N, C, coefs, gather, codebook, out_dist, out_idx);

@@ -159,12 +159,6 @@ int c3dgs_weighted_distance_ws(int64_t N, int32_t C, int32_t K, const float* coe
                                const float* codebook, float* out_dist, int64_t* out_idx, void* ws, size_t ws_bytes,
                                void* stream);
 
-/* diagnostics for tests: scores[n * C + c] = ||c||^2 - 2 x_n.c as the split-fp16 search forms them (fp32 accumulation of the three fp16 piece products,
- * divided back by the call's scale) (K = 48, N <= 256,
- * C >= 32; ws as above), so the error the ambiguity margin must cover can be measured against float64. */
-int c3dgs_debug_wd_scores(int64_t N, int32_t C, int32_t K, const float* coefs, const float* codebook, float* scores, void* ws,
-                          size_t ws_bytes, float* out_dist, int64_t* out_idx, void* stream);
-
 /* ---- VectorQuantize.update, split at the point where a sharded run all-reduces (compression/vq.py:28-35) ----
  * accumulate: S[k, 0..D) += w_n * x_n ; S[k, D] += w_n for k = idx[n];  *dist_sum += sum_n dist[n] (may be NULL).
  * S [K, D+1] fp32 must be zeroed by the caller (it is the all-reduce payload). */
@@ -477,37 +471,6 @@ typedef struct c3dgs_image_layout {   /* byte offsets into the image buffer     
     size_t tile_used;  /* uint32[T] max n_contrib over the tile's pixels                   */
     size_t tile_order; /* uint32[T] scratch of the backward: its tile schedule (ABI version 4)  */
 } c3dgs_image_layout;
-
-/* tests only: the binning stage's stable LSD radix sort (radix_sort.hip) on caller-provided pairs. key_bytes = 2 (tile
- * keys) or 4 (depth keys); bits [0, end_bit) are sorted; ties keep input order. temp >= c3dgs_debug_sort_temp_bytes(). */
-size_t c3dgs_debug_sort_temp_bytes(int32_t key_bytes, int64_t n, int32_t end_bit);
-int c3dgs_debug_sort_pairs(int32_t key_bytes, int64_t n, int32_t end_bit, const void* keys_in, void* keys_out,
-                           const uint32_t* values_in, uint32_t* values_out, void* temp, size_t temp_bytes, void* stream);
-
-/* tests only: the forward's tile-key sort for a grid of `tiles` tiles (1 .. 256 x 65535), taking the forward's own route: keys
- * are uint16 up to 65,536 tiles and uint32 above, sorted on min(higher_msb(tiles), key bits) bits, through the same dispatch
- * (hand-written sort, or rocPRIM with C3DGS_SORT_ROCPRIM=1). Ties keep input order. temp >= c3dgs_debug_tile_sort_temp_bytes(),
- * which is the forward's own sizing of that scratch (0 = bad arguments, see c3dgs_last_error). */
-size_t c3dgs_debug_tile_sort_temp_bytes(int32_t tiles, int64_t n);
-int c3dgs_debug_tile_sort_pairs(int32_t tiles, int64_t n, const void* keys_in, void* keys_out, const uint32_t* values_in,
-                                uint32_t* values_out, void* temp, size_t temp_bytes, void* stream);
-
-/* experiment builds only (radix_sort.hip compiled with -DC3DGS_OS_TIMING): phase time stamps of the last digit pass, 64 tiles x 8
- * stamps of the shader clock; fails in the product build. */
-int c3dgs_debug_sort_times(uint64_t* out /*[512], host*/);
-
-/* profiling only: access patterns with a KNOWN byte count, for calibrating the rocprofv3 FETCH_SIZE / WRITE_SIZE counters on this
- * GPU (tools/pmc_calibrate.py -> profiles/r03_pmc_calibration.txt). kind 0: coalesced 16-byte-per-lane read of n x 16 bytes of
- * `table`; 1: n lanes each read the 48-byte record index[i] (three 16-byte loads); 2: the 192-byte row index[i] (twelve); 3: n
- * lanes each store nine floats to the 36-byte slot index[i]. `out`: one word, practically never written. */
-int c3dgs_debug_gather_probe(int32_t kind, int64_t n, void* table, const uint32_t* index, uint32_t* out, void* stream);
-
-/* tests / profiling only: lane-efficiency counters of the two blend kernels, accumulated since the last call and cleared by it.
- * out[0..7] forward, out[8..15] backward: { (wave, Gaussian) pairs run, slots incl. list padding, pixel lanes that used the pair,
- * pairs with >= 1 such lane, iterations an 8x4-pixel half-wave unit would run, iterations a 4x4-pixel unit would run,
- * candidate lists walked, forward: lanes hit incl. finished pixels }. All zero unless the library is the "lanes" build
- * variant (render.hip compiled with -DC3DGS_COUNT_LANES; c3dgs_amd/build.py VARIANTS). Synchronises the stream. */
-int c3dgs_debug_lane_counters(uint64_t* out /*[16], host*/, void* stream);
 
 int c3dgs_get_geom_layout(int32_t P, c3dgs_geom_layout* out);
 int c3dgs_get_binning_layout(int32_t R, int32_t W, int32_t H, c3dgs_binning_layout* out);

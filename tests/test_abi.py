@@ -1,5 +1,6 @@
-"""CPU: the C-ABI shared library loads without a GPU, exports every symbol include/c3dgs_hip.h declares, and its
-argument validation (no device work) returns the documented codes."""
+"""CPU: the C-ABI shared library loads without a GPU, exports every symbol include/c3dgs_hip.h declares and the test hooks of
+include/c3dgs_hip_debug.h, keeps the measurement entries to the diag variants, and its argument validation (no device work)
+returns the documented codes."""
 import ctypes as C
 import os
 import re
@@ -16,8 +17,13 @@ def L():
     return _lib.lib()
 
 
-def _declared_symbols():
-    h = open(os.path.join(ROOT, "include", "c3dgs_hip.h")).read()
+TEST_HOOKS = {"c3dgs_debug_sort_temp_bytes", "c3dgs_debug_sort_pairs", "c3dgs_debug_tile_sort_temp_bytes",
+              "c3dgs_debug_tile_sort_pairs", "c3dgs_debug_wd_scores"}
+MEASUREMENT = {"c3dgs_debug_lane_counters", "c3dgs_debug_sort_times", "c3dgs_debug_gather_probe"}
+
+
+def _declared_symbols(header="c3dgs_hip.h"):
+    h = open(os.path.join(ROOT, "include", header)).read()
     h = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
     return sorted(set(re.findall(r"\b(c3dgs_[a-z0-9_]+)\s*\(", h)))
 
@@ -26,10 +32,29 @@ def test_every_declared_symbol_is_exported_and_bound(L):
     from c3dgs_amd import _lib
     syms = _declared_symbols()
     assert len(syms) >= 15
-    for s in syms:
-        assert hasattr(L, s), f"{s} declared in include/c3dgs_hip.h but not exported"
+    assert not [s for s in syms if s.startswith("c3dgs_debug_")], "the public header declares no debug entry"
+    assert set(_declared_symbols("c3dgs_hip_debug.h")) == TEST_HOOKS | MEASUREMENT
+    for s in syms + sorted(TEST_HOOKS):
+        assert hasattr(L, s), f"{s} declared in include/c3dgs_hip.h or as a test hook in c3dgs_hip_debug.h but not exported"
         assert s in _lib.PROTOTYPES, f"{s} has no ctypes prototype"
     assert L.c3dgs_abi_version() == 4
+
+
+def test_product_library_exports_no_measurement_entry(L):
+    from c3dgs_amd import _lib
+    assert set(_lib.DIAG_PROTOTYPES) == MEASUREMENT and not MEASUREMENT & set(_lib.PROTOTYPES)
+    for s in sorted(MEASUREMENT):
+        assert not hasattr(L, s), f"{s} is a measurement entry: only the diag variants may export it"
+
+
+def test_every_diag_variant_links_and_exports_the_measurement_entries(L):
+    from c3dgs_amd import build
+    assert set(build.VARIANTS) == {"spin1"} and set(build.DIAG_VARIANTS) == {"lanes", "bwdtime", "ostime"}
+    for name in build.DIAG_VARIANTS:
+        lib = C.CDLL(build.build_variant(name))             # loads: no undefined symbol
+        for s in sorted(MEASUREMENT | TEST_HOOKS) + _declared_symbols():
+            assert hasattr(lib, s), f"{s} missing from the {name} variant"
+        assert lib.c3dgs_debug_lane_counters(None, None) == 1 and lib.c3dgs_debug_sort_times(None) == 1   # NULL buffer: refused
 
 
 def test_layouts_are_consistent(L):

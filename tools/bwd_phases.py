@@ -1,5 +1,6 @@
 """Where render_backward's waves spend their time on the bench workload: shader-clock ticks per phase, summed over all waves
-("bwdtime" build variant).   C3DGS_LIB_PATH=c3dgs_amd/libc3dgs_hip_bwdtime.so python tools/bwd_phases.py [out.txt]"""
+("bwdtime" diag variant: python -m c3dgs_amd.build --diag; the phases are PhaseClock::Phase of csrc/render_diag.hpp).
+    C3DGS_LIB_PATH=c3dgs_amd/libc3dgs_hip_bwdtime.so python tools/bwd_phases.py [out.txt]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.getcwd())
 import torch
@@ -22,9 +23,9 @@ for it in range(3):
                                                    dL, t["shs"], 3, campos, o[3], o[0], o[4], o[5], False, t["sh_indices"], t["g_indices"])
     torch.cuda.synchronize()
 L.c3dgs_debug_lane_counters(out, None)
-fine = [int(x) for x in out][:5]
-v = [int(x) for x in out][8:]
-stage, lst, loop, flush, pro, waves, total = v[:7]
+pro, top, gather, clear, close, lst, loop, fbar, fstore, total, waves = [int(x) for x in out][:11]
+stage, flush = top + gather + clear + close, fbar + fstore
+fine = [top, gather, clear, close, fbar]
 txt = [f"render_backward on configs[2] (3M, 1920x1080, R={o[0]}): shader-clock ticks summed over {waves} waves that had work",
        f"  wave lifetime total {total:.3e} ticks = 100 %"]
 for name, x in (("prologue (pixel state, wave_last)", pro), ("staging of a batch incl. its two barriers", stage), ("candidate-list compaction", lst),

@@ -1,5 +1,5 @@
 """Lane efficiency of the two blend kernels on the bench workload (configs[2]: 3M Gaussians, 1920x1080, indexed), measured
-with the "lanes" build variant of the library (render.hip compiled with -DC3DGS_COUNT_LANES; c3dgs_amd/build.py).
+with the "lanes" diag variant of the library (python -m c3dgs_amd.build --diag; render.hip compiled with -DC3DGS_COUNT_LANES).
 
     C3DGS_LIB_PATH=c3dgs_amd/libc3dgs_hip_lanes.so python tools/lane_efficiency.py [out.txt]
 

@@ -1,9 +1,12 @@
-"""The profiled program of tools/pmc_calibrate.sh: known access patterns (csrc/probe.hip) on a table far larger than the
+"""The profiled program of tools/pmc_calibrate.sh: known access patterns (csrc/diag.hip) on a table far larger than the
 256 MiB Infinity Cache, with the byte counts every counting model would predict written next to the counters.
 
 Patterns: a coalesced 16-byte-per-lane stream (the case MI355X_MICROARCH.md calibrates: FETCH_SIZE reports 1/2), random
 48-byte records (the splat records the blend kernels gather), random 192-byte rows (the SH rows preprocess gathers), random
-36-byte slot stores (render_backward's partial sums)."""
+36-byte slot stores (render_backward's partial sums).
+
+The probe kernels are in the diag variants of the library only (python -m c3dgs_amd.build --diag), any of them:
+    C3DGS_LIB_PATH=c3dgs_amd/libc3dgs_hip_lanes.so python tools/pmc_calibrate.py"""
 import ctypes as C
 import json
 import os
@@ -16,6 +19,7 @@ from c3dgs_amd import _lib
 
 dev = torch.device("cuda", 0)
 L = _lib.lib()
+assert hasattr(L, "c3dgs_debug_gather_probe"), "run with C3DGS_LIB_PATH=c3dgs_amd/libc3dgs_hip_lanes.so (a diag variant)"
 TABLE = 6 * 1024 ** 3
 table = torch.empty(TABLE, dtype=torch.uint8, device=dev)
 table.zero_()

@@ -3,6 +3,7 @@
 # only, as MI355X_MICROARCH.md prescribes) over tools/pmc_calibrate.py, raw counters next to the byte counts each counting model
 # predicts.   bash tools/pmc_calibrate.sh [out.txt]
 export TMPDIR=/tmp
+export C3DGS_LIB_PATH=${C3DGS_LIB_PATH:-c3dgs_amd/libc3dgs_hip_lanes.so}   # the probe kernels are in the diag variants only
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 OUT=${1:-gpurun_out/pmc_calibration.txt}
 D=gpurun_out/pmc_cal; rm -rf $D; mkdir -p $D

@@ -1,9 +1,10 @@
 """Where a digit pass of the onesweep sorts spends its time: phase stamps (shader clock) of 64 tiles of the LAST pass of a sort,
-from the "ostime" build variant.  C3DGS_LIB_PATH=c3dgs_amd/libc3dgs_hip_ostime.so python tools/sort_phases.py"""
+from the "ostime" diag variant (python -m c3dgs_amd.build --diag).  C3DGS_LIB_PATH=c3dgs_amd/libc3dgs_hip_ostime.so python tools/sort_phases.py"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.getcwd())
 import torch
 from c3dgs_amd import _lib
+assert "ostime" in _lib.LIB_PATH, "run with C3DGS_LIB_PATH=c3dgs_amd/libc3dgs_hip_ostime.so"
 L = _lib.lib()
 dev = torch.device("cuda", 0)
 st = C.c_void_p(torch.cuda.current_stream().cuda_stream)

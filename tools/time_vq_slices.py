@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Assignment-kernel time for the per-rank slices of a sharded colour batch (2^18 points over 1/2/4/8 ranks; K=4096, D=48).
-C3DGS_VQ_SPLIT=0 / 1 forces the plain / codebook-split kernel (default: split below 512 four-wave workgroups)."""
+The dispatch takes the codebook-split kernel below 256 four-wave workgroups (N < 65,536), the plain one from there on."""
 import os
 import sys
 import time
@@ -26,4 +26,4 @@ for ranks in (1, 2, 4, 8):
     ms, n = _lib.profile_read()["weighted_distance"]
     _lib.profile_enable(False)
     tf = 2.0 * N * K * D / (ms / n * 1e-3) / 1e12
-    print(f"split_env={os.environ.get('C3DGS_VQ_SPLIT', 'auto')} ranks={ranks} N={N}: {ms / n * 1e3:.1f} us  {tf:.1f} TFLOP/s", flush=True)
+    print(f"ranks={ranks} N={N}: {ms / n * 1e3:.1f} us  {tf:.1f} TFLOP/s", flush=True)
