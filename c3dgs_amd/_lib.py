@@ -53,6 +53,10 @@ class ImageLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "final_T", "n_contrib", "ranges", "tile_used", "tile_order")]
 
 
+class BackwardLayout(C.Structure):    # c3dgs_get_backward_layout: the backward's workspace
+    _fields_ = [(n, C.c_size_t) for n in ("total_bytes", "partials", "touched", "live_ids", "live_slots", "live_count", "list_len")]
+
+
 class CompactLayout(C.Structure):     # c3dgs_get_compact_layout: the compact per-tile lists the backward walks
     _fields_ = [(n, C.c_size_t) for n in ("cqm", "cid", "tile_used_c", "n_contrib_c")]
 
@@ -154,6 +158,7 @@ PROTOTYPES = {
     "c3dgs_get_binning_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(BinningLayout)]),
     "c3dgs_get_image_layout": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(ImageLayout)]),
     "c3dgs_get_compact_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(CompactLayout)]),
+    "c3dgs_get_backward_layout": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(BackwardLayout)]),
     "c3dgs_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "c3dgs_profile_enable": (C.c_int, [C.c_int]),
     "c3dgs_profile_only": (C.c_int, [C.c_char_p]),

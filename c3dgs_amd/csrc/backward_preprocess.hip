@@ -27,14 +27,16 @@
 #ifndef C3DGS_BWD_FG
 #define C3DGS_BWD_FG 8
 #endif
-#ifndef C3DGS_SUM_WAVES
-#define C3DGS_SUM_WAVES 16  // waves per workgroup of sum_partials_kernel = 64 x this many Gaussians share one list of blended ones
-#endif
 #ifndef C3DGS_BWD_WAVES
 #define C3DGS_BWD_WAVES 3   // waves per SIMD of backward_preprocess_kernel (168 VGPRs, nothing spilled); measured on one box,
 #endif                      // interleaved: 3 -> 0.153 ms, 4 (128 VGPRs, 32 spilled) -> 0.166, 5 -> 0.20
 
 namespace c3dgs {
+
+// waves per workgroup of sum_partials_kernel: its BWD_LIST Gaussians (common.hpp) share one list of blended ones, which
+// backward_preprocess_kernel walks 256 entries per workgroup
+constexpr int SUM_WAVES = BWD_LIST / 64;
+static_assert(BWD_LIST % 256 == 0 && BWD_LIST <= 1024, "a list is one workgroup of sum_partials_kernel and whole ones of backward_preprocess_kernel");
 
 struct BwdArgs {
     int P, D, M, W, H;
@@ -131,9 +133,9 @@ __device__ __forceinline__ uint32_t nth_set_bit(unsigned long long m, uint32_t r
 // ---- kernel 1: per-Gaussian sums of the per-tile partials, zero rows, compact list of the blended Gaussians
 // 64 registers at most: two 1024-thread workgroups per CU (75 KB of LDS each) are eight waves per SIMD; at 72 registers only one
 // workgroup fits and the kernel runs 8 % slower on synth-v1
-__global__ void __launch_bounds__(64 * C3DGS_SUM_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) sum_partials_kernel(const BwdArgs a)
+__global__ void __launch_bounds__(BWD_LIST) __attribute__((amdgpu_waves_per_eu(8, 8))) sum_partials_kernel(const BwdArgs a)
 {
-    constexpr int SW = C3DGS_SUM_WAVES, LIST = 64 * SW;
+    constexpr int SW = SUM_WAVES, LIST = BWD_LIST;
     const int i = blockIdx.x * LIST + threadIdx.x;
     const size_t si = (size_t)i;
     const c3dgs_raster_grads& o = a.g;
@@ -145,7 +147,7 @@ __global__ void __launch_bounds__(64 * C3DGS_SUM_WAVES) __attribute__((amdgpu_wa
     // and every lane then adds up its own run from LDS. Fixed order -> still bitwise reproducible.
     constexpr int CH = C3DGS_BWD_CH;
     // one LDS staging area per wave for the partial sums [CH][9]; a wave only ever touches its own
-    __shared__ float s_buf[C3DGS_SUM_WAVES][CH * PARTIAL_FLOATS];
+    __shared__ float s_buf[SUM_WAVES][CH * PARTIAL_FLOATS];
 #define s_stage(w, sl, q) s_buf[w][(sl) * PARTIAL_FLOATS + (q)]
     // Only ~1/4 of the slots were ever written (the blend kernel stops at each tile's saturation point), so the wave
     // first reads the FLAG bytes of a whole sweep of FG*64 slots (independent byte loads, one wait), turns them into
@@ -153,8 +155,8 @@ __global__ void __launch_bounds__(64 * C3DGS_SUM_WAVES) __attribute__((amdgpu_wa
     // written slot. A lane's own run [start, end) maps to the contiguous entry range [below(start), below(end)), so the
     // summation loop touches no flags and one pass usually covers the wave's whole range.
     constexpr int FG = C3DGS_BWD_FG;
-    __shared__ unsigned long long s_fl[C3DGS_SUM_WAVES][FG];
-    __shared__ uint32_t s_pre[C3DGS_SUM_WAVES][FG + 1];
+    __shared__ unsigned long long s_fl[SUM_WAVES][FG];
+    __shared__ uint32_t s_pre[SUM_WAVES][FG + 1];
     bool any_written = false;            // did ANY pixel of ANY tile blend this Gaussian?
     float acc[PARTIAL_FLOATS];
 #pragma unroll
@@ -302,7 +304,7 @@ __global__ void __launch_bounds__(64 * C3DGS_SUM_WAVES) __attribute__((amdgpu_wa
             if (o.dL_drotations && a.scales) for (int q = 0; q < 4; q++) o.dL_drotations[4 * si + q] = 0.f;
         }
     }
-    // The blended ones go on the workgroup's list (256 entries per workgroup, filled from the front, in id order; a single
+    // The blended ones go on the workgroup's list (BWD_LIST entries per workgroup, filled from the front, in id order; a single
     // global list would cost one same-address atomic per wave). The nine sums are parked in the Gaussian's own FIRST slot
     // of the partial-sum array (only this wave reads this wave's slots, and it is done with them).
     __shared__ uint32_t s_cnt[SW];
@@ -338,12 +340,12 @@ backward_preprocess_kernel(const BwdArgs a, const float* __restrict__ cam_view, 
     // Lists fill from the front, so the populated quarters are spread evenly over the XCDs (consecutive workgroups go to
     // consecutive XCDs; quarter = blockIdx % 4 would send every full quarter to the same two of the eight) and the
     // mostly empty ones come last.
-    const uint32_t n_lists = gridDim.x / (C3DGS_SUM_WAVES / 4);
+    const uint32_t n_lists = gridDim.x / (BWD_LIST / 256);
     const uint32_t list = blockIdx.x % n_lists, quarter = blockIdx.x / n_lists;
     const uint32_t n_live = a.live_count[list];
     const uint32_t off = quarter * 256u + threadIdx.x;
     if ((off & ~63u) >= n_live) return;
-    const size_t pos = (size_t)list * (64 * C3DGS_SUM_WAVES) + off;
+    const size_t pos = (size_t)list * BWD_LIST + off;
     const bool live = off < n_live;
     const int i = live ? (int)a.live_ids[pos] : 0;
     const size_t si = (size_t)i;
@@ -606,9 +608,8 @@ backward_preprocess_kernel(const BwdArgs a, const float* __restrict__ cam_view, 
     }
 }
 
-void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g,
-                                float* partials, const uint8_t* touched, uint32_t* live_count, uint32_t* live_ids,
-                                uint32_t* live_slots, const c3dgs_raster_grads& gr, hipStream_t s)
+void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,
+                                const c3dgs_raster_grads& gr, hipStream_t s)
 {
     if (p.P <= 0) return;
     BwdArgs a;
@@ -621,12 +622,11 @@ void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* rad
     a.focal_x = p.W / (2.0f * p.tan_fovx);
     a.scale_modifier = p.scale_modifier;
     a.radii = radii; a.inst_offset = g.inst_offset; a.block_base = g.block_base; a.clamped = g.clamped; a.splat = g.splat;
-    a.partials = partials; a.touched = touched; a.g = gr;
-    a.live_count = live_count; a.live_ids = live_ids; a.live_slots = live_slots;
-    constexpr int LIST = 64 * C3DGS_SUM_WAVES;
-    const int n_lists = (p.P + LIST - 1) / LIST;
-    sum_partials_kernel<<<n_lists, LIST, 0, s>>>(a);
-    const dim3 grid(n_lists * (LIST / 256)), block(256);
+    a.partials = w.partials; a.touched = w.touched; a.g = gr;
+    a.live_count = w.live_count; a.live_ids = w.live_ids; a.live_slots = w.live_slots;
+    const int n_lists = (p.P + BWD_LIST - 1) / BWD_LIST;
+    sum_partials_kernel<<<n_lists, BWD_LIST, 0, s>>>(a);
+    const dim3 grid(n_lists * (BWD_LIST / 256)), block(256);
     const bool indexed = p.sh_indices != nullptr || p.g_indices != nullptr;
     const int deg = p.sh ? p.D : 0;
 #define C3DGS_LAUNCH(DEG)                                                                     \

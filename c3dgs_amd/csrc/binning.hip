@@ -41,9 +41,9 @@ size_t sort_temp_bytes(int R, int end_bit, int key_bytes)
                                         (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)R, 0u, (unsigned)end_bit);
     const size_t os = onesweep_tile_temp_bytes(R, end_bit, key_bytes);
     if (os > bytes) bytes = os;
-    // after the sort the region is reused for the tiles' compact lists: R mask bytes + R ids (compact_layout, common.hpp). Only
+    // after the sort the region is reused for the tiles' compact lists: R mask bytes + R ids (compact_bin_layout, common.hpp). Only
     // a one-pass sort (256 tiles or fewer) has no pair buffer that already is larger
-    const size_t reuse = compact_layout(R, 1, 1).bin_bytes;
+    const size_t reuse = compact_bin_layout(R).bin_bytes;
     if (reuse > bytes) bytes = reuse;
     return bytes < 256 ? 256 : bytes;
 }

@@ -15,16 +15,23 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 // ---- optional per-stage timing with HIP events recorded on the caller's stream (bench.py's roofline leg).
 // Disabled by default: zero cost. When enabled, every stage launch is bracketed by two events; nothing
 // synchronises until c3dgs_profile_read().
-enum Stage { ST_MARK_VISIBLE, ST_PREPROCESS, ST_DEPTH_SORT, ST_SCAN, ST_DUPLICATE, ST_SORT, ST_RANGES, ST_RENDER_FWD, ST_ZERO_PARTIALS,
-             ST_RENDER_BWD, ST_BWD_PREPROCESS, ST_WDIST, ST_VQ_ACC, ST_VQ_APPLY, ST_LOSS_FWD, ST_LOSS_BWD,
-             ST_QAT_OBSERVE, ST_QAT_CODEBOOKS, ST_QAT_VISIBLE, ST_QAT_POINTS, ST_QAT_POINTS_BWD, ST_QAT_CODEBOOKS_BWD, ST_ADAM,
-             ST_KNN_SORT, ST_KNN_BOUNDS, ST_KNN_QUERY, ST_COUNT };
-static const char* kStageNames[ST_COUNT] = { "mark_visible", "preprocess", "depth_sort", "scan", "duplicate_with_keys", "sort",
-                                             "identify_ranges", "render_forward", "zero_partials", "render_backward",
-                                             "backward_preprocess", "weighted_distance", "vq_accumulate", "vq_apply", "l1_ssim_forward",
-                                             "l1_ssim_backward", "qat_observe", "qat_codebooks", "qat_visible", "qat_points",
-                                             "qat_points_backward", "qat_codebooks_backward", "adam_step",
-                                             "knn_sort", "knn_bounds", "knn_query" };
+// The timed stages: ST_<id> and the name c3dgs_profile_read() reports and c3dgs_profile_only() selects (bench.py and tools/ go
+// by these names). Launches outside this table are checked with C3DGS_STAGE under a name of their own and never timed.
+#define C3DGS_STAGE_TABLE(X)                                                                                                   \
+    X(MARK_VISIBLE, "mark_visible") X(PREPROCESS, "preprocess") X(DEPTH_SORT, "depth_sort") X(SCAN, "scan")                    \
+    X(DUPLICATE, "duplicate_with_keys") X(SORT, "sort") X(RANGES, "identify_ranges") X(RENDER_FWD, "render_forward")           \
+    X(ZERO_PARTIALS, "zero_partials") X(RENDER_BWD, "render_backward") X(BWD_PREPROCESS, "backward_preprocess")                \
+    X(WDIST, "weighted_distance") X(VQ_ACC, "vq_accumulate") X(VQ_APPLY, "vq_apply") X(LOSS_FWD, "l1_ssim_forward")            \
+    X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
+    X(QAT_VISIBLE, "qat_visible") X(QAT_POINTS, "qat_points") X(QAT_POINTS_BWD, "qat_points_backward")                         \
+    X(QAT_CODEBOOKS_BWD, "qat_codebooks_backward") X(ADAM, "adam_step") X(KNN_SORT, "knn_sort") X(KNN_BOUNDS, "knn_bounds")    \
+    X(KNN_QUERY, "knn_query")
+#define C3DGS_X(id, name) ST_##id,
+enum Stage { C3DGS_STAGE_TABLE(C3DGS_X) ST_COUNT };
+#undef C3DGS_X
+#define C3DGS_X(id, name) name,
+static const char* const kStageNames[ST_COUNT] = { C3DGS_STAGE_TABLE(C3DGS_X) };
+#undef C3DGS_X
 struct ProfRec { int stage; hipEvent_t a, b; };
 static std::mutex g_prof_mu;
 static bool g_prof_on = false;
@@ -53,16 +60,25 @@ struct StageTimer {
         g_prof_recs.push_back({ stage, a, b });
     }
 };
+// after a timed stage: the launch check of C3DGS_STAGE under the stage's name in the table
+#define C3DGS_STAGE_CHECK(stage, debug, stream) C3DGS_STAGE(kStageNames[stage], debug, stream)
+// a timed stage that is ONE launch call: the events around it, then the check (a body that can return early stays written out)
+#define C3DGS_TIMED_STAGE(stage, debug, stream, ...)                                                \
+    do {                                                                                            \
+        { StageTimer t_(stage, stream); __VA_ARGS__; }                                              \
+        C3DGS_STAGE_CHECK(stage, debug, stream);                                                    \
+    } while (0)
 
 // Landing pad of the forward's single device->host read (one per calling thread): 64 bytes of page-locked host memory. When
 // the allocation can be MAPPED into the device's address space (coherent, fine-grained: the normal case), the kernel that
 // produces num_rendered stores {num_rendered, sort error word, sequence number} straight into it and the host polls the
 // sequence number -- no copy command on the stream (a ~4 us launch + a ~6 us bubble per forward). Otherwise (`dev` null):
 // a hipMemcpyAsync into it behind an event, as before.
+// One read is begin() -> [the producing kernel is launched with `dev` and the sequence number] -> queue_copy() -> wait().
 struct HostRead {
     uint32_t* pinned = nullptr;
     uint32_t* dev = nullptr;      // device-side address of `pinned`, or null
-    uint32_t seq = 0;
+    uint32_t seq = 0;             // mapped pad: sequence number of the read in flight
     hipEvent_t ev{};
     HostRead()
     {
@@ -77,6 +93,59 @@ struct HostRead {
             if (hipHostMalloc((void**)&pinned, 64, hipHostMallocDefault) != hipSuccess) { pinned = nullptr; return; }
         }
         if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(pinned); pinned = nullptr; dev = nullptr; }
+    }
+    // -> the sequence number the producing kernel stores behind the two words (0 on the copy path: nothing is stored)
+    uint32_t begin()
+    {
+        if (!dev) return 0u;
+        if (++seq == 0u) seq = 1u;                                       // (wrap-around: 0 is the pad's initial value)
+        return seq;
+    }
+    // the two words at `src`, {num_rendered, sort error word}, into the pad
+    int copy_words(const uint32_t* src, hipStream_t s)
+    {
+        C3DGS_HIP_TRY(hipMemcpyAsync(pinned, src, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        return C3DGS_OK;
+    }
+    // copy path: the copy lands in pinned memory behind an event; to be queued as soon as the words exist on the stream
+    int queue_copy(const uint32_t* src, hipStream_t s)
+    {
+        if (dev) return C3DGS_OK;
+        if (int rc = copy_words(src, s)) return rc;
+        C3DGS_HIP_TRY(hipEventRecord(ev, s));
+        return C3DGS_OK;
+    }
+    // -> words[2] of this read. Polls instead of sleeping in the driver: on a busy host the wake-up from a blocking event wait
+    // can take milliseconds (seen as a 2x slower step with unchanged kernel times); the words are normally there within ~100 us.
+    int wait(const uint32_t* src, hipStream_t s, uint32_t words[2])
+    {
+        if (dev) {
+            // mapped pad: wait for this read's sequence number. Every ~64k polls the stream is queried as well: if it has drained
+            // (or failed) and the number still is not there, the store never became visible -> fetch the two words with a copy
+            volatile uint32_t* pad = pinned;
+            bool seen = false;
+            for (long spins = 0; !seen; spins++) {
+                seen = __atomic_load_n(&pad[2], __ATOMIC_ACQUIRE) == seq;
+                if (!seen && (spins & 0xffff) == 0xffff) {
+                    const hipError_t q = hipStreamQuery(s);
+                    if (q == hipErrorNotReady) continue;
+                    if (q != hipSuccess) return fail(C3DGS_E_HIP, std::string("num_rendered read: ") + hipGetErrorString(q));
+                    seen = __atomic_load_n(&pad[2], __ATOMIC_ACQUIRE) == seq;
+                    if (!seen) {
+                        if (int rc = copy_words(src, s)) return rc;
+                        C3DGS_HIP_TRY(hipStreamSynchronize(s));
+                        seen = true;
+                    }
+                }
+            }
+        } else {
+            hipError_t q = hipErrorNotReady;
+            for (long spins = 0; spins < 20000000L && (q = hipEventQuery(ev)) == hipErrorNotReady; spins++) { }
+            if (q == hipErrorNotReady) q = hipEventSynchronize(ev);
+            if (q != hipSuccess) return fail(C3DGS_E_HIP, std::string("num_rendered read: ") + hipGetErrorString(q));
+        }
+        words[0] = pinned[0]; words[1] = pinned[1];
+        return C3DGS_OK;
     }
 };
 static HostRead& host_read()
@@ -134,7 +203,7 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
     const int gx = tiles_x(W), gy = tiles_y(H);
     *num_rendered = 0;
 
-    c3dgs_image_layout IL; image_layout(W, H, &IL);
+    ImageLayout IL; image_layout(W, H, &IL);
     void* img_base = image_resize(image_user, IL.total_bytes);
     if (!img_base) return fail(C3DGS_E_ALLOC, "image buffer allocation failed");
     const ImgPtrs img = img_ptrs(img_base, W, H);
@@ -156,61 +225,31 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
     if (!sort_err) return fail(C3DGS_E_HIP, "cannot resolve the sort error word");
     HostRead& hr = host_read();
     if (!hr.pinned) return fail(C3DGS_E_HIP, "pinned host buffer allocation failed");
-    const uint32_t seq = hr.dev ? ++hr.seq : 0u;
-    if (hr.dev && seq == 0u) hr.seq = 1u;                                // (wrap-around: 0 is the pad's initial value)
-    const uint32_t want_seq = hr.dev ? hr.seq : 0u;
+    const uint32_t host_seq = hr.begin();
     // the depth sort's control words are cleared by preprocess's workgroups (0 bytes: that sort clears its own)
     const size_t dclear = depth_sort_clear_bytes(P) <= g.scan_temp_bytes ? depth_sort_clear_bytes(P) : 0;
     { StageTimer t_(ST_PREPROCESS, s);
       if (geom_gtab_bytes(p)) launch_pack_codebook(p, g.gtab, s);
-      launch_preprocess(p, g, radii, img.ranges, sort_err, g.scan_temp, dclear / 16, hr.dev, want_seq, s); }
-    C3DGS_STAGE("preprocess", p.debug, s);
+      launch_preprocess(p, g, radii, img.ranges, sort_err, g.scan_temp, dclear / 16, hr.dev, host_seq, s); }
+    C3DGS_STAGE_CHECK(ST_PREPROCESS, p.debug, s);
     // The one device->host read of the forward (K4, num_rendered) is issued as EARLY as its value exists: R is the last
-    // entry of block_base[]. The copy lands in pinned memory behind an event while the depth sort and the depth-order
-    // scan are already queued, so the GPU keeps working while the host waits, sizes the binning buffer and queues the
-    // rest (the reference blocks the stream at this point, rasterizer_impl.cu:279).
+    // entry of block_base[]. It lands in the host pad while the depth sort and the depth-order scan are already queued, so
+    // the GPU keeps working while the host waits, sizes the binning buffer and queues the rest (the reference blocks the
+    // stream at this point, rasterizer_impl.cu:279).
     // second word: the device's sticky sort time-out flag as of the start of this call (radix_sort.hip)
-    if (!hr.dev) {
-        C3DGS_HIP_TRY(hipMemcpyAsync(hr.pinned, g.block_base + (P + 255) / 256, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        C3DGS_HIP_TRY(hipEventRecord(hr.ev, s));
-    }
+    const uint32_t* r_words = g.block_base + (P + 255) / 256;
+    if (int rc = hr.queue_copy(r_words, s)) return rc;
     { StageTimer t_(ST_DEPTH_SORT, s);                                               // binning stage 1: P Gaussians by depth
       C3DGS_HIP_TRY(run_depth_sort(g.scan_temp, g.scan_temp_bytes, g.depth_keys, g.depth_keys_sorted, nullptr, g.depth_order, P,
                                    reinterpret_cast<const uint2*>(g.rects), g.sorted_offsets, s, dclear != 0,
                                    /*rects_fit_bytes=*/gx <= 255 && gy <= 255)); }
-    C3DGS_STAGE("depth_sort", p.debug, s);
+    C3DGS_STAGE_CHECK(ST_DEPTH_SORT, p.debug, s);
     if (p.debug && onesweep_timed_out(s)) return fail(C3DGS_E_HIP, "depth sort: look-back timed out");
-    { StageTimer t_(ST_SCAN, s); launch_depth_order_scan(P, g, s); }                 // K3, in depth order (two-level)
-    C3DGS_STAGE("scan", p.debug, s);
-    // Poll instead of sleeping in the driver: on a busy host the wake-up from a blocking event wait can take
-    // milliseconds (seen as a 2x slower step with unchanged kernel times); the copy is normally done within ~100 us.
-    if (hr.dev) {
-        // mapped pad: wait for this call's sequence number. Every ~64k polls the stream is queried as well: if it has drained
-        // (or failed) and the number still is not there, the store never became visible -> fetch the two words with a copy
-        volatile uint32_t* pad = hr.pinned;
-        bool seen = false;
-        for (long spins = 0; !seen; spins++) {
-            seen = __atomic_load_n(&pad[2], __ATOMIC_ACQUIRE) == want_seq;
-            if (!seen && (spins & 0xffff) == 0xffff) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q == hipErrorNotReady) continue;
-                if (q != hipSuccess) return fail(C3DGS_E_HIP, std::string("num_rendered read: ") + hipGetErrorString(q));
-                seen = __atomic_load_n(&pad[2], __ATOMIC_ACQUIRE) == want_seq;
-                if (!seen) {
-                    C3DGS_HIP_TRY(hipMemcpyAsync(hr.pinned, g.block_base + (P + 255) / 256, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-                    C3DGS_HIP_TRY(hipStreamSynchronize(s));
-                    seen = true;
-                }
-            }
-        }
-    } else {
-        hipError_t q = hipErrorNotReady;
-        for (long spins = 0; spins < 20000000L && (q = hipEventQuery(hr.ev)) == hipErrorNotReady; spins++) { }
-        if (q == hipErrorNotReady) q = hipEventSynchronize(hr.ev);
-        if (q != hipSuccess) return fail(C3DGS_E_HIP, std::string("num_rendered read: ") + hipGetErrorString(q));
-    }
-    const uint32_t R_u = hr.pinned[0];
-    if (hr.pinned[1] != 0) {
+    C3DGS_TIMED_STAGE(ST_SCAN, p.debug, s, launch_depth_order_scan(P, g, s));        // K3, in depth order (two-level)
+    uint32_t words[2];
+    if (int rc = hr.wait(r_words, s, words)) return rc;
+    const uint32_t R_u = words[0];
+    if (words[1] != 0) {
         // A radix-sort look-back timed out in an EARLIER rasterizer call on this device (that call's image was poisoned with
         // NaN by render_forward). Not silent outside debug mode: fail here, at the forward's one natural host read.
         C3DGS_HIP_TRY(hipMemsetAsync(sort_err, 0, sizeof(uint32_t), s));
@@ -231,21 +270,18 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
         // the tile sort's control words are cleared by the pair emission's workgroups (0 bytes: that sort clears its own)
         size_t tclear = tile_sort_clear_bytes(R, end_bit, b.key_bytes);
         if (tclear > b.sort_temp_bytes) tclear = 0;
-        { StageTimer t_(ST_DUPLICATE, s); launch_duplicate_with_keys(P, g, b, gx, sort_err, b.sort_temp, tclear / 16, s); } // K5
-        C3DGS_STAGE("duplicate_with_keys", p.debug, s);
+        C3DGS_TIMED_STAGE(ST_DUPLICATE, p.debug, s, launch_duplicate_with_keys(P, g, b, gx, sort_err, b.sort_temp, tclear / 16, s)); // K5
         { StageTimer t_(ST_SORT, s);
           C3DGS_HIP_TRY(run_tile_sort(b.sort_temp, b.sort_temp_bytes, b.keys_unsorted, b.keys_sorted, b.key_bytes, b.values_unsorted,
                                       b.point_list, R, end_bit, s, tclear != 0)); }  // K6, binning stage 2
-        C3DGS_STAGE("sort", p.debug, s);
+        C3DGS_STAGE_CHECK(ST_SORT, p.debug, s);
         if (p.debug && onesweep_timed_out(s)) return fail(C3DGS_E_HIP, "tile sort: look-back timed out");
-        { StageTimer t_(ST_RANGES, s); launch_identify_ranges(R, b.keys_sorted, b.key_bytes, img.ranges, sort_err, s); } // K8
-        C3DGS_STAGE("identify_ranges", p.debug, s);
+        C3DGS_TIMED_STAGE(ST_RANGES, p.debug, s, launch_identify_ranges(R, b.keys_sorted, b.key_bytes, img.ranges, sort_err, s)); // K8
     }
-    { StageTimer t_(ST_RENDER_FWD, s);
-      // the tiles' compact lists (ids + quadrant masks of the entries that can reach their tile) go to the now idle sort scratch:
-      // 5 R bytes, what the backward walks instead of the point list
-      launch_render_forward(W, H, img, b.point_list, g.splat, p.background, out_color, compact_ptrs(b, R, W, H), sort_err, s); } // K9
-    C3DGS_STAGE("render_forward", p.debug, s);
+    // the tiles' compact lists (ids + quadrant masks of the entries that can reach their tile) go to the now idle sort scratch:
+    // 5 R bytes, what the backward walks instead of the point list
+    C3DGS_TIMED_STAGE(ST_RENDER_FWD, p.debug, s,
+                      launch_render_forward(W, H, img, b.point_list, g.splat, p.background, out_color, compact_ptrs(b, R), sort_err, s)); // K9
     return C3DGS_OK;
 }
 
@@ -291,35 +327,25 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
 
     const GeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
     const ImgPtrs img = img_ptrs(const_cast<void*>(image_buffer), W, H);
-    const size_t ws_bytes = c3dgs_backward_workspace_bytes(P, R);
-    float* partials = (float*)ws_resize(ws_user, ws_bytes);
-    if (!partials) return fail(C3DGS_E_ALLOC, "backward workspace allocation failed");
+    void* ws_base = ws_resize(ws_user, c3dgs_backward_workspace_bytes(P, R));
+    if (!ws_base) return fail(C3DGS_E_ALLOC, "backward workspace allocation failed");
+    const BwdPtrs w = bwd_ptrs(ws_base, P, R);
 
     // only the 1-byte "written" flags are cleared (R bytes, not 36 R): the blend kernel never visits the instances
     // behind each tile's saturation point (73 % of them on the bench scene) and the per-Gaussian kernel skips them.
-    // Workspace: partial sums | flags | tile schedule | per-workgroup lists of the blended Gaussians (id, slot) and their lengths
-    const size_t r1 = (size_t)(R > 0 ? R : 1), p256 = ((size_t)P + 1023) / 1024 * 1024;   // whole lists (<= 1024 entries each)
-    uint8_t* touched = (uint8_t*)partials + align_up(r1 * PARTIAL_FLOATS * sizeof(float));
-    uint32_t* tile_order = img.tile_order;                     // T words of the image buffer (scratch of this call)
-    uint32_t* live_ids = (uint32_t*)(touched + align_up(r1)) + 65536;   // (the 256 KB in front are the pre-version-4 home of the tile schedule)
-    uint32_t* live_slots = live_ids + p256;
-    uint32_t* live_count = live_slots + p256;
-    // one launch: tile schedule of the blend kernel + the flag clear. The codebook-gradient clear (80 MB on the bench view, needed
-    // only by the per-Gaussian kernel's scatter-adds) rides in the blend kernel itself, a slice per tile workgroup: that kernel is
-    // bound by vector issue and leaves the memory system idle (without a blend launch the clear stays here)
+    // one launch: tile schedule of the blend kernel (img.tile_order: scratch of this call) + the flag clear. The codebook-gradient
+    // clear (80 MB on the bench view, needed only by the per-Gaussian kernel's scatter-adds) rides in the blend kernel itself, a
+    // slice per tile workgroup: that kernel is bound by vector issue and leaves the memory system idle (without a blend launch
+    // the clear stays here)
     { StageTimer t_(ST_ZERO_PARTIALS, s);
-      launch_backward_prep(R > 0 ? W : 0, H, img, tile_order, touched, align_up(r1) / 16, R > 0 ? nullptr : cb_zero,
-                           R > 0 ? 0 : cb_zero16, s); }
+      launch_backward_prep(R > 0 ? W : 0, H, img, w.touched, w.touched_bytes / 16, R > 0 ? nullptr : cb_zero, R > 0 ? 0 : cb_zero16, s); }
     if (R > 0) {
         const BinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), R, W, H);
-        { StageTimer t_(ST_RENDER_BWD, s);
-          launch_render_backward(W, H, img, g.splat, g.block_base, p.background, dL_dout_color, partials, touched,
-                                 compact_ptrs(b, R, W, H), tile_order, cb_zero, cb_zero16, s); } // K10
-        C3DGS_STAGE("render_backward", p.debug, s);
+        C3DGS_TIMED_STAGE(ST_RENDER_BWD, p.debug, s,
+                          launch_render_backward(W, H, img, g.splat, g.block_base, p.background, dL_dout_color, w.partials, w.touched,
+                                                 compact_ptrs(b, R), cb_zero, cb_zero16, s)); // K10
     }
-    { StageTimer t_(ST_BWD_PREPROCESS, s);
-      launch_backward_preprocess(p, radii, g, partials, touched, live_count, live_ids, live_slots, *grads, s); } // K11 + K12(i)
-    C3DGS_STAGE("backward_preprocess", p.debug, s);
+    C3DGS_TIMED_STAGE(ST_BWD_PREPROCESS, p.debug, s, launch_backward_preprocess(p, radii, g, w, *grads, s)); // K11 + K12(i)
     return C3DGS_OK;
 }
 
@@ -396,25 +422,30 @@ int c3dgs_get_binning_layout(int32_t R, int32_t W, int32_t H, c3dgs_binning_layo
 int c3dgs_get_image_layout(int32_t W, int32_t H, c3dgs_image_layout* out)
 {
     if (!out || W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, "bad arguments");
-    image_layout(W, H, out);
+    ImageLayout L; image_layout(W, H, &L);
+    *out = L;                                                        // the public fields
     return C3DGS_OK;
 }
 int c3dgs_get_compact_layout(int32_t R, int32_t W, int32_t H, c3dgs_compact_layout* out)
 {
     if (!out || R < 0 || W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, "bad arguments");
     c3dgs_binning_layout BL; binning_layout(R, W, H, &BL);
-    const CompactLayout C = compact_layout(R, W, H);
+    const CompactBinLayout C = compact_bin_layout(R);
+    ImageLayout IL; image_layout(W, H, &IL);
     out->cqm = BL.sort_temp + C.cqm; out->cid = BL.sort_temp + C.cid;
-    out->tile_used_c = C.tile_used_c; out->n_contrib_c = C.n_contrib_c;
+    out->tile_used_c = IL.tile_used_c; out->n_contrib_c = IL.n_contrib_c;
+    return C3DGS_OK;
+}
+int c3dgs_get_backward_layout(int32_t P, int32_t R, c3dgs_backward_layout* out)
+{
+    if (!out || P < 0 || R < 0) return fail(C3DGS_E_INVALID, "bad arguments");
+    backward_layout(P, R, out);
     return C3DGS_OK;
 }
 size_t c3dgs_backward_workspace_bytes(int32_t P, int32_t R)
 {
-    const size_t r = (size_t)(R > 0 ? R : 1), p256 = ((size_t)(P > 0 ? P : 1) + 1023) / 1024 * 1024;
-    // partial sums + 1-byte written flags + the backward's tile schedule (at most 65536 tiles) + the per-workgroup lists of
-    // blended Gaussians (id, slot of its sums: 256 entries per workgroup) + their lengths
-    return align_up(r * PARTIAL_FLOATS * sizeof(float)) + align_up(r) + 65536 * sizeof(uint32_t) +
-           (2 * p256 + p256 / 256) * sizeof(uint32_t) + 256;
+    c3dgs_backward_layout L; backward_layout(P, R, &L);
+    return L.total_bytes;
 }
 
 int c3dgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
@@ -424,8 +455,7 @@ int c3dgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix,
     if (P < 0) return fail(C3DGS_E_INVALID, "P must be >= 0");
     if (P == 0) return C3DGS_OK;
     if (!means3D || !viewmatrix || !present) return fail(C3DGS_E_INVALID, "means3D, viewmatrix and present are required");
-    { StageTimer t_(ST_MARK_VISIBLE, (hipStream_t)stream); launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream); }
-    C3DGS_STAGE("mark_visible", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_MARK_VISIBLE, 0, (hipStream_t)stream, launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream));
     return C3DGS_OK;
 }
 
@@ -434,8 +464,7 @@ int c3dgs_mark_visible_pose(int32_t P, const float* means3D, const float* extrin
     if (P < 0) return fail(C3DGS_E_INVALID, "P must be >= 0");
     if (P == 0) return C3DGS_OK;
     if (!means3D || !extrinsic_vector || !present) return fail(C3DGS_E_INVALID, "means3D, extrinsic_vector and present are required");
-    { StageTimer t_(ST_MARK_VISIBLE, (hipStream_t)stream); launch_mark_visible_pose(P, means3D, extrinsic_vector, present, (hipStream_t)stream); }
-    C3DGS_STAGE("mark_visible", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_MARK_VISIBLE, 0, (hipStream_t)stream, launch_mark_visible_pose(P, means3D, extrinsic_vector, present, (hipStream_t)stream));
     return C3DGS_OK;
 }
 
@@ -493,7 +522,7 @@ int c3dgs_weighted_distance(int64_t N, int32_t C, int32_t K, const float* coefs,
         if (launch_weighted_distance(N, C, K, coefs, gather, codebook, out_dist, out_idx, (hipStream_t)stream))
             return fail(C3DGS_E_INVALID, "unsupported channel count");
     }
-    C3DGS_STAGE("weighted_distance", 0, (hipStream_t)stream);
+    C3DGS_STAGE_CHECK(ST_WDIST, 0, (hipStream_t)stream);
     return C3DGS_OK;
 }
 
@@ -510,7 +539,7 @@ int c3dgs_weighted_distance_ws(int64_t N, int32_t C, int32_t K, const float* coe
         if (launch_weighted_distance(N, C, K, coefs, gather, codebook, out_dist, out_idx, (hipStream_t)stream, ws, ws ? ws_bytes : 0))
             return fail(C3DGS_E_INVALID, "unsupported channel count");
     }
-    C3DGS_STAGE("weighted_distance", 0, (hipStream_t)stream);
+    C3DGS_STAGE_CHECK(ST_WDIST, 0, (hipStream_t)stream);
     return C3DGS_OK;
 }
 
@@ -520,8 +549,7 @@ int c3dgs_vq_accumulate(int64_t B, int32_t K, int32_t D, const float* x, const f
     if (B < 0 || K <= 0 || D <= 0) return fail(C3DGS_E_INVALID, "bad sizes");
     if (B == 0) return C3DGS_OK;
     if (!x || !w || !idx || !S) return fail(C3DGS_E_INVALID, "x, w, idx and S are required");
-    { StageTimer t_(ST_VQ_ACC, (hipStream_t)stream); launch_vq_accumulate(B, K, D, x, w, gather, idx, dist, S, dist_sum, (hipStream_t)stream); }
-    C3DGS_STAGE("vq_accumulate", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_VQ_ACC, 0, (hipStream_t)stream, launch_vq_accumulate(B, K, D, x, w, gather, idx, dist, S, dist_sum, (hipStream_t)stream));
     return C3DGS_OK;
 }
 
@@ -540,7 +568,7 @@ int c3dgs_vq_sums(int64_t B, int32_t K, int32_t D, const float* x, const float* 
         if (launch_weighted_distance(B, K, D, x, gather, codebook, dist, idx, (hipStream_t)stream, ws, ws ? ws_bytes : 0))
             return fail(C3DGS_E_INVALID, "unsupported channel count");
     }
-    C3DGS_STAGE("weighted_distance", 0, (hipStream_t)stream);
+    C3DGS_STAGE_CHECK(ST_WDIST, 0, (hipStream_t)stream);
     return c3dgs_vq_accumulate(B, K, D, x, w, gather, idx, dist, S, dist_sum, stream);
 }
 
@@ -568,10 +596,9 @@ int c3dgs_vq_step_sums(int32_t step, int64_t B, int32_t K, int32_t D, const floa
             return fail(C3DGS_E_INVALID, "vq_step_sums: unsupported shape");
         if (step == 0) launch_vq_seed_words(K, D, ws, s);
     }
-    C3DGS_STAGE("weighted_distance", 0, s);
-    { StageTimer t_(ST_VQ_ACC, s);
-      launch_vq_accumulate(B, K, D, x, w, gather, idx, dist, S, dist_sum, s, vq_next_absmax_word(K, D, ws, step & 1)); }
-    C3DGS_STAGE("vq_accumulate", 0, s);
+    C3DGS_STAGE_CHECK(ST_WDIST, 0, s);
+    C3DGS_TIMED_STAGE(ST_VQ_ACC, 0, s,
+                      launch_vq_accumulate(B, K, D, x, w, gather, idx, dist, S, dist_sum, s, vq_next_absmax_word(K, D, ws, step & 1)));
     return C3DGS_OK;
 }
 
@@ -582,7 +609,7 @@ int c3dgs_vq_step_apply(int32_t step, int32_t K, int32_t D, float* S, float* cod
     { StageTimer t_(ST_VQ_APPLY, (hipStream_t)stream);
       if (launch_vq_apply_split(K, D, S, codebook, entry_importance, decay, alpha, eps, scale_normalize, ws, ws_bytes, step & 1, (hipStream_t)stream))
           return fail(C3DGS_E_INVALID, "vq_step_apply: shape / scratch not served by the fused step (see c3dgs_vq_step_supported)"); }
-    C3DGS_STAGE("vq_apply", 0, (hipStream_t)stream);
+    C3DGS_STAGE_CHECK(ST_VQ_APPLY, 0, (hipStream_t)stream);
     return C3DGS_OK;
 }
 
@@ -590,8 +617,8 @@ int c3dgs_vq_apply(int32_t K, int32_t D, const float* S, float* codebook, float*
                    float alpha, float eps, int32_t scale_normalize, void* stream)
 {
     if (K <= 0 || D <= 0 || !S || !codebook || !entry_importance) return fail(C3DGS_E_INVALID, "bad arguments");
-    { StageTimer t_(ST_VQ_APPLY, (hipStream_t)stream); launch_vq_apply(K, D, S, codebook, entry_importance, decay, alpha, eps, scale_normalize, (hipStream_t)stream); }
-    C3DGS_STAGE("vq_apply", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_VQ_APPLY, 0, (hipStream_t)stream,
+                      launch_vq_apply(K, D, S, codebook, entry_importance, decay, alpha, eps, scale_normalize, (hipStream_t)stream));
     return C3DGS_OK;
 }
 
@@ -617,11 +644,9 @@ int c3dgs_knn_mean_dist2(int32_t P, const float* xyz, float* out, void* workspac
     hipStream_t s = (hipStream_t)stream;
     { StageTimer t_(ST_KNN_SORT, s);
       if (run_knn_sort(P, xyz, workspace, s)) return fail(C3DGS_E_HIP, "knn_mean_dist2: sort failed"); }
-    C3DGS_STAGE("knn_sort", 0, s);
-    { StageTimer t_(ST_KNN_BOUNDS, s); launch_knn_bounds(P, workspace, s); }
-    C3DGS_STAGE("knn_bounds", 0, s);
-    { StageTimer t_(ST_KNN_QUERY, s); launch_knn_query(P, workspace, out, s); }
-    C3DGS_STAGE("knn_query", 0, s);
+    C3DGS_STAGE_CHECK(ST_KNN_SORT, 0, s);
+    C3DGS_TIMED_STAGE(ST_KNN_BOUNDS, 0, s, launch_knn_bounds(P, workspace, s));
+    C3DGS_TIMED_STAGE(ST_KNN_QUERY, 0, s, launch_knn_query(P, workspace, out, s));
     return C3DGS_OK;
 }
 
@@ -641,8 +666,7 @@ int c3dgs_adam_step(int32_t n_tensors, const c3dgs_adam_tensor* tensors, double 
     for (int k = 0; k < n_tensors; k++)
         if (tensors[k].n > 0 && (!tensors[k].param || !tensors[k].grad || !tensors[k].exp_avg || !tensors[k].exp_avg_sq))
             return fail(C3DGS_E_INVALID, "adam_step: NULL tensor pointer");
-    { StageTimer t_(ST_ADAM, (hipStream_t)stream); launch_adam(n_tensors, tensors, beta1, beta2, eps, (hipStream_t)stream); }
-    C3DGS_STAGE("adam_step", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_ADAM, 0, (hipStream_t)stream, launch_adam(n_tensors, tensors, beta1, beta2, eps, (hipStream_t)stream));
     return C3DGS_OK;
 }
 
@@ -742,11 +766,8 @@ int c3dgs_l1_ssim_forward(int32_t C, int32_t H, int32_t W, const float* img, con
     hipStream_t s = (hipStream_t)stream;
     C3DGS_HIP_TRY(hipMemsetAsync(sums, 0, 128 * sizeof(double), s));
     const size_t n = (size_t)C * H * W;
-    {
-        StageTimer t_(ST_LOSS_FWD, s);
-        launch_l1_ssim_forward(C, H, W, img, gt, dmaps, dmaps ? dmaps + n : nullptr, dmaps ? dmaps + 2 * n : nullptr, sums, s);
-    }
-    C3DGS_STAGE("l1_ssim_forward", 0, s);
+    C3DGS_TIMED_STAGE(ST_LOSS_FWD, 0, s,
+                      launch_l1_ssim_forward(C, H, W, img, gt, dmaps, dmaps ? dmaps + n : nullptr, dmaps ? dmaps + 2 * n : nullptr, sums, s));
     return C3DGS_OK;
 }
 
@@ -765,11 +786,8 @@ int c3dgs_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float* img, co
         return fail(C3DGS_E_INVALID, "l1_ssim_backward: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)C * H * W;
-    {
-        StageTimer t_(ST_LOSS_BWD, s);
-        launch_l1_ssim_backward(C, H, W, img, gt, dmaps, dmaps + n, dmaps + 2 * n, grad_loss, l1_coeff, ssim_coeff, dL_dimg, s);
-    }
-    C3DGS_STAGE("l1_ssim_backward", 0, s);
+    C3DGS_TIMED_STAGE(ST_LOSS_BWD, 0, s,
+                      launch_l1_ssim_backward(C, H, W, img, gt, dmaps, dmaps + n, dmaps + 2 * n, grad_loss, l1_coeff, ssim_coeff, dL_dimg, s));
     return C3DGS_OK;
 }
 
@@ -813,8 +831,7 @@ int c3dgs_qat_observe(const c3dgs_qat_params* q, void* workspace, void* stream)
 {
     if (int rc = qat_validate(q, "qat_observe")) return rc;
     if (!workspace) return fail(C3DGS_E_INVALID, "qat_observe: workspace is required");
-    { StageTimer t_(ST_QAT_OBSERVE, (hipStream_t)stream); launch_qat_observe(*q, workspace, (hipStream_t)stream); }
-    C3DGS_STAGE("qat_observe", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_QAT_OBSERVE, 0, (hipStream_t)stream, launch_qat_observe(*q, workspace, (hipStream_t)stream));
     return C3DGS_OK;
 }
 
@@ -822,8 +839,7 @@ int c3dgs_qat_codebooks(const c3dgs_qat_params* q, float* scales_n, float* rotat
 {
     if (int rc = qat_validate(q, "qat_codebooks")) return rc;
     if (misaligned16(rotations) || misaligned16(shs)) return fail(C3DGS_E_INVALID, "qat_codebooks: outputs must be 16-byte aligned");
-    { StageTimer t_(ST_QAT_CODEBOOKS, (hipStream_t)stream); launch_qat_codebooks(*q, scales_n, rotations, shs, (hipStream_t)stream); }
-    C3DGS_STAGE("qat_codebooks", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_QAT_CODEBOOKS, 0, (hipStream_t)stream, launch_qat_codebooks(*q, scales_n, rotations, shs, (hipStream_t)stream));
     return C3DGS_OK;
 }
 
@@ -836,12 +852,9 @@ int c3dgs_qat_codebooks_backward(const c3dgs_qat_params* q, const float* dL_dsca
         return fail(C3DGS_E_INVALID, "qat_codebooks_backward: rotation / sh gradients must be 16-byte aligned");
     if (dL_dshs && q->features_dc && (!dL_dfeatures_dc || (q->M > 1 && !dL_dfeatures_rest)))
         return fail(C3DGS_E_INVALID, "qat_codebooks_backward: dL_dfeatures_dc / dL_dfeatures_rest are required with dL_dshs");
-    {
-        StageTimer t_(ST_QAT_CODEBOOKS_BWD, (hipStream_t)stream);
-        launch_qat_codebooks_backward(*q, dL_dscales_n, dL_drotations, dL_dshs, dL_dscaling, dL_drotation, dL_dfeatures_dc,
-                                      dL_dfeatures_rest, (hipStream_t)stream);
-    }
-    C3DGS_STAGE("qat_codebooks_backward", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_QAT_CODEBOOKS_BWD, 0, (hipStream_t)stream,
+                      launch_qat_codebooks_backward(*q, dL_dscales_n, dL_drotations, dL_dshs, dL_dscaling, dL_drotation, dL_dfeatures_dc,
+                                                    dL_dfeatures_rest, (hipStream_t)stream));
     return C3DGS_OK;
 }
 
@@ -854,7 +867,7 @@ int c3dgs_qat_visible(const c3dgs_qat_params* q, const float* viewmatrix, uint8_
     if (q->P == 0) { C3DGS_HIP_TRY(hipMemsetAsync(count, 0, sizeof(int32_t), s)); return C3DGS_OK; }
     if (!q->xyz || !viewmatrix || !visible || !rank || !scan_workspace) return fail(C3DGS_E_INVALID, "qat_visible: bad arguments");
     { StageTimer t_(ST_QAT_VISIBLE, s); C3DGS_HIP_TRY(run_qat_visible(*q, viewmatrix, visible, rank, count, scan_workspace, s)); }
-    C3DGS_STAGE("qat_visible", 0, s);
+    C3DGS_STAGE_CHECK(ST_QAT_VISIBLE, 0, s);
     return C3DGS_OK;
 }
 
@@ -864,12 +877,9 @@ int c3dgs_qat_points(const c3dgs_qat_params* q, const uint8_t* visible, const in
 {
     if (int rc = qat_validate(q, "qat_points")) return rc;
     if ((visible == nullptr) != (rank == nullptr)) return fail(C3DGS_E_INVALID, "qat_points: visible and rank go together");
-    {
-        StageTimer t_(ST_QAT_POINTS, (hipStream_t)stream);
-        launch_qat_points(*q, visible, rank, sh_indices, g_indices, means3D, opacities, scale_factors, sh_indices_out,
-                          g_indices_out, (hipStream_t)stream);
-    }
-    C3DGS_STAGE("qat_points", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_QAT_POINTS, 0, (hipStream_t)stream,
+                      launch_qat_points(*q, visible, rank, sh_indices, g_indices, means3D, opacities, scale_factors, sh_indices_out,
+                                        g_indices_out, (hipStream_t)stream));
     return C3DGS_OK;
 }
 
@@ -881,12 +891,9 @@ int c3dgs_qat_points_backward(const c3dgs_qat_params* q, const uint8_t* visible,
     if ((visible == nullptr) != (rank == nullptr)) return fail(C3DGS_E_INVALID, "qat_points_backward: visible and rank go together");
     if ((dL_dopacity && dL_dopacities && !q->opacity) || (dL_dscaling_factor && dL_dscale_factors && !q->scaling_factor))
         return fail(C3DGS_E_INVALID, "qat_points_backward: the raw opacity / scaling_factor are needed to recompute the masks");
-    {
-        StageTimer t_(ST_QAT_POINTS_BWD, (hipStream_t)stream);
-        launch_qat_points_backward(*q, visible, rank, dL_dmeans3D, dL_dmeans2D, dL_dopacities, dL_dscale_factors, dL_dxyz,
-                                   dL_dscreenspace, dL_dopacity, dL_dscaling_factor, (hipStream_t)stream);
-    }
-    C3DGS_STAGE("qat_points_backward", 0, (hipStream_t)stream);
+    C3DGS_TIMED_STAGE(ST_QAT_POINTS_BWD, 0, (hipStream_t)stream,
+                      launch_qat_points_backward(*q, visible, rank, dL_dmeans3D, dL_dmeans2D, dL_dopacities, dL_dscale_factors, dL_dxyz,
+                                                 dL_dscreenspace, dL_dopacity, dL_dscaling_factor, (hipStream_t)stream));
     return C3DGS_OK;
 }
 

@@ -15,6 +15,7 @@ constexpr int TILE = 16;          // reference BLOCK_X = BLOCK_Y = 16 (cuda_rast
 constexpr int TILE_PIX = 256;
 constexpr int SPLAT_F4 = 3;       // float4 per splat record (48 B)
 constexpr int PARTIAL_FLOATS = 9; // dcolor(3) dmean2D(2) dconic(3) dopacity(1) per (Gaussian,tile) instance
+constexpr int BWD_LIST = 1024;    // Gaussians that share one list of blended ones = threads of a sum_partials_kernel workgroup
 
 // ---------------------------------------------------------------- errors
 void set_error(const std::string& msg);
@@ -126,36 +127,48 @@ inline void binning_layout(int R, int W, int H, c3dgs_binning_layout* L)
     L->total_bytes = o;
 }
 
-inline size_t compact_image_bytes(int W, int H)
-{
-    return align_up((size_t)tiles_x(W) * tiles_y(H) * 4) + align_up((size_t)W * H * 4);
-}
-inline void image_layout(int W, int H, c3dgs_image_layout* L)
+// The whole image buffer: the public fields (c3dgs_image_layout) and, behind them and private to the library, the same two
+// per-tile / per-pixel quantities in compact-list indices (below).
+struct ImageLayout : c3dgs_image_layout { size_t tile_used_c, n_contrib_c; };
+inline void image_layout(int W, int H, ImageLayout* L)
 {
     size_t o = 0, n = (size_t)W * H, t = (size_t)tiles_x(W) * tiles_y(H);
-    L->final_T = o;   o = align_up(o + n * 4);
-    L->n_contrib = o; o = align_up(o + n * 4);
-    L->ranges = o;    o = align_up(o + t * 8);
-    L->tile_used = o; o = align_up(o + t * 4);
-    L->tile_order = o; o = align_up(o + t * 4);
-    L->total_bytes = o + compact_image_bytes(W, H);   // tile_used_c | n_contrib_c behind it (compact_layout below)
+    L->final_T = o;     o = align_up(o + n * 4);
+    L->n_contrib = o;   o = align_up(o + n * 4);
+    L->ranges = o;      o = align_up(o + t * 8);
+    L->tile_used = o;   o = align_up(o + t * 4);
+    L->tile_order = o;  o = align_up(o + t * 4);
+    L->tile_used_c = o; o = align_up(o + t * 4);
+    L->n_contrib_c = o; o = align_up(o + n * 4);
+    L->total_bytes = o;
 }
 
 // Compact per-tile lists (render.hip): of a tile's visited list entries only those whose quadrant mask is non-zero ("live") can
 // touch a pixel of the tile. The forward writes their Gaussian ids (cid) and masks (cqm) densely from the start of the tile's
 // own segment [range.x, ...) of two arrays in the idle sort scratch, and per pixel / per tile the 1-based COMPACT index of the last
-// contributor (n_contrib_c, tile_used_c) behind the public part of the image buffer; the backward walks only those. Offsets are
-// private to the library (tests: c3dgs_get_compact_layout); the public layout structs do not change.
-struct CompactLayout { size_t cqm, cid, bin_bytes; size_t tile_used_c, n_contrib_c; };
-inline CompactLayout compact_layout(int R, int W, int H)
+// contributor (ImageLayout: n_contrib_c, tile_used_c); the backward walks only those. Offsets are private to the library
+// (tests: c3dgs_get_compact_layout); the public layout structs do not change.
+struct CompactBinLayout { size_t cqm, cid, bin_bytes; };       // relative to sort_temp
+inline CompactBinLayout compact_bin_layout(int R)
 {
-    const size_t r = (size_t)(R > 0 ? R : 1), t = (size_t)tiles_x(W) * tiles_y(H);
-    c3dgs_image_layout IL; image_layout(W, H, &IL);
-    CompactLayout C;
-    C.cqm = 0; C.cid = align_up(r); C.bin_bytes = C.cid + align_up(r * 4);          // relative to sort_temp
-    C.tile_used_c = IL.tile_order + align_up(t * 4);
-    C.n_contrib_c = C.tile_used_c + align_up(t * 4);
+    const size_t r = (size_t)(R > 0 ? R : 1);
+    CompactBinLayout C;
+    C.cqm = 0; C.cid = align_up(r); C.bin_bytes = C.cid + align_up(r * 4);
     return C;
+}
+
+// Backward workspace: partial sums f32[R][9] | their 1-byte "written" flags | the lists of blended Gaussians, one per BWD_LIST
+// Gaussians in id order and filled from the front: ids, where each one's nine sums are parked (slot), and the lists' lengths
+inline void backward_layout(int P, int R, c3dgs_backward_layout* L)
+{
+    size_t o = 0, r = (size_t)(R > 0 ? R : 1), n_lists = ((size_t)(P > 0 ? P : 1) + BWD_LIST - 1) / BWD_LIST;
+    L->partials = o;   o = align_up(o + r * PARTIAL_FLOATS * sizeof(float));
+    L->touched = o;    o = align_up(o + r);
+    L->live_ids = o;   o = align_up(o + n_lists * BWD_LIST * 4);
+    L->live_slots = o; o = align_up(o + n_lists * BWD_LIST * 4);
+    L->live_count = o; o = align_up(o + n_lists * 4);
+    L->list_len = BWD_LIST;
+    L->total_bytes = o;
 }
 
 // ---------------------------------------------------------------- kernel launchers (one per .hip file)
@@ -172,6 +185,8 @@ struct BinPtrs {
 struct ImgPtrs { float* final_T; uint32_t* n_contrib; uint2* ranges; uint32_t* tile_used; uint32_t* tile_order;
                  uint32_t* tile_used_c; uint32_t* n_contrib_c; };
 struct CompactPtrs { uint8_t* cqm; uint32_t* cid; };   // inside BinPtrs::sort_temp, valid once the tile sort has run
+struct BwdPtrs { float* partials; uint8_t* touched; size_t touched_bytes;   // the flags' whole region: what a call clears
+                 uint32_t* live_ids; uint32_t* live_slots; uint32_t* live_count; };
 
 inline GeomPtrs geom_ptrs(void* base, int P)
 {
@@ -191,16 +206,22 @@ inline BinPtrs bin_ptrs(void* base, int R, int W, int H)
 }
 inline ImgPtrs img_ptrs(void* base, int W, int H)
 {
-    c3dgs_image_layout L; image_layout(W, H, &L);
-    const CompactLayout C = compact_layout(0, W, H);
+    ImageLayout L; image_layout(W, H, &L);
     char* b = (char*)base;
     return { (float*)(b + L.final_T), (uint32_t*)(b + L.n_contrib), (uint2*)(b + L.ranges), (uint32_t*)(b + L.tile_used),
-             (uint32_t*)(b + L.tile_order), (uint32_t*)(b + C.tile_used_c), (uint32_t*)(b + C.n_contrib_c) };
+             (uint32_t*)(b + L.tile_order), (uint32_t*)(b + L.tile_used_c), (uint32_t*)(b + L.n_contrib_c) };
 }
-inline CompactPtrs compact_ptrs(const BinPtrs& bp, int R, int W, int H)
+inline CompactPtrs compact_ptrs(const BinPtrs& bp, int R)
 {
-    const CompactLayout C = compact_layout(R, W, H);
+    const CompactBinLayout C = compact_bin_layout(R);
     return { (uint8_t*)bp.sort_temp + C.cqm, (uint32_t*)((char*)bp.sort_temp + C.cid) };
+}
+inline BwdPtrs bwd_ptrs(void* base, int P, int R)
+{
+    c3dgs_backward_layout L; backward_layout(P, R, &L);
+    char* b = (char*)base;
+    return { (float*)(b + L.partials), (uint8_t*)(b + L.touched), L.live_ids - L.touched,
+             (uint32_t*)(b + L.live_ids), (uint32_t*)(b + L.live_slots), (uint32_t*)(b + L.live_count) };
 }
 
 // preprocess.hip
@@ -245,16 +266,13 @@ hipError_t onesweep_tile_sort(void* temp, size_t temp_bytes, const uint16_t* kin
 // render.hip
 void launch_render_forward(int W, int H, const ImgPtrs& img, const uint32_t* point_list, const float4* splat,
                            const float* bg, float* out_color, const CompactPtrs& cl, const uint32_t* sort_err, hipStream_t s);
-void launch_backward_prep(int W, int H, const ImgPtrs& img, uint32_t* tile_order, void* zero_a, size_t n16_a, void* zero_b,
-                          size_t n16_b, hipStream_t s);
+void launch_backward_prep(int W, int H, const ImgPtrs& img, void* zero_a, size_t n16_a, void* zero_b, size_t n16_b, hipStream_t s);
 void launch_render_backward(int W, int H, const ImgPtrs& img, const float4* splat,
                             const uint32_t* block_base, const float* bg, const float* dL_dpix, float* partials,
-                            uint8_t* touched, const CompactPtrs& cl, const uint32_t* tile_order, void* zero_span, size_t zero_n16,
-                            hipStream_t s);
+                            uint8_t* touched, const CompactPtrs& cl, void* zero_span, size_t zero_n16, hipStream_t s);
 // backward_preprocess.hip
-void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g,
-                                float* partials, const uint8_t* touched, uint32_t* live_count, uint32_t* live_ids,
-                                uint32_t* live_slots, const c3dgs_raster_grads& gr, hipStream_t s);
+void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,
+                                const c3dgs_raster_grads& gr, hipStream_t s);
 // vq.hip
 int launch_weighted_distance(int64_t N, int C, int K, const float* coefs, const int64_t* gather, const float* codebook,
                              float* out_dist, int64_t* out_idx, hipStream_t s, void* ws = nullptr, size_t ws_bytes = 0, int presplit = -1);

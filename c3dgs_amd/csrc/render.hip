@@ -688,26 +688,24 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
 }
 
 // tile schedule + the backward's fills in one launch; zero_a / zero_b: 16-byte aligned spans of n16 x 16 bytes (or null / 0)
-void launch_backward_prep(int W, int H, const ImgPtrs& img, uint32_t* tile_order, void* zero_a, size_t n16_a, void* zero_b,
-                          size_t n16_b, hipStream_t s)
+void launch_backward_prep(int W, int H, const ImgPtrs& img, void* zero_a, size_t n16_a, void* zero_b, size_t n16_b, hipStream_t s)
 {
-    const int T = (W > 0 && H > 0 && tile_order) ? tiles_x(W) * tiles_y(H) : 0;
+    const int T = (W > 0 && H > 0) ? tiles_x(W) * tiles_y(H) : 0;
     const size_t n16 = n16_a + n16_b;
     if (T <= 0 && n16 == 0) return;
     // fill workgroups: 16 KB each per sweep, at most four per CU
     const unsigned fill = n16 ? (unsigned)std::min<size_t>((n16 + 1023) / 1024, 1024) : 0u;
-    backward_prep_kernel<<<1 + fill, 1024, 0, s>>>(T, img.tile_used_c, tile_order, (uint4*)zero_a, n16_a, (uint4*)zero_b, n16_b);
+    backward_prep_kernel<<<1 + fill, 1024, 0, s>>>(T, img.tile_used_c, img.tile_order, (uint4*)zero_a, n16_a, (uint4*)zero_b, n16_b);
 }
 
 void launch_render_backward(int W, int H, const ImgPtrs& img, const float4* splat,
                             const uint32_t* block_base, const float* bg, const float* dL_dpix, float* partials,
-                            uint8_t* touched, const CompactPtrs& cl, const uint32_t* tile_order, void* zero_span, size_t zero_n16,
-                            hipStream_t s)
+                            uint8_t* touched, const CompactPtrs& cl, void* zero_span, size_t zero_n16, hipStream_t s)
 {
     const int gx = tiles_x(W), T = gx * tiles_y(H);
     const int grid = ((T + 7) / 8) * 8;
     render_backward_kernel<<<grid, 256, 0, s>>>(W, H, gx, T, img.ranges, img.tile_used_c, cl.cid, splat, block_base, bg, img.final_T,
-                                                img.n_contrib_c, dL_dpix, partials, touched, cl.cqm, tile_order, (uint4*)zero_span,
+                                                img.n_contrib_c, dL_dpix, partials, touched, cl.cqm, img.tile_order, (uint4*)zero_span,
                                                 zero_span ? zero_n16 : 0);
 }
 

@@ -474,8 +474,20 @@ typedef struct c3dgs_image_layout {   /* byte offsets into the image buffer     
 
 int c3dgs_get_geom_layout(int32_t P, c3dgs_geom_layout* out);
 int c3dgs_get_binning_layout(int32_t R, int32_t W, int32_t H, c3dgs_binning_layout* out);
+typedef struct c3dgs_backward_layout { /* byte offsets into the backward workspace for P Gaussians and R instances */
+    size_t total_bytes;  /* what the backward asks its workspace callback for = c3dgs_backward_workspace_bytes(P, R)       */
+    size_t partials;     /* float[9*R] one slot of nine sums per (Gaussian, tile) instance, contiguous per Gaussian, id order */
+    size_t touched;      /* uint8[R] 1 = the blend wrote the slot; the only part cleared per call                          */
+    size_t live_ids;     /* uint32[n_lists*list_len], n_lists = ceil(max(P,1) / list_len): list k holds, from its front and in
+                          * id order, the blended ones of the Gaussians [k*list_len, (k+1)*list_len)                         */
+    size_t live_slots;   /* uint32[n_lists*list_len] the slot of `partials` where the listed Gaussian's nine sums are parked   */
+    size_t live_count;   /* uint32[n_lists] entries of each list                                                          */
+    size_t list_len;     /* Gaussians per list (1024)                                                                     */
+} c3dgs_backward_layout;
+
 int c3dgs_get_image_layout(int32_t W, int32_t H, c3dgs_image_layout* out);
-size_t c3dgs_backward_workspace_bytes(int32_t P, int32_t R);
+int c3dgs_get_backward_layout(int32_t P, int32_t R, c3dgs_backward_layout* out);
+size_t c3dgs_backward_workspace_bytes(int32_t P, int32_t R);   /* total_bytes of c3dgs_backward_layout */
 
 /* tests / tools only: where the forward leaves the tiles' COMPACT lists -- of the list entries a tile visits, those that can reach
  * a pixel of it (non-zero quadrant mask), in list order, densely from the start of the tile's own segment [ranges[tile].x, ...).

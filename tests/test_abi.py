@@ -75,6 +75,70 @@ def test_layouts_are_consistent(L):
     assert L.c3dgs_get_geom_layout(-1, C.byref(g)) == 1
 
 
+def _up256(v):
+    return (v + 255) // 256 * 256
+
+
+def test_backward_layout_is_the_workspace_the_backward_asks_for(L):
+    """One layout (csrc/common.hpp: backward_layout) gives the size the library asks its workspace callback for and every pointer
+    it carves from it. Regions are 256-byte aligned, in order, and large enough for R instances and ceil(P / list_len) lists."""
+    from c3dgs_amd import _lib
+    for P in (0, 1, 1023, 1024, 1025, 2048, 2049, 3_000_000):
+        for R in (0, 1, 255, 256, 257, 16_400_000):
+            b = _lib.BackwardLayout()
+            assert L.c3dgs_get_backward_layout(P, R, C.byref(b)) == 0, (P, R)
+            assert b.list_len == 1024
+            r, n_lists = max(R, 1), (max(P, 1) + b.list_len - 1) // b.list_len
+            offs = [b.partials, b.touched, b.live_ids, b.live_slots, b.live_count, b.total_bytes]
+            assert all(x < y for x, y in zip(offs, offs[1:])) and all(o % 256 == 0 for o in offs), (P, R, offs)
+            assert b.touched - b.partials >= 36 * r
+            assert b.live_ids - b.touched >= r
+            assert b.live_slots - b.live_ids >= 4 * n_lists * b.list_len
+            assert b.live_count - b.live_slots >= 4 * n_lists * b.list_len
+            assert b.total_bytes - b.live_count >= 4 * n_lists
+            assert b.total_bytes == L.c3dgs_backward_workspace_bytes(P, R), (P, R)
+    b = _lib.BackwardLayout()
+    assert L.c3dgs_get_backward_layout(-1, 10, C.byref(b)) == 1
+    assert L.c3dgs_get_backward_layout(10, -1, C.byref(b)) == 1
+
+
+def test_image_and_compact_layouts_agree(L):
+    """The image buffer's private tail (tile_used_c | n_contrib_c) sits right behind its public fields and ends the buffer; the
+    binning half of the compact layout depends on R alone."""
+    from c3dgs_amd import _lib
+    for W, H in ((9, 5), (203, 131), (1920, 1080), (4096, 4096), (7680, 4320)):
+        T = ((W + 15) // 16) * ((H + 15) // 16)
+        il = _lib.ImageLayout()
+        assert L.c3dgs_get_image_layout(W, H, C.byref(il)) == 0
+        for R in (0, 1, 255, 256, 257, 5000, 16_400_000):
+            cl, bl = _lib.CompactLayout(), _lib.BinningLayout()
+            assert L.c3dgs_get_compact_layout(R, W, H, C.byref(cl)) == 0
+            assert L.c3dgs_get_binning_layout(R, W, H, C.byref(bl)) == 0
+            assert il.total_bytes == cl.n_contrib_c + _up256(4 * W * H), (W, H)
+            assert cl.tile_used_c == il.tile_order + _up256(4 * T), (W, H)
+            assert cl.n_contrib_c == cl.tile_used_c + _up256(4 * T), (W, H)
+            assert cl.cqm == bl.sort_temp and cl.cid - cl.cqm == _up256(max(R, 1)), (W, H, R)
+            assert cl.cid + 4 * max(R, 1) <= bl.sort_temp + bl.sort_temp_bytes, (W, H, R)
+
+
+STAGE_NAMES = ("mark_visible", "preprocess", "depth_sort", "scan", "duplicate_with_keys", "sort", "identify_ranges",
+               "render_forward", "zero_partials", "render_backward", "backward_preprocess", "weighted_distance", "vq_accumulate",
+               "vq_apply", "l1_ssim_forward", "l1_ssim_backward", "qat_observe", "qat_codebooks", "qat_visible", "qat_points",
+               "qat_points_backward", "qat_codebooks_backward", "adam_step", "knn_sort", "knn_bounds", "knn_query")
+
+
+def test_profile_only_knows_every_stage_name(L):
+    """The 26 names bench.py and tools/ select stages by, spelled out: they are the contract, not the library's table."""
+    assert len(set(STAGE_NAMES)) == 26
+    try:
+        for name in STAGE_NAMES:
+            assert L.c3dgs_profile_only(name.encode()) == 0, name
+        assert L.c3dgs_profile_only(b"render_backwards") == 1 and b"unknown stage" in L.c3dgs_last_error()
+        assert L.c3dgs_profile_only(b"camera_from_pose") == 1            # launch-checked, never timed
+    finally:
+        assert L.c3dgs_profile_only(None) == 0
+
+
 def test_validation_without_gpu(L):
     from c3dgs_amd import _lib
     # N == 0 is legal and touches nothing

@@ -91,6 +91,73 @@ def test_backward_parity(hip, orc, name):
     fullsize.check_grads(st, gpu_util.unpack(fw), got, ref, GRAD_TOL, name)
 
 
+@pytest.mark.parametrize("name,boundary_id", [("p1024", 1023), ("p1025", 1024), ("indexed_p1025", 1024), ("p2049", 2048)])
+def test_list_boundary_cases_blend_the_gaussian_at_the_boundary(hip, orc, name, boundary_id):
+    """What makes p1024 / p1025 / p2049 / indexed_p1025 list-boundary cases of the backward (lists of blended Gaussians, one per
+    list_len ids): the Gaussian that ends the last full list (p1024) or is alone in the list behind it (the others) IS blended.
+    Read off the oracle's gradients, so a changed seed or scene cannot hollow the cases out; the kernels' row for it is checked
+    by test_backward_parity and must be non-zero here."""
+    import ctypes as C
+    from c3dgs_amd import _lib
+    inp, cam, indexed = cases.make_case(name)
+    st = cases.oracle_forward(inp, cam)
+    dL = synth.grad_image(cam["W"], cam["H"]).numpy()
+    ref = orc.rasterize_backward(st, dL)
+    bl = _lib.BackwardLayout()
+    assert _lib.lib().c3dgs_get_backward_layout(st.P, st.num_rendered, C.byref(bl)) == 0
+    blended = np.nonzero((np.abs(ref["dL_dopacity"]).reshape(st.P, -1).max(1) > 0)
+                         | (np.abs(ref["dL_dmeans2D"]).reshape(st.P, -1).max(1) > 0))[0]
+    assert boundary_id == st.P - 1 and boundary_id in blended
+    first_of_last_list = (st.P - 1) // bl.list_len * bl.list_len
+    if name == "p1024":
+        assert st.P == bl.list_len                                      # one list, full to its last id
+    else:
+        assert boundary_id == first_of_last_list and first_of_last_list > 0
+        assert (blended >= first_of_last_list).sum() == 1               # the last list holds exactly one entry
+    got = gpu_util.hip_backward(gpu_util.hip_forward(inp, cam, indexed), dL)
+    assert np.abs(got["dL_dopacity"][boundary_id]).max() > 0 and np.abs(got["dL_dmeans3D"][boundary_id]).max() > 0
+
+
+@pytest.mark.parametrize("name", ["tiny", "p1025", "indexed_p1025", "all_behind"])
+def test_backward_stays_inside_its_workspace(hip, monkeypatch, name):
+    """The backward asks its callback for c3dgs_backward_workspace_bytes(P, R) and writes nowhere else: handed a pointer 4096
+    bytes into a larger buffer filled with 0xA5, it leaves the 4096 bytes on either side as they were and computes what it
+    computes in a plain allocation (bitwise; the scatter-added codebook gradients of the indexed path within the parity bar)."""
+    from c3dgs_amd import _lib, rasterizer
+    GUARD = 4096
+    handed = []
+
+    class GuardedScratch(rasterizer._Scratch):
+        def callback(self, name_):
+            def _resize(_user, nbytes):
+                t = torch.full((int(nbytes) + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=self.device)
+                handed.append((name_, int(nbytes), t))
+                return t.data_ptr() + GUARD
+            cb = rasterizer.RESIZE_FN(_resize)
+            self._cbs[name_] = cb
+            return cb
+
+    inp, cam, indexed = cases.make_case(name)
+    dL = synth.grad_image(cam["W"], cam["H"]).numpy()
+    fw = gpu_util.hip_forward(inp, cam, indexed)
+    plain = gpu_util.hip_backward(fw, dL)
+    with monkeypatch.context() as m:
+        m.setattr(rasterizer, "_Scratch", GuardedScratch)
+        got = gpu_util.hip_backward(fw, dL)                              # synchronises
+    P, R = int(fw["radii"].numel()), fw["num_rendered"]
+    assert (R == 0) == (name == "all_behind")
+    assert [(n, b) for n, b, _ in handed] == [("ws", _lib.lib().c3dgs_backward_workspace_bytes(P, R))]
+    _, nbytes, buf = handed[0]
+    assert buf.data_ptr() % 256 == 0
+    assert bool((buf[:GUARD] == 0xA5).all()) and bool((buf[GUARD + nbytes:] == 0xA5).all()), "the backward wrote outside its workspace"
+    assert plain.keys() == got.keys()
+    for k in got:
+        if indexed and k in ("dL_dsh", "dL_dscales", "dL_drotations"):  # float atomics: the order of the adds is not fixed
+            assert gpu_util.rel_inf(got[k], plain[k]) <= GRAD_TOL, k
+        else:
+            np.testing.assert_array_equal(got[k].view(np.uint32), plain[k].view(np.uint32), err_msg=k)
+
+
 def test_backward_is_deterministic(hip, orc):
     """No global float atomics on the non-indexed path: two runs are bitwise identical."""
     inp, cam, indexed = cases.make_case("base")
