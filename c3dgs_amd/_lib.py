@@ -131,6 +131,8 @@ PROTOTYPES = {
     "c3dgs_rows_apply": (C.c_int, [C.c_int32, C.c_int64, _vp, _vp, _vp, C.c_int32, C.POINTER(RowsTensor), C.c_int32, C.c_int64,
                                    _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
     "c3dgs_densify_stats": (C.c_int, [C.c_int32] + [_vp] * 7),
+    "c3dgs_index_plan_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "c3dgs_index_plan": (C.c_int, [C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64] + [_vp] * 8),
     "c3dgs_extract_rot_scale": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
     "c3dgs_l1_ssim_forward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),

@@ -749,6 +749,32 @@ int c3dgs_densify_stats(int32_t P, const float* grad, const uint8_t* filter, con
     return C3DGS_OK;
 }
 
+// ---- prune / codebook compaction of an indexed model (index_plan.hip)
+static const int32_t kIndexPlanMaxRows = INT32_MAX - 255;     // one lane per row in 256-lane workgroups, int arithmetic
+
+size_t c3dgs_index_plan_workspace_bytes(int32_t P, int32_t K0, int32_t K1) { return index_plan_workspace_bytes(P, K0, K1); }
+
+int c3dgs_index_plan(int32_t P, const uint8_t* keep, const int64_t* idx0, int32_t K0, const int64_t* idx1, int32_t K1, int64_t cap_rows,
+                     int64_t cap_cb0, int64_t cap_cb1, int32_t* src, int64_t* new_idx0, int64_t* new_idx1, int32_t* cb_src0,
+                     int32_t* cb_src1, int32_t* totals, void* workspace, void* stream)
+{
+    if (P < 0 || K0 < 0 || K1 < 0) return fail(C3DGS_E_INVALID, "index_plan: P, K0 and K1 must be >= 0");
+    if (P > kIndexPlanMaxRows || K0 > kIndexPlanMaxRows || K1 > kIndexPlanMaxRows)
+        return fail(C3DGS_E_INVALID, "index_plan: P, K0 and K1 must be at most INT32_MAX - 255");
+    if (cap_rows < 0 || cap_cb0 < 0 || cap_cb1 < 0) return fail(C3DGS_E_INVALID, "index_plan: capacities must be >= 0");
+    if ((idx0 && K0 <= 0) || (idx1 && K1 <= 0)) return fail(C3DGS_E_INVALID, "index_plan: an index array needs a codebook of K > 0 rows");
+    if (!totals) return fail(C3DGS_E_INVALID, "index_plan: totals is required");
+    if (!workspace) return fail(C3DGS_E_INVALID, "index_plan: workspace is required");
+    if (src && ((idx0 && (!new_idx0 || !cb_src0)) || (idx1 && (!new_idx1 || !cb_src1))))
+        return fail(C3DGS_E_INVALID, "index_plan: src, and new_idx and cb_src of every index space given, go together");
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0) { C3DGS_HIP_TRY(hipMemsetAsync(totals, 0, 4 * sizeof(int32_t), s)); return C3DGS_OK; }
+    C3DGS_HIP_TRY(run_index_plan(P, keep, idx0, K0, idx1, K1, cap_rows, cap_cb0, cap_cb1, src, new_idx0, new_idx1, cb_src0, cb_src1,
+                                 totals, workspace, s));
+    C3DGS_STAGE("index_plan", 0, s);
+    return C3DGS_OK;
+}
+
 int c3dgs_extract_rot_scale(int32_t n, const float* cov6, float* rot, float* scale, void* stream)
 {
     if (n < 0) return fail(C3DGS_E_INVALID, "extract_rot_scale: n must be >= 0");

@@ -313,6 +313,11 @@ void launch_rows_apply(int P, long long P_new, const int32_t* src, const uint8_t
                        const float* z, int log_scaling, int half_xyz, hipStream_t s);
 void launch_densify_stats(int P, const float* grad, const uint8_t* filter, const int32_t* radii, float* accum, float* denom,
                           float* max_radii, hipStream_t s);
+// index_plan.hip (prune / codebook compaction of an indexed model): flags -> scans -> emit
+size_t index_plan_workspace_bytes(int P, int K0, int K1);
+hipError_t run_index_plan(int P, const uint8_t* keep, const int64_t* idx0, int K0, const int64_t* idx1, int K1, long long cap_rows,
+                          long long cap_cb0, long long cap_cb1, int32_t* src, int64_t* new_idx0, int64_t* new_idx1, int32_t* cb_src0,
+                          int32_t* cb_src1, int32_t* totals, void* workspace, hipStream_t s);
 // loss.hip
 void launch_l1_ssim_value(const double* sums, double l1_scale, double ssim_scale, double constant, float* out, hipStream_t s);
 void launch_l1_ssim_forward(int C, int H, int W, const float* img, const float* gt, float* Dmu, float* Ds1, float* Ds12,

@@ -754,7 +754,8 @@ class GaussianModel:
     def _dense_only(self, what):
         if self._feature_indices is not None or self._gaussian_indices is not None:
             raise NotImplementedError(f"c3dgs_amd: {what} supports non-indexed models only (the reference's index remapping in "
-                                      "prune_points is not mirrored)")
+                                      "prune_points is not mirrored here: prune_points_indexed prunes an indexed model, "
+                                      "to_unindexed converts it)")
 
     def _density_stats(self):
         """xyz_gradient_accum / denom / max_radii2D of the current length (training_setup and load_ply create them; a model
@@ -882,6 +883,18 @@ class GaussianModel:
                                             N * S, rotation.data_ptr(), _ptr(std),
                                             draws.data_ptr() if draws.numel() else None,
                                             int(not self.use_factor_scaling), int(self.quantization), _stream(dev)))
+        self._install(new, moments)
+        if stats_new is not None:
+            self.xyz_gradient_accum, self.denom, self.max_radii2D = stats_new
+        else:                                                 # densification_postfix, :1209-1211
+            self.xyz_gradient_accum = torch.zeros((P_new, 1), device=dev)
+            self.denom = torch.zeros((P_new, 1), device=dev)
+            self.max_radii2D = torch.zeros((P_new,), device=dev)
+        return src, kind, draw_row, tot
+
+    def _install(self, new, moments):
+        """The new parameter tensors {attr: tensor} become the model's leaves; each one's param group is re-pointed and its
+        optimizer state follows it (`step` kept, moments replaced where `moments` has them)."""
         for name, attr, _ in self._GROUPS:
             if attr not in new:
                 continue
@@ -896,13 +909,6 @@ class GaussianModel:
                                 st["exp_avg"], st["exp_avg_sq"] = moments[attr]
                             self.optimizer.state[param] = st
             setattr(self, attr, param)
-        if stats_new is not None:
-            self.xyz_gradient_accum, self.denom, self.max_radii2D = stats_new
-        else:                                                 # densification_postfix, :1209-1211
-            self.xyz_gradient_accum = torch.zeros((P_new, 1), device=dev)
-            self.denom = torch.zeros((P_new, 1), device=dev)
-            self.max_radii2D = torch.zeros((P_new,), device=dev)
-        return src, kind, draw_row, tot
 
     def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, draws=None, N=2):
         """:1336-1349 fused: the reference's clone stage, split stage and final prune decided per row in one classification
@@ -976,6 +982,160 @@ class GaussianModel:
         with torch.no_grad():
             code = (~mask.to(self.device).bool()).to(torch.uint8).contiguous()
             return self._rebuild(code, carry_stats=True)
+
+    # ---- indexed models: prune, codebook compaction and the two conversions (:889-910, :1101-1158); csrc/index_plan.hip
+    _COLOR_ATTRS = ("_features_dc", "_features_rest")
+    _GEOMETRY_ATTRS = ("_scaling", "_rotation")
+
+    def _gather_rows(self, attrs, n_in, src, extra=()):
+        """out[j] = in[src[j]] for the parameter tensors named by `attrs`, each with its two Adam moments, and for the plain
+        tensors of `extra`: ONE copy-only c3dgs_rows_apply launch (kind all original, so moments are copied).
+        -> ({attr: new tensor}, {attr: (exp_avg, exp_avg_sq)}, [new extra tensors]); nothing is installed."""
+        dev = self.device
+        n_out = int(src.shape[0])
+        table, new, moments, extra_new = [], {}, {}, []
+
+        def job(old, st=None):
+            old_c = _need_gpu(old.detach(), "tensor")
+            out = torch.empty((n_out,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
+            t = _lib.RowsTensor()
+            t.in_param, t.out_param = old_c.data_ptr(), out.data_ptr()
+            t.row_floats, t.role = int(torch.Size(old.shape[1:]).numel()), _lib.ROLE_COPY
+            keep, mom = [old_c], None
+            if st is not None and "exp_avg" in st:
+                m, v = st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous()
+                mom = (torch.empty_like(out), torch.empty_like(out))
+                t.in_exp_avg, t.in_exp_avg_sq, t.out_exp_avg, t.out_exp_avg_sq = m.data_ptr(), v.data_ptr(), mom[0].data_ptr(), mom[1].data_ptr()
+                keep += [m, v]
+            if t.row_floats > 0:
+                table.append((t, keep))
+            return out, mom
+
+        for attr in attrs:
+            old = getattr(self, attr)
+            if old is None:
+                continue
+            new[attr], mom = job(old, self.optimizer.state.get(old) if self.optimizer is not None else None)
+            if mom is not None:
+                moments[attr] = mom
+        for old in extra:
+            extra_new.append(job(old)[0])
+        if n_out > 0 and n_in > 0 and table:
+            kind = torch.zeros(n_out, dtype=torch.uint8, device=dev)            # C3DGS_KIND_ORIGINAL
+            arr = (_lib.RowsTensor * len(table))(*[t for t, _ in table])
+            # draw_row is read for child rows only: any [n_out] int32 buffer serves
+            _lib.check(_lib.lib().c3dgs_rows_apply(n_in, n_out, src.data_ptr(), kind.data_ptr(), src.data_ptr(), len(table), arr, 1, 0,
+                                                   None, None, None, 0, 0, _stream(dev)))
+        return new, moments, extra_new
+
+    def plan_index_prune(self, keep, idx0, K0, idx1, K1):
+        """c3dgs_index_plan in its two calls around the one host read. keep: uint8 [P] or None; idx: int64 [P] or None.
+        -> (src int32 [P_new], new_idx0, new_idx1 (int64 [P_new] or None), cb_src0, cb_src1 (int32 [K_new] or None),
+        (P_new, K0_new, K1_new, out_of_range))."""
+        lib = _lib.lib()
+        dev = self.device
+        s = _stream(dev)
+        P = int(idx0.shape[0] if idx0 is not None else idx1.shape[0] if idx1 is not None else keep.shape[0])
+        K0, K1 = (int(K0) if idx0 is not None else 0), (int(K1) if idx1 is not None else 0)
+        ws = torch.empty(max(int(lib.c3dgs_index_plan_workspace_bytes(P, K0, K1)), 256), dtype=torch.uint8, device=dev)
+        totals = torch.empty(4, dtype=torch.int32, device=dev)
+        args = (P, _ptr(keep), _ptr(idx0), K0, _ptr(idx1), K1)
+        _lib.check(lib.c3dgs_index_plan(*args, 0, 0, 0, None, None, None, None, None, totals.data_ptr(), ws.data_ptr(), s))
+        tot = tuple(self._read_totals(totals))
+        P_new, K0n, K1n, bad = tot
+        if bad:
+            raise RuntimeError(f"{bad} codebook indices lie outside their codebook ({K0} colour rows, {K1} geometry rows)")
+        src = torch.empty(P_new, dtype=torch.int32, device=dev)
+        new0 = torch.empty(P_new, dtype=torch.int64, device=dev) if idx0 is not None else None
+        new1 = torch.empty(P_new, dtype=torch.int64, device=dev) if idx1 is not None else None
+        cb0 = torch.empty(K0n, dtype=torch.int32, device=dev) if idx0 is not None else None
+        cb1 = torch.empty(K1n, dtype=torch.int32, device=dev) if idx1 is not None else None
+        if P_new > 0:
+            _lib.check(lib.c3dgs_index_plan(*args, P_new, K0n, K1n, src.data_ptr(), _ptr(new0), _ptr(new1), _ptr(cb0), _ptr(cb1),
+                                            totals.data_ptr(), ws.data_ptr(), s))
+        return src, new0, new1, cb0, cb1, tot
+
+    def prune_points_indexed(self, mask):
+        """:1101-1158 for a model with either or both index arrays: the Gaussians with `mask` go, every codebook row no
+        survivor references is dropped from _features_dc / _features_rest and from _scaling / _rotation together with its Adam
+        moments, and both index arrays are remapped. Surviving Gaussians keep their order, surviving codebook rows are the
+        referenced old rows in ascending old id, the new index is the rank of the old one among them (the reference's result,
+        without its Python loop over the ids). Optimizer handling as in _rebuild: groups re-pointed, moments gathered, `step`
+        kept; xyz_gradient_accum, denom and max_radii2D are gathered like the per-Gaussian parameters. One device->host read
+        (the four totals), at most three gather launches, no getter: no observer moves.
+
+        All rows pruned: the reference crashes (`unique_ids[-1]` of an empty tensor); here the result is a model with empty
+        parameters, empty codebooks and empty index arrays. An index outside its codebook raises before anything is changed.
+
+        Returns (src, cb_src0, cb_src1, (P_new, K0_new, K1_new, out_of_range)): the source row of every surviving Gaussian and
+        the old id of every surviving colour / geometry codebook row (None for a half that is not indexed)."""
+        fi, gi = self._feature_indices, self._gaussian_indices
+        if fi is None and gi is None:
+            raise RuntimeError("prune_points_indexed: the model has no index array; use prune_points")
+        dev = self.device
+        with torch.no_grad():
+            P = self._xyz.shape[0]
+            keep = None
+            if mask is not None:
+                if mask.shape[0] != P:
+                    raise RuntimeError(f"prune_points_indexed: mask of {mask.shape[0]} rows for {P} Gaussians")
+                keep = (~mask.to(dev).bool()).contiguous().view(torch.uint8)
+            for idx, what in ((fi, "_feature_indices"), (gi, "_gaussian_indices")):        # the reference asserts this, :1131-1132
+                if idx is not None and tuple(idx.shape) != (P,):
+                    raise RuntimeError(f"prune_points_indexed: {what} has shape {tuple(idx.shape)} for {P} Gaussians")
+            K0 = self._features_dc.shape[0] if fi is not None else 0
+            K1 = self._scaling.shape[0] if gi is not None else 0
+            accum, denom, max_radii = self._density_stats()
+            src, new0, new1, cb0, cb1, tot = self.plan_index_prune(keep, fi, K0, gi, K1)
+            rows = ["_xyz", "_opacity", "_scaling_factor"]
+            rows += [] if fi is not None else list(self._COLOR_ATTRS)
+            rows += [] if gi is not None else list(self._GEOMETRY_ATTRS)
+            new, moments, stats = self._gather_rows(rows, P, src, extra=(accum, denom, max_radii))
+            for attrs, n_in, cb in ((self._COLOR_ATTRS, K0, cb0), (self._GEOMETRY_ATTRS, K1, cb1)):
+                if cb is not None:
+                    n, m, _ = self._gather_rows(attrs, n_in, cb)
+                    new.update(n)
+                    moments.update(m)
+            self._install(new, moments)
+            self.xyz_gradient_accum, self.denom, self.max_radii2D = stats
+            if fi is not None:
+                self._feature_indices = new0
+            if gi is not None:
+                self._gaussian_indices = new1
+        return src, cb0, cb1, tot
+
+    def compact_codebooks(self):
+        """prune_points_indexed with nothing masked: drops the codebook rows no Gaussian references (mask_splats and a pruning
+        compress_gaussians leave them behind) and renumbers the indices. Nothing calls it implicitly."""
+        return self.prune_points_indexed(None)
+
+    def to_indexed(self):
+        """:902-910: identity index arrays, no compression. Parameters and optimizer are untouched; a half that is already
+        indexed keeps its array."""
+        n = self._xyz.shape[0]
+        if self._feature_indices is None:
+            self._feature_indices = torch.arange(0, n, dtype=torch.int64, device=self.device)
+        if self._gaussian_indices is None:
+            self._gaussian_indices = torch.arange(0, n, dtype=torch.int64, device=self.device)
+        self.color_index_mode = ColorMode.ALL_INDEXED
+
+    def to_unindexed(self):
+        """:889-899: the four codebook tensors become per-Gaussian tensors, codebook[indices], and the index arrays go; a
+        half-indexed model expands the half it has. Unlike the reference, which leaves the optimizer pointing at the dead
+        codebook tensors, the param groups are re-pointed and every expanded row takes a copy of its codebook row's Adam
+        moments (`step` kept). An index outside its codebook gives a zero row, it is never dereferenced."""
+        with torch.no_grad():
+            for attrs, name in ((self._COLOR_ATTRS, "_feature_indices"), (self._GEOMETRY_ATTRS, "_gaussian_indices")):
+                idx = getattr(self, name)
+                if idx is None:
+                    continue
+                K = getattr(self, attrs[0]).shape[0]
+                # decided on the int64 value: narrowing first would fold 2^32 + 3 onto row 3
+                src = torch.where((idx >= 0) & (idx < K), idx, -1).to(torch.int32)
+                new, moments, _ = self._gather_rows(attrs, K, src)
+                self._install(new, moments)
+                setattr(self, name, None)
+        self.color_index_mode = ColorMode.NOT_INDEXED
 
     def reset_opacity(self):
         """:1391-1397 with replace_tensor_to_optimizer (:1061-1079): opacity <- inverse_sigmoid(min(get_opacity, 0.01)), its

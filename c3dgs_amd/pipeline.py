@@ -89,7 +89,7 @@ def _train_cameras(scene):
     return list(scene.getTrainCameras()) if hasattr(scene, "getTrainCameras") else list(scene)
 
 
-def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None):
+def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_interval=0, prune_min_opacity=0.005):
     """finetune.py:10-66. One camera per iteration, drawn without replacement from a stack that is refilled when empty
     (`pop(randint(0, len - 1))` on Python's `random`, like the reference); render -> (1 - l) L1 + l (1 - SSIM) ->
     backward -> learning-rate update -> Adam step (not after the last iteration).
@@ -97,7 +97,12 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None):
     The reference reads `loss.item()` every iteration for its progress bar, which drains the GPU queue each time; here
     the losses stay on the device and the same exponential moving average (0.4 / 0.6) is evaluated every 10 iterations.
     Returns that average after the last iteration. `dataset` needs `white_background` only; `log(iteration, ema)` is
-    called where the reference updates its progress bar."""
+    called where the reference updates its progress bar.
+
+    `prune_interval` = N > 0 (not in the reference; 0 changes nothing): after the optimizer step of every N-th iteration the
+    Gaussians with sigmoid(_opacity) < `prune_min_opacity` are removed, on the raw parameter (get_opacity would move the opacity
+    observer), with prune_points_indexed on an indexed model (unreferenced codebook rows go with them) and prune_points
+    otherwise; `log(iteration, ema)` is called once more after each prune."""
     gaussians = scene.gaussians if hasattr(scene, "gaussians") else dataset.gaussians
     first_iter = int(getattr(scene, "loaded_iter", 0) or 0)
     max_iter = first_iter + comp.finetune_iterations
@@ -133,6 +138,15 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None):
         if iteration < max_iter:
             gaussians.optimizer.step()
             gaussians.optimizer.zero_grad(set_to_none=True)
+            if prune_interval > 0 and (iteration - first_iter + 1) % prune_interval == 0:
+                with torch.no_grad():
+                    mask = (torch.sigmoid(gaussians._opacity.detach()) < prune_min_opacity).squeeze(-1)
+                    if gaussians.is_color_indexed or gaussians.is_gaussian_indexed:
+                        gaussians.prune_points_indexed(mask)
+                    else:
+                        gaussians.prune_points(mask)
+                if log is not None:
+                    log(iteration, ema_loss_for_log)
     return ema_loss_for_log
 
 

@@ -346,6 +346,41 @@ int c3dgs_rows_apply(int32_t P, int64_t P_new, const int32_t* src /*[P_new]*/, c
 int c3dgs_densify_stats(int32_t P, const float* grad /*[P,3]*/, const uint8_t* filter /*[P]*/, const int32_t* radii /*[P] or NULL*/,
                         float* accum /*[P]*/, float* denom /*[P]*/, float* max_radii /*[P] or NULL*/, void* stream);
 
+/* ---- prune / codebook compaction of an INDEXED model (scene/gaussian_model.py:1101-1158, the index remapping the entry points
+ * above do not mirror). A model keeps up to two index spaces: space 0 = colour (idx0 = _feature_indices into the K0 rows of
+ * _features_dc / _features_rest), space 1 = geometry (idx1 = _gaussian_indices into the K1 rows of _scaling / _rotation).
+ * The plan removes the Gaussians with keep[i] == 0 (keep == NULL: all survive), drops every codebook row no survivor
+ * references and renumbers the indices; c3dgs_rows_apply then moves the rows (kind all C3DGS_KIND_ORIGINAL, role copy: one
+ * launch per row space, by src, cb_src0 and cb_src1). Added without an ABI version bump: new entry points only.
+ *
+ * Order contract:
+ *   src[j]       source row of surviving Gaussian j, in source order                              j < P_new
+ *   cb_srcX[r]   old id of surviving codebook row r: the referenced old ids in ASCENDING order     r < KX_new
+ *   new_idxX[j]  rank of idxX[src[j]] among the referenced ids, so  cb_srcX[new_idxX[j]] == idxX[src[j]]
+ * which is the reference's result (sorted unique ids, index_map[u] = position of u, :1110-1114) without its Python loop
+ * over the ids. An index space whose idx is NULL is skipped: its total is 0 and its outputs are not touched.
+ *
+ * totals (device int32[4]) = {P_new, K0_new, K1_new, out_of_range}. Two-call protocol, like c3dgs_rows_plan: with
+ * src == NULL only the totals are computed (the caller reads them once, allocates and calls again; the second call
+ * recomputes flags, scans and totals from the inputs, nothing is carried over in the workspace); otherwise src, and
+ * new_idxX and cb_srcX of every index space given, are required, rows j < cap_rows of src / new_idx0 / new_idx1,
+ * r < cap_cb0 of cb_src0 and r < cap_cb1 of cb_src1 are written and nothing beyond the capacities is touched.
+ *
+ * Bad indices: an index outside [0, KX) is never dereferenced. Every one of them is counted in totals[3], over ALL P rows of
+ * every index space given (the reference asserts index.max() < n_feats on the whole array, :1106), it references no row,
+ * and where its Gaussian survives new_idxX[j] = -1. The caller is expected to treat totals[3] != 0 as an error.
+ *
+ * Limits: row counts are int32 and at most INT32_MAX - 255, indices int64. P = 0 (totals = 0, nothing else touched), KX = 0 with idxX NULL, and
+ * P_new = 0 are valid. P, K0, K1 or a capacity < 0, P, K0 or K1 > INT32_MAX - 255, idxX given with KX <= 0, a NULL totals or workspace, and src given
+ * without the outputs of a given index space return C3DGS_E_INVALID before any launch.
+ * workspace >= c3dgs_index_plan_workspace_bytes(P, K0, K1); the library clears the flags it keeps there itself. */
+size_t c3dgs_index_plan_workspace_bytes(int32_t P, int32_t K0, int32_t K1);
+int c3dgs_index_plan(int32_t P, const uint8_t* keep /*[P] or NULL*/, const int64_t* idx0 /*[P] or NULL*/, int32_t K0,
+                     const int64_t* idx1 /*[P] or NULL*/, int32_t K1, int64_t cap_rows, int64_t cap_cb0, int64_t cap_cb1,
+                     int32_t* src /*[P_new]*/, int64_t* new_idx0 /*[P_new]*/, int64_t* new_idx1 /*[P_new]*/,
+                     int32_t* cb_src0 /*[K0_new]*/, int32_t* cb_src1 /*[K1_new]*/, int32_t* totals /*device [4]*/,
+                     void* workspace, void* stream);
+
 /* ---- sensitivity pass (compress.py:110-113): acc[i] += |g[i]| for n floats, one launch */
 int c3dgs_abs_accumulate(int64_t n, const float* g, float* acc, void* stream);
 
