@@ -40,6 +40,7 @@ SOURCES = {
     "qat.hip": ["-ffp-contract=off"],
     "densify.hip": ["-ffp-contract=off"],   # sqrt(gx*gx + gy*gy) of the densification stats is torch's two-rounding sum
     "index_plan.hip": [],
+    "ray_fill.hip": ["-ffp-contract=off"],  # x * (1 - a) + a * y of the new positions is four separately rounded operations
 }
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), os.path.join(CSRC, "render_diag.hpp"),
            os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h")]

@@ -2,6 +2,8 @@
 // Stage order follows the reference's Rasterizer::forward / backward (cuda_rasterizer/rasterizer_impl.cu:194-334,
 // 338-435, 440-586, 590-697); the stages themselves are the gfx950 kernels in this directory.
 #include "common.hpp"
+#include <cfloat>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -650,6 +652,20 @@ int c3dgs_knn_mean_dist2(int32_t P, const float* xyz, float* out, void* workspac
     return C3DGS_OK;
 }
 
+int c3dgs_knn_neighbours(int32_t P, const float* xyz, int32_t* idx, float* d2, void* workspace, void* stream)
+{
+    if (P < 0) return fail(C3DGS_E_INVALID, "knn_neighbours: P must be >= 0");
+    if (P == 0) return C3DGS_OK;
+    if (!xyz || !idx || !d2 || !workspace) return fail(C3DGS_E_INVALID, "knn_neighbours: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    { StageTimer t_(ST_KNN_SORT, s);
+      if (run_knn_sort(P, xyz, workspace, s)) return fail(C3DGS_E_HIP, "knn_neighbours: sort failed"); }
+    C3DGS_STAGE_CHECK(ST_KNN_SORT, 0, s);
+    C3DGS_TIMED_STAGE(ST_KNN_BOUNDS, 0, s, launch_knn_bounds(P, workspace, s));
+    C3DGS_TIMED_STAGE(ST_KNN_QUERY, 0, s, launch_knn_query_neighbours(P, workspace, idx, d2, s));
+    return C3DGS_OK;
+}
+
 int c3dgs_abs_accumulate(int64_t n, const float* g, float* acc, void* stream)
 {
     if (n < 0 || (n > 0 && (!g || !acc))) return fail(C3DGS_E_INVALID, "abs_accumulate: bad arguments");
@@ -746,6 +762,40 @@ int c3dgs_densify_stats(int32_t P, const float* grad, const uint8_t* filter, con
     if ((radii == nullptr) != (max_radii == nullptr)) return fail(C3DGS_E_INVALID, "densify_stats: radii and max_radii go together");
     launch_densify_stats(P, grad, filter, radii, accum, denom, max_radii, (hipStream_t)stream);
     C3DGS_STAGE("densify_stats", 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
+// ---- initial densification (ray_fill.hip)
+size_t c3dgs_ray_fill_plan_workspace_bytes(int32_t P, int64_t rows) { return ray_fill_plan_workspace_bytes(P, rows); }
+
+int c3dgs_ray_fill_plan(int32_t P, const float* d2, float step, int64_t capacity, int32_t* src, uint8_t* slot, int32_t* level,
+                        int32_t* totals, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (P < 0 || capacity < 0) return fail(C3DGS_E_INVALID, "ray_fill_plan: P and capacity must be >= 0");
+    if (P > INT32_MAX - 255) return fail(C3DGS_E_INVALID, "ray_fill_plan: P must be at most INT32_MAX - 255");
+    if (!(step > 0.f) || !(step <= FLT_MAX)) return fail(C3DGS_E_INVALID, "ray_fill_plan: step must be a positive finite number");
+    if (!totals) return fail(C3DGS_E_INVALID, "ray_fill_plan: totals is required");
+    if (src && (!slot || !level)) return fail(C3DGS_E_INVALID, "ray_fill_plan: src, slot and level go together");
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0) { C3DGS_HIP_TRY(hipMemsetAsync(totals, 0, 4 * sizeof(int32_t), s)); return C3DGS_OK; }
+    if (!d2 || !workspace) return fail(C3DGS_E_INVALID, "ray_fill_plan: NULL buffer");
+    std::string problem;
+    C3DGS_HIP_TRY(run_ray_fill_plan(P, d2, step, capacity, src, slot, level, totals, workspace, workspace_bytes, s, &problem));
+    if (!problem.empty()) return fail(C3DGS_E_INVALID, "ray_fill_plan: " + problem);
+    C3DGS_STAGE("ray_fill_plan", 0, s);
+    return C3DGS_OK;
+}
+
+int c3dgs_ray_fill_xyz(int32_t P, const float* xyz, const int32_t* idx, const float* d2, float step, int64_t n_new,
+                       const int32_t* src, const uint8_t* slot, const int32_t* level, float* out, void* stream)
+{
+    if (P < 0 || n_new < 0) return fail(C3DGS_E_INVALID, "ray_fill_xyz: sizes must be >= 0");
+    if (n_new > INT32_MAX - 255) return fail(C3DGS_E_INVALID, "ray_fill_xyz: n_new must be at most INT32_MAX - 255");
+    if (!(step > 0.f) || !(step <= FLT_MAX)) return fail(C3DGS_E_INVALID, "ray_fill_xyz: step must be a positive finite number");
+    if (n_new == 0) return C3DGS_OK;
+    if (!xyz || !idx || !d2 || !src || !slot || !level || !out) return fail(C3DGS_E_INVALID, "ray_fill_xyz: NULL buffer");
+    launch_ray_fill_xyz(P, xyz, idx, d2, step, n_new, src, slot, level, out, (hipStream_t)stream);
+    C3DGS_STAGE("ray_fill_xyz", 0, (hipStream_t)stream);
     return C3DGS_OK;
 }
 

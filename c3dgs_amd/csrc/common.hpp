@@ -298,6 +298,14 @@ size_t knn_workspace_bytes(int P);
 int run_knn_sort(int P, const float* xyz, void* workspace, hipStream_t s);
 void launch_knn_bounds(int P, void* workspace, hipStream_t s);
 void launch_knn_query(int P, const void* workspace, float* out, hipStream_t s);
+void launch_knn_query_neighbours(int P, const void* workspace, int32_t* idx, float* d2, hipStream_t s);
+// ray_fill.hip (initial densification): top-2 -> counts -> scan -> emit -> per-slot level sort; then the positions.
+// A request the workspace cannot serve comes back in `problem` (hipSuccess, nothing written).
+size_t ray_fill_plan_workspace_bytes(int P, long long rows);
+hipError_t run_ray_fill_plan(int P, const float* d2, float step, long long capacity, int32_t* src, uint8_t* slot, int32_t* level,
+                             int32_t* totals, void* workspace, size_t workspace_bytes, hipStream_t s, std::string* problem);
+void launch_ray_fill_xyz(int P, const float* xyz, const int32_t* idx, const float* d2, float step, long long n_new,
+                         const int32_t* src, const uint8_t* slot, const int32_t* level, float* out, hipStream_t s);
 // adam.hip
 void launch_adam(int n_tensors, const c3dgs_adam_tensor* tensors, double beta1, double beta2, double eps, hipStream_t s);
 void launch_abs_accumulate(int64_t n, const float* g, float* acc, hipStream_t s);

@@ -18,8 +18,19 @@
 // The lower bound of a box uses the same fp32 operations in the same order as d(i,j), on the box point nearest to the
 // query (per axis a clamp, which is exact). |fl(a - q)| is monotone in |a - q| and fl(u + v) in u and v, so the bound is
 // <= d(i,j) for every point of the box after rounding too: pruning never drops a neighbour that would change the result.
+//
+// knn_query has two compile-time variants of one body. KnnBest (above) keeps the three distances only. KnnBestIdx keeps
+// (distance, original index) pairs for c3dgs_knn_neighbours, whose contract is the three smallest PAIRS in lexicographic
+// order: among equal distances the lowest original index wins, whatever order the tree is walked in. That tie rule changes
+// two things and only in that variant. A candidate is compared as (d, id), the id read from ids_sorted only when d <= the
+// third-best distance. And a node is pruned only when its bound is STRICTLY greater than the third-best: a box whose bound
+// equals it can hold a point at exactly that distance with a lower index, so it is visited (while the third-best is
+// non-zero; at zero the search stops as before, and the three coincident points found are reported in ascending index
+// order). The bound's exactness argument is untouched. The cost is the extra visits of equal-bound nodes, which only
+// exact ties produce (lattices, duplicated points), and three more registers per lane.
 #include "common.hpp"
 #include <cfloat>
+#include <climits>
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace c3dgs {
@@ -181,7 +192,12 @@ __device__ __forceinline__ float knn_box_d2(const float4 lo, const float4 hi, co
 }
 
 struct KnnBest {
+    using Out = float* __restrict__;                             // [P]: ((d0 + d1) + d2) / 3
+    static constexpr bool kIndices = false;
     float d0, d1, d2;
+    static __device__ __forceinline__ KnnBest empty() { return { INFINITY, INFINITY, INFINITY }; }
+    __device__ __forceinline__ void consider(float d, const uint32_t* __restrict__, int) { insert(d); }
+    __device__ __forceinline__ bool visits(float bound) const { return bound < d2; }
     __device__ __forceinline__ void insert(float d)
     {
         if (d < d2) {
@@ -193,39 +209,69 @@ struct KnnBest {
     }
 };
 
+// The three smallest (distance, original index) pairs in lexicographic order (see the head of the file).
+struct KnnNeighboursOut { int32_t* idx; float* d2; };           // [P,3] each
+struct KnnBestIdx {
+    using Out = KnnNeighboursOut;
+    static constexpr bool kIndices = true;
+    float d0, d1, d2;
+    int i0, i1, i2;
+    static __device__ __forceinline__ KnnBestIdx empty() { return { INFINITY, INFINITY, INFINITY, INT_MAX, INT_MAX, INT_MAX }; }
+    __device__ __forceinline__ void consider(float d, const uint32_t* __restrict__ ids_sorted, int j)
+    {
+        if (!(d <= d2)) return;
+        const int id = (int)ids_sorted[j];
+        if (d < d2 || id < i2) {
+            if (d < d1 || (d == d1 && id < i1)) {
+                d2 = d1; i2 = i1;
+                if (d < d0 || (d == d0 && id < i0)) { d1 = d0; i1 = i0; d0 = d; i0 = id; } else { d1 = d; i1 = id; }
+            } else { d2 = d; i2 = id; }
+        }
+    }
+    __device__ __forceinline__ bool visits(float bound) const { return bound <= d2; }
+    __device__ __forceinline__ void store(Out out, size_t id, int P) const   // missing slots: idx -1 (their d is FLT_MAX)
+    {
+        out.idx[3 * id] = P < 2 ? -1 : i0; out.idx[3 * id + 1] = P < 3 ? -1 : i1; out.idx[3 * id + 2] = P < 4 ? -1 : i2;
+        out.d2[3 * id] = d0; out.d2[3 * id + 1] = d1; out.d2[3 * id + 2] = d2;
+    }
+};
+
 // every point of leaf `leaf` except the query and the seed window (already counted)
-__device__ __forceinline__ void knn_scan_leaf(int P, int leaf, int s, const float4* __restrict__ pts, const float4 q, KnnBest& b)
+template <class Best>
+__device__ __forceinline__ void knn_scan_leaf(int P, int leaf, int s, const float4* __restrict__ pts,
+                                              const uint32_t* __restrict__ ids_sorted, const float4 q, Best& b)
 {
     const int j1 = min(P, (leaf + 1) * KNN_LEAF);
     for (int j = leaf * KNN_LEAF; j < j1; j++) {
         if (j >= s - KNN_WINDOW && j <= s + KNN_WINDOW) continue;
-        b.insert(knn_d2(pts[j], q));
+        b.consider(knn_d2(pts[j], q), ids_sorted, j);
         if (b.d2 == 0.f) return;
     }
 }
 
+template <class Best>
 __global__ void __launch_bounds__(256)
 knn_query(int P, int npow, int levels, const float4* __restrict__ pts, const float4* __restrict__ nodes,
-          const uint32_t* __restrict__ ids_sorted, float* __restrict__ out)
+          const uint32_t* __restrict__ ids_sorted, typename Best::Out out)
 {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= P) return;
     const float4 q = pts[s];
-    KnnBest b{ INFINITY, INFINITY, INFINITY };
+    Best b = Best::empty();
     for (int j = max(0, s - KNN_WINDOW); j <= min(P - 1, s + KNN_WINDOW); j++)
-        if (j != s) b.insert(knn_d2(pts[j], q));
+        if (j != s) b.consider(knn_d2(pts[j], q), ids_sorted, j);
     const int two_npow = 2 * npow;
     if (b.d2 > 0.f) {
         int leaf = s / KNN_LEAF;
-        knn_scan_leaf(P, leaf, s, pts, q, b);
+        knn_scan_leaf(P, leaf, s, pts, ids_sorted, q, b);
         // climb: at level l the subtree of the sibling of the query's own ancestor; depth first, left child first
         for (int l0 = 0; l0 + 1 < levels && b.d2 > 0.f; l0++, leaf >>= 1) {
             int l = l0, k = leaf ^ 1;
             for (;;) {
                 const float4* nd = nodes + 2 * ((size_t)knn_level_offset(two_npow, l) + k);
-                if (knn_box_d2(nd[0], nd[1], q) < b.d2) {
+                if (b.visits(knn_box_d2(nd[0], nd[1], q))) {
                     if (l > 0) { l--; k <<= 1; continue; }
-                    knn_scan_leaf(P, k, s, pts, q, b);
+                    knn_scan_leaf(P, k, s, pts, ids_sorted, q, b);
                     if (b.d2 == 0.f) break;
                 }
                 while (l != l0 && (k & 1)) { k >>= 1; l++; }     // next node of the subtree in depth-first order
@@ -239,7 +285,8 @@ knn_query(int P, int npow, int levels, const float4* __restrict__ pts, const flo
         if (P < 3) b.d1 = FLT_MAX;
         if (P < 2) b.d0 = FLT_MAX;
     }
-    out[ids_sorted[s]] = __fdiv_rn((b.d0 + b.d1) + b.d2, 3.0f);
+    if constexpr (Best::kIndices) b.store(out, ids_sorted[s], P);
+    else out[ids_sorted[s]] = __fdiv_rn((b.d0 + b.d1) + b.d2, 3.0f);
 }
 
 static int knn_grid(size_t n) { return (int)((n + 255) / 256); }
@@ -278,8 +325,17 @@ void launch_knn_query(int P, const void* workspace, float* out, hipStream_t s)
 {
     const KnnLayout L = knn_layout(P);
     const char* w = (const char*)workspace;
-    knn_query<<<knn_grid((size_t)P), 256, 0, s>>>(P, L.npow, L.levels, (const float4*)(w + L.pts), (const float4*)(w + L.nodes),
-                                                   (const uint32_t*)(w + L.ids_sorted), out);
+    knn_query<KnnBest><<<knn_grid((size_t)P), 256, 0, s>>>(P, L.npow, L.levels, (const float4*)(w + L.pts),
+                                                            (const float4*)(w + L.nodes), (const uint32_t*)(w + L.ids_sorted), out);
+}
+
+void launch_knn_query_neighbours(int P, const void* workspace, int32_t* idx, float* d2, hipStream_t s)
+{
+    const KnnLayout L = knn_layout(P);
+    const char* w = (const char*)workspace;
+    knn_query<KnnBestIdx><<<knn_grid((size_t)P), 256, 0, s>>>(P, L.npow, L.levels, (const float4*)(w + L.pts),
+                                                               (const float4*)(w + L.nodes), (const uint32_t*)(w + L.ids_sorted),
+                                                               KnnNeighboursOut{ idx, d2 });
 }
 
 } // namespace c3dgs

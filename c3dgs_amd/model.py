@@ -8,6 +8,7 @@ Mirrors of scene/gaussian_model.py:
     FakeQuantizationHalf                          :1405-1414
     save_ply / load / load_ply                    :324-503  (PLY IO in ply.py; distCUDA2 scales in knn.py)
     adaptive density control (non-indexed)        :288-290, :1061-1403  (csrc/densify.hip)
+    densify_initial                               :1352-1389  (csrc/ray_fill.hip, knn.py)
 
 The reference evaluates every getter with torch ops and seven torch.ao FakeQuantize modules: about a hundred small
 launches and twenty host syncs per view (aminmax + float(scale) / int(zero_point) per module, one nonzero per
@@ -17,6 +18,7 @@ launch, the rasterizer, and two backward launches (csrc/qat.hip). A single 4-byt
 remains; it overlaps the observe / codebook kernels.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -829,16 +831,21 @@ class GaussianModel:
         return src, kind, draw_row, (K, Cn, S, CK)
 
     def _rebuild(self, code, N=2, std=None, draws=None, carry_stats=False):
-        """plan -> one host read -> allocate every new tensor once -> ONE apply launch -> install parameters and optimizer
-        state (cat_tensors_to_optimizer / _prune_optimizer, :1081-1099, :1161-1185: `step` kept, moments of surviving originals
-        copied, zero for new rows). Returns (src, kind, draw_row, totals)."""
+        """plan -> one host read -> _apply_plan. Returns (src, kind, draw_row, totals)."""
+        src, kind, draw_row, tot = self.plan_rows(code, N)
+        K, Cn, S, CK = tot
+        self._apply_plan(src, kind, draw_row, K + Cn + N * CK, N, S, std=std, draws=draws, carry_stats=carry_stats)
+        return src, kind, draw_row, tot
+
+    def _apply_plan(self, src, kind, draw_row, P_new, N=2, S=0, std=None, draws=None, carry_stats=False, new_xyz=None):
+        """A given plan (include/c3dgs_hip.h c3dgs_rows_apply) -> allocate every new tensor once -> ONE apply launch -> install
+        parameters and optimizer state (cat_tensors_to_optimizer / _prune_optimizer, :1081-1099, :1161-1185: `step` kept,
+        moments of surviving originals copied, zero for new rows). `new_xyz(xyz_out)`, if given, runs between the launch and
+        the install and overwrites positions in the new xyz tensor."""
         lib = _lib.lib()
         dev = self.device
         P = self._xyz.shape[0]
         accum, denom, max_radii = self._density_stats()
-        src, kind, draw_row, tot = self.plan_rows(code, N)
-        K, Cn, S, CK = tot
-        P_new = K + Cn + N * CK
         if S > 0 and std is None:
             raise RuntimeError("split rows need their activated scales")
         if draws is None:
@@ -883,6 +890,8 @@ class GaussianModel:
                                             N * S, rotation.data_ptr(), _ptr(std),
                                             draws.data_ptr() if draws.numel() else None,
                                             int(not self.use_factor_scaling), int(self.quantization), _stream(dev)))
+        if new_xyz is not None:
+            new_xyz(new["_xyz"])
         self._install(new, moments)
         if stats_new is not None:
             self.xyz_gradient_accum, self.denom, self.max_radii2D = stats_new
@@ -890,7 +899,6 @@ class GaussianModel:
             self.xyz_gradient_accum = torch.zeros((P_new, 1), device=dev)
             self.denom = torch.zeros((P_new, 1), device=dev)
             self.max_radii2D = torch.zeros((P_new,), device=dev)
-        return src, kind, draw_row, tot
 
     def _install(self, new, moments):
         """The new parameter tensors {attr: tensor} become the model's leaves; each one's param group is re-pointed and its
@@ -955,14 +963,108 @@ class GaussianModel:
                 classify(min_opacity)
             return self._rebuild(code, N, std=s2, draws=draws)
 
-    def densify_and_clone(self, grads, grad_threshold, scene_extent):
-        """:1279-1330 (the gradient-mask form). Row order: every original, then the clones."""
+    def _append_clones(self, rows, new_xyz=None):
+        """Every original, then a copy of each row of `rows` (int32, in the order given; moments zero), through the one apply
+        launch; `new_xyz(xyz_out)` as in _apply_plan."""
+        dev = self.device
+        P, n = self._xyz.shape[0], int(rows.shape[0])
+        src = torch.cat((torch.arange(P, dtype=torch.int32, device=dev), rows))
+        kind = torch.zeros(P + n, dtype=torch.uint8, device=dev)
+        kind[P:] = 1                                              # C3DGS_KIND_CLONE
+        draw_row = torch.full((P + n,), -1, dtype=torch.int32, device=dev)
+        self._apply_plan(src, kind, draw_row, P + n, new_xyz=new_xyz)
+        return src, kind, draw_row
+
+    def densify_and_clone(self, grads=None, grad_threshold=None, scene_extent=None, selected_pts_mask=None, new_xyz=None):
+        """:1279-1330. The gradient-mask form: row order every original, then the clones; returns (src, kind, draw_row,
+        totals). The explicit form (`selected_pts_mask`: a bool mask or an index tensor; `new_xyz`: [n,3] positions that
+        replace the copies' own): the selected rows are appended in the order given; returns (src, kind, draw_row)."""
         self._dense_only("densify_and_clone")
+        if selected_pts_mask is not None:
+            with torch.no_grad():
+                P = self._xyz.shape[0]
+                sel = torch.as_tensor(selected_pts_mask, device=self.device)
+                if sel.dtype == torch.bool:
+                    if tuple(sel.shape) != (P,):
+                        raise ValueError(f"densify_and_clone: a bool mask must have shape ({P},), got {tuple(sel.shape)}")
+                    rows = torch.nonzero(sel).squeeze(1)
+                else:
+                    rows = sel.reshape(-1).to(torch.int64)
+                    rows = torch.where(rows < 0, rows + P, rows)          # torch indexing counts negatives from the end
+                    if rows.numel() and not bool(((rows >= 0) & (rows < P)).all()):
+                        raise IndexError(f"densify_and_clone: row index out of range for {P} rows")
+                n = int(rows.shape[0])
+                if P + n > 2**31 - 256:
+                    raise ValueError(f"densify_and_clone: {P + n} rows do not fit the row plan")
+                fill = None
+                if new_xyz is not None:
+                    pos = torch.as_tensor(new_xyz, dtype=torch.float32, device=self.device)
+                    if tuple(pos.shape) != (n, 3):
+                        raise ValueError(f"densify_and_clone: new_xyz must be [{n}, 3], got {tuple(pos.shape)}")
+
+                    def fill(out):
+                        out[P:] = pos
+                return self._append_clones(rows.to(torch.int32), fill)
+        if new_xyz is not None:
+            raise ValueError("densify_and_clone: new_xyz goes with selected_pts_mask")
         with torch.no_grad():
             mask = torch.norm(grads, dim=-1) >= grad_threshold
             mask &= self.get_scaling.detach().amax(dim=1) <= self.percent_dense * scene_extent
             code = mask.to(torch.uint8) * _lib.ROW_CLONE + _lib.ROW_KEEP
             return self._rebuild(code.contiguous())
+
+    def densify_initial(self, dist_thr_coeff=1.0, max_points=None):
+        """:1352-1389 in one pass (csrc/ray_fill.hip; DESIGN.md "Initial densification"): the gaps between every point and its
+        three nearest neighbours are filled with new points one `average_step` apart. Every other attribute of a new row is
+        its source row's, its moments are zero, the accumulators restart at the new length. Returns (src int32[n], slot
+        uint8[n], level int32[n], (n0, n1, n2)) for the n new rows, in the reference's row order: slot, then level, then
+        source index. A call that adds no row leaves the model untouched. Two host reads (the step, the totals).
+        ValueError, with the model unchanged: fewer than 4 points, a zero or non-finite step (a planar cloud), and a new
+        row count that overflows int32 or exceeds `max_points` (checked before anything is allocated)."""
+        self._dense_only("densify_initial")
+        from .knn import knn3
+        lib = _lib.lib()
+        dev = self.device
+        with torch.no_grad():
+            x = _need_gpu(self._xyz.detach(), "xyz")                      # the raw _xyz, not get_xyz (:1355-1364)
+            P = int(x.shape[0])
+            if P < 4:
+                raise ValueError(f"densify_initial: three neighbours need at least 4 points, the model has {P}")
+            # :1355-1358: the product in fp32 (on the host, where its order is the reference's on a CPU model), the rest in doubles
+            volume = torch.prod((x.max(dim=0)[0] - x.min(dim=0)[0]).cpu()).item() / P
+            average_step = dist_thr_coeff * volume ** (1.0 / 3)
+            step = C.c_float(average_step).value                          # numpy divides float32 by it: used rounded to fp32
+            if not (math.isfinite(step) and step > 0.0):
+                raise ValueError(f"densify_initial: the average step is {average_step!r} (bounding-box volume {volume * P!r}): "
+                                 "the cloud has no extent on some axis, or dist_thr_coeff is not a positive finite number")
+            idx, d2 = knn3(x)
+            s = _stream(dev)
+            totals = torch.empty(4, dtype=torch.int32, device=dev)
+            ws = torch.empty(int(lib.c3dgs_ray_fill_plan_workspace_bytes(P, 0)), dtype=torch.uint8, device=dev)
+            _lib.check(lib.c3dgs_ray_fill_plan(P, d2.data_ptr(), step, 0, None, None, None, totals.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), s))
+            n0, n1, n2, overflow = self._read_totals(totals)
+            n = n0 + n1 + n2
+            if overflow:
+                raise ValueError(f"densify_initial: more than {2**31 - 256 - P} new rows (at least {n} counted) for {P} points "
+                                 f"at step {step!r}: an outlier far from the cloud? Raise dist_thr_coeff or remove it")
+            if max_points is not None and P + n > max_points:
+                raise ValueError(f"densify_initial: {P} points would become {P + n} rows, more than max_points = {max_points} "
+                                 f"(step {step!r}); an outlier adds one row per step of its distance")
+            src = torch.empty(n, dtype=torch.int32, device=dev)
+            slot = torch.empty(n, dtype=torch.uint8, device=dev)
+            level = torch.empty(n, dtype=torch.int32, device=dev)
+            if n == 0:
+                return src, slot, level, (0, 0, 0)
+            ws = torch.empty(int(lib.c3dgs_ray_fill_plan_workspace_bytes(P, n)), dtype=torch.uint8, device=dev)
+            _lib.check(lib.c3dgs_ray_fill_plan(P, d2.data_ptr(), step, n, src.data_ptr(), slot.data_ptr(), level.data_ptr(),
+                                               totals.data_ptr(), ws.data_ptr(), ws.numel(), s))
+
+            def fill(out):
+                _lib.check(lib.c3dgs_ray_fill_xyz(P, x.data_ptr(), idx.data_ptr(), d2.data_ptr(), step, n, src.data_ptr(),
+                                                  slot.data_ptr(), level.data_ptr(), out[P:].data_ptr(), s))
+            self._append_clones(src, fill)
+            return src, slot, level, (n0, n1, n2)
 
     def densify_and_split(self, grads, grad_threshold, scene_extent, N=2, draws=None):
         """:1213-1277. Row order: the originals that are not selected, then child copy 0 .. N-1 of the selected ones."""

@@ -261,6 +261,14 @@ int c3dgs_morton_order(int32_t P, const float* xyz /*[P,3]*/, int64_t* codes /*[
  * workspace: c3dgs_knn_workspace_bytes(P) bytes. P == 0 is a no-op that touches no pointer. */
 size_t c3dgs_knn_workspace_bytes(int32_t P);
 int c3dgs_knn_mean_dist2(int32_t P, const float* xyz /*[P,3]*/, float* out /*[P]*/, void* workspace, void* stream);
+/* The same search with the neighbours' indices (what GaussianModel.densify_initial needs, scene/gaussian_model.py:1366-1367).
+ * (d2[i,k], idx[i,k]), k = 0..2, are the three smallest (distance, index) pairs over j != i by index, in ascending
+ * lexicographic order: among equal distances the lowest index wins, so the result does not depend on the search order.
+ * One exception keeps coincident clouds cheap: a point with three or more other points at distance 0 reports any three of
+ * them, in ascending index order, all with d2 = 0. Missing slots (P <= 3): idx = -1, d2 = FLT_MAX. The distances are those
+ * c3dgs_knn_mean_dist2 averages. Same workspace, same no-op for P == 0. Added without an ABI version bump. */
+int c3dgs_knn_neighbours(int32_t P, const float* xyz /*[P,3]*/, int32_t* idx /*[P,3]*/, float* d2 /*[P,3]*/, void* workspace,
+                         void* stream);
 
 /* ---- fused Adam step (the optimizer.step() that closes the QAT inner loop, finetune.py:65-66; optimizer set-up
  * scene/gaussian_model.py:296-308: torch.optim.Adam(param groups, lr=0.0, eps=1e-15), no weight decay, no amsgrad).
@@ -345,6 +353,34 @@ int c3dgs_rows_apply(int32_t P, int64_t P_new, const int32_t* src /*[P_new]*/, c
  * max_radii = max(max_radii, radii). */
 int c3dgs_densify_stats(int32_t P, const float* grad /*[P,3]*/, const uint8_t* filter /*[P]*/, const int32_t* radii /*[P] or NULL*/,
                         float* accum /*[P]*/, float* denom /*[P]*/, float* max_radii /*[P] or NULL*/, void* stream);
+
+/* ---- initial densification (GaussianModel.densify_initial, scene/gaussian_model.py:1352-1389): new points one `step` apart
+ * on the ray from every point to each of its three nearest neighbours, planned in one pass from the neighbour table of
+ * c3dgs_knn_neighbours instead of the reference's loop over levels (DESIGN.md "Initial densification"). With
+ *   rel[i,nb] = fl(fl(sqrt(d2[i,nb])) / step)      and r2[nb] the second-largest rel of slot nb, counted with multiplicity,
+ * point i receives c = max(0, floor(min(rel, r2)) - 1) rows for slot nb, at levels 1..c (the min with r2 is the reference's
+ * `slot.sum() > 1`: levels only the single farthest point reaches insert nothing). Added without an ABI version bump.
+ *
+ * plan: the source map of the NEW rows in the reference's order: slot-major (nb = 0, 1, 2), then level ascending, then
+ * source index ascending. totals (device int32[4]) = {rows of slot 0, slot 1, slot 2, overflow}. Per-point counts saturate
+ * at INT32_MAX, sums are formed in 64 bits, and overflow = 1 when P + new rows > INT32_MAX - 255; then the slot totals are
+ * clamped and nothing else is written. Two-call protocol, like c3dgs_rows_plan: with src == NULL only the totals are
+ * computed (workspace >= c3dgs_ray_fill_plan_workspace_bytes(P, 0)); the caller reads them, allocates and calls again with
+ * workspace >= c3dgs_ray_fill_plan_workspace_bytes(P, rows of all three slots). The second call recomputes everything from
+ * its inputs, reads the totals back itself (one small synchronising read: they size its launches and the key bits of the
+ * level sort), writes rows j < capacity of src, slot (0..2) and level (1..c) and touches nothing beyond. P == 0: totals = 0.
+ * P or capacity < 0, P > INT32_MAX - 255, a step that is not a positive finite number, NULL d2, totals or workspace, src
+ * without slot and level, and a workspace too small for the rows return C3DGS_E_INVALID; all but the last before any launch. */
+size_t c3dgs_ray_fill_plan_workspace_bytes(int32_t P, int64_t rows);
+int c3dgs_ray_fill_plan(int32_t P, const float* d2 /*[P,3]*/, float step, int64_t capacity, int32_t* src, uint8_t* slot,
+                        int32_t* level, int32_t* totals /*device [4]*/, void* workspace, size_t workspace_bytes, void* stream);
+/* positions: out[r] = xyz[i] * (1 - a) + a * xyz[idx[i,nb]], a = fl(float(level[r]) / rel[i,nb]), i = src[r], nb = slot[r];
+ * one subtraction, two multiplications and one addition, each rounded to fp32 on its own (:1379, :1385). `out` is the
+ * [n_new,3] block behind the P originals of the new xyz tensor. A row whose src, slot or neighbour is out of range gets
+ * zeros and reads nothing. */
+int c3dgs_ray_fill_xyz(int32_t P, const float* xyz /*[P,3]*/, const int32_t* idx /*[P,3]*/, const float* d2 /*[P,3]*/, float step,
+                       int64_t n_new, const int32_t* src, const uint8_t* slot, const int32_t* level, float* out /*[n_new,3]*/,
+                       void* stream);
 
 /* ---- prune / codebook compaction of an INDEXED model (scene/gaussian_model.py:1101-1158, the index remapping the entry points
  * above do not mirror). A model keeps up to two index spaces: space 0 = colour (idx0 = _feature_indices into the K0 rows of
