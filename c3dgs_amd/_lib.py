@@ -128,6 +128,7 @@ PROTOTYPES = {
     "c3dgs_ray_fill_plan_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "c3dgs_ray_fill_plan": (C.c_int, [C.c_int32, _vp, C.c_float, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "c3dgs_ray_fill_xyz": (C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_float, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "c3dgs_image_from_u8": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     "c3dgs_adam_step": (C.c_int, [C.c_int32, C.POINTER(AdamTensor), C.c_double, C.c_double, C.c_double, _vp]),
     "c3dgs_densify_classify": (C.c_int, [C.c_int32] + [_vp] * 7 + [C.c_float] * 4 + [_vp, _vp]),
     "c3dgs_rows_plan_workspace_bytes": (C.c_size_t, [C.c_int32]),

@@ -41,6 +41,7 @@ SOURCES = {
     "densify.hip": ["-ffp-contract=off"],   # sqrt(gx*gx + gy*gy) of the densification stats is torch's two-rounding sum
     "index_plan.hip": [],
     "ray_fill.hip": ["-ffp-contract=off"],  # x * (1 - a) + a * y of the new positions is four separately rounded operations
+    "image_io.hip": ["-ffp-contract=off"],  # t0 * (1 - f) + t1 * f of the bilinear taps is separately rounded (csrc/image_io.hip)
 }
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), os.path.join(CSRC, "render_diag.hpp"),
            os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h")]

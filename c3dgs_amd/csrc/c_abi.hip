@@ -799,6 +799,21 @@ int c3dgs_ray_fill_xyz(int32_t P, const float* xyz, const int32_t* idx, const fl
     return C3DGS_OK;
 }
 
+// ---- ground-truth image of a camera (image_io.hip)
+int c3dgs_image_from_u8(int32_t Hs, int32_t Ws, int32_t C, const uint8_t* src, int32_t flip, const float* bg, int32_t Hd, int32_t Wd,
+                        float* out, void* stream)
+{
+    const int32_t kMax = 32768;
+    if (Hs < 1 || Ws < 1 || Hd < 1 || Wd < 1 || Hs > kMax || Ws > kMax || Hd > kMax || Wd > kMax)
+        return fail(C3DGS_E_INVALID, "image_from_u8: every dimension must be in [1, 32768]");
+    if (C != 3 && C != 4) return fail(C3DGS_E_INVALID, "image_from_u8: C must be 3 or 4");
+    if (bg && C == 3) return fail(C3DGS_E_INVALID, "image_from_u8: a background needs an alpha channel (C == 4)");
+    if (!src || !out) return fail(C3DGS_E_INVALID, "image_from_u8: NULL buffer");
+    launch_image_from_u8(Hs, Ws, C, src, flip != 0, bg, Hd, Wd, out, (hipStream_t)stream);
+    C3DGS_STAGE("image_from_u8", 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
 // ---- prune / codebook compaction of an indexed model (index_plan.hip)
 static const int32_t kIndexPlanMaxRows = INT32_MAX - 255;     // one lane per row in 256-lane workgroups, int arithmetic
 

@@ -306,6 +306,9 @@ hipError_t run_ray_fill_plan(int P, const float* d2, float step, long long capac
                              int32_t* totals, void* workspace, size_t workspace_bytes, hipStream_t s, std::string* problem);
 void launch_ray_fill_xyz(int P, const float* xyz, const int32_t* idx, const float* d2, float step, long long n_new,
                          const int32_t* src, const uint8_t* slot, const int32_t* level, float* out, hipStream_t s);
+// image_io.hip
+void launch_image_from_u8(int Hs, int Ws, int C, const uint8_t* src, int flip, const float* bg, int Hd, int Wd, float* out,
+                          hipStream_t s);
 // adam.hip
 void launch_adam(int n_tensors, const c3dgs_adam_tensor* tensors, double beta1, double beta2, double eps, hipStream_t s);
 void launch_abs_accumulate(int64_t n, const float* g, float* acc, hipStream_t s);

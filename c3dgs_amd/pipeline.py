@@ -3,9 +3,9 @@
     train(...)               <- train.py:15-173          (optimise a scene from a point cloud, with adaptive density control)
     finetune(...)            <- finetune.py:10-66        (hot loop C of SURVEY.md section 3)
     run_vq(...)              <- compress.py:202-303      (sensitivity -> prune + VQ -> fine-tune -> npz [-> evaluation])
-    OptimizationParams / CompressionParams               <- arguments/__init__.py:85-136 (defaults only, no argparse)
+    OptimizationParams / CompressionParams / ModelParams <- arguments/__init__.py:43-136 (defaults only, no argparse)
 
-The reference's `Scene` (COLMAP / Blender loaders, camera JSON) is outside the path: here `scene` is anything with
+c3dgs_amd.scene.Scene builds a scene from a COLMAP / Blender / Dust3r dataset; the drivers take anything with
 `getTrainCameras()` -> sequence of cameras carrying `intrinsic`, `extrinsic_vector` and `original_image` (a plain list
 of such cameras is accepted too), and `loaded_iter` (default 0). Everything numeric runs in the package's HIP kernels:
 GaussianModel.render (fused getters + rasterizer), the fused L1+SSIM loss, the fused Adam.
@@ -48,6 +48,26 @@ class OptimizationParams:
         self.random_background = False
         self.not_quantization_aware = False
         _apply(self, overrides)
+
+
+class ModelParams:
+    """arguments/__init__.py:43-73: where a scene is read from and written to (c3dgs_amd.scene.Scene reads these)."""
+
+    def __init__(self, **overrides):
+        self.sh_degree = 3
+        self.source_path = ""
+        self.model_path = ""
+        self.images = "images"
+        self.resolution = -1
+        self.white_background = False
+        self.data_device = "cuda"
+        self.eval = False
+        _apply(self, overrides)
+
+    def extract(self, args=None):
+        """The reference's extract() without its argparse half: the source path made absolute."""
+        self.source_path = os.path.abspath(self.source_path)
+        return self
 
 
 class CompressionParams:

@@ -382,6 +382,25 @@ int c3dgs_ray_fill_xyz(int32_t P, const float* xyz /*[P,3]*/, const int32_t* idx
                        int64_t n_new, const int32_t* src, const uint8_t* slot, const int32_t* level, float* out /*[n_new,3]*/,
                        void* stream);
 
+/* ---- ground-truth image of a camera (scene/cameras.py:67-92, Camera.original_image): decoded 8-bit texels -> the planar fp32
+ * image the loss reads, at the camera's resolution, in one launch. Added without an ABI version bump: a new entry point only.
+ * Every step is ONE separately rounded fp32 operation unless fp64 is stated:
+ *   texel    v = fl(float(u) / 255), correctly rounded
+ *   alpha    C == 4: a = fl(float(u_a) / 255), v = v * a;  with bg != NULL: v = v * a + bg[c] * (1 - a)
+ *   flip     flip != 0: texel (y, x) is read from (Hs-1-y, Ws-1-x), an index remap in front of the resize
+ *   resize   OpenCV's documented INTER_LINEAR (half-pixel centres, edge clamp, no antialiasing). Per axis, in fp64:
+ *            scale = 1.0 / ((double)dst / (double)src), f = (float)((d + 0.5) * scale - 0.5); then s = floor(f), f -= s;
+ *            s < 0 -> s = 0, f = 0; s >= src - 1 -> s = src - 1, f = 0; second tap at min(s + 1, src - 1).
+ *            h = t0 * (1 - fx) + t1 * fx on both rows, then o = h0 * (1 - fy) + h1 * fy. Equal sizes give the texel value.
+ *   output   out[c][y][x] = min(max(o, 0), 1)
+ * Nothing outside `out` is written; `src` is read through the aligned dwords that hold its bytes and nothing beyond them.
+ * No atomics: bit-identical from run to run. A NULL src or out, C not in {3, 4}, bg with C == 3 and a dimension outside
+ * [1, 32768] return C3DGS_E_INVALID before any launch. The image path is our own contract (tests/image_ref.py): cv2.resize
+ * itself is not pinned. */
+int c3dgs_image_from_u8(int32_t Hs, int32_t Ws, int32_t C /*3|4*/, const uint8_t* src /*device [Hs][Ws][C]*/, int32_t flip,
+                        const float* bg /*device [3] or NULL*/, int32_t Hd, int32_t Wd, float* out /*device [3][Hd][Wd]*/,
+                        void* stream);
+
 /* ---- prune / codebook compaction of an INDEXED model (scene/gaussian_model.py:1101-1158, the index remapping the entry points
  * above do not mirror). A model keeps up to two index spaces: space 0 = colour (idx0 = _feature_indices into the K0 rows of
  * _features_dc / _features_rest), space 1 = geometry (idx1 = _gaussian_indices into the K1 rows of _scaling / _rotation).
