@@ -6,13 +6,23 @@ DISCRETE structure from an oracle forward (which Gaussians are in which tile, in
 it pins the oracle's analytic backward (K10-K12) and forward colours on tiny scenes.
 
 Reference semantics mirrored on purpose:
-  * alpha = min(0.99, o*G); skip power>0, alpha<1/255; stop before blending when T(1-alpha)<1e-4
+  * alpha = min(0.99, o*G); skip power>0, alpha<1/255; stop before blending when T(1-alpha)<1e-4.  The three thresholds
+    are the fp32 roundings the reference compiles (0.99f, 1.0f/255.0f, 0.0001f), not the decimals: behind two clamped
+    layers T = (1-0.99)^2 is 1.0000000000000018e-4 in float64 decimals (no stop) but 9.99998e-5 with 0.99f (stop)
+  * the 0.99 clamp passes the gradient STRAIGHT THROUGH: the reference's backward (backward.cu:499-554) recomputes
+    alpha = min(0.99, o*G) and then differentiates o*G as if unclamped (dL/dG = o * dL/dalpha, dL/do = G * dL/dalpha),
+    so a clamped blend still moves its Gaussian; autograd of a hard min() would give it zero
   * colour = SH + 0.5, clamped at 0 only if clamp_color
   * quaternions are NOT normalised inside the op
   * the t-clamp of computeCov2D passes no gradient through the clamped coordinate
   * dL/dmeans2D is in NDC units (0.5*W, 0.5*H factors)
 """
+import numpy as np
 import torch
+
+A_MAX = float(np.float32(0.99))                       # the reference's fp32 constants, as tests/fullsize.py takes them
+A_THR = float(np.float32(1.0) / np.float32(255.0))
+T_THR = float(np.float32(0.0001))
 
 C0 = 0.28209479177387814
 C1 = 0.4886025119029199
@@ -48,10 +58,14 @@ def _rot(q):
     return R
 
 
-def dense_render(st, leaves, dL_dout=None):
+def dense_render(st, leaves, dL_dout=None, hard_clamp=False, keep=None):
     """st: oracle RasterState (for the discrete structure + camera); leaves: dict of float64 tensors
     (requires_grad as wanted): means3D, means2D(zeros[P,3]), opacities[P], and one of shs|colors_precomp,
-    one of (scales, rotations[, scale_factors])|cov3D_precomp.  Returns image [3,H,W] (float64)."""
+    one of (scales, rotations[, scale_factors])|cov3D_precomp.  Returns image [3,H,W] (float64).
+    hard_clamp=True differentiates min(0.99, o*G) as autograd would (zero where clamped): NOT the reference's semantics,
+    kept so that a test can show the two are told apart.
+    keep: a dict that receives the intermediates the op also returns gradients for -- "cov3D" [P,6] (upper triangle) and
+    "colors" [P,3] (after the clamp) -- with retain_grad() set."""
     i = st.inputs
     dd = torch.float64
     view = torch.tensor(i["viewmatrix"], dtype=dd).reshape(4, 4)   # = W2C^T
@@ -84,6 +98,12 @@ def dense_render(st, leaves, dL_dout=None):
             Rm = _rot(rt)
         Lm = Rm * s[:, None, :]
         Sigma = Lm @ Lm.transpose(1, 2)
+        if keep is not None:
+            c6 = torch.stack([Sigma[:, 0, 0], Sigma[:, 0, 1], Sigma[:, 0, 2], Sigma[:, 1, 1], Sigma[:, 1, 2], Sigma[:, 2, 2]], -1)
+            c6.retain_grad()
+            keep["cov3D"] = c6
+            Sigma = torch.stack([c6[:, 0], c6[:, 1], c6[:, 2], c6[:, 1], c6[:, 3], c6[:, 4], c6[:, 2], c6[:, 4], c6[:, 5]],
+                                -1).reshape(-1, 3, 3)
 
     limx, limy = 1.3 * tfx, 1.3 * tfy
     txtz, tytz = t[:, 0] / t[:, 2], t[:, 1] / t[:, 2]
@@ -116,6 +136,9 @@ def dense_render(st, leaves, dL_dout=None):
         col = _sh_color(int(i["degree"]), sh, d) + 0.5
         if i["clamp_color"]:
             col = torch.clamp_min(col, 0.0)
+        if keep is not None:
+            col.retain_grad()
+            keep["colors"] = col
 
     opac = leaves["opacities"].reshape(-1)
     bg = torch.tensor(i["bg"], dtype=dd)
@@ -137,10 +160,13 @@ def dense_render(st, leaves, dL_dout=None):
             dx, dy = pixx[g] - px, pixy[g] - py
             power = -0.5 * (con[g, 0] * dx * dx + con[g, 2] * dy * dy) - con[g, 1] * dx * dy
             G = torch.exp(power)
-            alpha = torch.clamp_max(opac[g] * G, 0.99)
-            ok = (power <= 0) & (alpha >= 1.0 / 255.0) & ~done
+            raw = opac[g] * G
+            alpha = torch.clamp_max(raw, A_MAX)
+            if not hard_clamp:
+                alpha = raw + (alpha - raw).detach()
+            ok = (power <= 0) & (alpha >= A_THR) & ~done
             test_T = T * (1 - alpha)
-            newly = ok & (test_T < 0.0001)
+            newly = ok & (test_T < T_THR)
             done = done | newly
             contrib = ok & ~newly
             Cc = Cc + torch.where(contrib, alpha * T, torch.zeros_like(T))[None] * col[g][:, None, None]
@@ -148,3 +174,34 @@ def dense_render(st, leaves, dL_dout=None):
         y0, x0 = int(ys[0]), int(xs[0])
         img[:, y0:y0 + len(ys), x0:x0 + len(xs)] = Cc + T[None] * bg[:, None, None]
     return img
+
+
+def leaves_of(inp):
+    """Float64 autograd leaves of a tests/cases.py input dict."""
+    dd = torch.float64
+    P = inp["means3D"].shape[0]
+    lv = dict(means3D=inp["means3D"].to(dd).requires_grad_(), means2D=torch.zeros(P, 3, dtype=dd, requires_grad=True),
+              opacities=inp["opacities"].to(dd).requires_grad_())
+    for k in ("shs", "colors_precomp", "scales", "rotations", "cov3D_precomp", "scale_factors"):
+        if inp.get(k) is not None:
+            lv[k] = inp[k].to(dd).requires_grad_()
+    return lv
+
+
+def truth(st, inp, dL, hard_clamp=False):
+    """Float64 image and gradients of sum(image * dL), named and shaped like oracle.rasterize_backward's.
+    -> (image [3,H,W] numpy float64, dict of numpy float64)"""
+    lv = leaves_of(inp)
+    keep = {}
+    img = dense_render(st, lv, hard_clamp=hard_clamp, keep=keep)
+    (img * torch.as_tensor(dL, dtype=torch.float64)).sum().backward()
+    P = inp["means3D"].shape[0]
+    g = dict(dL_dmeans3D=lv["means3D"].grad, dL_dmeans2D=lv["means2D"].grad, dL_dopacity=lv["opacities"].grad.reshape(P, 1))
+    for name, k in (("dL_dsh", "shs"), ("dL_dscales", "scales"), ("dL_drotations", "rotations")):
+        if k in lv:
+            g[name] = lv[k].grad
+    if "scale_factors" in lv:
+        g["dL_dscale_factors"] = lv["scale_factors"].grad.reshape(P, 1)
+    g["dL_dcolors"] = lv["colors_precomp"].grad if "colors_precomp" in lv else keep["colors"].grad
+    g["dL_dcov3D"] = lv["cov3D_precomp"].grad if "cov3D_precomp" in lv else keep["cov3D"].grad
+    return img.detach().numpy(), {k: (torch.zeros_like(lv["means3D"][:, :0]) if v is None else v).numpy() for k, v in g.items()}

@@ -208,12 +208,21 @@ def grad_errors(st, flipped, got, ref):
     return errs, errs_clean, int(affected.sum())
 
 
-def check_grads(st, u, got, ref, tol, what=""):
+def truth_tols(d_ref, tol, factor):
+    """Per-tensor rel-inf bars against a float64 truth T, from d_ref[k] = ||oracle - T||_inf / ||T||_inf (the reference's own
+    fp32 deviation): max(tol, factor x d_ref[k]), i.e. ||kernel - T||_inf <= max(tol ||T||_inf, factor ||oracle - T||_inf)."""
+    return {k: max(tol, factor * d) for k, d in d_ref.items()}
+
+
+def check_grads(st, u, got, ref, tol, what="", target=None, tols=None):
     """The gradient bar of the parity tests, aware of flipped pixels: every gradient within `tol` (rel-inf) -- or, when the
     forward has flipped pixels, within `tol` over everything that shares no tile with one and within 5 x tol overall
     (a flipped pixel adds or drops one whole contribution for the Gaussians of its tile). At most max(2, 2e-5 x pixels)
     pixels may flip, and EVERY flipped pixel must be proven a true fp32 borderline by prove_flips (the kernel's result and
     the oracle's each equal a leaf of a float64 walk that branches only at decisions inside their fp32 error band).
+    target / tols: compare `got` against `target` (a dict like `ref`, e.g. the float64 truth) in place of the oracle's
+    gradients, tensor k at tols[k] in place of `tol` -- for inputs on which the reference's own fp32 formula leaves `tol`.
+    The flips are still those against the oracle state `st`, and are treated exactly as above.
     -> number of flipped pixels"""
     flipped = flipped_pixels(u, st) if st.num_rendered > 0 else np.zeros((st.H, st.W), bool)
     n_flip = int(flipped.sum())
@@ -221,9 +230,13 @@ def check_grads(st, u, got, ref, tol, what=""):
     if n_flip:          # every flip must be a PROVEN fp32 borderline (float64 walk, see prove_flips), not merely rare
         proof = prove_flips(u, st, flipped)
         assert proof["outside_band"] == 0 and proof["oracle_outside_band"] == 0, f"{what}: flip outside the fp32 band: {proof}"
+    if target is not None:
+        ref = target
     clean = grad_errors(st, flipped, got, ref)[1] if n_flip else None
+    default_tol = tol
     for k, v in got.items():
         r = ref[k]
+        tol = default_tol if tols is None else tols[k]
         if r.size == 0 and v.size == 0:
             continue
         if v.shape != r.shape:          # absent inputs: reference shape [P,..] zeros vs oracle's empty
