@@ -98,6 +98,7 @@ PROTOTYPES = {
     "c3dgs_rasterize_gaussians_backward_indexed": (C.c_int, [C.POINTER(RasterParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                                              C.c_void_p, C.c_int32, C.c_void_p, RESIZE_FN, C.c_void_p,
                                                              C.POINTER(RasterGrads), C.c_void_p]),
+    "c3dgs_render_depth": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c3dgs_weighted_distance": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     "c3dgs_vq_accumulate": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -22,6 +22,7 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 #define C3DGS_STAGE_TABLE(X)                                                                                                   \
     X(MARK_VISIBLE, "mark_visible") X(PREPROCESS, "preprocess") X(DEPTH_SORT, "depth_sort") X(SCAN, "scan")                    \
     X(DUPLICATE, "duplicate_with_keys") X(SORT, "sort") X(RANGES, "identify_ranges") X(RENDER_FWD, "render_forward")           \
+    X(RENDER_DEPTH, "render_depth")                                                                                            \
     X(ZERO_PARTIALS, "zero_partials") X(RENDER_BWD, "render_backward") X(BWD_PREPROCESS, "backward_preprocess")                \
     X(WDIST, "weighted_distance") X(VQ_ACC, "vq_accumulate") X(VQ_APPLY, "vq_apply") X(LOSS_FWD, "l1_ssim_forward")            \
     X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
@@ -511,6 +512,33 @@ int c3dgs_rasterize_gaussians_backward_indexed(const c3dgs_raster_params* p, con
 {
     return backward_impl(p, true, radii, geom_buffer, binning_buffer, image_buffer, R, dL_dout_color, workspace_resize,
                          workspace_user, grads, stream);
+}
+
+int c3dgs_render_depth(int32_t P, int32_t W, int32_t H, int32_t R, const void* geom_buffer, const void* binning_buffer,
+                       const void* image_buffer, float* out_depth, float* out_alpha, float* out_median, void* stream)
+{
+    if (W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, "render_depth: W and H must be positive");
+    if (P < 0 || R < 0) return fail(C3DGS_E_INVALID, "render_depth: P and R must be >= 0");
+    if (!out_depth && !out_alpha && !out_median) return fail(C3DGS_E_INVALID, "render_depth: at least one output is required");
+    if (R > 0 && P == 0) return fail(C3DGS_E_INVALID, "render_depth: R > 0 instances cannot come from P = 0");
+    if (R > 0 && (!geom_buffer || !binning_buffer || !image_buffer))
+        return fail(C3DGS_E_INVALID, "render_depth: the forward's geometry, binning and image buffers are required");
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0 || R == 0) {            // nothing was blended anywhere: T stays 1
+        const size_t bytes = (size_t)W * H * sizeof(float);
+        for (float* o : { out_depth, out_alpha, out_median })
+            if (o) C3DGS_HIP_TRY(hipMemsetAsync(o, 0, bytes, s));
+        return C3DGS_OK;
+    }
+    uint32_t* sort_err = onesweep_error_word();
+    if (!sort_err) return fail(C3DGS_E_HIP, "cannot resolve the sort error word");
+    const GeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
+    const ImgPtrs img = img_ptrs(const_cast<void*>(image_buffer), W, H);
+    const BinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), R, W, H);
+    C3DGS_TIMED_STAGE(ST_RENDER_DEPTH, 0, s,
+                      launch_render_depth(W, H, img, compact_ptrs(b, R), g.splat, g.depth_keys, out_depth, out_alpha, out_median,
+                                          sort_err, s));
+    return C3DGS_OK;
 }
 
 int c3dgs_weighted_distance(int64_t N, int32_t C, int32_t K, const float* coefs, const int64_t* gather,

@@ -270,6 +270,9 @@ void launch_backward_prep(int W, int H, const ImgPtrs& img, void* zero_a, size_t
 void launch_render_backward(int W, int H, const ImgPtrs& img, const float4* splat,
                             const uint32_t* block_base, const float* bg, const float* dL_dpix, float* partials,
                             uint8_t* touched, const CompactPtrs& cl, void* zero_span, size_t zero_n16, hipStream_t s);
+// render_depth.hip (forward-only replay of the blend: depth / accumulated opacity / median depth; null outputs are skipped)
+void launch_render_depth(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const float4* splat, const uint32_t* depth_keys,
+                         float* out_depth, float* out_alpha, float* out_median, const uint32_t* sort_err, hipStream_t s);
 // backward_preprocess.hip
 void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,
                                 const c3dgs_raster_grads& gr, hipStream_t s);

@@ -25,90 +25,10 @@
 //    result is bitwise reproducible (the reference's 9 atomics per pixel-Gaussian pair, backward.cu:523-554, are not).
 #include "common.hpp"
 #include "render_diag.hpp"   // LaneCount, PhaseClock: the instruments the kernels call; empty bodies in the product build
+#include "render_common.hpp" // BATCH, gaussian_alpha, prescale_conic, quadrant_mask, tile_of_block: shared with render_depth.hip
 #include <algorithm>
 
 namespace c3dgs {
-
-constexpr int BATCH = 256;
-
-// The staged LDS records carry the conic PRE-SCALED for the blend loops: {-0.5 a, -b, -0.5 c} x log2(e), so that the
-// exponent of  G = exp(-0.5 (a dx^2 + c dy^2) - b dx dy)  is three multiplies and three multiply-adds feeding v_exp_f32
-// (= 2^x) directly: two vector instructions per (pixel, Gaussian) pair fewer than the reference's form + exp (which is
-// exp2 of a product with log2(e) on this hardware anyway). Done once per staged entry, after the culling mask, which
-// works on the true conic.
-__device__ __forceinline__ void prescale_conic(float4& a, float4& b)
-{
-    constexpr float LOG2E = 1.4426950408889634f;
-    a.z *= -0.5f * LOG2E;
-    a.w *= -LOG2E;
-    b.x *= -0.5f * LOG2E;
-}
-
-// alpha of one Gaussian at one pixel; the SAME instruction sequence in forward and backward so both
-// take identical skip decisions (explicit fma placement, independent of -ffp-contract).
-// (ka, kb, kc) = the pre-scaled conic of prescale_conic().
-// returns false when the reference `continue`s (forward.cu:344-354 / backward.cu:494-501).
-__device__ __forceinline__ bool gaussian_alpha(float mx, float my, float ka, float kb, float kc, float op,
-                                               float pxf, float pyf, float& dx, float& dy, float& G, float& alpha)
-{
-    dx = mx - pxf;
-    dy = my - pyf;
-    const float power2 = fmaf(kb, dx * dy, fmaf(kc, dy * dy, ka * (dx * dx)));     // = power * log2(e)
-    // no early return: G and alpha are always written (callers select on the result anyway), which saves the compiler
-    // a select per call; for power > 0 they hold values nobody uses
-    G = __builtin_amdgcn_exp2f(power2);
-    alpha = fminf(0.99f, op * G);
-    return !(power2 > 0.0f) && !(alpha < 1.0f / 255.0f);
-}
-
-// Which of the tile's four 8x8 quadrants (= waves) can this Gaussian touch at all?  A pixel only blends the
-// Gaussian if alpha = min(0.99, o*exp(power)) >= 1/255, i.e. f(d) = 0.5*d^T C d <= tau with tau = ln(255*o).
-// f is convex, so its minimum over a quadrant's pixel rectangle is 0 if the mean lies inside it and otherwise sits
-// on one of the four edges, where it is a clamped 1-D parabola minimum. A quadrant whose minimum exceeds tau
-// (inflated by 1e-4 relative + 1e-4 absolute and 0.01 px of rectangle slack, far above the fp32 error of the
-// per-pixel test) contains no contributing pixel, so skipping it changes no result. Bit q = qy*2+qx.
-// Anything non-finite or non-positive-definite -> no culling.
-__device__ __forceinline__ float min_power_on_rect(float ca, float cb, float cc, float nb_c, float nb_a,
-                                                   float dx0, float dx1, float dy0, float dy1)
-{
-    if (dx0 <= 0.f && dx1 >= 0.f && dy0 <= 0.f && dy1 >= 0.f) return 0.f;
-    auto f = [&](float dx, float dy) { return 0.5f * (ca * dx * dx + cc * dy * dy) + cb * dx * dy; };
-    const float ya = fminf(fmaxf(nb_c * dx0, dy0), dy1), yb = fminf(fmaxf(nb_c * dx1, dy0), dy1);
-    const float xa = fminf(fmaxf(nb_a * dy0, dx0), dx1), xb = fminf(fmaxf(nb_a * dy1, dx0), dx1);
-    return fminf(fminf(f(dx0, ya), f(dx1, yb)), fminf(f(xa, dy0), f(xb, dy1)));
-}
-
-__device__ __forceinline__ uint32_t quadrant_mask(const float4 a, const float4 b, float tile_x0, float tile_y0)
-{
-    const float mx = a.x, my = a.y, ca = a.z, cb = a.w, cc = b.x, op = b.y;
-    if (op < (1.0f / 255.0f) * 0.999f) return 0u;          // alpha <= o < 1/255 everywhere
-    const float det = ca * cc - cb * cb;
-    const float tau = __logf(255.0f * op) * 1.0001f + 1e-4f;
-    if (!(det > 0.0f) || !(ca > 0.0f) || !(cc > 0.0f) || !(tau < 1e30f)) return 0xfu;
-    const float nb_c = -cb / cc, nb_a = -cb / ca;           // argmin of f along a vertical / horizontal line
-    uint32_t mask = 0u;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const float x0 = tile_x0 + (float)((q & 1) * 8) - 0.01f - mx, y0 = tile_y0 + (float)((q >> 1) * 8) - 0.01f - my;
-        const float fmin = min_power_on_rect(ca, cb, cc, nb_c, nb_a, x0, x0 + 7.02f, y0, y0 + 7.02f);
-        mask |= (uint32_t)(!(fmin > tau)) << q;              // NaN -> keep
-    }
-    return mask;
-}
-
-__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v)
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// XCD-aware tile order: workgroups b, b+8, b+16, ... share an XCD (and its L2) under the observed
-// round-robin dispatch, so give every XCD one contiguous band of row-major tiles. Speed only.
-__device__ __forceinline__ int tile_of_block(int b, int T)
-{
-    const int chunk = (T + 7) >> 3;
-    return (b & 7) * chunk + (b >> 3);
-}
 
 // Tile schedule of the backward: tiles in descending order of the work they carry (tile_used = entries the tile really
 // visits, known from the forward), so that the last workgroups to start are the short ones: -3 % on the bench scene.

@@ -1261,14 +1261,16 @@ class GaussianModel:
 
     # ---- render (gaussian_model.py:766-886)
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, clamp_color=True,
-               cov3d=None, gather_visible=True):
+               cov3d=None, gather_visible=True, return_depth=False):
+        """return_depth=True: the dict also carries "depth" (sum of alpha T z, not normalised), "alpha" (accumulated opacity)
+        and "median_depth", each [H, W] (rasterizer._C.render_depth); forward-only, no gradient flows through them."""
         if pipe.convert_SHs_python and override_color is None:
             raise NotImplementedError("convert_SHs_python: SH evaluation in Python is outside the mirrored render path")
         dev = self.device
         settings = GaussianRasterizationSettings(
             intrinsic=viewpoint_camera.intrinsic.to(dev), extrinsic_vector=viewpoint_camera.extrinsic_vector.to(dev),
             bg=bg_color.to(dev), scale_modifier=scaling_modifier, sh_degree=self.active_sh_degree, prefiltered=False,
-            debug=pipe.debug, clamp_color=clamp_color)
+            debug=pipe.debug, clamp_color=clamp_color, depth=bool(return_depth))
         indexed = self.color_index_mode == ColorMode.ALL_INDEXED and self.is_gaussian_indexed
         fused = indexed and self.use_factor_scaling and cov3d is None and override_color is None and \
             not pipe.compute_cov3D_python
@@ -1315,10 +1317,16 @@ class GaussianModel:
         # what GaussianRasterizerIndexed(settings, optimize_camera=True)(...) calls, without building an nn.Module per view
         # (the host has ~0.2 ms of Python between the visible count's arrival and the rasterizer's first launch, and the GPU
         # idles for the part of it the getter kernels do not cover)
-        image, radii = _rz.rasterize_gaussians_indexed_camera(means3D, means2D, shs, sh_idx, g_idx, _rz._empty(), opac, scales_n, sfac,
-                                                              rotations, _rz._empty(), settings, settings.extrinsic_vector)
+        image, radii, *extras = _rz.rasterize_gaussians_indexed_camera(means3D, means2D, shs, sh_idx, g_idx, _rz._empty(), opac,
+                                                                       scales_n, sfac, rotations, _rz._empty(), settings,
+                                                                       settings.extrinsic_vector)
         return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
-                "visible": visible.bool()}
+                "visible": visible.bool(), **self._depth_keys(extras)}
+
+    @staticmethod
+    def _depth_keys(extras):
+        """the rasterizer's extra outputs under settings.depth -> the keys render(return_depth=True) adds"""
+        return dict(zip(("depth", "alpha", "median_depth"), extras))
 
     def _render_composed(self, settings, screenspace_points, indexed, pipe, scaling_modifier, override_color, cov3d,
                          gather_visible=True):
@@ -1354,18 +1362,18 @@ class GaussianModel:
         else:
             pick = lambda t: t  # noqa: E731
         if indexed:
-            image, radii = rasterizer(means3D=pick(means3D), means2D=pick(screenspace_points), shs=shs,
-                                      sh_indices=pick(self._feature_indices), g_indices=pick(self._gaussian_indices),
-                                      colors_precomp=None, opacities=pick(opacity), scales=scales,
-                                      scale_factors=pick(scale_factors), rotations=rotations,
-                                      cov3D_precomp=pick(cov3D_precomp), extrinsic_vector=settings.extrinsic_vector)
+            image, radii, *extras = rasterizer(means3D=pick(means3D), means2D=pick(screenspace_points), shs=shs,
+                                               sh_indices=pick(self._feature_indices), g_indices=pick(self._gaussian_indices),
+                                               colors_precomp=None, opacities=pick(opacity), scales=scales,
+                                               scale_factors=pick(scale_factors), rotations=rotations,
+                                               cov3D_precomp=pick(cov3D_precomp), extrinsic_vector=settings.extrinsic_vector)
         else:
-            image, radii = rasterizer(means3D=pick(means3D), means2D=pick(screenspace_points), shs=pick(shs),
-                                      colors_precomp=pick(colors_precomp), opacities=pick(opacity), scales=pick(scales),
-                                      rotations=pick(rotations), cov3D_precomp=pick(cov3D_precomp),
-                                      extrinsic_vector=settings.extrinsic_vector)
+            image, radii, *extras = rasterizer(means3D=pick(means3D), means2D=pick(screenspace_points), shs=pick(shs),
+                                               colors_precomp=pick(colors_precomp), opacities=pick(opacity), scales=pick(scales),
+                                               rotations=pick(rotations), cov3D_precomp=pick(cov3D_precomp),
+                                               extrinsic_vector=settings.extrinsic_vector)
         return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
-                "visible": visible}
+                "visible": visible, **self._depth_keys(extras)}
 
 
 class _MaskGather(torch.autograd.Function):

@@ -7,6 +7,9 @@ on top of the MI355X C-ABI library.  Same names, argument order and error behavi
     getProjectionMatrix, quat_to_mat, mat_to_quat, and `_C` with the five pybind entry points
     (submodules/diff-gaussian-rasterization/ext.cpp:15-21).
 
+Beyond the reference: `GaussianRasterizationSettings(depth=True)` / `_C.render_depth` add depth, accumulated-opacity and
+median-depth maps of a forward (forward-only, csrc/render_depth.hip).
+
 PyTorch is plumbing only here (device memory, streams, autograd bookkeeping); every numeric stage
 runs in libc3dgs_hip.so.  There is no CPU path: tensors must live on the GPU.
 """
@@ -466,7 +469,26 @@ def _mark_visible_from_pose(positions, extrinsic_vector):
     return present
 
 
+def _c_render_depth(P, W, H, R, geomBuffer, binningBuffer, imgBuffer):
+    """Depth, accumulated opacity and median depth of the forward that filled the three buffers (c3dgs_render_depth):
+    -> (depth, alpha, median), each [H, W] fp32, on the current stream. `depth` = sum_k alpha_k T_k z_k is NOT normalised
+    (divide by `alpha`); `median` = depth of the first blended Gaussian that takes T below 0.5, 0 where none does.
+    Forward-only. Valid before or after the matching backward."""
+    if not imgBuffer.is_cuda:
+        raise RuntimeError("c3dgs_amd: render_depth needs the forward's GPU buffers (there is no CPU path)")
+    dev = imgBuffer.device
+    P, W, H, R = int(P), int(W), int(H), int(R)
+    with torch.cuda.device(dev):
+        out = torch.empty((3, max(H, 0), max(W, 0)), dtype=torch.float32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        rc = _lib.lib().c3dgs_render_depth(P, W, H, R, ptr(geomBuffer), ptr(binningBuffer), ptr(imgBuffer), ptr(out[0]), ptr(out[1]),
+                                           ptr(out[2]), _stream(dev))
+    _lib.check(rc)
+    return out[0], out[1], out[2]
+
+
 _C = SimpleNamespace(
+    render_depth=_c_render_depth,
     rasterize_gaussians=_c_rasterize_gaussians,
     rasterize_gaussians_backward=_c_rasterize_gaussians_backward,
     rasterize_gaussians_indexed=_c_rasterize_gaussians_indexed,
@@ -506,16 +528,16 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _C.rasterize_gaussians, args, raster_settings.debug, "snapshot_fw.dump")
             if all(g.ok() for g in guard):
                 break
+        extras = _extras(raster_settings, int(means3D.size(0)), H, W, num_rendered, geomBuffer, binningBuffer, imgBuffer)
         ctx.raster_settings = raster_settings
         ctx.num_rendered = num_rendered
         ctx.camera = (view, proj, campos, tanfovx, tanfovy)
         ctx.save_for_backward(extrinsic_vector, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
                               geomBuffer, binningBuffer, imgBuffer)
         ctx.image_shape = tuple(color.shape)
-        ctx.mark_non_differentiable(radii)
         # without this, autograd hands backward a zero-filled int32[P] "gradient" for radii on every call (a 12 MB fill at P = 3M)
         ctx.set_materialize_grads(False)
-        return color, radii
+        return _outputs(ctx, color, radii, extras)
 
     @staticmethod
     def backward(ctx, grad_out_color, *params):
@@ -536,6 +558,21 @@ class _RasterizeGaussians(torch.autograd.Function):
         return (grad_means3D, grad_means2D, _fit(grad_sh, sh), _fit(grad_colors_precomp, colors_precomp), grad_opacities,
                 _fit(grad_scales, scales), _fit(grad_rotations, rotations), _fit(grad_cov3Ds_precomp, cov3Ds_precomp),
                 None, None)
+
+
+def _extras(raster_settings, P, H, W, num_rendered, geomBuffer, binningBuffer, imgBuffer):
+    """With `raster_settings.depth`: the (depth, alpha, median) maps of _C.render_depth, queued right behind the forward on
+    the same stream; otherwise () and no launch."""
+    if not getattr(raster_settings, "depth", False):
+        return ()
+    return _C.render_depth(P, W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer)
+
+
+def _outputs(ctx, color, radii, extras):
+    """What the three autograd Functions return: (color, radii) + extras. The extras are forward-only: they are marked
+    non-differentiable like radii, and no gradient flows through them."""
+    ctx.mark_non_differentiable(radii, *extras)
+    return (color, radii) + tuple(extras)
 
 
 def _fit(grad, inp):
@@ -560,15 +597,15 @@ def _indexed_forward(ctx, means3D, sh, sh_indices, g_indices, colors_precomp, op
             _C.rasterize_gaussians_indexed, args, raster_settings.debug, "snapshot_fw.dump")
         if all(g.ok() for g in guard):
             break
+    extras = _extras(raster_settings, int(means3D.size(0)), H, W, num_rendered, geomBuffer, binningBuffer, imgBuffer)
     ctx.raster_settings = raster_settings
     ctx.num_rendered = num_rendered
     ctx.camera = (view, proj, campos, tanfovx, tanfovy)
     ctx.save_for_backward(extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii,
                           sh, geomBuffer, binningBuffer, imgBuffer, sh_indices, g_indices)
-    ctx.mark_non_differentiable(radii)
     ctx.set_materialize_grads(False)       # no zero-filled int32[P] "gradient" for radii (see _RasterizeGaussians.forward)
     ctx.image_shape = tuple(color.shape)
-    return color, radii
+    return _outputs(ctx, color, radii, extras)
 
 
 def _dense_grad(grad_out_color, ctx):
@@ -711,7 +748,7 @@ def rasterize_gaussians_indexed_camera(means3D, means2D, sh, sh_indices, g_indic
 
 # ----------------------------------------------------------------------------- public modules
 class GaussianRasterizationSettings(NamedTuple):
-    """reference __init__.py:868-878."""
+    """reference __init__.py:868-878, plus `depth` (last, optional)."""
     intrinsic: torch.Tensor
     extrinsic_vector: torch.Tensor
     bg: torch.Tensor
@@ -720,6 +757,9 @@ class GaussianRasterizationSettings(NamedTuple):
     prefiltered: bool
     debug: bool
     clamp_color: bool
+    # True: the rasterizers return (color, radii, depth, alpha, median) -- see _C.render_depth. Forward-only: the three extra
+    # maps are non-differentiable, no gradient flows through them. False: (color, radii), the same launches as ever.
+    depth: bool = False
 
 
 def _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp):

@@ -135,6 +135,26 @@ int c3dgs_rasterize_gaussians_backward_indexed(const c3dgs_raster_params* p, con
                                                c3dgs_resize_fn workspace_resize, void* workspace_user,
                                                const c3dgs_raster_grads* grads, void* stream);
 
+/* ---- depth, accumulated opacity and median depth of a finished forward (csrc/render_depth.hip; no reference counterpart) ----
+ * geom/binning/image buffers are the ones a forward of the same P, W, H filled; R is its num_rendered. Per pixel, over the
+ * entries k = 1..m the forward blended (w_k = alpha_k T_k, T_{k+1} = T_k (1 - alpha_k), T_1 = 1, z_k = the fp32 view-space
+ * depth of the Gaussian):
+ *   out_depth  = sum_k w_k z_k, accumulated like a colour channel of the forward; NOT normalised (divide by out_alpha)
+ *   out_alpha  = 1 - T_{m+1}
+ *   out_median = z_k of the first blended entry with T_{k+1} < 0.5, or 0 when T never falls below 0.5 (empty pixels too)
+ * The call replays the forward's own decisions and is bitwise reproducible. It READS: the splat records and depth_keys of the
+ * geometry buffer; ranges, the per-pixel / per-tile compact cuts (c3dgs_compact_layout: n_contrib_c, tile_used_c) of the image
+ * buffer; the compact lists (cid, cqm) in the binning buffer's sort scratch; the device's sort time-out word (set: every
+ * output is NaN, like the forward's image). It writes nothing but its outputs. The backward only reads those fields too (its
+ * scratch in the image buffer is tile_order, which this call does not use), so the call is valid before or after the
+ * matching backward, with the same result.
+ * A NULL output is skipped; at least one must be non-NULL. P == 0 or R == 0: zeros, no blend launch. Forward-only: no
+ * gradient flows through these maps. Stage name: "render_depth". */
+int c3dgs_render_depth(int32_t P, int32_t W, int32_t H, int32_t R,
+                       const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                       float* out_depth /*[H,W] | NULL*/, float* out_alpha /*[H,W] | NULL*/,
+                       float* out_median /*[H,W] | NULL*/, void* stream);
+
 /* ---- weighted_distance._C.weightedDistance (weighted_distance.cu:46-93) ----
  * coefs [N,K], codebook [C,K] row-major fp32 -> min squared distance [N] and argmin [N] (int64).
  * Exact reference semantics: fp32 k-ordered FMA chain, strict '<' (lowest index wins ties).
