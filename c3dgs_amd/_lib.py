@@ -3,6 +3,8 @@ missing or cannot be loaded, importing any op raises immediately."""
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # C3DGS_LIB_PATH: test hook only -- loads a variant build of the SAME library (c3dgs_amd/build.py VARIANTS, DIAG_VARIANTS)
 LIB_PATH = os.environ.get("C3DGS_LIB_PATH") or os.path.join(_HERE, "libc3dgs_hip.so")
@@ -210,6 +212,25 @@ def check(rc):
     if rc != 0:
         msg = lib().c3dgs_last_error()
         raise RuntimeError((msg or b"unknown error").decode("utf-8", "replace"))
+
+
+# ---- the three things every caller of the library does with a torch tensor
+def stream(device):
+    """torch's current stream on `device`, as the library's stream argument."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def gpu_tensor(t, name, dtype=torch.float32):
+    """`t` as the library reads it: contiguous, of `dtype`, on a GPU. Raises with `name` otherwise."""
+    if not t.is_cuda:
+        raise RuntimeError(f"c3dgs_amd: {name} must be a GPU tensor (there is no CPU path)")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{name} must be {str(dtype).split('.')[-1]}")
+    return t.contiguous()
 
 
 def profile_enable(on=True, only=None):

@@ -7,8 +7,6 @@
     extract_rot_scale(cov) -> (rot [n,4], scaling [n,3])   utils/splats.py:27-35 (accepts [n,3,3] or the stripped [n,6])
 
 Reference: scene/gaussian_model.py:997-1003 and :1417-1432; utils/splats.py.  No CPU path."""
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -28,7 +26,7 @@ def _run(xyz):
         ws = torch.empty(int(L.c3dgs_morton_workspace_bytes(P)), dtype=torch.uint8, device=x.device)
         with torch.cuda.device(x.device):
             rc = L.c3dgs_morton_order(P, x.data_ptr(), codes.data_ptr(), order.data_ptr(), ws.data_ptr(),
-                                      C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+                                      _lib.stream(x.device))
         _lib.check(rc)
     return codes, order
 
@@ -62,5 +60,5 @@ def extract_rot_scale(cov):
     scale = torch.empty(n, 3, dtype=torch.float32, device=c6.device)
     if n:
         _lib.check(_lib.lib().c3dgs_extract_rot_scale(n, c6.data_ptr(), rot.data_ptr(), scale.data_ptr(),
-                                                      C.c_void_p(torch.cuda.current_stream(c6.device).cuda_stream)))
+                                                      _lib.stream(c6.device)))
     return rot, scale

@@ -5,7 +5,6 @@
 
 The contract of the kernel is in include/c3dgs_hip.h (c3dgs_image_from_u8); tests/image_ref.py restates it in numpy.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -48,7 +47,6 @@ def image_from_u8(src, height, width, flip=False, background=None, out=None):
         raise ValueError("image_from_u8: out must be a contiguous float32 [3][height][width] GPU tensor")
     with torch.cuda.device(dev):
         rc = _lib.lib().c3dgs_image_from_u8(Hs, Ws, Cn, src.data_ptr(), 1 if flip else 0, bg.data_ptr() if bg is not None else None,
-                                            int(height), int(width), out.data_ptr(),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                            int(height), int(width), out.data_ptr(), _lib.stream(dev))
     _lib.check(rc)
     return out

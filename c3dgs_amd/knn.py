@@ -7,8 +7,6 @@ GaussianModel.load_ply uses it for a point cloud without scale_* properties (COL
 of a point is log(sqrt(max(distCUDA2, 1e-7))) on every axis. The search is exact (csrc/knn.hip; DESIGN.md "3-NN"):
 the result equals a brute force over all pairs bit for bit. No CPU path.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -37,7 +35,7 @@ def distCUDA2(points):
     ws = torch.empty(int(L.c3dgs_knn_workspace_bytes(P)), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
         rc = L.c3dgs_knn_mean_dist2(P, x.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                    C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+                                    _lib.stream(x.device))
     _lib.check(rc)
     return out
 
@@ -57,6 +55,6 @@ def knn3(points):
     ws = torch.empty(int(L.c3dgs_knn_workspace_bytes(P)), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
         rc = L.c3dgs_knn_neighbours(P, x.data_ptr(), idx.data_ptr(), d2.data_ptr(), ws.data_ptr(),
-                                    C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+                                    _lib.stream(x.device))
     _lib.check(rc)
     return idx, d2

@@ -7,15 +7,10 @@ fused QAT loss of finetune.py:48.  (the step right after 
 All three are differentiable w.r.t. their FIRST argument (the rendered image); the ground truth is treated as a constant,
 which is how every call site of the reference uses them.  One fused forward kernel + one fused backward kernel instead of
 five grouped convolutions and their autograd graph.  No CPU path."""
-import ctypes as C
-
 import torch
 
 from . import _lib
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+from ._lib import stream as _stream
 
 
 def _check(img, gt):

@@ -8,16 +8,12 @@
 One forward-only kernel pass (csrc/metrics.hip) yields MSE, SSIM and L1 of every image of a batch, with a deterministic
 two-kernel reduction. Nothing here carries a gradient: the differentiable SSIM / L1 are c3dgs_amd.loss.ssim / l1_loss /
 l1_ssim_loss. No CPU path."""
-import ctypes as C
 import os
 
 import torch
 
 from . import _lib
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+from ._lib import stream as _stream
 
 
 def _check(img1, img2):

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from . import rasterizer as _rz
+from ._lib import ptr as _ptr, stream as _stream
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed
 
 SLOTS = ("opacity", "scaling", "scaling_factor", "rotation", "features_dc", "features_rest")
@@ -34,22 +35,6 @@ AVERAGING_CONSTANT = 0.01       # MovingAverageMinMaxObserver default
 class ColorMode:                # scene/gaussian_model.py:49-51
     NOT_INDEXED = 0
     ALL_INDEXED = 1
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _need_gpu(t, name):
-    if not t.is_cuda:
-        raise RuntimeError(f"c3dgs_amd: {name} must be a GPU tensor (there is no CPU path)")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32")
-    return t.contiguous()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def new_fq_state(device, n=1):
@@ -94,7 +79,7 @@ class _Observer:
 class _FakeQuantizeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, module):
-        xc = _need_gpu(x, "FakeQuantize input")
+        xc = _lib.gpu_tensor(x, "FakeQuantize input")
         out = torch.empty_like(xc)
         row = module._row
         _lib.check(_lib.lib().c3dgs_fake_quantize(xc.numel(), xc.data_ptr(), row.data_ptr(), int(module.observer_enabled),
@@ -214,7 +199,7 @@ class _QatGetters(torch.autograd.Function):
         lib = _lib.lib()
         raw = dict(xyz=xyz, opacity=opacity, scaling_factor=scaling_factor, scaling=scaling, rotation=rotation, fdc=fdc,
                    frest=frest)
-        raw = {k: (None if v is None else _need_gpu(v, k)) for k, v in raw.items()}
+        raw = {k: (None if v is None else _lib.gpu_tensor(v, k)) for k, v in raw.items()}
         anyt = next(v for v in raw.values() if v is not None)
         dev = anyt.device
         s = _stream(dev)
@@ -778,7 +763,7 @@ class GaussianModel:
         P = self._xyz.shape[0]
         if grad is None or tuple(grad.shape) != (P, 3) or update_filter.shape[0] != P:
             raise RuntimeError("add_densification_stats: viewspace gradient [P,3] and filter [P] of the model's length are needed")
-        grad = _need_gpu(grad, "viewspace gradient")
+        grad = _lib.gpu_tensor(grad, "viewspace gradient")
         flt = update_filter.contiguous()
         if flt.dtype == torch.bool:
             flt = flt.view(torch.uint8)
@@ -852,15 +837,15 @@ class GaussianModel:
             draws = torch.randn((N * S, 3), device=dev)     # torch.normal(mean, std) is randn * std + mean (:1242)
         if tuple(draws.shape) != (N * S, 3):
             raise RuntimeError(f"draws must be [N*S, 3] = [{N * S}, 3] unit normals, got {tuple(draws.shape)}")
-        draws = _need_gpu(draws, "draws")
-        std = None if std is None else _need_gpu(std, "std")
-        rotation = _need_gpu(self._rotation.detach(), "rotation")
+        draws = _lib.gpu_tensor(draws, "draws")
+        std = None if std is None else _lib.gpu_tensor(std, "std")
+        rotation = _lib.gpu_tensor(self._rotation.detach(), "rotation")
         table, new, moments = [], {}, {}
         for name, attr, role in self._GROUPS:
             old = getattr(self, attr)
             if old is None:
                 continue
-            old_c = _need_gpu(old.detach(), attr)
+            old_c = _lib.gpu_tensor(old.detach(), attr)
             out = torch.empty((P_new,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
             st = self.optimizer.state.get(old) if self.optimizer is not None else None
             t = _lib.RowsTensor()
@@ -1026,7 +1011,7 @@ class GaussianModel:
         lib = _lib.lib()
         dev = self.device
         with torch.no_grad():
-            x = _need_gpu(self._xyz.detach(), "xyz")                      # the raw _xyz, not get_xyz (:1355-1364)
+            x = _lib.gpu_tensor(self._xyz.detach(), "xyz")                      # the raw _xyz, not get_xyz (:1355-1364)
             P = int(x.shape[0])
             if P < 4:
                 raise ValueError(f"densify_initial: three neighbours need at least 4 points, the model has {P}")
@@ -1098,7 +1083,7 @@ class GaussianModel:
         table, new, moments, extra_new = [], {}, {}, []
 
         def job(old, st=None):
-            old_c = _need_gpu(old.detach(), "tensor")
+            old_c = _lib.gpu_tensor(old.detach(), "tensor")
             out = torch.empty((n_out,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
             t = _lib.RowsTensor()
             t.in_param, t.out_param = old_c.data_ptr(), out.data_ptr()

@@ -5,7 +5,6 @@ scene/gaussian_model.py:296-308: torch.optim.Adam(param_groups, lr=0.0, eps=1e-1
 "exp_avg_sq": state dicts are interchangeable), whose step() updates every parameter of every group with ONE kernel
 launch per 16 tensors (csrc/adam.hip) instead of torch's dozen multi-tensor passes. weight_decay, amsgrad and maximize
 are not used by the reference and are rejected. No CPU path."""
-import ctypes as C
 import math
 
 import torch
@@ -37,8 +36,7 @@ class Adam(torch.optim.Optimizer):
             (beta1, beta2), eps, dev = key
             arr = (_lib.AdamTensor * len(batch))(*batch)
             with torch.cuda.device(dev):
-                _lib.check(L.c3dgs_adam_step(len(batch), arr, beta1, beta2, eps,
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                _lib.check(L.c3dgs_adam_step(len(batch), arr, beta1, beta2, eps, _lib.stream(dev)))
             batch.clear()
             keep.clear()
 

@@ -5,7 +5,7 @@ on top of the MI355X C-ABI library.  Same names, argument order and error behavi
     GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,
     rasterize_gaussians, rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,
     getProjectionMatrix, quat_to_mat, mat_to_quat, and `_C` with the five pybind entry points
-    (submodules/diff-gaussian-rasterization/ext.cpp:15-21).
+    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`.
 
 Beyond the reference: `GaussianRasterizationSettings(depth=True)` / `_C.render_depth` add depth, accumulated-opacity and
 median-depth maps of a forward (forward-only, csrc/render_depth.hip).
@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import RESIZE_FN, RasterGrads, RasterParams
+from ._lib import RESIZE_FN, RasterGrads, RasterParams, ptr as _ptr, stream as _stream
 
 
 # ----------------------------------------------------------------------------- camera helpers
@@ -235,58 +235,38 @@ class _Scratch:
         bufs, self.bufs, self._cbs = self.bufs, {}, {}
         return bufs
 
-    def _or_empty(self, bufs, name):
-        t = bufs.get(name)
-        return t if t is not None else torch.empty(0, dtype=torch.uint8, device=self.device)
+
+def _buffer_or_empty(bufs, name, device):
+    t = bufs.get(name)
+    return t if t is not None else torch.empty(0, dtype=torch.uint8, device=device)
 
 
-def _f32c(t, name):
+def _optional(t, name, dtype=torch.float32):
+    """An optional input of the library: None or empty -> None (absent), otherwise checked by _lib.gpu_tensor."""
     if t is None:
         return None
     if not isinstance(t, torch.Tensor):
         raise RuntimeError(f"{name} must be a tensor")
     if t.numel() == 0:
         return None
-    if not t.is_cuda:
-        raise RuntimeError(f"c3dgs_amd: {name} must be a GPU tensor (there is no CPU path)")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32")
-    return t.contiguous()
+    return _lib.gpu_tensor(t, name, dtype)
 
 
-def _i64c(t, name):
-    if t is None or t.numel() == 0:
-        return None
-    if not t.is_cuda:
-        raise RuntimeError(f"c3dgs_amd: {name} must be a GPU tensor (there is no CPU path)")
-    if t.dtype != torch.int64:
-        raise RuntimeError(f"{name} must be int64")
-    return t.contiguous()
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _params(keep, *, background, means3D, colors, opacity, scales, scale_factors, rotations, scale_modifier, cov3D_precomp,
+def _params(*, background, means3D, colors, opacity, scales, scale_factors, rotations, scale_modifier, cov3D_precomp,
             viewmatrix, projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, sh_indices, g_indices, prefiltered,
             debug, clamp_color):
+    """-> (RasterParams, tensors). `tensors` owns the memory the struct points into: hold it until the call has returned."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")      # rasterize_points.cu:58-60
     if not means3D.is_cuda:
         raise RuntimeError("c3dgs_amd: means3D must be a GPU tensor (there is no CPU path)")
-    t = dict(background=_f32c(background, "background"), means3D=_f32c(means3D, "means3D"), sh=_f32c(sh, "sh"),
-             colors_precomp=_f32c(colors, "colors_precomp"), opacities=_f32c(opacity, "opacities"),
-             scales=_f32c(scales, "scales"), scale_factors=_f32c(scale_factors, "scale_factors"),
-             rotations=_f32c(rotations, "rotations"), cov3D_precomp=_f32c(cov3D_precomp, "cov3D_precomp"),
-             sh_indices=_i64c(sh_indices, "sh_indices"), g_indices=_i64c(g_indices, "g_indices"),
-             viewmatrix=_f32c(viewmatrix, "viewmatrix"), projmatrix=_f32c(projmatrix, "projmatrix"),
-             campos=_f32c(campos, "campos"))
-    keep.append(t)
+    t = dict(background=_optional(background, "background"), means3D=_optional(means3D, "means3D"), sh=_optional(sh, "sh"),
+             colors_precomp=_optional(colors, "colors_precomp"), opacities=_optional(opacity, "opacities"),
+             scales=_optional(scales, "scales"), scale_factors=_optional(scale_factors, "scale_factors"),
+             rotations=_optional(rotations, "rotations"), cov3D_precomp=_optional(cov3D_precomp, "cov3D_precomp"),
+             sh_indices=_optional(sh_indices, "sh_indices", torch.int64), g_indices=_optional(g_indices, "g_indices", torch.int64),
+             viewmatrix=_optional(viewmatrix, "viewmatrix"), projmatrix=_optional(projmatrix, "projmatrix"),
+             campos=_optional(campos, "campos"))
     p = RasterParams()
     p.P = int(means3D.size(0))
     p.D = int(degree)
@@ -295,9 +275,8 @@ def _params(keep, *, background, means3D, colors, opacity, scales, scale_factors
     p.W, p.H = int(W), int(H)
     p.SHS = int(shp.size(0)) if shp is not None else 0
     p.GS = int(t["scales"].size(0)) if t["scales"] is not None else 0
-    for k in ("background", "means3D", "sh", "colors_precomp", "opacities", "scales", "scale_factors", "rotations",
-              "cov3D_precomp", "sh_indices", "g_indices", "viewmatrix", "projmatrix", "campos"):
-        setattr(p, k, _ptr(t[k]))
+    for k, v in t.items():
+        setattr(p, k, _ptr(v))
     p.tan_fovx, p.tan_fovy, p.scale_modifier = float(tan_fovx), float(tan_fovy), float(scale_modifier)
     p.prefiltered, p.clamp_color, p.debug = int(bool(prefiltered)), int(bool(clamp_color)), int(bool(debug))
     return p, t
@@ -307,12 +286,11 @@ def _forward(indexed, background, means3D, colors, opacity, scales, scale_factor
              viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, sh_indices,
              g_indices, prefiltered, debug, clamp_color):
     L = _lib.lib()
-    keep = []
-    p, _ = _params(keep, background=background, means3D=means3D, colors=colors, opacity=opacity, scales=scales,
-                   scale_factors=scale_factors, rotations=rotations, scale_modifier=scale_modifier,
-                   cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix, projmatrix=projmatrix, tan_fovx=tan_fovx,
-                   tan_fovy=tan_fovy, H=image_height, W=image_width, sh=sh, degree=degree, campos=campos,
-                   sh_indices=sh_indices, g_indices=g_indices, prefiltered=prefiltered, debug=debug, clamp_color=clamp_color)
+    p, tensors = _params(background=background, means3D=means3D, colors=colors, opacity=opacity, scales=scales,
+                         scale_factors=scale_factors, rotations=rotations, scale_modifier=scale_modifier,
+                         cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix, projmatrix=projmatrix, tan_fovx=tan_fovx,
+                         tan_fovy=tan_fovy, H=image_height, W=image_width, sh=sh, degree=degree, campos=campos,
+                         sh_indices=sh_indices, g_indices=g_indices, prefiltered=prefiltered, debug=debug, clamp_color=clamp_color)
     dev = means3D.device
     P, H, W = p.P, p.H, p.W
     with torch.cuda.device(dev):
@@ -325,24 +303,20 @@ def _forward(indexed, background, means3D, colors, opacity, scales, scale_factor
                 out_color.data_ptr(), radii.data_ptr() if P > 0 else None, C.byref(num_rendered), _stream(dev))
     bufs = scratch.release()
     _lib.check(rc)
-    return (int(num_rendered.value), out_color, radii, scratch._or_empty(bufs, "geom"), scratch._or_empty(bufs, "binning"),
-            scratch._or_empty(bufs, "img"))
-
-
-# Outputs the autograd wrappers do not need (gradients of ABSENT optional inputs) are neither allocated nor written:
-# dL_dcolors (12 B x P) and dL_dcov3D (24 B x P) are 108 MB of stores per 3M-Gaussian backward. The pybind-order
-# entry points (_C.*) keep returning every tensor like the reference.
-_SKIP = threading.local()
+    return (int(num_rendered.value), out_color, radii, _buffer_or_empty(bufs, "geom", dev), _buffer_or_empty(bufs, "binning", dev),
+            _buffer_or_empty(bufs, "img", dev))
 
 
 def _backward(indexed, background, means3D, radii, colors, scales, scale_factors, rotations, scale_modifier, cov3D_precomp,
               viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-              imageBuffer, debug, sh_indices, g_indices):
+              imageBuffer, debug, sh_indices, g_indices, skip=()):
+    """`skip`: names among ("dL_dcolors", "dL_dcov3D") that are neither allocated nor written and come back as None. The
+    autograd wrappers name the gradients of ABSENT optional inputs: dL_dcolors (12 B x P) and dL_dcov3D (24 B x P) are
+    108 MB of stores per 3M-Gaussian backward. The pybind-order entry points (_C.*) skip nothing, like the reference."""
     L = _lib.lib()
-    keep = []
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))               # rasterize_points.cu:143-145
     # opacities are not an input of the reference's backward either (they live in the geometry buffer)
-    p, t = _params(keep, background=background, means3D=means3D, colors=colors, opacity=None, scales=scales,
+    p, t = _params(background=background, means3D=means3D, colors=colors, opacity=None, scales=scales,
                    scale_factors=scale_factors, rotations=rotations, scale_modifier=scale_modifier,
                    cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix, projmatrix=projmatrix, tan_fovx=tan_fovx,
                    tan_fovy=tan_fovy, H=H, W=W, sh=sh, degree=degree, campos=campos, sh_indices=sh_indices,
@@ -354,7 +328,6 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
     with torch.cuda.device(dev):
         dL_dmeans3D = torch.empty((P, 3), **opt)
         dL_dmeans2D = torch.empty((P, 3), **opt)
-        skip = getattr(_SKIP, "names", ())
         dL_dcolors = None if "dL_dcolors" in skip else torch.empty((P, 3), **opt)
         dL_dopacity = torch.empty((P, 1), **opt)
         dL_dcov3D = None if "dL_dcov3D" in skip else torch.empty((P, 6), **opt)
@@ -382,7 +355,7 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
         g.dL_drotations = dL_drotations.data_ptr() if dL_drotations.numel() else None
         g.dL_dscale_factors = dL_dscale_factors.data_ptr() if (dL_dscale_factors is not None and P > 0) else None
         radii_c = radii.contiguous()
-        dpix = _f32c(dL_dout_color, "dL_dout_color")
+        dpix = _optional(dL_dout_color, "dL_dout_color")
         scratch = _Scratch(dev)
         fn = L.c3dgs_rasterize_gaussians_backward_indexed if indexed else L.c3dgs_rasterize_gaussians_backward
         rc = fn(C.byref(p), radii_c.data_ptr() if P > 0 else None,
@@ -400,7 +373,7 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
 
-# ---- the five entry points with the pybind argument order (ext.cpp:15-21, rasterize_points.h:18-122)
+# ---- the five entry points with the pybind argument order (ext.cpp:15-21, rasterize_points.h:18-122), and render_depth
 def _c_rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                            projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
                            clamp_color):
@@ -419,19 +392,19 @@ def _c_rasterize_gaussians_indexed(background, means3D, colors, opacity, scales,
 
 def _c_rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                                    geomBuffer, R, binningBuffer, imageBuffer, debug):
+                                    geomBuffer, R, binningBuffer, imageBuffer, debug, skip=()):
     return _backward(False, background, means3D, radii, colors, scales, None, rotations, scale_modifier, cov3D_precomp,
                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
-                     binningBuffer, imageBuffer, debug, None, None)
+                     binningBuffer, imageBuffer, debug, None, None, skip)
 
 
 def _c_rasterize_gaussians_backward_indexed(background, means3D, radii, colors, scales, scale_factors, rotations,
                                             scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                                             dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-                                            debug, sh_indices, g_indices):
+                                            debug, sh_indices, g_indices, skip=()):
     return _backward(True, background, means3D, radii, colors, scales, scale_factors, rotations, scale_modifier,
                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer,
-                     R, binningBuffer, imageBuffer, debug, sh_indices, g_indices)
+                     R, binningBuffer, imageBuffer, debug, sh_indices, g_indices, skip)
 
 
 def _c_mark_visible(means3D, viewmatrix, projmatrix):
@@ -439,11 +412,11 @@ def _c_mark_visible(means3D, viewmatrix, projmatrix):
     L = _lib.lib()
     if not means3D.is_cuda:
         raise RuntimeError("c3dgs_amd: means3D must be a GPU tensor (there is no CPU path)")
-    m = _f32c(means3D, "means3D")
+    m = _optional(means3D, "means3D")
     P = int(means3D.size(0))
     present = torch.empty((P,), dtype=torch.bool, device=means3D.device)     # the kernel writes every element
     if P != 0:
-        v, pr = _f32c(viewmatrix, "viewmatrix"), _f32c(projmatrix, "projmatrix")
+        v, pr = _optional(viewmatrix, "viewmatrix"), _optional(projmatrix, "projmatrix")
         with torch.cuda.device(means3D.device):
             rc = L.c3dgs_mark_visible(P, m.data_ptr(), v.data_ptr(), pr.data_ptr(), present.data_ptr(), _stream(means3D.device))
         _lib.check(rc)
@@ -459,7 +432,7 @@ def _mark_visible_from_pose(positions, extrinsic_vector):
     pose = extrinsic_vector.detach()
     if pose.device != dev or pose.dtype != torch.float32 or not pose.is_contiguous():
         pose = pose.to(device=dev, dtype=torch.float32).contiguous()
-    m = _f32c(positions, "means3D")
+    m = _optional(positions, "means3D")
     P = int(positions.size(0))
     present = torch.empty((P,), dtype=torch.bool, device=dev)
     if P != 0:
@@ -498,79 +471,55 @@ _C = SimpleNamespace(
 
 
 # ----------------------------------------------------------------------------- autograd functions
-def _call_debug(fn, args, debug, dump):
-    """reference __init__.py:179-206: on failure under debug, dump a CPU copy of the arguments and re-raise."""
+def _call_debug(fn, args, debug, dump, **kwargs):
+    """reference __init__.py:179-206: on failure under debug, dump a CPU copy of the (positional) arguments and re-raise."""
     if debug:
         cpu_args = cpu_deep_copy_tuple(args)
         try:
-            return fn(*args)
+            return fn(*args, **kwargs)
         except Exception as ex:
             torch.save(cpu_args, dump)
             print(f"\nAn error occured. Writing {dump} for debugging.")
             raise ex
-    return fn(*args)
+    return fn(*args, **kwargs)
 
 
-class _RasterizeGaussians(torch.autograd.Function):
-    """reference __init__.py:136-323."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                extrinsic_vector):
-        dev = means3D.device
-        for _attempt in range(2):      # a second pass only if the cached intrinsic scalars turn out stale (_IntrinsicGuard)
-            guard = []
-            view, proj, campos, tanfovx, tanfovy, H, W = camera_matrices(raster_settings.intrinsic, extrinsic_vector, dev, guard)
-            args = (raster_settings.bg, means3D, colors_precomp, opacities, scales, rotations, raster_settings.scale_modifier,
-                    cov3Ds_precomp, view, proj, tanfovx, tanfovy, H, W, sh, raster_settings.sh_degree, campos,
-                    raster_settings.prefiltered, raster_settings.debug, raster_settings.clamp_color)
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call_debug(
-                _C.rasterize_gaussians, args, raster_settings.debug, "snapshot_fw.dump")
-            if all(g.ok() for g in guard):
-                break
-        extras = _extras(raster_settings, int(means3D.size(0)), H, W, num_rendered, geomBuffer, binningBuffer, imgBuffer)
-        ctx.raster_settings = raster_settings
-        ctx.num_rendered = num_rendered
-        ctx.camera = (view, proj, campos, tanfovx, tanfovy)
-        ctx.save_for_backward(extrinsic_vector, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
-                              geomBuffer, binningBuffer, imgBuffer)
-        ctx.image_shape = tuple(color.shape)
-        # without this, autograd hands backward a zero-filled int32[P] "gradient" for radii on every call (a 12 MB fill at P = 3M)
-        ctx.set_materialize_grads(False)
-        return _outputs(ctx, color, radii, extras)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, *params):
-        rs = ctx.raster_settings
-        (extrinsic_vector, colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer) = ctx.saved_tensors
-        grad_out_color = _dense_grad(grad_out_color, ctx)
-        view, proj, campos, tanfovx, tanfovy = ctx.camera
-        args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
-                tanfovx, tanfovy, grad_out_color, sh, rs.sh_degree, campos, geomBuffer, ctx.num_rendered, binningBuffer,
-                imgBuffer, rs.debug)
-        _SKIP.names = tuple(n for n, t in (("dL_dcolors", colors_precomp), ("dL_dcov3D", cov3Ds_precomp)) if t is None or t.numel() == 0)
-        try:
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-             grad_rotations) = _call_debug(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump")
-        finally:
-            _SKIP.names = ()
-        return (grad_means3D, grad_means2D, _fit(grad_sh, sh), _fit(grad_colors_precomp, colors_precomp), grad_opacities,
-                _fit(grad_scales, scales), _fit(grad_rotations, rotations), _fit(grad_cov3Ds_precomp, cov3Ds_precomp),
-                None, None)
-
-
-def _extras(raster_settings, P, H, W, num_rendered, geomBuffer, binningBuffer, imgBuffer):
-    """With `raster_settings.depth`: the (depth, alpha, median) maps of _C.render_depth, queued right behind the forward on
-    the same stream; otherwise () and no launch."""
-    if not getattr(raster_settings, "depth", False):
-        return ()
-    return _C.render_depth(P, W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer)
-
-
-def _outputs(ctx, color, radii, extras):
-    """What the three autograd Functions return: (color, radii) + extras. The extras are forward-only: they are marked
-    non-differentiable like radii, and no gradient flows through them."""
+def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_precomp, opacities, scales, scale_factors,
+                      rotations, cov3Ds_precomp, raster_settings, extrinsic_vector):
+    """forward of the three Functions (reference __init__.py:138-211, 328-408, 539-620). Not indexed: sh_indices, g_indices
+    and scale_factors are None. `args` is the pybind order of the entry it goes to (what snapshot_fw.dump holds)."""
+    rs = raster_settings
+    dev = means3D.device
+    for _attempt in range(2):          # a second pass only if the cached intrinsic scalars turn out stale (_IntrinsicGuard)
+        guard = []
+        view, proj, campos, tanfovx, tanfovy, H, W = camera_matrices(rs.intrinsic, extrinsic_vector, dev, guard)
+        if indexed:
+            fn = _C.rasterize_gaussians_indexed
+            args = (rs.bg, means3D, colors_precomp, opacities, scales, scale_factors, rotations, rs.scale_modifier, cov3Ds_precomp,
+                    view, proj, tanfovx, tanfovy, H, W, sh, rs.sh_degree, campos, sh_indices, g_indices, rs.prefiltered, rs.debug,
+                    rs.clamp_color)
+        else:
+            fn = _C.rasterize_gaussians
+            args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
+                    tanfovx, tanfovy, H, W, sh, rs.sh_degree, campos, rs.prefiltered, rs.debug, rs.clamp_color)
+        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call_debug(fn, args, rs.debug, "snapshot_fw.dump")
+        if all(g.ok() for g in guard):
+            break
+    # with `raster_settings.depth`: the (depth, alpha, median) maps, queued right behind the forward on the same stream;
+    # otherwise no launch
+    extras = ()
+    if getattr(rs, "depth", False):
+        extras = _C.render_depth(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer)
+    ctx.raster_settings = rs
+    ctx.indexed = indexed
+    ctx.num_rendered = num_rendered
+    ctx.camera = (view, proj, campos, tanfovx, tanfovy)
+    ctx.save_for_backward(extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii, sh,
+                          geomBuffer, binningBuffer, imgBuffer, sh_indices, g_indices)
+    ctx.image_shape = tuple(color.shape)
+    # without this, autograd hands backward a zero-filled int32[P] "gradient" for radii on every call (a 12 MB fill at P = 3M)
+    ctx.set_materialize_grads(False)
+    # the extras are forward-only: non-differentiable like radii, no gradient flows through them
     ctx.mark_non_differentiable(radii, *extras)
     return (color, radii) + tuple(extras)
 
@@ -583,54 +532,51 @@ def _fit(grad, inp):
     return grad
 
 
-def _indexed_forward(ctx, means3D, sh, sh_indices, g_indices, colors_precomp, opacities, scales, scale_factors, rotations,
-                     cov3Ds_precomp, raster_settings, extrinsic_vector):
-    dev = means3D.device
-    for _attempt in range(2):          # a second pass only if the cached intrinsic scalars turn out stale (_IntrinsicGuard)
-        guard = []
-        view, proj, campos, tanfovx, tanfovy, H, W = camera_matrices(raster_settings.intrinsic, extrinsic_vector, dev, guard)
-        args = (raster_settings.bg, means3D, colors_precomp, opacities, scales, scale_factors, rotations,
-                raster_settings.scale_modifier, cov3Ds_precomp, view, proj, tanfovx, tanfovy, H, W, sh,
-                raster_settings.sh_degree, campos, sh_indices, g_indices, raster_settings.prefiltered, raster_settings.debug,
-                raster_settings.clamp_color)
-        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call_debug(
-            _C.rasterize_gaussians_indexed, args, raster_settings.debug, "snapshot_fw.dump")
-        if all(g.ok() for g in guard):
-            break
-    extras = _extras(raster_settings, int(means3D.size(0)), H, W, num_rendered, geomBuffer, binningBuffer, imgBuffer)
-    ctx.raster_settings = raster_settings
-    ctx.num_rendered = num_rendered
-    ctx.camera = (view, proj, campos, tanfovx, tanfovy)
-    ctx.save_for_backward(extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii,
-                          sh, geomBuffer, binningBuffer, imgBuffer, sh_indices, g_indices)
-    ctx.set_materialize_grads(False)       # no zero-filled int32[P] "gradient" for radii (see _RasterizeGaussians.forward)
-    ctx.image_shape = tuple(color.shape)
-    return _outputs(ctx, color, radii, extras)
-
-
-def _dense_grad(grad_out_color, ctx):
-    """set_materialize_grads(False): an image nobody differentiated through arrives as None (backward still runs when only
-    `radii` was used downstream of a graph that needs grad); the library wants a dense dL/dC."""
-    if grad_out_color is not None:
-        return grad_out_color
-    return torch.zeros(ctx.image_shape, dtype=torch.float32, device=ctx.saved_tensors[2].device)
-
-
-def _indexed_backward(ctx, grad_out_color):
+def _autograd_backward(ctx, grad_out_color):
+    """backward of the three Functions -> the gradients BY THE NAME OF THE forward INPUT they belong to (None for an absent
+    input); each Function lays them out in its own input order. `args`: pybind order again (snapshot_bw.dump)."""
     rs = ctx.raster_settings
-    grad_out_color = _dense_grad(grad_out_color, ctx)
     (extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
      binningBuffer, imgBuffer, sh_indices, g_indices) = ctx.saved_tensors
+    if grad_out_color is None:
+        # set_materialize_grads(False): an image nobody differentiated through arrives as None (backward still runs when only
+        # `radii` was used downstream of a graph that needs grad); the library wants a dense dL/dC
+        grad_out_color = torch.zeros(ctx.image_shape, dtype=torch.float32, device=means3D.device)
     view, proj, campos, tanfovx, tanfovy = ctx.camera
-    args = (rs.bg, means3D, radii, colors_precomp, scales, scale_factors, rotations, rs.scale_modifier, cov3Ds_precomp, view,
-            proj, tanfovx, tanfovy, grad_out_color, sh, rs.sh_degree, campos, geomBuffer, ctx.num_rendered, binningBuffer,
-            imgBuffer, rs.debug, sh_indices, g_indices)
-    _SKIP.names = tuple(n for n, t in (("dL_dcolors", colors_precomp), ("dL_dcov3D", cov3Ds_precomp)) if t is None or t.numel() == 0)
-    try:
-        out = _call_debug(_C.rasterize_gaussians_backward_indexed, args, rs.debug, "snapshot_bw.dump")
-    finally:
-        _SKIP.names = ()
-    return out, (extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, sh)
+    skip = tuple(n for n, t in (("dL_dcolors", colors_precomp), ("dL_dcov3D", cov3Ds_precomp)) if t is None or t.numel() == 0)
+    grad_scale_factors = None
+    if ctx.indexed:
+        args = (rs.bg, means3D, radii, colors_precomp, scales, scale_factors, rotations, rs.scale_modifier, cov3Ds_precomp, view,
+                proj, tanfovx, tanfovy, grad_out_color, sh, rs.sh_degree, campos, geomBuffer, ctx.num_rendered, binningBuffer,
+                imgBuffer, rs.debug, sh_indices, g_indices)
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+         grad_scale_factors, grad_rotations) = _call_debug(_C.rasterize_gaussians_backward_indexed, args, rs.debug,
+                                                           "snapshot_bw.dump", skip=skip)
+    else:
+        args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
+                tanfovx, tanfovy, grad_out_color, sh, rs.sh_degree, campos, geomBuffer, ctx.num_rendered, binningBuffer,
+                imgBuffer, rs.debug)
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+         grad_rotations) = _call_debug(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump", skip=skip)
+    return SimpleNamespace(means3D=grad_means3D, means2D=grad_means2D, sh=_fit(grad_sh, sh),
+                           colors_precomp=_fit(grad_colors_precomp, colors_precomp), opacities=grad_opacities,
+                           scales=_fit(grad_scales, scales), scale_factors=_fit(grad_scale_factors, scale_factors),
+                           rotations=_fit(grad_rotations, rotations), cov3Ds_precomp=_fit(grad_cov3Ds_precomp, cov3Ds_precomp))
+
+
+class _RasterizeGaussians(torch.autograd.Function):
+    """reference __init__.py:136-323."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                extrinsic_vector):
+        return _autograd_forward(ctx, False, means3D, sh, None, None, colors_precomp, opacities, scales, None, rotations,
+                                 cov3Ds_precomp, raster_settings, extrinsic_vector)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, *params):
+        g = _autograd_backward(ctx, grad_out_color)
+        return (g.means3D, g.means2D, g.sh, g.colors_precomp, g.opacities, g.scales, g.rotations, g.cov3Ds_precomp, None, None)
 
 
 class _RasterizeGaussiansIndexed(torch.autograd.Function):
@@ -639,17 +585,14 @@ class _RasterizeGaussiansIndexed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities, scales, scale_factors, rotations,
                 cov3Ds_precomp, raster_settings, extrinsic_vector):
-        return _indexed_forward(ctx, means3D, sh, sh_indices, g_indices, colors_precomp, opacities, scales, scale_factors,
-                                rotations, cov3Ds_precomp, raster_settings, extrinsic_vector)
+        return _autograd_forward(ctx, True, means3D, sh, sh_indices, g_indices, colors_precomp, opacities, scales,
+                                 scale_factors, rotations, cov3Ds_precomp, raster_settings, extrinsic_vector)
 
     @staticmethod
     def backward(ctx, grad_out_color, *params):
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_scale_factors, grad_rotations), (_, colors_precomp, _m, scales, scale_factors, rotations, cov3Ds_precomp,
-                                               sh) = _indexed_backward(ctx, grad_out_color)
-        return (grad_means3D, grad_means2D, _fit(grad_sh, sh), None, None, _fit(grad_colors_precomp, colors_precomp),
-                grad_opacities, _fit(grad_scales, scales), _fit(grad_scale_factors, scale_factors),
-                _fit(grad_rotations, rotations), _fit(grad_cov3Ds_precomp, cov3Ds_precomp), None, None)
+        g = _autograd_backward(ctx, grad_out_color)
+        return (g.means3D, g.means2D, g.sh, None, None, g.colors_precomp, g.opacities, g.scales, g.scale_factors, g.rotations,
+                g.cov3Ds_precomp, None, None)
 
 
 def camera_pose_jacobian_sum(means3D, intrinsic, extrinsic_vector, du, dv):
@@ -710,21 +653,19 @@ class _RasterizeGaussiansIndexedCamera(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities, scales, scale_factors, rotations,
                 cov3Ds_precomp, raster_settings, extrinsic_vector):
-        return _indexed_forward(ctx, means3D, sh, sh_indices, g_indices, colors_precomp, opacities, scales, scale_factors,
-                                rotations, cov3Ds_precomp, raster_settings, extrinsic_vector)
+        return _autograd_forward(ctx, True, means3D, sh, sh_indices, g_indices, colors_precomp, opacities, scales,
+                                 scale_factors, rotations, cov3Ds_precomp, raster_settings, extrinsic_vector)
 
     @staticmethod
     def backward(ctx, grad_out_color, *params):
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_scale_factors, grad_rotations), (extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations,
-                                               cov3Ds_precomp, sh) = _indexed_backward(ctx, grad_out_color)
+        g = _autograd_backward(ctx, grad_out_color)
         grad_mat = None
         if ctx.needs_input_grad[12]:
+            extrinsic_vector, _, means3D = ctx.saved_tensors[:3]
             grad_mat = camera_pose_jacobian_sum(means3D, ctx.raster_settings.intrinsic, extrinsic_vector,
-                                                grad_means2D[:, 0], grad_means2D[:, 1]).to(extrinsic_vector.device)
-        return (grad_means3D, grad_means2D, _fit(grad_sh, sh), None, None, _fit(grad_colors_precomp, colors_precomp),
-                grad_opacities, _fit(grad_scales, scales), _fit(grad_scale_factors, scale_factors),
-                _fit(grad_rotations, rotations), _fit(grad_cov3Ds_precomp, cov3Ds_precomp), None, grad_mat)
+                                                g.means2D[:, 0], g.means2D[:, 1]).to(extrinsic_vector.device)
+        return (g.means3D, g.means2D, g.sh, None, None, g.colors_precomp, g.opacities, g.scales, g.scale_factors, g.rotations,
+                g.cov3Ds_precomp, None, grad_mat)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
@@ -774,63 +715,57 @@ def _empty():
     return torch.Tensor([])
 
 
-class GaussianRasterizer(nn.Module):
-    """reference __init__.py:881-948. `forward` accepts the pose as `extrinsic_vector=` (what the reference's own
-    caller passes, scene/gaussian_model.py:874) and, for compatibility with the declared signature, `extrinsic=`."""
+def _absent_to_empty(*tensors):
+    """The reference's `if x is None: x = torch.Tensor([])` for the optional inputs of a module's forward."""
+    return [_empty() if t is None else t for t in tensors]
+
+
+class _Rasterizer(nn.Module):
+    """What the module classes of both packages share."""
 
     def __init__(self, raster_settings):
         super().__init__()
         self.raster_settings = raster_settings
 
     def markVisible(self, positions, extrinsic_vector):
+        """A 7-element pose on the GPU takes the one-launch path; a 4x4 matrix (or CPU tensors) the general one."""
         with torch.no_grad():
             present = _mark_visible_from_pose(positions, extrinsic_vector)
             if present is not None:
                 return present
             view, proj = camera_matrices(self.raster_settings.intrinsic, extrinsic_vector, positions.device)[:2]
             return _C.mark_visible(positions, view, proj)
+
+
+class GaussianRasterizer(_Rasterizer):
+    """reference __init__.py:881-948. `forward` accepts the pose as `extrinsic_vector=` (what the reference's own
+    caller passes, scene/gaussian_model.py:874) and, for compatibility with the declared signature, `extrinsic=`."""
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, extrinsic_vector=None, extrinsic=None):
         _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
         if extrinsic_vector is None:
             extrinsic_vector = extrinsic if extrinsic is not None else self.raster_settings.extrinsic_vector
-        shs = _empty() if shs is None else shs
-        colors_precomp = _empty() if colors_precomp is None else colors_precomp
-        scales = _empty() if scales is None else scales
-        rotations = _empty() if rotations is None else rotations
-        cov3D_precomp = _empty() if cov3D_precomp is None else cov3D_precomp
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_to_empty(shs, colors_precomp, scales, rotations,
+                                                                                 cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    self.raster_settings, extrinsic_vector)
 
 
-class GaussianRasterizerIndexed(nn.Module):
+class GaussianRasterizerIndexed(_Rasterizer):
     """reference __init__.py:951-1046."""
 
     def __init__(self, raster_settings, optimize_camera=False):
-        super().__init__()
-        self.raster_settings = raster_settings
+        super().__init__(raster_settings)
         self.optimize_camera = optimize_camera
-
-    def markVisible(self, positions, extrinsic_vector):
-        with torch.no_grad():
-            present = _mark_visible_from_pose(positions, extrinsic_vector)
-            if present is not None:
-                return present
-            view, proj = camera_matrices(self.raster_settings.intrinsic, extrinsic_vector, positions.device)[:2]
-            return _C.mark_visible(positions, view, proj)
 
     def forward(self, means3D, means2D, opacities, sh_indices, g_indices, shs=None, colors_precomp=None, scales=None,
                 scale_factors=None, rotations=None, cov3D_precomp=None, extrinsic_vector=None):
         _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
         if extrinsic_vector is None:
             extrinsic_vector = self.raster_settings.extrinsic_vector
-        shs = _empty() if shs is None else shs
-        colors_precomp = _empty() if colors_precomp is None else colors_precomp
-        scales = _empty() if scales is None else scales
-        scale_factors = _empty() if scale_factors is None else scale_factors
-        rotations = _empty() if rotations is None else rotations
-        cov3D_precomp = _empty() if cov3D_precomp is None else cov3D_precomp
+        shs, colors_precomp, scales, scale_factors, rotations, cov3D_precomp = _absent_to_empty(
+            shs, colors_precomp, scales, scale_factors, rotations, cov3D_precomp)
         fn = rasterize_gaussians_indexed_camera if self.optimize_camera else rasterize_gaussians_indexed
         return fn(means3D, means2D, shs, sh_indices, g_indices, colors_precomp, opacities, scales, scale_factors, rotations,
                   cov3D_precomp, self.raster_settings, extrinsic_vector)

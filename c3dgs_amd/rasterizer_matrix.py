@@ -10,11 +10,9 @@ SURVEY App. C): not reproduced -- the pose receives no gradient here."""
 from typing import NamedTuple
 
 import torch
-import torch.nn as nn
 
-from . import rasterizer as _r
-from .rasterizer import (_C, _check_exclusive, _empty, _RasterizeGaussians, _RasterizeGaussiansIndexed,  # noqa: F401
-                         cpu_deep_copy_tuple, getProjectionMatrix, mat_to_quat, quat_to_mat)
+from .rasterizer import (_C, _absent_to_empty, _check_exclusive, _empty, _Rasterizer, _RasterizeGaussians,  # noqa: F401
+                         _RasterizeGaussiansIndexed, cpu_deep_copy_tuple, getProjectionMatrix, mat_to_quat, quat_to_mat)
 
 
 def _pose(extrinsic):
@@ -48,50 +46,31 @@ class GaussianRasterizationSettings(NamedTuple):
     clamp_color: bool
 
 
-class GaussianRasterizer(nn.Module):
+class GaussianRasterizer(_Rasterizer):
     """reference :516-584."""
 
-    def __init__(self, raster_settings):
-        super().__init__()
-        self.raster_settings = raster_settings
-
     def markVisible(self, positions, extrinsic):
-        with torch.no_grad():
-            view, proj = _r.camera_matrices(self.raster_settings.intrinsic, _pose(extrinsic), positions.device)[:2]
-            return _C.mark_visible(positions, view, proj)
+        return super().markVisible(positions, _pose(extrinsic))
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, extrinsic=None):
         _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        shs = _empty() if shs is None else shs
-        colors_precomp = _empty() if colors_precomp is None else colors_precomp
-        scales = _empty() if scales is None else scales
-        rotations = _empty() if rotations is None else rotations
-        cov3D_precomp = _empty() if cov3D_precomp is None else cov3D_precomp
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_to_empty(shs, colors_precomp, scales, rotations,
+                                                                                 cov3D_precomp)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    self.raster_settings, extrinsic)
 
 
-class GaussianRasterizerIndexed(nn.Module):
+class GaussianRasterizerIndexed(_Rasterizer):
     """reference :587-659."""
 
-    def __init__(self, raster_settings):
-        super().__init__()
-        self.raster_settings = raster_settings
-
     def markVisible(self, positions, extrinsic):
-        with torch.no_grad():
-            view, proj = _r.camera_matrices(self.raster_settings.intrinsic, _pose(extrinsic), positions.device)[:2]
-            return _C.mark_visible(positions, view, proj)
+        return super().markVisible(positions, _pose(extrinsic))
 
     def forward(self, means3D, means2D, opacities, sh_indices, g_indices, shs=None, colors_precomp=None, scales=None,
                 scale_factors=None, rotations=None, cov3D_precomp=None, extrinsic=None):
         _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        shs = _empty() if shs is None else shs
-        colors_precomp = _empty() if colors_precomp is None else colors_precomp
-        scales = _empty() if scales is None else scales
-        scale_factors = _empty() if scale_factors is None else scale_factors
-        rotations = _empty() if rotations is None else rotations
-        cov3D_precomp = _empty() if cov3D_precomp is None else cov3D_precomp
+        shs, colors_precomp, scales, scale_factors, rotations, cov3D_precomp = _absent_to_empty(
+            shs, colors_precomp, scales, scale_factors, rotations, cov3D_precomp)
         return rasterize_gaussians_indexed(means3D, means2D, shs, sh_indices, g_indices, colors_precomp, opacities, scales,
                                            scale_factors, rotations, cov3D_precomp, self.raster_settings, extrinsic)

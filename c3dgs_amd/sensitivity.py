@@ -24,8 +24,7 @@ def _abs_accumulate(acc: torch.Tensor, grad: torch.Tensor) -> None:
         from . import _lib
         g = grad.contiguous()
         with torch.cuda.device(acc.device):
-            _lib.check(_lib.lib().c3dgs_abs_accumulate(acc.numel(), g.data_ptr(), acc.data_ptr(),
-                                                      torch.cuda.current_stream(acc.device).cuda_stream))
+            _lib.check(_lib.lib().c3dgs_abs_accumulate(acc.numel(), g.data_ptr(), acc.data_ptr(), _lib.stream(acc.device)))
     else:
         acc += torch.abs(grad)
 

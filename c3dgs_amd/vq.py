@@ -24,10 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+from ._lib import stream as _stream
 
 
 def weightedDistance(coefs: torch.Tensor, codebook: torch.Tensor, gather: Optional[torch.Tensor] = None):
@@ -322,7 +319,7 @@ class _BatchDraws:
         if self._dev is None:            # device-side staging, once per loop: raw words + indices (reused every step, stream-ordered)
             self._dev = (torch.empty(self.chunk, dtype=torch.int32, device=self.device),
                          torch.empty(self.chunk, dtype=torch.int64, device=self.device),
-                         torch.cuda.current_stream(self.device).cuda_stream)
+                         _stream(self.device))
         raw, out, stream = self._dev
         L = _lib.lib()
         if self._pool is not None and k + 1 < self.steps:

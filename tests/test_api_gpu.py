@@ -1,5 +1,7 @@
 """-m gpu: the drop-in Python surface (reference diff_gaussian_rasterization_no_camera/__init__.py) end to end
 through torch.autograd, for both module classes."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -344,3 +346,131 @@ def test_matrix_extrinsic_api_of_the_sibling_packages(hip, orc):
                 sys.modules.pop(k, None)
             else:
                 sys.modules[k] = v
+
+
+# ------------------------------------------------------------- named gradients -> input positions, and the explicit skip
+_ENTRIES = ("rasterize_gaussians", "rasterize_gaussians_indexed", "rasterize_gaussians_indexed_camera")
+_GRAD_OF = dict(means3D="dL_dmeans3D", means2D="dL_dmeans2D", shs="dL_dsh", colors_precomp="dL_dcolors", opacities="dL_dopacity",
+                scales="dL_dscales", scale_factors="dL_dscale_factors", rotations="dL_drotations", cov3D_precomp="dL_dcov3D")
+_ATOMIC = ("dL_dsh", "dL_dscales", "dL_drotations")     # indexed path: scatter-added with float atomics
+_PW, _PH, _PF, _PN = 40, 24, 30.0, 300                  # 3 x 2 tiles, ragged on both edges
+
+
+@functools.lru_cache(maxsize=None)
+def _position_scene():
+    """CPU tensors, built once. The indexed variant refers to every codebook row from exactly ONE Gaussian, so that each
+    scatter-added element is 0 + one value and two launches agree bit for bit whatever order the atomics retire in."""
+    from tests.dense_ref import _rot
+    sc = synth.scene(_PN, _PW, _PH, _PF, seed=31, scale_median=0.08, zmin=2, zmax=6)
+    ix = synth.index_scene(sc, seed=32, sh_frac=1.0, g_frac=1.0)
+    g = torch.Generator().manual_seed(33)
+    ix["sh_indices"], ix["g_indices"] = torch.randperm(_PN, generator=g), torch.randperm(_PN, generator=g)
+    Lm = _rot(sc["rotations"].double()) * sc["scales"].double()[:, None, :]
+    Sg = Lm @ Lm.transpose(1, 2)
+    cov = torch.stack([Sg[:, 0, 0], Sg[:, 0, 1], Sg[:, 0, 2], Sg[:, 1, 1], Sg[:, 1, 2], Sg[:, 2, 2]], 1).float().contiguous()
+    return sc, ix, cov, torch.rand(_PN, 3, generator=g), synth.grad_image(_PW, _PH)
+
+
+@functools.lru_cache(maxsize=None)
+def _position_run(entry, color, cov, depth):
+    """One forward + backward(dL) through autograd, then the matching _C backward entry on the buffers of that very forward
+    (taken from a spy on the _C forward entry). Results as CPU tensors; cached, so a depth=True case meets its depth=False twin."""
+    import c3dgs_amd
+    from c3dgs_amd import rasterizer as rz
+    sc, ix, cov6, rgb, dL = _position_scene()
+    indexed = entry != "rasterize_gaussians"
+    src = ix if indexed else sc
+    intr, ev = synth.camera(_PW, _PH, _PF, extrinsic_vector=(0.05, -0.03, 0.02, 0.99, 0.1, -0.05, 0.2))
+    kw = dict(intrinsic=intr.cuda(), extrinsic_vector=ev.cuda(), bg=torch.tensor((0.2, 0.4, 0.1), device="cuda"), scale_modifier=1.0,
+              sh_degree=3, prefiltered=False, debug=False, clamp_color=True)
+    rs = c3dgs_amd.GaussianRasterizationSettings(**kw, depth=True) if depth else c3dgs_amd.GaussianRasterizationSettings(**kw)
+    present = {"means3D": src["means3D"], "means2D": torch.zeros(_PN, 3), "opacities": src["opacities"]}
+    present.update({"shs": src["shs"]} if color == "shs" else {"colors_precomp": rgb})
+    present.update({"scales": src["scales"], "rotations": src["rotations"]} if cov == "scales" else {"cov3D_precomp": cov6})
+    if indexed:
+        present["scale_factors"] = ix["scale_factors"]
+    # every input is a leaf that asks for a gradient, the absent ones (the modules' `_empty()`) and the pose included
+    leaf = {k: (present[k].cuda() if k in present else rz._empty()).requires_grad_() for k in _GRAD_OF}
+    pose = ev.cuda().requires_grad_()
+    fw_name = "rasterize_gaussians_indexed" if indexed else "rasterize_gaussians"
+    bw_name = "rasterize_gaussians_backward_indexed" if indexed else "rasterize_gaussians_backward"
+    fw_real, bw_real, seen = getattr(rz._C, fw_name), getattr(rz._C, bw_name), {}
+
+    def fw_spy(*a):
+        seen["args"], seen["out"] = a, fw_real(*a)
+        return seen["out"]
+
+    def bw_spy(*a, **k):
+        seen["bw"] = bw_real(*a, **k)
+        return seen["bw"]
+    setattr(rz._C, fw_name, fw_spy)
+    setattr(rz._C, bw_name, bw_spy)
+    try:
+        if indexed:
+            out = getattr(rz, entry)(leaf["means3D"], leaf["means2D"], leaf["shs"], ix["sh_indices"].cuda(), ix["g_indices"].cuda(),
+                                     leaf["colors_precomp"], leaf["opacities"], leaf["scales"], leaf["scale_factors"],
+                                     leaf["rotations"], leaf["cov3D_precomp"], rs, pose)
+        else:
+            out = rz.rasterize_gaussians(leaf["means3D"], leaf["means2D"], leaf["shs"], leaf["colors_precomp"], leaf["opacities"],
+                                         leaf["scales"], leaf["rotations"], leaf["cov3D_precomp"], rs, pose)
+        out[0].backward(dL.cuda())
+    finally:
+        setattr(rz._C, fw_name, fw_real)
+        setattr(rz._C, bw_name, bw_real)
+    R, _, radii, geom, binning, img = seen["out"]
+    fw = dict(args=seen["args"], num_rendered=R, radii=radii, geom=geom, binning=binning, img=img, indexed=indexed)
+    entry_grads = gpu_util.hip_backward(fw, dL)                 # detaches every output: the entry returned all of them
+    order = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D")
+    return dict(n_out=len(out), color=out[0].detach().cpu(), radii=out[1].cpu(), extras_need_grad=[t.requires_grad for t in out[2:]],
+                extras_shape=[tuple(t.shape) for t in out[2:]], R=R, present=set(present),
+                grads={k: (None if v.grad is None else v.grad.cpu()) for k, v in leaf.items()},
+                pose_grad=None if pose.grad is None else pose.grad.cpu(), entry=entry_grads,
+                autograd_skipped={n for n, t in zip(order, seen["bw"]) if t is None},
+                pose_want=rz.camera_pose_jacobian_sum(leaf["means3D"].detach(), rs.intrinsic, pose.detach(),
+                                                      leaf["means2D"].grad[:, 0], leaf["means2D"].grad[:, 1]).cpu())
+
+
+def _bits(t):
+    return (t.numpy() if isinstance(t, torch.Tensor) else t).view(np.uint32)
+
+
+@pytest.mark.parametrize("depth", [False, True])
+@pytest.mark.parametrize("cov", ["scales", "cov3D_precomp"])
+@pytest.mark.parametrize("color", ["shs", "colors_precomp"])
+@pytest.mark.parametrize("entry", _ENTRIES)
+def test_autograd_delivers_each_named_gradient_to_its_input(hip, entry, color, cov, depth):
+    """The three Functions share one backward body that names its gradients; each lays them out in its own input order. For
+    every input combination: each leaf's .grad is the _C backward entry's tensor OF THAT NAME on the same forward buffers
+    (bit for bit; the three atomics-summed codebook gradients of the indexed path within GRAD_TOL, the bar of
+    tests/test_raster_gpu.py), absent inputs get none, the pose gets one only from the _camera variant, the autograd call
+    skipped exactly the outputs of absent inputs while the entry itself returns all, and depth=True changes nothing."""
+    from tests.test_raster_gpu import GRAD_TOL
+    r = _position_run(entry, color, cov, depth)
+    indexed = entry != "rasterize_gaussians"
+    assert r["R"] > 0
+    for k, name in _GRAD_OF.items():
+        got = r["grads"][k]
+        if k not in r["present"]:
+            assert got is None, k
+            continue
+        want = r["entry"][name].reshape(got.shape)
+        assert np.abs(want).max() > 0 or (k == "scale_factors" and cov == "cov3D_precomp"), k
+        if indexed and name in _ATOMIC:
+            assert gpu_util.rel_inf(got.numpy(), want) <= GRAD_TOL, k
+        else:
+            np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=k)
+    assert r["autograd_skipped"] == {_GRAD_OF[k] for k in ("colors_precomp", "cov3D_precomp") if k not in r["present"]}
+    if entry == "rasterize_gaussians_indexed_camera":
+        assert r["pose_grad"] is not None and torch.equal(r["pose_grad"], r["pose_want"]) and bool(r["pose_grad"].abs().max() > 0)
+    else:
+        assert r["pose_grad"] is None
+    assert r["n_out"] == (5 if depth else 2) and r["extras_need_grad"] == [False] * (3 if depth else 0)
+    if depth:
+        assert r["extras_shape"] == [(_PH, _PW)] * 3
+        plain = _position_run(entry, color, cov, False)
+        np.testing.assert_array_equal(_bits(r["color"]), _bits(plain["color"]))
+        assert torch.equal(r["radii"], plain["radii"])
+        for k, g in r["grads"].items():
+            assert (g is None) == (plain["grads"][k] is None), k
+            if g is not None:
+                np.testing.assert_array_equal(_bits(g), _bits(plain["grads"][k]), err_msg=k)
