@@ -67,12 +67,19 @@ size_t tile_sort_clear_bytes(int R, int end_bit, int key_bytes)
     return (onesweep_enabled() && (size_t)R < ((size_t)1 << 30)) ? onesweep_tile_clear_bytes(R, end_bit, key_bytes) : 0;
 }
 
+hipError_t run_depth_hist_scan(void* temp, size_t temp_bytes, const uint32_t* keys, int P, int nb, uint32_t* base,
+                               const uint32_t* sort_err, uint32_t* host_out, uint32_t host_seq, hipStream_t s)
+{
+    if (depth_sort_clear_bytes(P) == 0) return hipErrorInvalidValue;      // the rocPRIM path has no histogram launch to share
+    return onesweep_depth_hist_scan(temp, temp_bytes, keys, P, nb, base, sort_err, host_out, host_seq, s);
+}
+
 hipError_t run_depth_sort(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout, const uint32_t* vin,
                           uint32_t* vout, int P, const uint2* rects, uint2* rects_sorted, hipStream_t s, bool ctrl_cleared,
-                          bool rects_fit_bytes)
+                          bool rects_fit_bytes, bool hist_done)
 {
     if (onesweep_enabled() && (size_t)P < ((size_t)1 << 30))
-        return onesweep_depth_sort(temp, temp_bytes, kin, kout, vin, vout, P, rects, rects_sorted, s, ctrl_cleared, rects_fit_bytes);
+        return onesweep_depth_sort(temp, temp_bytes, kin, kout, vin, vout, P, rects, rects_sorted, s, ctrl_cleared, rects_fit_bytes, hist_done);
     // vin == nullptr: the payload is the Gaussian id itself (0 .. P-1)
     hipError_t e = vin ? rocprim::radix_sort_pairs(temp, temp_bytes, kin, kout, vin, vout, (size_t)P, 0u, 32u, s)
                        : rocprim::radix_sort_pairs(temp, temp_bytes, kin, kout, rocprim::counting_iterator<uint32_t>(0u), vout,

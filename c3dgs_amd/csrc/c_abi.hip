@@ -231,21 +231,29 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
     const uint32_t host_seq = hr.begin();
     // the depth sort's control words are cleared by preprocess's workgroups (0 bytes: that sort clears its own)
     const size_t dclear = depth_sort_clear_bytes(P) <= g.scan_temp_bytes ? depth_sort_clear_bytes(P) : 0;
+    // the id-order scan behind preprocess shares its launch with the depth sort's histograms where that sort is the hand-written
+    // one and preprocess has cleared its control words; otherwise it runs alone and the sort does everything itself
+    const bool hist_with_scan = dclear != 0;
+    const int nb = (P + 255) / 256;
     { StageTimer t_(ST_PREPROCESS, s);
       if (geom_gtab_bytes(p)) launch_pack_codebook(p, g.gtab, s);
-      launch_preprocess(p, g, radii, img.ranges, sort_err, g.scan_temp, dclear / 16, hr.dev, host_seq, s); }
+      launch_preprocess(p, g, radii, img.ranges, g.scan_temp, dclear / 16, s);
+      if (hist_with_scan)
+          C3DGS_HIP_TRY(run_depth_hist_scan(g.scan_temp, g.scan_temp_bytes, g.depth_keys, P, nb, g.block_base, sort_err, hr.dev, host_seq, s));
+      else
+          launch_scan_blocks(nb, g.block_base, sort_err, hr.dev, host_seq, s); }
     C3DGS_STAGE_CHECK(ST_PREPROCESS, p.debug, s);
     // The one device->host read of the forward (K4, num_rendered) is issued as EARLY as its value exists: R is the last
     // entry of block_base[]. It lands in the host pad while the depth sort and the depth-order scan are already queued, so
     // the GPU keeps working while the host waits, sizes the binning buffer and queues the rest (the reference blocks the
     // stream at this point, rasterizer_impl.cu:279).
     // second word: the device's sticky sort time-out flag as of the start of this call (radix_sort.hip)
-    const uint32_t* r_words = g.block_base + (P + 255) / 256;
+    const uint32_t* r_words = g.block_base + nb;
     if (int rc = hr.queue_copy(r_words, s)) return rc;
     { StageTimer t_(ST_DEPTH_SORT, s);                                               // binning stage 1: P Gaussians by depth
       C3DGS_HIP_TRY(run_depth_sort(g.scan_temp, g.scan_temp_bytes, g.depth_keys, g.depth_keys_sorted, nullptr, g.depth_order, P,
                                    reinterpret_cast<const uint2*>(g.rects), g.sorted_offsets, s, dclear != 0,
-                                   /*rects_fit_bytes=*/gx <= 255 && gy <= 255)); }
+                                   /*rects_fit_bytes=*/gx <= 255 && gy <= 255, hist_with_scan)); }
     C3DGS_STAGE_CHECK(ST_DEPTH_SORT, p.debug, s);
     if (p.debug && onesweep_timed_out(s)) return fail(C3DGS_E_HIP, "depth sort: look-back timed out");
     C3DGS_TIMED_STAGE(ST_SCAN, p.debug, s, launch_depth_order_scan(P, g, s));        // K3, in depth order (two-level)
@@ -270,7 +278,8 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
 
     if (R > 0) {
         const int end_bit = tile_sort_end_bit(W, H);                                // tile bits only (rasterizer_impl.cu:298)
-        // the tile sort's control words are cleared by the pair emission's workgroups (0 bytes: that sort clears its own)
+        // the tile sort's control words are cleared by the pair emission's workgroups (0 bytes: that sort clears its own, or --
+        // the table-driven sort of 16-bit keys -- has none to clear)
         size_t tclear = tile_sort_clear_bytes(R, end_bit, b.key_bytes);
         if (tclear > b.sort_temp_bytes) tclear = 0;
         C3DGS_TIMED_STAGE(ST_DUPLICATE, p.debug, s, launch_duplicate_with_keys(P, g, b, gx, sort_err, b.sort_temp, tclear / 16, s)); // K5

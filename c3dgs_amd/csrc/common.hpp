@@ -229,10 +229,13 @@ void launch_camera_from_pose(const float* pose, float inv_tan_x, float inv_tan_y
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 void launch_mark_visible_pose(int P, const float* means3D, const float* pose7, uint8_t* present, hipStream_t s);
 void launch_pack_codebook(const c3dgs_raster_params& p, float4* gtab, hipStream_t s);
-// zero_span / zero_n16: 16-byte words every workgroup clears a slice of before anything else (the depth sort's control words);
-// host_out / host_seq: mapped host words {num_rendered, sort error flag, host_seq} the closing scan writes (or null)
-void launch_preprocess(const c3dgs_raster_params& p, const GeomPtrs& g, int32_t* radii, uint2* ranges, const uint32_t* sort_err,
-                       void* zero_span, size_t zero_n16, uint32_t* host_out, uint32_t host_seq, hipStream_t s);
+// zero_span / zero_n16: 16-byte words every workgroup clears a slice of before anything else (the depth sort's control words).
+// Leaves the workgroup totals in g.block_base: the caller runs the scan behind it (launch_scan_blocks / run_depth_hist_scan)
+void launch_preprocess(const c3dgs_raster_params& p, const GeomPtrs& g, int32_t* radii, uint2* ranges, void* zero_span, size_t zero_n16,
+                       hipStream_t s);
+// exclusive scan of nb workgroup totals in place, base[nb] = total; sort_err: the sticky sort time-out word, copied to base[nb + 1];
+// host_out / host_seq: mapped host words {num_rendered, sort error flag, host_seq} the scan writes last (or null)
+void launch_scan_blocks(int nb, uint32_t* base, const uint32_t* sort_err, uint32_t* host_out, uint32_t host_seq, hipStream_t s);
 void launch_depth_order_scan(int P, const GeomPtrs& g, hipStream_t s);   // block totals of tiles_sorted -> depth_base[]
 void launch_duplicate_with_keys(int P, const GeomPtrs& g, const BinPtrs& b, int grid_x, const uint32_t* sort_err,
                                 void* zero_span, size_t zero_n16, hipStream_t s);   // zero span: the tile sort's control words
@@ -241,9 +244,14 @@ void launch_identify_ranges(int R, const void* keys_sorted, int key_bytes, uint2
 // ctrl_cleared: the first *_sort_clear_bytes(...) bytes of `temp` were zeroed by an earlier kernel on the same stream
 // (0 bytes = this configuration's sort clears its own control words: pass false)
 // rects_fit_bytes: all rectangle coordinates < 256 (at most 255 x 255 tiles): the rectangles may ride through the sort packed
+// hist_done: run_depth_hist_scan has run on this scratch (only with ctrl_cleared)
 hipError_t run_depth_sort(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout, const uint32_t* vin,
                           uint32_t* vout, int P, const uint2* rects, uint2* rects_sorted, hipStream_t s, bool ctrl_cleared = false,
-                          bool rects_fit_bytes = false);
+                          bool rects_fit_bytes = false, bool hist_done = false);
+// launch_scan_blocks and the depth sort's digit histograms in one launch. Only where depth_sort_clear_bytes(P) is not 0 (the
+// hand-written sort) and those bytes of `temp` have been cleared by an earlier kernel on the stream
+hipError_t run_depth_hist_scan(void* temp, size_t temp_bytes, const uint32_t* keys, int P, int nb, uint32_t* base,
+                               const uint32_t* sort_err, uint32_t* host_out, uint32_t host_seq, hipStream_t s);
 hipError_t run_tile_sort(void* temp, size_t temp_bytes, const void* kin, void* kout, int key_bytes, const uint32_t* vin,
                          uint32_t* vout, int R, int end_bit, hipStream_t s, bool ctrl_cleared = false);
 size_t depth_sort_clear_bytes(int P);
@@ -258,7 +266,9 @@ size_t onesweep_depth_clear_bytes(int P);
 size_t onesweep_tile_clear_bytes(int R, int end_bit, int key_bytes);
 hipError_t onesweep_depth_sort(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout,
                                int P, const uint2* gather_src, uint2* gather_dst, hipStream_t s, bool ctrl_cleared = false,
-                               bool rects_fit_bytes = false);
+                               bool rects_fit_bytes = false, bool hist_done = false);
+hipError_t onesweep_depth_hist_scan(void* temp, size_t temp_bytes, const uint32_t* keys, int P, int nb, uint32_t* base,
+                                    const uint32_t* sort_err, uint32_t* host_out, uint32_t host_seq, hipStream_t s);
 hipError_t onesweep_tile_sort32(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout,
                                 int R, int end_bit, hipStream_t s, bool ctrl_cleared = false);   // 32-bit tile keys (more than 65,536 tiles)
 hipError_t onesweep_tile_sort(void* temp, size_t temp_bytes, const uint16_t* kin, uint16_t* kout, const uint32_t* vin, uint32_t* vout,

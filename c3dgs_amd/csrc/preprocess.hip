@@ -16,6 +16,7 @@
 // extra gather (see render.hip).
 #include "common.hpp"
 #include "gsmath.hpp"
+#include "scan_blocks.hpp"
 
 namespace c3dgs {
 
@@ -181,7 +182,8 @@ struct PreArgs {
 // The id-order scan of tiles_touched (where a Gaussian's backward partial-sum slots live; its total is num_rendered) is
 // split in two levels so that no separate P-sized scan pass and no scattered "stamp" pass are needed: this kernel scans
 // inside each 256-Gaussian workgroup (inst_offset = inclusive offset WITHIN the workgroup, record word 9 = exclusive one)
-// and emits the workgroup totals; scan_blocks_kernel turns the ~P/256 totals into block_base[]. Consumers add
+// and emits the workgroup totals; scan_blocks_body (scan_blocks.hpp: workgroup 0 of os_hist_scan_kernel in the forward, alone in
+// scan_blocks_kernel on the rocPRIM path) turns the ~P/256 totals into block_base[]. Consumers add
 // block_base[id >> 8].
 template <int DEG>
 __global__ void __launch_bounds__(256) preprocess_kernel(const PreArgs a)
@@ -313,77 +315,20 @@ __global__ void __launch_bounds__(256) preprocess_kernel(const PreArgs a)
     a.depth_keys[i] = out_key;
 }
 
-// exclusive scan of the workgroup totals, in place: base[b] = instances of all Gaussians before workgroup b;
-// base[nb] = num_rendered. One workgroup; nb = P/256 is a few thousand to a few ten-thousand.
-// `sort_err` (optional): the device's sticky sort time-out word, copied behind the total so that the forward's single
-// device->host read of num_rendered brings it along (radix_sort.hip).
-// `host_out` (optional): three words of MAPPED, coherent host memory {total, sort error word, host_seq}: the forward's one
-// device->host read without a copy command -- the host polls the third word for `host_seq` (c_abi.hip). A copy command behind
-// this kernel cost a 4 us launch of its own plus a ~6 us bubble on the stream.
-__global__ void __launch_bounds__(1024) scan_blocks_kernel(int nb, uint32_t* __restrict__ base, const uint32_t* __restrict__ sort_err,
-                                                           uint32_t* __restrict__ host_out, uint32_t host_seq)
+// the scan alone in a launch: scan_blocks.hpp has the body and its description
+__global__ void __launch_bounds__(SCAN_BLOCKS_THREADS) scan_blocks_kernel(int nb, uint32_t* __restrict__ base, const uint32_t* __restrict__ sort_err,
+                                                                          uint32_t* __restrict__ host_out, uint32_t host_seq)
 {
-    // One workgroup; a thread owns 16 CONSECUTIVE totals (four independent 16-byte loads), so 16384 totals cost one
-    // memory round trip and one barrier. (One total per thread and a round trip + barrier per 1024 totals took 12 us for the
-    // 11.7k totals of P = 3M: pure latency.) `base` is 256-byte aligned with room up to the next multiple of 16 entries + 2.
-    __shared__ uint32_t s_w[2][16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    uint32_t carry = 0;                                   // every thread tracks the running total itself
-    int buf = 0;
-    for (int c0 = 0; c0 < nb; c0 += 16384, buf ^= 1) {
-        const int i0 = c0 + t * 16;
-        uint32_t v[16];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            uint4 x = make_uint4(0u, 0u, 0u, 0u);
-            if (i0 + 4 * q + 3 < nb) x = reinterpret_cast<const uint4*>(base + i0)[q];
-            else {
-                if (i0 + 4 * q < nb) x.x = base[i0 + 4 * q];
-                if (i0 + 4 * q + 1 < nb) x.y = base[i0 + 4 * q + 1];
-                if (i0 + 4 * q + 2 < nb) x.z = base[i0 + 4 * q + 2];
-            }
-            v[4 * q] = x.x; v[4 * q + 1] = x.y; v[4 * q + 2] = x.z; v[4 * q + 3] = x.w;
-        }
-        uint32_t mine = 0;
-#pragma unroll
-        for (int q = 0; q < 16; q++) mine += v[q];
-        uint32_t incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o); if (lane >= o) incl += u; }
-        if (lane == 63) s_w[buf][wave] = incl;
-        __syncthreads();                                  // s_w is double-buffered: one barrier per sweep
-        uint32_t off = carry, all = 0;
-#pragma unroll
-        for (int w = 0; w < 16; w++) { const uint32_t x = s_w[buf][w]; if (w < wave) off += x; all += x; }
-        uint32_t run = off + incl - mine;                 // exclusive base of this thread's first total
-#pragma unroll
-        for (int q = 0; q < 16; q++) { const uint32_t x = v[q]; v[q] = run; run += x; }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (i0 + 4 * q + 3 < nb) reinterpret_cast<uint4*>(base + i0)[q] = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-            else {
-                if (i0 + 4 * q < nb) base[i0 + 4 * q] = v[4 * q];
-                if (i0 + 4 * q + 1 < nb) base[i0 + 4 * q + 1] = v[4 * q + 1];
-                if (i0 + 4 * q + 2 < nb) base[i0 + 4 * q + 2] = v[4 * q + 2];
-            }
-        }
-        carry += all;
-    }
-    __syncthreads();                                      // the last sweep's stores precede the two words behind them
-    if (t == 0) {
-        base[nb] = carry;
-        const uint32_t err = sort_err ? *sort_err : 0u;
-        if (sort_err) base[nb + 1] = err;
-        if (host_out) {
-            __hip_atomic_store(host_out, carry, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_out + 1, err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_out + 2, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // publishes the two words above
-        }
-    }
+    scan_blocks_body(nb, base, sort_err, host_out, host_seq);
 }
 
-void launch_preprocess(const c3dgs_raster_params& p, const GeomPtrs& g, int32_t* radii, uint2* ranges, const uint32_t* sort_err,
-                       void* zero_span, size_t zero_n16, uint32_t* host_out, uint32_t host_seq, hipStream_t s)
+void launch_scan_blocks(int nb, uint32_t* base, const uint32_t* sort_err, uint32_t* host_out, uint32_t host_seq, hipStream_t s)
+{
+    scan_blocks_kernel<<<1, SCAN_BLOCKS_THREADS, 0, s>>>(nb, base, sort_err, host_out, host_seq);
+}
+
+void launch_preprocess(const c3dgs_raster_params& p, const GeomPtrs& g, int32_t* radii, uint2* ranges, void* zero_span, size_t zero_n16,
+                       hipStream_t s)
 {
     if (p.P <= 0) return;
     PreArgs a;
@@ -399,7 +344,7 @@ void launch_preprocess(const c3dgs_raster_params& p, const GeomPtrs& g, int32_t*
     a.radii = radii; a.splat = g.splat; a.rects = g.rects;
     a.clamped = g.clamped; a.depth_keys = g.depth_keys;
     a.inst_offset = g.inst_offset;
-    a.block_total = g.block_base;     // totals in, exclusive bases out (scan_blocks_kernel)
+    a.block_total = g.block_base;     // totals in, exclusive bases out (scan_blocks_body, launched by the caller)
     a.ranges = ranges; a.T = a.gx * a.gy;
     a.gtab = g.gtab;
     a.zero_span = (uint4*)zero_span; a.zero_n16 = zero_span ? zero_n16 : 0;
@@ -411,7 +356,6 @@ void launch_preprocess(const c3dgs_raster_params& p, const GeomPtrs& g, int32_t*
         case 2: preprocess_kernel<2><<<grid, block, 0, s>>>(a); break;
         default: preprocess_kernel<3><<<grid, block, 0, s>>>(a); break;
     }
-    scan_blocks_kernel<<<1, 1024, 0, s>>>((int)grid.x, g.block_base, sort_err, host_out, host_seq);
 }
 
 // ---- K5: one (tile, Gaussian) pair per Gaussian x tile, reference rasterizer_impl.cu:70-111, walked in
@@ -445,8 +389,8 @@ duplicate_with_keys_kernel(int P, const uint32_t* __restrict__ order, const uint
                            const uint32_t* __restrict__ depth_base, K* __restrict__ keys, uint32_t* __restrict__ values,
                            int grid_x, const uint32_t* __restrict__ sort_err, uint4* __restrict__ zero_span, size_t zero_n16)
 {
-    // the tile sort's control words (look-back status, tickets) are cleared here, a slice per workgroup, instead of by a fill
-    // launch in front of the sort -- BEFORE the early-out below: that sort runs either way and must not walk stale status words
+    // the tile sort's control words (look-back status, tickets: the sort of 32-bit keys only) are cleared here, a slice per
+    // workgroup, instead of by a fill launch in front of the sort -- BEFORE the early-out below: that sort runs either way and must not walk stale status words
     if (zero_n16) {
         const size_t per = (zero_n16 + gridDim.x - 1) / gridDim.x, z0 = (size_t)blockIdx.x * per, z1 = min(z0 + per, zero_n16);
         for (size_t q = z0 + threadIdx.x; q < z1; q += 256) zero_span[q] = make_uint4(0u, 0u, 0u, 0u);
@@ -471,7 +415,7 @@ duplicate_with_keys_kernel(int P, const uint32_t* __restrict__ order, const uint
         const uint32_t w = (rc.y & 0xffff) - (rc.x & 0xffff);
         s_inv[t] = w > 1 ? 0xffffffffu / w + 1u : 0u;         // width 1: quotient = local (handled below); width 0: no instances
     }
-    // depth-order scan inside the workgroup (the workgroup bases come from scan_blocks_kernel)
+    // depth-order scan inside the workgroup (the workgroup bases, depth_base[], come from launch_depth_order_scan)
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if (lane >= o) incl += v; }
     if (lane == 63) s_wsum[wave] = incl;
@@ -553,7 +497,7 @@ void launch_depth_order_scan(int P, const GeomPtrs& g, hipStream_t s)
     if (P <= 0) return;
     const int nb = (P + 255) / 256;
     block_totals_kernel<<<nb, 256, 0, s>>>(P, g.sorted_offsets, g.depth_base);
-    scan_blocks_kernel<<<1, 1024, 0, s>>>(nb, g.depth_base, nullptr, nullptr, 0u);
+    launch_scan_blocks(nb, g.depth_base, nullptr, nullptr, 0u, s);
 }
 
 void launch_duplicate_with_keys(int P, const GeomPtrs& g, const BinPtrs& b, int grid_x, const uint32_t* sort_err,

@@ -1,24 +1,32 @@
 // radix_sort.hip -- stable LSD radix sort of (key, u32 value) pairs for the two sorts of the binning stage (gfx950).
 //
 // Replaces rocPRIM's radix_sort_pairs in run_depth_sort / run_tile_sort (binning.hip keeps the rocPRIM path, selectable
-// with C3DGS_SORT_ROCPRIM=1). Same algorithm family (onesweep: one read and one write of the data per digit, chained
-// look-back instead of a global scan), written for this workload:
-//   * ONE memset per sort (digit histograms + look-back words + tickets are one contiguous block) instead of the two
-//     5-microsecond fill launches rocPRIM issues in front of every digit pass (14 per forward);
+// with C3DGS_SORT_ROCPRIM=1). One read and one write of the data per digit, no global scan pass, written for this workload:
 //   * 8192-item tiles of 1024 threads for the u16 tile keys, 12288-item tiles of 512 threads for the u32 depth keys: measured 0.228 ms against 0.267 ms for the 16.4 M (u16, u32) tile-key pairs;
-//   * digit widths chosen per sort (13 tile bits = 7 + 6), keys of the native width.
-// Structure of one digit pass (os_pass_kernel), per 8192-item tile:
-//   ticket      blocks take their tile index from an atomic counter, so every predecessor of a block is already running
-//               (forward progress of the look-back does not depend on the dispatch order);
+//   * digit widths chosen per sort (13 tile bits = 7 + 6), keys of the native width;
+//   * where a tile's digit offsets come from depends on the key width:
+//       u16 keys (tile sort up to 65,536 tiles)  TABLE-DRIVEN, every pass: os_tile_hist_kernel counts the pass's digit per tile,
+//           os_table_scan_kernel turns the counts into exclusive prefixes over the tiles, os_pass_kernel<.., PRE = true> reads them.
+//           No ticket, no look-back (`ticket` is null and `status` is the table in these launches), no control words to clear,
+//           no time-out;
+//       u32 keys (depth sort; tile sort above 65,536 tiles)  onesweep: os_hist_kernel builds all digit histograms in one read,
+//           os_pass_kernel<.., PRE = false> finds the offsets by a chained look-back over the earlier tiles' status words. ONE
+//           clear per sort (digit histograms + look-back words + tickets are one contiguous block, normally cleared by the kernel
+//           in front of the sort) instead of the two 5-microsecond fill launches rocPRIM issues in front of every digit pass.
+// Structure of one digit pass (os_pass_kernel), per tile:
+//   ticket      (look-back passes only) blocks take their tile index from an atomic counter, so every predecessor of a block is
+//               already running (forward progress of the look-back does not depend on the dispatch order); table-driven passes
+//               use blockIdx.x;
 //   rank        wave w owns a contiguous chunk of the tile and walks it 64 items at a time; lanes with the same digit find
 //               each other with BITS ballots, rank = wave counter + popcount(peers below me), the first peer bumps the
 //               counter -> ranks are in input order (stable);
-//   look-back   thread d publishes the tile's count of digit d (aggregate), adds up the predecessors' words until it meets
-//               an inclusive prefix, publishes its own inclusive prefix (one 32-bit word: 2 flag bits + 30 count bits,
-//               relaxed agent-scope atomics);
+//   offsets     table-driven: thread d reads the tile's exclusive prefix of digit d from the table. Look-back: thread d publishes
+//               the tile's count of digit d (aggregate), adds up the predecessors' words until it meets an inclusive prefix,
+//               publishes its own inclusive prefix (one 32-bit word: 2 flag bits + 30 count bits, relaxed agent-scope atomics);
 //   scatter     items are reordered through LDS into tile-sorted order, then written with consecutive threads on
 //               consecutive positions of each digit run.
 #include "common.hpp"
+#include "scan_blocks.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -33,7 +41,7 @@ constexpr int OS_RADIX = 256;
 #ifndef C3DGS_OS_BLOCK32
 #define C3DGS_OS_BLOCK32 512
 #endif
-// u16 keys: fixed shape. os_tile_hist_kernel (the look-back-free first pass) counts the SAME tiles with one 16-byte load of
+// u16 keys: fixed shape. os_tile_hist_kernel (in front of every table-driven pass) counts the SAME tiles with one 16-byte load of
 // 8 keys per thread, so tile = 8 x 1024 is not a build knob (measured alternatives before that pre-pass existed, 16.4 M
 // (u16, u32) pairs: 8192 x 1024 0.215 ms, 12288 x 1024 0.243, 16384 x 1024 0.225)
 constexpr int OS_TILE16 = 8192, OS_BLOCK16 = 1024;
@@ -76,6 +84,8 @@ __device__ unsigned long long g_os_times[64 * 8];   // stays zero in a diag vari
 
 struct OsPlan { int passes; int bits[OS_MAX_PASSES]; };
 
+// Measured for the two table-driven passes of the 13-bit tile sort (16.4 M pairs, whole sort): 7 + 6 153.6 us, 6 + 7 154.4 us,
+// 8 + 5 158.9 us -- an 8-bit pass costs 8 us more than a 7-bit one (scatter runs half as long), a 5-bit pass saves 5 us on a 6-bit one
 static OsPlan os_plan(int total_bits)
 {
     OsPlan p;
@@ -91,23 +101,30 @@ static OsPlan os_plan(int total_bits)
 }
 
 template <class K> static size_t os_blocks(size_t n) { return (n + OsShape<K>::TILE - 1) / OsShape<K>::TILE; }
-// The tile-key sort (u16 keys, two passes) runs its FIRST pass without the chained look-back: the histogram kernel works tile by
-// tile and leaves every tile's digit counts in a table, one small kernel turns the table's columns into exclusive prefixes
-// over the tiles (and their totals into the global histograms), and the pass reads its offsets from there. Measured on the
-// 16.4 M pairs of the bench view: the look-back costs ~30 us per pass at 2002 tiles (tools/time_sort.py knock-out).
-template <class K> constexpr bool os_pre_pass0() { return sizeof(K) == 2; }
-constexpr int OS_TABLE_ROW = 2 * OS_RADIX;          // table columns: [pass 0 digits | pass 1 digits], each over all tiles
-template <class K> static size_t os_table_words(size_t n) { return os_pre_pass0<K>() ? os_blocks<K>(n) * OS_TABLE_ROW : 0; }
+// The tile-key sort (u16 keys, at most two passes) runs EVERY pass without the chained look-back: in front of the pass a histogram
+// kernel counts the pass's digit tile by tile over the pass's input and leaves the counts in a table, one small kernel turns the
+// table's columns into exclusive prefixes over the tiles (and their totals into the pass's global histogram), and the pass reads
+// its offsets from there. Measured on the 16.4 M pairs of the bench view: the look-back costs ~30 us per pass at 2002 tiles
+// (tools/time_sort.py knock-out), the histogram + scan of one digit about half of that.
+// Control block: u16 keys  [global histograms: passes x 256 | table: 256 columns x tiles, reused by the second pass];
+//                u32 keys  [global histograms: passes x 256 | look-back words: passes x tiles x 256 | 64 tickets].
+template <class K> constexpr bool os_table_driven() { return sizeof(K) == 2; }
+template <class K> static size_t os_table_words(size_t n) { return os_table_driven<K>() ? os_blocks<K>(n) * OS_RADIX : 0; }
+template <class K> static size_t os_lookback_words(size_t n, int passes)
+{
+    return os_table_driven<K>() ? 0 : (size_t)passes * os_blocks<K>(n) * OS_RADIX + 64;
+}
 template <class K> static size_t os_ctrl_bytes(size_t n, int passes)
 {
-    return align_up(((size_t)passes * OS_RADIX + (size_t)passes * os_blocks<K>(n) * OS_RADIX + 64 + os_table_words<K>(n)) * sizeof(uint32_t));
+    return align_up(((size_t)passes * OS_RADIX + os_lookback_words<K>(n, passes) + os_table_words<K>(n)) * sizeof(uint32_t));
 }
 
 // all digit histograms in one read of the keys: 1024-thread workgroups (at most 512 of them, so the final flush stays a
-// few hundred atomics per global bin), four independent 16-byte loads in flight per thread
+// few hundred atomics per global bin), four independent 16-byte loads in flight per thread. `block` of `nblocks` workgroups.
 constexpr int OS_HIST_BLOCK = 1024;
 template <class K>
-__global__ void __launch_bounds__(OS_HIST_BLOCK) os_hist_kernel(const K* __restrict__ keys, size_t n, OsPlan plan, uint32_t* __restrict__ hist)
+__device__ __forceinline__ void os_hist_body(const K* __restrict__ keys, size_t n, const OsPlan& plan, uint32_t* __restrict__ hist,
+                                             unsigned block, unsigned nblocks)
 {
     __shared__ uint32_t s_h[OS_MAX_PASSES][OS_RADIX];
     for (int q = threadIdx.x; q < OS_MAX_PASSES * OS_RADIX; q += OS_HIST_BLOCK) (&s_h[0][0])[q] = 0;
@@ -130,14 +147,14 @@ __global__ void __launch_bounds__(OS_HIST_BLOCK) os_hist_kernel(const K* __restr
             else { add(w[e] & 0xffffu); add(w[e] >> 16); }
         }
     };
-    const size_t stride = (size_t)gridDim.x * OS_HIST_BLOCK;
-    size_t i = (size_t)blockIdx.x * OS_HIST_BLOCK + threadIdx.x;
+    const size_t stride = (size_t)nblocks * OS_HIST_BLOCK;
+    size_t i = (size_t)block * OS_HIST_BLOCK + threadIdx.x;
     for (; i + 3 * stride < nvec; i += 4 * stride) {
         const uint4 v0 = k4[i], v1 = k4[i + stride], v2 = k4[i + 2 * stride], v3 = k4[i + 3 * stride];
         add4(v0); add4(v1); add4(v2); add4(v3);
     }
     for (; i < nvec; i += stride) add4(k4[i]);
-    for (size_t j = nvec * VEC + (size_t)blockIdx.x * OS_HIST_BLOCK + threadIdx.x; j < n; j += stride) add((uint32_t)keys[j]);
+    for (size_t j = nvec * VEC + (size_t)block * OS_HIST_BLOCK + threadIdx.x; j < n; j += stride) add((uint32_t)keys[j]);
     __syncthreads();
     for (int q = threadIdx.x; q < plan.passes * OS_RADIX; q += OS_HIST_BLOCK) {
         const uint32_t v = (&s_h[0][0])[q];
@@ -145,22 +162,38 @@ __global__ void __launch_bounds__(OS_HIST_BLOCK) os_hist_kernel(const K* __restr
     }
 }
 
-// tile-by-tile histograms of the u16 sort: workgroup b counts the digits of tile b (the pass kernel's tile b) for the first
-// two passes and stores them as row b of the table -- plain stores, no global atomics (the closing atomics of os_hist_kernel
-// are what makes it slower with more workgroups)
-__global__ void __launch_bounds__(1024) os_tile_hist_kernel(const uint16_t* __restrict__ keys, uint32_t n, OsPlan plan, uint32_t* __restrict__ table)
+template <class K>
+__global__ void __launch_bounds__(OS_HIST_BLOCK) os_hist_kernel(const K* __restrict__ keys, size_t n, OsPlan plan, uint32_t* __restrict__ hist)
+{
+    os_hist_body<K>(keys, n, plan, hist, blockIdx.x, gridDim.x);
+}
+
+// The depth sort's histograms and the id-order scan of the instance totals (scan_blocks.hpp) in ONE launch: both read only what
+// preprocess wrote and neither reads the other's output, but alone each is a launch-latency-bound kernel that holds the whole
+// chip. Workgroup 0 runs the scan (and its mapped-host-memory store of num_rendered, unchanged and as early as before), workgroups
+// 1 .. gridDim.x - 1 the histogram. No hand-off: the two bodies sit side by side, each with its own LDS (4 KB + 128 B).
+static_assert(SCAN_BLOCKS_THREADS == OS_HIST_BLOCK, "one workgroup shape for both bodies");
+__global__ void __launch_bounds__(OS_HIST_BLOCK)
+os_hist_scan_kernel(const uint32_t* __restrict__ keys, size_t n, OsPlan plan, uint32_t* __restrict__ hist, int nb, uint32_t* __restrict__ base,
+                    const uint32_t* __restrict__ sort_err, uint32_t* __restrict__ host_out, uint32_t host_seq)
+{
+    if (blockIdx.x == 0) scan_blocks_body(nb, base, sort_err, host_out, host_seq);
+    else os_hist_body<uint32_t>(keys, n, plan, hist, blockIdx.x - 1, gridDim.x - 1);
+}
+
+// tile-by-tile histogram of ONE digit of the u16 sort: workgroup b counts the digit (bits [shift, shift + bits)) over tile b of
+// `keys` (the tile b of the pass kernel that reads the same keys) and stores the counts as row b of the table -- plain stores, no
+// global atomics (the closing atomics of os_hist_kernel are what makes it slower with more workgroups)
+__global__ void __launch_bounds__(1024) os_tile_hist_kernel(const uint16_t* __restrict__ keys, uint32_t n, int shift, int bits, uint32_t* __restrict__ table)
 {
     constexpr int TILE = OsShape<uint16_t>::TILE;
     static_assert(TILE == 8 * 1024, "one 16-byte load of 8 keys per thread");
-    __shared__ uint32_t s_h[OS_TABLE_ROW];
-    if (threadIdx.x < OS_TABLE_ROW) s_h[threadIdx.x] = 0;
+    __shared__ uint32_t s_h[OS_RADIX];
+    if (threadIdx.x < OS_RADIX) s_h[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * (uint32_t)TILE + threadIdx.x * 8u;
-    const uint32_t m0 = (1u << plan.bits[0]) - 1u, m1 = plan.passes > 1 ? (1u << plan.bits[1]) - 1u : 0u;
-    auto add = [&](uint32_t k) {
-        atomicAdd(&s_h[k & m0], 1u);
-        if (plan.passes > 1) atomicAdd(&s_h[OS_RADIX + ((k >> plan.bits[0]) & m1)], 1u);
-    };
+    const uint32_t mask = (1u << bits) - 1u;
+    auto add = [&](uint32_t k) { atomicAdd(&s_h[(k >> shift) & mask], 1u); };
     if (base + 8 <= n && (reinterpret_cast<uintptr_t>(keys) & 15u) == 0) {
         const uint4 v = *reinterpret_cast<const uint4*>(keys + base);
         const uint32_t w[4] = { v.x, v.y, v.z, v.w };
@@ -170,44 +203,50 @@ __global__ void __launch_bounds__(1024) os_tile_hist_kernel(const uint16_t* __re
         for (uint32_t i = base; i < min(base + 8u, n); i++) add((uint32_t)keys[i]);
     }
     __syncthreads();
-    // column-major table (a column = one (pass, digit) over all tiles, contiguous for the scan); unused digit columns stay unwritten
+    // column-major table (a column = one digit over all tiles, contiguous for the scan); unused digit columns stay unwritten
     const int t = threadIdx.x;
-    if (t < OS_TABLE_ROW && (t >> 8) < plan.passes && (t & (OS_RADIX - 1)) < (1 << plan.bits[(t >> 8) & 1]))
-        table[(size_t)t * gridDim.x + blockIdx.x] = s_h[t];
+    if (t < (1 << bits)) table[(size_t)t * gridDim.x + blockIdx.x] = s_h[t];
 }
 
-// one workgroup per USED table column (pass, digit): the column's total goes to the global histogram of that pass; the pass-0
-// columns are replaced by their exclusive prefixes over the tiles (what the look-back would have produced)
-__global__ void __launch_bounds__(256) os_table_scan_kernel(uint32_t* __restrict__ table, uint32_t blocks, OsPlan plan, uint32_t* __restrict__ hist)
+// one workgroup per USED table column (digit) of the pass: the column is replaced by its exclusive prefixes over the tiles (what
+// the look-back would have produced) and its total goes to `hist`, the global histogram of that pass (256 words, all written:
+// the unused digits get zero, so the sort needs no cleared control words). A thread owns OS_SCAN_V consecutive tiles, so a sweep
+// covers 2048 tiles (16.8 M items) with one memory round trip and two barriers: the kernel is latency, not bytes.
+constexpr int OS_SCAN_V = 8;
+__global__ void __launch_bounds__(256) os_table_scan_kernel(uint32_t* __restrict__ table, uint32_t blocks, uint32_t* __restrict__ hist)
 {
+    static_assert(OS_RADIX == 256, "one thread per histogram word");
     __shared__ uint32_t s_w[4];
-    const int n0 = 1 << plan.bits[0];
-    const int pass = (int)blockIdx.x < n0 ? 0 : 1, digit = (int)blockIdx.x - (pass ? n0 : 0), col = pass * OS_RADIX + digit;
-    uint32_t* column = table + (size_t)col * blocks;
+    const int digit = (int)blockIdx.x;                              // gridDim.x = digits in use
+    uint32_t* column = table + (size_t)digit * blocks;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (digit == 0 && threadIdx.x >= gridDim.x) hist[threadIdx.x] = 0u;
     uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < blocks; b0 += 256) {                 // 256 tiles per sweep, coalesced
-        const uint32_t b = b0 + threadIdx.x;
-        const uint32_t c = b < blocks ? column[b] : 0u;
-        uint32_t incl = c;
+    for (uint32_t b0 = 0; b0 < blocks; b0 += 256 * OS_SCAN_V) {
+        const uint32_t b = b0 + threadIdx.x * OS_SCAN_V;
+        uint32_t c[OS_SCAN_V], mine = 0;
+#pragma unroll
+        for (int q = 0; q < OS_SCAN_V; q++) { c[q] = b + q < blocks ? column[b + q] : 0u; mine += c[q]; }
+        uint32_t incl = mine;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o); if (lane >= o) incl += t; }
         __syncthreads();                                            // previous sweep's s_w has been read
         if (lane == 63) s_w[wave] = incl;
         __syncthreads();
-        uint32_t off = carry;
-        for (int w = 0; w < wave; w++) off += s_w[w];
-        if (pass == 0 && b < blocks) column[b] = off + incl - c;
+        uint32_t run = carry + incl - mine;
+        for (int w = 0; w < wave; w++) run += s_w[w];
+#pragma unroll
+        for (int q = 0; q < OS_SCAN_V; q++) { if (b + q < blocks) column[b + q] = run; run += c[q]; }
         carry += s_w[0] + s_w[1] + s_w[2] + s_w[3];
     }
-    if (threadIdx.x == 0) hist[col] = carry;                        // hist is [pass][256]
+    if (threadIdx.x == 0) hist[digit] = carry;
 }
 
 __device__ __forceinline__ uint32_t os_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void os_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// PRE: the tile's exclusive digit prefixes come from the table os_table_scan_kernel prepared (`status` = the table, no ticket,
-// no look-back); otherwise they are found by the chained look-back over the earlier tiles' status words.
+// PRE: the tile's exclusive digit prefixes come from the table os_table_scan_kernel prepared for this pass (`status` = the table,
+// no ticket, no look-back); otherwise they are found by the chained look-back over the earlier tiles' status words.
 // PAY2 (depth sort): a SECOND 32-bit payload travels with every item -- the Gaussian's tile rectangle packed to four bytes
 // (os_pack_rect: grids up to 255 x 255 tiles). The first pass reads the rectangles coalesced, in id order, from `gather_src`
 // (p2in == null); the passes hand the packed word on through p2in / p2out; the last pass (p2out == null) unpacks it into
@@ -320,7 +359,7 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
         s_start[tid] = start;
         // decoupled look-back over the earlier tiles for digit `tid`
         uint32_t* my = status + (size_t)bid * OS_RADIX + tid;
-        if (PRE) pre = tid < (1 << BITS) ? status[(size_t)tid * gridDim.x + bid] : 0u;   // column-major table, pass-0 columns
+        if (PRE) pre = tid < (1 << BITS) ? status[(size_t)tid * gridDim.x + bid] : 0u;   // column-major table of this pass's digit
         else if (bid == 0) os_store(my, OS_FLAG_PRE | tot);
         else {
             os_store(my, OS_FLAG_AGG | tot);
@@ -396,6 +435,14 @@ static void os_launch_pass(int bits, unsigned blocks, hipStream_t s, const K* ki
 #undef C3DGS_OS_CASE
 }
 
+// 4 x 16 bytes per thread, at most 512 workgroups: measured optimum on both sorts (fewer workgroups: LDS-atomic bound;
+// more: the closing global atomics, one per workgroup and non-empty bin on the same few hundred words, take over)
+template <class K> static unsigned os_hist_blocks(size_t n)
+{
+    const size_t nvec16 = n * sizeof(K) / 16 + 1;
+    return (unsigned)std::min<size_t>((nvec16 + OS_HIST_BLOCK * 4 - 1) / (OS_HIST_BLOCK * 4), 512);
+}
+
 // temp = [control block | ping buffer (keys, values) | pong buffer]; the input arrays are never written
 template <class K>
 static size_t os_temp_bytes(size_t n, int total_bits, bool pay2 = false)
@@ -411,87 +458,85 @@ static size_t os_temp_bytes(size_t n, int total_bits, bool pay2 = false)
 // the control words at the front of `temp` that must be ZERO when the sort starts (digit histograms the histogram kernel adds
 // into, look-back status words, tickets). os_sort clears them itself unless the caller says a kernel it ran just before on the
 // same stream already did (`ctrl_cleared`: the rasterizer folds the two clears of a forward into preprocess / duplicate_with_keys,
-// whose thousands of workgroups do it for free -- a separate fill launch costs ~5 us of an otherwise idle GPU each)
+// whose thousands of workgroups do it for free -- a separate fill launch costs ~5 us of an otherwise idle GPU each).
+// The table-driven sort has none: its histograms and its table are written in full with plain stores before they are read.
 template <class K>
 static size_t os_clear_bytes(size_t n, int total_bits)
 {
-    const OsPlan plan = os_plan(total_bits);
-    if (!os_pre_pass0<K>()) return os_ctrl_bytes<K>(n, plan.passes);
-    return ((size_t)plan.passes * OS_RADIX + (size_t)plan.passes * os_blocks<K>(n) * OS_RADIX + 64) * sizeof(uint32_t);   // the table behind is written in full
+    if (os_table_driven<K>()) return 0;
+    return os_ctrl_bytes<K>(n, os_plan(total_bits).passes);
 }
 
 template <class K>
 static hipError_t os_sort(void* temp, size_t temp_bytes, const K* kin, K* kout, const uint32_t* vin, uint32_t* vout, size_t n,
                           int total_bits, hipStream_t s, const uint2* gather_src = nullptr, uint2* gather_dst = nullptr,
-                          bool ctrl_cleared = false, bool pay2 = false)
+                          bool ctrl_cleared = false, bool pay2 = false, bool hist_done = false)
 {
     if (n == 0) return hipSuccess;
     // second payload (see os_pass_kernel): u32 keys in four 8-bit passes with a rectangle table only, and only if the caller's
     // scratch has room for its two buffers
     if (pay2 && (sizeof(K) != 4 || total_bits != 32 || !gather_src || !gather_dst || vin || os_temp_bytes<K>(n, total_bits, true) > temp_bytes))
         pay2 = false;
-    if (n >= ((size_t)1 << 30) || os_temp_bytes<K>(n, total_bits) > temp_bytes) return hipErrorInvalidValue;
+    if (n >= ((size_t)1 << 30) || total_bits > 8 * (int)sizeof(K) || os_temp_bytes<K>(n, total_bits) > temp_bytes) return hipErrorInvalidValue;
     const OsPlan plan = os_plan(total_bits);
-    // the look-back-free first pass's table holds the global histograms of passes 0 and 1 only (OS_TABLE_ROW): a third pass
-    // would scatter with zero digit offsets, so more than 16 bits on u16 keys is refused instead of sorted wrong
-    if (os_pre_pass0<K>() && plan.passes > 2) return hipErrorInvalidValue;
     const size_t blocks = os_blocks<K>(n);
     char* base = (char*)temp;
     const size_t ctrl = os_ctrl_bytes<K>(n, plan.passes);
-    uint32_t* hist = (uint32_t*)base;
-    uint32_t* status = hist + (size_t)plan.passes * OS_RADIX;
-    uint32_t* ticket = status + (size_t)plan.passes * blocks * OS_RADIX;
-    uint32_t* table = ticket + 64;                                  // [OS_TABLE_ROW columns][blocks], u16 sort only
-    constexpr bool pre0 = os_pre_pass0<K>();
+    uint32_t* hist = (uint32_t*)base;                               // [passes][OS_RADIX]
+    uint32_t* behind_hist = hist + (size_t)plan.passes * OS_RADIX;
     K* tk[2]; uint32_t* tv[2];
     char* q = base + ctrl;
     for (int i = 0; i < 2; i++) { tk[i] = (K*)q; q += align_up(n * sizeof(K)); tv[i] = (uint32_t*)q; q += align_up(n * sizeof(uint32_t)); }
-    uint32_t* t2[2] = { nullptr, nullptr };
-    if (pay2) {
-        q = base + os_temp_bytes<K>(n, total_bits);
-        for (int i = 0; i < 2; i++) { t2[i] = (uint32_t*)q; q += align_up(n * sizeof(uint32_t)); }
-    }
-    // the table is written in full by os_tile_hist_kernel: only the words in front of it need clearing
-    if (!ctrl_cleared) {
-        const hipError_t e = hipMemsetAsync(base, 0, os_clear_bytes<K>(n, total_bits), s);
-        if (e != hipSuccess) return e;
-    }
-    if constexpr (pre0) {
-        os_tile_hist_kernel<<<(unsigned)blocks, 1024, 0, s>>>((const uint16_t*)kin, (uint32_t)n, plan, table);
-        os_table_scan_kernel<<<(unsigned)((1 << plan.bits[0]) + (plan.passes > 1 ? (1 << plan.bits[1]) : 0)), 256, 0, s>>>(table, (uint32_t)blocks, plan, hist);
+    if constexpr (os_table_driven<K>()) {
+        // per pass: count the pass's digit per tile of the pass's input, scan the table's columns, scatter from the table. The one
+        // table is reused: the stream orders a pass behind its scan and the next histogram behind the pass.
+        uint32_t* table = behind_hist;                              // [digit columns][blocks]
+        int shift = 0;
+        for (int p = 0; p < plan.passes; p++) {
+            const bool last = p == plan.passes - 1;
+            const K* ki = p == 0 ? kin : tk[(p - 1) & 1];
+            const uint32_t* vi = p == 0 ? vin : tv[(p - 1) & 1];
+            uint32_t* h = hist + (size_t)p * OS_RADIX;
+            os_tile_hist_kernel<<<(unsigned)blocks, 1024, 0, s>>>((const uint16_t*)ki, (uint32_t)n, shift, plan.bits[p], table);
+            os_table_scan_kernel<<<1u << plan.bits[p], 256, 0, s>>>(table, (uint32_t)blocks, h);
+            os_launch_pass<K, true>(plan.bits[p], (unsigned)blocks, s, ki, last ? kout : tk[p & 1], vi, last ? vout : tv[p & 1], (uint32_t)n,
+                                    shift, h, table, nullptr, last ? gather_src : nullptr, last ? gather_dst : nullptr);
+            shift += plan.bits[p];
+        }
+        return hipGetLastError();
     } else {
-        const size_t nvec16 = n * sizeof(K) / 16 + 1;
-        // 4 x 16 bytes per thread, at most 512 workgroups: measured optimum on both sorts (fewer workgroups: LDS-atomic bound;
-        // more: the closing global atomics, one per workgroup and non-empty bin on the same few hundred words, take over)
-        const unsigned hb = (unsigned)std::min<size_t>((nvec16 + OS_HIST_BLOCK * 4 - 1) / (OS_HIST_BLOCK * 4), 512);
-        os_hist_kernel<K><<<hb, OS_HIST_BLOCK, 0, s>>>(kin, n, plan, hist);
-    }
-    int shift = 0;
-    for (int p = 0; p < plan.passes; p++) {
-        const K* ki = p == 0 ? kin : tk[(p - 1) & 1];
-        const uint32_t* vi = p == 0 ? vin : tv[(p - 1) & 1];
-        K* ko = p == plan.passes - 1 ? kout : tk[p & 1];
-        uint32_t* vo = p == plan.passes - 1 ? vout : tv[p & 1];
-        const bool last = p == plan.passes - 1;
-        // ticket + p is this pass's counter
-        if constexpr (sizeof(K) == 4) {
-            if (pay2) {
+        uint32_t* status = behind_hist;                             // [passes][blocks][OS_RADIX]
+        uint32_t* ticket = status + (size_t)plan.passes * blocks * OS_RADIX;
+        uint32_t* t2[2] = { nullptr, nullptr };
+        if (pay2) {
+            q = base + os_temp_bytes<K>(n, total_bits);
+            for (int i = 0; i < 2; i++) { t2[i] = (uint32_t*)q; q += align_up(n * sizeof(uint32_t)); }
+        }
+        if (!ctrl_cleared) {
+            const hipError_t e = hipMemsetAsync(base, 0, os_clear_bytes<K>(n, total_bits), s);
+            if (e != hipSuccess) return e;
+        }
+        // hist_done: the caller has run the histogram on cleared control words already (onesweep_depth_hist_scan)
+        if (!hist_done) os_hist_kernel<K><<<os_hist_blocks<K>(n), OS_HIST_BLOCK, 0, s>>>(kin, n, plan, hist);
+        int shift = 0;
+        for (int p = 0; p < plan.passes; p++) {
+            const K* ki = p == 0 ? kin : tk[(p - 1) & 1];
+            const uint32_t* vi = p == 0 ? vin : tv[(p - 1) & 1];
+            K* ko = p == plan.passes - 1 ? kout : tk[p & 1];
+            uint32_t* vo = p == plan.passes - 1 ? vout : tv[p & 1];
+            const bool last = p == plan.passes - 1;
+            // ticket + p is this pass's counter
+            if (pay2)
                 os_pass_kernel<K, 8, false, true><<<(unsigned)blocks, OsShape<K>::BLOCK, 0, s>>>(
                     ki, ko, vi, vo, (uint32_t)n, shift, hist + (size_t)p * OS_RADIX, status + (size_t)p * blocks * OS_RADIX, ticket + p,
                     gather_src, gather_dst, p == 0 ? nullptr : t2[(p - 1) & 1], last ? nullptr : t2[p & 1]);
-                shift += plan.bits[p];
-                continue;
-            }
+            else
+                os_launch_pass<K, false>(plan.bits[p], (unsigned)blocks, s, ki, ko, vi, vo, (uint32_t)n, shift, hist + (size_t)p * OS_RADIX,
+                                         status + (size_t)p * blocks * OS_RADIX, ticket + p, last ? gather_src : nullptr, last ? gather_dst : nullptr);
+            shift += plan.bits[p];
         }
-        if (pre0 && p == 0)
-            os_launch_pass<K, true>(plan.bits[p], (unsigned)blocks, s, ki, ko, vi, vo, (uint32_t)n, shift, hist, table, ticket,
-                                    last ? gather_src : nullptr, last ? gather_dst : nullptr);
-        else
-            os_launch_pass<K, false>(plan.bits[p], (unsigned)blocks, s, ki, ko, vi, vo, (uint32_t)n, shift, hist + (size_t)p * OS_RADIX,
-                                     status + (size_t)p * blocks * OS_RADIX, ticket + p, last ? gather_src : nullptr, last ? gather_dst : nullptr);
-        shift += plan.bits[p];
+        return hipGetLastError();
     }
-    return hipGetLastError();
 }
 
 #ifdef C3DGS_DIAG
@@ -547,14 +592,27 @@ hipError_t onesweep_tile_sort32(void* temp, size_t temp_bytes, const uint32_t* k
 {
     return os_sort<uint32_t>(temp, temp_bytes, kin, kout, vin, vout, (size_t)R, end_bit, s, nullptr, nullptr, ctrl_cleared);
 }
+// the depth sort's histogram launch with the id-order scan of `nb` workgroup totals in its workgroup 0 (os_hist_scan_kernel).
+// `temp`: the depth sort's scratch, its first onesweep_depth_clear_bytes(P) bytes cleared by an earlier kernel on the stream; the
+// sort that follows is told `hist_done`.
+hipError_t onesweep_depth_hist_scan(void* temp, size_t temp_bytes, const uint32_t* keys, int P, int nb, uint32_t* base,
+                                    const uint32_t* sort_err, uint32_t* host_out, uint32_t host_seq, hipStream_t s)
+{
+    const size_t n = (size_t)P;
+    if (P <= 0 || n >= ((size_t)1 << 30) || os_temp_bytes<uint32_t>(n, 32) > temp_bytes) return hipErrorInvalidValue;
+    os_hist_scan_kernel<<<1u + os_hist_blocks<uint32_t>(n), OS_HIST_BLOCK, 0, s>>>(keys, n, os_plan(32), (uint32_t*)temp, nb, base,
+                                                                                  sort_err, host_out, host_seq);
+    return hipGetLastError();
+}
 hipError_t onesweep_depth_sort(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout,
-                               int P, const uint2* gather_src, uint2* gather_dst, hipStream_t s, bool ctrl_cleared, bool rects_fit_bytes)
+                               int P, const uint2* gather_src, uint2* gather_dst, hipStream_t s, bool ctrl_cleared, bool rects_fit_bytes,
+                               bool hist_done)
 {
     // rects_fit_bytes: every coordinate of the tile rectangles is below 256 (grid of at most 255 x 255 tiles), so they can
     // travel with the items as a packed 32-bit second payload instead of being gathered behind the last pass
     static const bool no_pay2 = []() { const char* e = std::getenv("C3DGS_DEPTH_SORT_GATHER"); return e && e[0] == '1'; }();
     return os_sort<uint32_t>(temp, temp_bytes, kin, kout, vin, vout, (size_t)P, 32, s, gather_src, gather_dst, ctrl_cleared,
-                             rects_fit_bytes && !no_pay2);
+                             rects_fit_bytes && !no_pay2, hist_done && ctrl_cleared);
 }
 hipError_t onesweep_tile_sort(void* temp, size_t temp_bytes, const uint16_t* kin, uint16_t* kout, const uint32_t* vin, uint32_t* vout,
                               int R, int end_bit, hipStream_t s, bool ctrl_cleared)
