@@ -101,6 +101,9 @@ PROTOTYPES = {
                                                              C.c_void_p, C.c_int32, C.c_void_p, RESIZE_FN, C.c_void_p,
                                                              C.POINTER(RasterGrads), C.c_void_p]),
     "c3dgs_render_depth": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c3dgs_contrib_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "c3dgs_render_contrib": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8),
+    "c3dgs_contrib_accumulate": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 10),
     "c3dgs_weighted_distance": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     "c3dgs_vq_accumulate": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

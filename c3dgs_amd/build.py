@@ -31,6 +31,8 @@ SOURCES = {
     "render.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the depth / alpha / median replay of the forward's blend: render.hip's flags, so that the shared alpha expression compiles alike
     "render_depth.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
+    # the per-Gaussian blend statistics: the same replay, the same flags
+    "render_contrib.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # MFMA accumulators in VGPRs (no v_accvgpr_read per value in the top-2 update of the search kernel)
     "vq.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + os.environ.get("C3DGS_VQ_FLAGS", "").split(),
     "draws.hip": [],

@@ -23,6 +23,7 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(MARK_VISIBLE, "mark_visible") X(PREPROCESS, "preprocess") X(DEPTH_SORT, "depth_sort") X(SCAN, "scan")                    \
     X(DUPLICATE, "duplicate_with_keys") X(SORT, "sort") X(RANGES, "identify_ranges") X(RENDER_FWD, "render_forward")           \
     X(RENDER_DEPTH, "render_depth")                                                                                            \
+    X(RENDER_CONTRIB, "render_contrib") X(RENDER_CONTRIB_BLEND, "render_contrib_blend") X(RENDER_CONTRIB_SUM, "render_contrib_sum") \
     X(ZERO_PARTIALS, "zero_partials") X(RENDER_BWD, "render_backward") X(BWD_PREPROCESS, "backward_preprocess")                \
     X(WDIST, "weighted_distance") X(VQ_ACC, "vq_accumulate") X(VQ_APPLY, "vq_apply") X(LOSS_FWD, "l1_ssim_forward")            \
     X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
@@ -547,6 +548,61 @@ int c3dgs_render_depth(int32_t P, int32_t W, int32_t H, int32_t R, const void* g
     C3DGS_TIMED_STAGE(ST_RENDER_DEPTH, 0, s,
                       launch_render_depth(W, H, img, compact_ptrs(b, R), g.splat, g.depth_keys, out_depth, out_alpha, out_median,
                                           sort_err, s));
+    return C3DGS_OK;
+}
+
+size_t c3dgs_contrib_workspace_bytes(int32_t P, int32_t R) { return contrib_layout(P, R).total_bytes; }
+
+int c3dgs_render_contrib(int32_t P, int32_t W, int32_t H, int32_t R, const void* geom_buffer, const void* binning_buffer,
+                         const void* image_buffer, void* workspace, float* out_weight_sum, float* out_weight_max,
+                         uint32_t* out_hits, void* stream)
+{
+    if (W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, "render_contrib: W and H must be positive");
+    if (P < 0 || R < 0) return fail(C3DGS_E_INVALID, "render_contrib: P and R must be >= 0");
+    if (!out_weight_sum && !out_weight_max && !out_hits) return fail(C3DGS_E_INVALID, "render_contrib: at least one output is required");
+    if (R > 0 && P == 0) return fail(C3DGS_E_INVALID, "render_contrib: R > 0 instances cannot come from P = 0");
+    if (R > 0 && (!geom_buffer || !binning_buffer || !image_buffer || !workspace))
+        return fail(C3DGS_E_INVALID, "render_contrib: the forward's geometry, binning and image buffers and a workspace are required");
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0 || R == 0) {            // nothing was blended anywhere
+        if (P > 0) {
+            if (out_weight_sum) C3DGS_HIP_TRY(hipMemsetAsync(out_weight_sum, 0, (size_t)P * sizeof(float), s));
+            if (out_weight_max) C3DGS_HIP_TRY(hipMemsetAsync(out_weight_max, 0, (size_t)P * sizeof(float), s));
+            if (out_hits) C3DGS_HIP_TRY(hipMemsetAsync(out_hits, 0, (size_t)P * sizeof(uint32_t), s));
+        }
+        return C3DGS_OK;
+    }
+    uint32_t* sort_err = onesweep_error_word();
+    if (!sort_err) return fail(C3DGS_E_HIP, "cannot resolve the sort error word");
+    const GeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
+    const ImgPtrs img = img_ptrs(const_cast<void*>(image_buffer), W, H);
+    const BinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), R, W, H);
+    const ContribPtrs w = contrib_ptrs(workspace, P, R);
+    {
+        StageTimer t_(ST_RENDER_CONTRIB, s);
+        // only the 1-byte "written" flags are cleared, by the fill workgroups of the backward's prep kernel (no tiles: nothing is
+        // ordered, img.tile_order stays as it is)
+        launch_backward_prep(0, H, img, w.touched, w.touched_bytes / 16, nullptr, 0, s);
+        { StageTimer a_(ST_RENDER_CONTRIB_BLEND, s); launch_render_contrib(W, H, img, compact_ptrs(b, R), g, w, sort_err, s); }
+        { StageTimer b_(ST_RENDER_CONTRIB_SUM, s); launch_contrib_sum(P, g, w, out_weight_sum, out_weight_max, out_hits, sort_err, s); }
+    }
+    C3DGS_STAGE_CHECK(ST_RENDER_CONTRIB, 0, s);
+    return C3DGS_OK;
+}
+
+int c3dgs_contrib_accumulate(int32_t P_model, int32_t P_rows, const uint8_t* visible, const int32_t* rank, const float* weight_sum,
+                             const float* weight_max, const uint32_t* hits, float* acc_sum, float* acc_max, int64_t* acc_hits,
+                             uint32_t* acc_views, void* stream)
+{
+    if (P_model < 0 || P_rows < 0) return fail(C3DGS_E_INVALID, "contrib_accumulate: P_model and P_rows must be >= 0");
+    if ((visible == nullptr) != (rank == nullptr)) return fail(C3DGS_E_INVALID, "contrib_accumulate: visible and rank come as a pair");
+    if (!visible && P_rows != P_model) return fail(C3DGS_E_INVALID, "contrib_accumulate: without visible / rank the rows are the model's");
+    if (P_model == 0 || P_rows == 0) return C3DGS_OK;
+    if (!weight_sum || !weight_max || !hits || !acc_sum || !acc_max || !acc_hits || !acc_views)
+        return fail(C3DGS_E_INVALID, "contrib_accumulate: the three rows and the four accumulators are required");
+    launch_contrib_accumulate(P_model, P_rows, visible, rank, weight_sum, weight_max, hits, acc_sum, acc_max, acc_hits, acc_views,
+                              (hipStream_t)stream);
+    C3DGS_STAGE("contrib_accumulate", 0, (hipStream_t)stream);
     return C3DGS_OK;
 }
 

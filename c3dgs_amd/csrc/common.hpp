@@ -171,6 +171,22 @@ inline void backward_layout(int P, int R, c3dgs_backward_layout* L)
     L->total_bytes = o;
 }
 
+// Blend-statistics workspace (render_contrib.hip): one {sum, max, hits} record per backward slot, f32 f32 u32 [R] | their
+// 1-byte "written" flags. Same slot numbering as the backward's partials; only the flags are cleared per call.
+struct ContribSlot { float sum, max; uint32_t hits; };
+struct ContribLayout { size_t slots, touched, touched_bytes, total_bytes; };
+inline ContribLayout contrib_layout(int P, int R)
+{
+    (void)P;
+    size_t o = 0, r = (size_t)(R > 0 ? R : 1);
+    ContribLayout L;
+    L.slots = o;   o = align_up(o + r * sizeof(ContribSlot));
+    L.touched = o; o = align_up(o + r);
+    L.touched_bytes = o - L.touched;
+    L.total_bytes = o;
+    return L;
+}
+
 // ---------------------------------------------------------------- kernel launchers (one per .hip file)
 struct GeomPtrs {
     float4* splat; uint32_t* depth_keys; uint32_t* depth_keys_sorted;
@@ -187,6 +203,7 @@ struct ImgPtrs { float* final_T; uint32_t* n_contrib; uint2* ranges; uint32_t* t
 struct CompactPtrs { uint8_t* cqm; uint32_t* cid; };   // inside BinPtrs::sort_temp, valid once the tile sort has run
 struct BwdPtrs { float* partials; uint8_t* touched; size_t touched_bytes;   // the flags' whole region: what a call clears
                  uint32_t* live_ids; uint32_t* live_slots; uint32_t* live_count; };
+struct ContribPtrs { ContribSlot* slots; uint8_t* touched; size_t touched_bytes; };
 
 inline GeomPtrs geom_ptrs(void* base, int P)
 {
@@ -222,6 +239,13 @@ inline BwdPtrs bwd_ptrs(void* base, int P, int R)
     char* b = (char*)base;
     return { (float*)(b + L.partials), (uint8_t*)(b + L.touched), L.live_ids - L.touched,
              (uint32_t*)(b + L.live_ids), (uint32_t*)(b + L.live_slots), (uint32_t*)(b + L.live_count) };
+}
+
+inline ContribPtrs contrib_ptrs(void* base, int P, int R)
+{
+    const ContribLayout L = contrib_layout(P, R);
+    char* b = (char*)base;
+    return { (ContribSlot*)(b + L.slots), (uint8_t*)(b + L.touched), L.touched_bytes };
 }
 
 // preprocess.hip
@@ -283,6 +307,16 @@ void launch_render_backward(int W, int H, const ImgPtrs& img, const float4* spla
 // render_depth.hip (forward-only replay of the blend: depth / accumulated opacity / median depth; null outputs are skipped)
 void launch_render_depth(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const float4* splat, const uint32_t* depth_keys,
                          float* out_depth, float* out_alpha, float* out_median, const uint32_t* sort_err, hipStream_t s);
+// render_contrib.hip (forward-only replay of the blend: per-Gaussian sum / max of alpha T and blended-pair count; null outputs are
+// skipped): the blend replay into the slots (the caller has cleared w.touched on the stream), the per-Gaussian fold of the slots,
+// and the fold of one view's rows into model-sized accumulators.
+void launch_render_contrib(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const ContribPtrs& w,
+                           const uint32_t* sort_err, hipStream_t s);
+void launch_contrib_sum(int P, const GeomPtrs& g, const ContribPtrs& w, float* out_sum, float* out_max, uint32_t* out_hits,
+                        const uint32_t* sort_err, hipStream_t s);
+void launch_contrib_accumulate(int P_model, int P_rows, const uint8_t* visible, const int32_t* rank, const float* weight_sum,
+                               const float* weight_max, const uint32_t* hits, float* acc_sum, float* acc_max, int64_t* acc_hits,
+                               uint32_t* acc_views, hipStream_t s);
 // backward_preprocess.hip
 void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,
                                 const c3dgs_raster_grads& gr, hipStream_t s);

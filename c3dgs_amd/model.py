@@ -1246,16 +1246,19 @@ class GaussianModel:
 
     # ---- render (gaussian_model.py:766-886)
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, clamp_color=True,
-               cov3d=None, gather_visible=True, return_depth=False):
+               cov3d=None, gather_visible=True, return_depth=False, return_contrib=False):
         """return_depth=True: the dict also carries "depth" (sum of alpha T z, not normalised), "alpha" (accumulated opacity)
-        and "median_depth", each [H, W] (rasterizer._C.render_depth); forward-only, no gradient flows through them."""
+        and "median_depth", each [H, W] (rasterizer._C.render_depth); forward-only, no gradient flows through them.
+        return_contrib=True: the dict also carries "contrib_sum", "contrib_max" (sum / max of alpha T over the (pixel, entry)
+        pairs the forward blended) and "contrib_hits" (their number), indexed like "radii" (rasterizer._C.render_contrib), and
+        "contrib_rank" (see _extra_keys); forward-only as well."""
         if pipe.convert_SHs_python and override_color is None:
             raise NotImplementedError("convert_SHs_python: SH evaluation in Python is outside the mirrored render path")
         dev = self.device
         settings = GaussianRasterizationSettings(
             intrinsic=viewpoint_camera.intrinsic.to(dev), extrinsic_vector=viewpoint_camera.extrinsic_vector.to(dev),
             bg=bg_color.to(dev), scale_modifier=scaling_modifier, sh_degree=self.active_sh_degree, prefiltered=False,
-            debug=pipe.debug, clamp_color=clamp_color, depth=bool(return_depth))
+            debug=pipe.debug, clamp_color=clamp_color, depth=bool(return_depth), contrib=bool(return_contrib))
         indexed = self.color_index_mode == ColorMode.ALL_INDEXED and self.is_gaussian_indexed
         fused = indexed and self.use_factor_scaling and cov3d is None and override_color is None and \
             not pipe.compute_cov3D_python
@@ -1306,12 +1309,63 @@ class GaussianModel:
                                                                        scales_n, sfac, rotations, _rz._empty(), settings,
                                                                        settings.extrinsic_vector)
         return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
-                "visible": visible.bool(), **self._depth_keys(extras)}
+                "visible": visible.bool(), **self._extra_keys(settings, extras, rank)}
 
     @staticmethod
-    def _depth_keys(extras):
-        """the rasterizer's extra outputs under settings.depth -> the keys render(return_depth=True) adds"""
-        return dict(zip(("depth", "alpha", "median_depth"), extras))
+    def _extra_keys(settings, extras, rank):
+        """the rasterizer's extra outputs -> the keys render() adds: the three maps under settings.depth, then under
+        settings.contrib the three per-Gaussian rows and "contrib_rank" (int32 [P]: the row of a visible Gaussian in them, or
+        None when they are indexed by Gaussian)"""
+        names = (("depth", "alpha", "median_depth") if settings.depth else ()) + \
+            (("contrib_sum", "contrib_max", "contrib_hits") if settings.contrib else ())
+        assert len(names) == len(extras)
+        out = dict(zip(names, extras))
+        if settings.contrib:
+            out["contrib_rank"] = rank
+        return out
+
+    # ---- contribution statistics over a set of views, and pruning by them (csrc/render_contrib.hip; not in the reference)
+    def contribution_stats(self, cameras, pipe, bg_color):
+        """-> dict(weight_sum f32 [P], weight_max f32 [P], hits int64 [P], views int32 [P]) over `cameras`: per Gaussian the sum
+        and the maximum of its blend weight alpha T, the number of (pixel, entry) pairs that blended it, and the number of views
+        in which at least one did. One render(return_contrib=True) per camera under no_grad and one c3dgs_contrib_accumulate
+        launch per view (through the view's visible flags and the ranks render() hands out with them); no host read of its own.
+        The renders go through the getters, which on a quantisation-aware model move the observers; the observer / quantiser
+        state is saved in front of the pass and put back behind it, so the statistics leave the model as they found it."""
+        dev = self.device
+        P = self._xyz.shape[0]
+        acc = dict(weight_sum=torch.zeros(P, dtype=torch.float32, device=dev), weight_max=torch.zeros(P, dtype=torch.float32, device=dev),
+                   hits=torch.zeros(P, dtype=torch.int64, device=dev), views=torch.zeros(P, dtype=torch.int32, device=dev))
+        lib = _lib.lib()
+        with torch.no_grad():
+            fq_saved = self._fq_state.clone()
+            for cam in cameras:
+                out = self.render(cam, pipe, bg_color, return_contrib=True)
+                visible, rank = out["visible"], out["contrib_rank"]       # bool [P] (one byte each), int32 [P]
+                ws, wm, h = out["contrib_sum"], out["contrib_max"], out["contrib_hits"]
+                with torch.cuda.device(dev):
+                    _lib.check(lib.c3dgs_contrib_accumulate(P, int(ws.shape[0]), _ptr(visible), _ptr(rank), _ptr(ws), _ptr(wm), _ptr(h),
+                                                            acc["weight_sum"].data_ptr(), acc["weight_max"].data_ptr(),
+                                                            acc["hits"].data_ptr(), acc["views"].data_ptr(), _stream(dev)))
+            self._fq_state.copy_(fq_saved)
+        return acc
+
+    def prune_by_contribution(self, stats, min_views=1, min_weight_max=0.0):
+        """Removes the Gaussians that `stats` (contribution_stats) saw blended in fewer than `min_views` views or whose largest
+        blend weight is below `min_weight_max`, with prune_points_indexed on an indexed model and prune_points otherwise, as
+        finetune prunes. -> how many went (one host read)."""
+        P = self._xyz.shape[0]
+        if stats["views"].shape[0] != P:
+            raise RuntimeError(f"prune_by_contribution: statistics of {stats['views'].shape[0]} rows for {P} Gaussians")
+        with torch.no_grad():
+            mask = (stats["views"] < int(min_views)) | (stats["weight_max"] < float(min_weight_max))
+            n = int(mask.sum())
+            if n:
+                if self.is_color_indexed or self.is_gaussian_indexed:
+                    self.prune_points_indexed(mask)
+                else:
+                    self.prune_points(mask)
+        return n
 
     def _render_composed(self, settings, screenspace_points, indexed, pipe, scaling_modifier, override_color, cov3d,
                          gather_visible=True):
@@ -1341,8 +1395,11 @@ class GaussianModel:
         # `t[visible]` of the reference (gaussian_model.py:851-862) for every input, from ONE nonzero: a boolean-mask index
         # runs nonzero (with its host sync) per tensor, and its backward is a sort-based index_put(accumulate) -- 2 ms
         # per tensor for 6M rows -- although the rows are unique.
+        rank = None
         if gather_visible:
             rows = visible.nonzero(as_tuple=False).squeeze(1)
+            if settings.contrib:                                # model row -> row of the gathered tensors: the exclusive scan of the flags
+                rank = torch.cumsum(visible, 0, dtype=torch.int32) - visible.to(torch.int32)
             pick = lambda t: None if t is None else (_MaskGather.apply(t, rows) if t.requires_grad else t.index_select(0, rows))  # noqa: E731
         else:
             pick = lambda t: t  # noqa: E731
@@ -1358,7 +1415,7 @@ class GaussianModel:
                                                rotations=pick(rotations), cov3D_precomp=pick(cov3D_precomp),
                                                extrinsic_vector=settings.extrinsic_vector)
         return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
-                "visible": visible, **self._depth_keys(extras)}
+                "visible": visible, **self._extra_keys(settings, extras, rank)}
 
 
 class _MaskGather(torch.autograd.Function):

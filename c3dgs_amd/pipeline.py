@@ -109,7 +109,8 @@ def _train_cameras(scene):
     return list(scene.getTrainCameras()) if hasattr(scene, "getTrainCameras") else list(scene)
 
 
-def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_interval=0, prune_min_opacity=0.005):
+def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_interval=0, prune_min_opacity=0.005,
+             prune_min_views=0):
     """finetune.py:10-66. One camera per iteration, drawn without replacement from a stack that is refilled when empty
     (`pop(randint(0, len - 1))` on Python's `random`, like the reference); render -> (1 - l) L1 + l (1 - SSIM) ->
     backward -> learning-rate update -> Adam step (not after the last iteration).
@@ -122,7 +123,11 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
     `prune_interval` = N > 0 (not in the reference; 0 changes nothing): after the optimizer step of every N-th iteration the
     Gaussians with sigmoid(_opacity) < `prune_min_opacity` are removed, on the raw parameter (get_opacity would move the opacity
     observer), with prune_points_indexed on an indexed model (unreferenced codebook rows go with them) and prune_points
-    otherwise; `log(iteration, ema)` is called once more after each prune."""
+    otherwise; `log(iteration, ema)` is called once more after each prune.
+    `prune_min_views` = V > 0 (0 changes nothing): when `prune_interval` fires, the Gaussians that
+    GaussianModel.contribution_stats over the training cameras sees blended in fewer than V views go as well
+    (prune_by_contribution): what no training view blends costs sort, list and codebook space in every view. The statistics
+    pass renders every training camera once but leaves the QAT observers as it found them (contribution_stats restores them)."""
     gaussians = scene.gaussians if hasattr(scene, "gaussians") else dataset.gaussians
     first_iter = int(getattr(scene, "loaded_iter", 0) or 0)
     max_iter = first_iter + comp.finetune_iterations
@@ -165,6 +170,9 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
                         gaussians.prune_points_indexed(mask)
                     else:
                         gaussians.prune_points(mask)
+                if prune_min_views > 0:
+                    stats = gaussians.contribution_stats(_train_cameras(scene), pipe, background)
+                    gaussians.prune_by_contribution(stats, min_views=prune_min_views)
                 if log is not None:
                     log(iteration, ema_loss_for_log)
     return ema_loss_for_log

@@ -5,10 +5,12 @@ on top of the MI355X C-ABI library.  Same names, argument order and error behavi
     GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,
     rasterize_gaussians, rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,
     getProjectionMatrix, quat_to_mat, mat_to_quat, and `_C` with the five pybind entry points
-    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`.
+    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth` and `render_contrib`.
 
 Beyond the reference: `GaussianRasterizationSettings(depth=True)` / `_C.render_depth` add depth, accumulated-opacity and
-median-depth maps of a forward (forward-only, csrc/render_depth.hip).
+median-depth maps of a forward (forward-only, csrc/render_depth.hip); `GaussianRasterizationSettings(contrib=True)` /
+`_C.render_contrib` add every Gaussian's blend statistics: sum and max of alpha T and the number of (pixel, entry) pairs the
+forward blended (forward-only, csrc/render_contrib.hip).
 
 PyTorch is plumbing only here (device memory, streams, autograd bookkeeping); every numeric stage
 runs in libc3dgs_hip.so.  There is no CPU path: tensors must live on the GPU.
@@ -460,8 +462,50 @@ def _c_render_depth(P, W, H, R, geomBuffer, binningBuffer, imgBuffer):
     return out[0], out[1], out[2]
 
 
+class _GrowOnly:
+    """One uint8 device buffer per device that only grows (a _Scratch whose buffer outlives the call): the workspace of
+    _C.render_contrib, R x 13 bytes per call. Its content means nothing between calls (the library clears the flag bytes it reads),
+    so calls on one stream may share it; like every scratch here it belongs to the stream the calls are queued on."""
+
+    def __init__(self):
+        self.bufs = {}
+
+    def get(self, device, nbytes):
+        t = self.bufs.get(device)
+        if t is None or t.numel() < nbytes:
+            t = self.bufs[device] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+        return t
+
+
+_contrib_workspace = _GrowOnly()
+
+
+def _c_render_contrib(P, W, H, R, geomBuffer, binningBuffer, imgBuffer):
+    """Blend statistics of the forward that filled the three buffers (c3dgs_render_contrib): -> (weight_sum f32 [P],
+    weight_max f32 [P], hits int32 [P] holding the library's uint32 counts), on the current stream. Over the (pixel, entry)
+    pairs the forward blended, with w = alpha T: sum of w, max of w, number of pairs. Rows of culled or never-blended Gaussians
+    are exact zeros. Forward-only. Valid before or after the matching backward."""
+    if not imgBuffer.is_cuda:
+        raise RuntimeError("c3dgs_amd: render_contrib needs the forward's GPU buffers (there is no CPU path)")
+    dev = imgBuffer.device
+    P, W, H, R = int(P), int(W), int(H), int(R)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        out = torch.empty((2, max(P, 0)), dtype=torch.float32, device=dev)
+        hits = torch.empty((max(P, 0),), dtype=torch.int32, device=dev)
+        if P == 0:
+            return out[0], out[1], hits
+        ws = _contrib_workspace.get(dev, L.c3dgs_contrib_workspace_bytes(P, R))
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        rc = L.c3dgs_render_contrib(P, W, H, R, ptr(geomBuffer), ptr(binningBuffer), ptr(imgBuffer), ws.data_ptr(), ptr(out[0]),
+                                    ptr(out[1]), ptr(hits), _stream(dev))
+    _lib.check(rc)
+    return out[0], out[1], hits
+
+
 _C = SimpleNamespace(
     render_depth=_c_render_depth,
+    render_contrib=_c_render_contrib,
     rasterize_gaussians=_c_rasterize_gaussians,
     rasterize_gaussians_backward=_c_rasterize_gaussians_backward,
     rasterize_gaussians_indexed=_c_rasterize_gaussians_indexed,
@@ -510,6 +554,9 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     extras = ()
     if getattr(rs, "depth", False):
         extras = _C.render_depth(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer)
+    # with `raster_settings.contrib`: (weight_sum, weight_max, hits) per Gaussian, behind whatever `depth` added
+    if getattr(rs, "contrib", False):
+        extras = tuple(extras) + _C.render_contrib(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer)
     ctx.raster_settings = rs
     ctx.indexed = indexed
     ctx.num_rendered = num_rendered
@@ -688,7 +735,7 @@ def rasterize_gaussians_indexed_camera(means3D, means2D, sh, sh_indices, g_indic
 
 
 # ----------------------------------------------------------------------------- public modules
-class GaussianRasterizationSettings(NamedTuple):
+class _SettingsFields(NamedTuple):
     """reference __init__.py:868-878, plus `depth` (last, optional)."""
     intrinsic: torch.Tensor
     extrinsic_vector: torch.Tensor
@@ -701,6 +748,32 @@ class GaussianRasterizationSettings(NamedTuple):
     # True: the rasterizers return (color, radii, depth, alpha, median) -- see _C.render_depth. Forward-only: the three extra
     # maps are non-differentiable, no gradient flows through them. False: (color, radii), the same launches as ever.
     depth: bool = False
+
+
+class GaussianRasterizationSettings(_SettingsFields):
+    """The settings tuple above plus `contrib`, the last constructor argument (optional, by keyword or as the tenth positional).
+    True: the rasterizers append (weight_sum, weight_max, hits), each [P] -- see _C.render_contrib -- behind the outputs they
+    return otherwise: (color, radii, weight_sum, weight_max, hits), or with `depth` (color, radii, depth, alpha, median,
+    weight_sum, weight_max, hits). Forward-only and non-differentiable. False: no launch.
+    `contrib` is an attribute beside the tuple's elements, not one of them: the tuple keeps the length, order and `_fields` that
+    callers who unpack or index it rely on (`depth` stays its last element). `_replace` carries it (and accepts it); what
+    works on the tuple's elements alone does not see it: `==`, `hash`, `_asdict`, `_make` and pickling compare, list or rebuild the
+    nine elements only, and two settings that differ in `contrib` alone compare equal."""
+    contrib = False
+
+    def __new__(cls, *args, contrib=False, **kwargs):
+        n = len(cls._fields)
+        if len(args) == n + 1:
+            args, contrib = args[:n], args[n]
+        self = super().__new__(cls, *args, **kwargs)
+        self.contrib = bool(contrib)
+        return self
+
+    def _replace(self, **kwargs):
+        contrib = kwargs.pop("contrib", self.contrib)
+        new = super()._replace(**kwargs)
+        new.contrib = bool(contrib)
+        return new
 
 
 def _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp):

@@ -155,6 +155,36 @@ int c3dgs_render_depth(int32_t P, int32_t W, int32_t H, int32_t R,
                        float* out_depth /*[H,W] | NULL*/, float* out_alpha /*[H,W] | NULL*/,
                        float* out_median /*[H,W] | NULL*/, void* stream);
 
+/* ---- per-Gaussian blend statistics of a finished forward (csrc/render_contrib.hip; no reference counterpart) ----
+ * geom/binning/image buffers are the ones a forward of the same P, W, H filled; R is its num_rendered. For every Gaussian g,
+ * over the (pixel, entry) pairs the forward BLENDED (a hit that passed the T test; the entry that only stopped a pixel is not
+ * one), with w = alpha T in fp32 as c3dgs_render_depth forms it:
+ *   out_weight_sum[g] = sum w      out_weight_max[g] = max w      out_hits[g] = number of such pairs
+ * Rows of culled or never-blended Gaussians are exact zeros; every row of every non-NULL output is written. The call replays
+ * the forward's own decisions like c3dgs_render_depth and reads what that call reads, plus block_base / inst_offset of the
+ * geometry buffer (the backward's slot numbering). No float atomics: per-(Gaussian, tile) records go with plain stores to
+ * `workspace` (c3dgs_contrib_workspace_bytes(P, R) bytes, 256-byte aligned; only its flag bytes are cleared, inside the call)
+ * and a second kernel folds each Gaussian's run in slot order, so the result is bitwise reproducible. It writes nothing but
+ * the workspace and its outputs: valid before or after the matching backward, with the same result, and the backward's own
+ * workspace is not touched.
+ * Sort time-out word set: every out_weight_sum / out_weight_max row is NaN, every out_hits row 0. A NULL output is skipped; at
+ * least one must be non-NULL. P == 0 or R == 0: zeros, no blend launch. Argument errors return C3DGS_E_INVALID before any
+ * device work. Stage name: "render_contrib" (the clear and both kernels; "render_contrib_blend" / "render_contrib_sum" are the
+ * two kernels alone). */
+size_t c3dgs_contrib_workspace_bytes(int32_t P, int32_t R);
+int c3dgs_render_contrib(int32_t P, int32_t W, int32_t H, int32_t R,
+                         const void* geom_buffer, const void* binning_buffer, const void* image_buffer, void* workspace,
+                         float* out_weight_sum /*[P] | NULL*/, float* out_weight_max /*[P] | NULL*/,
+                         uint32_t* out_hits /*[P] | NULL*/, void* stream);
+/* One view's rows into model-sized accumulators, one launch: for model row i, r = rank[i] if visible[i] (the pair
+ * c3dgs_qat_visible produces; rows not visible are left alone), or r = i when both are NULL (then P_rows == P_model):
+ *   acc_sum[i] += weight_sum[r]; acc_max[i] = max(acc_max[i], weight_max[r]); acc_hits[i] += hits[r]; acc_views[i] += hits[r] > 0
+ * NaN rows of a timed-out view propagate into acc_sum and acc_max. */
+int c3dgs_contrib_accumulate(int32_t P_model, int32_t P_rows, const uint8_t* visible /*[P_model] | NULL*/,
+                             const int32_t* rank /*[P_model] | NULL*/, const float* weight_sum, const float* weight_max,
+                             const uint32_t* hits, float* acc_sum, float* acc_max, int64_t* acc_hits, uint32_t* acc_views,
+                             void* stream);
+
 /* ---- weighted_distance._C.weightedDistance (weighted_distance.cu:46-93) ----
  * coefs [N,K], codebook [C,K] row-major fp32 -> min squared distance [N] and argmin [N] (int64).
  * Exact reference semantics: fp32 k-ordered FMA chain, strict '<' (lowest index wins ties).
