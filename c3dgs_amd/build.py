@@ -33,6 +33,8 @@ SOURCES = {
     "render_depth.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the per-Gaussian blend statistics: the same replay, the same flags
     "render_contrib.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
+    # the per-Gaussian error scores: the same replay and the same reduction network, the same flags
+    "render_error.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # MFMA accumulators in VGPRs (no v_accvgpr_read per value in the top-2 update of the search kernel)
     "vq.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + os.environ.get("C3DGS_VQ_FLAGS", "").split(),
     "draws.hip": [],

@@ -24,6 +24,8 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(DUPLICATE, "duplicate_with_keys") X(SORT, "sort") X(RANGES, "identify_ranges") X(RENDER_FWD, "render_forward")           \
     X(RENDER_DEPTH, "render_depth")                                                                                            \
     X(RENDER_CONTRIB, "render_contrib") X(RENDER_CONTRIB_BLEND, "render_contrib_blend") X(RENDER_CONTRIB_SUM, "render_contrib_sum") \
+    X(RENDER_ERROR, "render_error") X(RENDER_ERROR_BLEND, "render_error_blend") X(RENDER_ERROR_SUM, "render_error_sum")           \
+    X(ERROR_MAP_L1, "error_map_l1")                                                                                            \
     X(ZERO_PARTIALS, "zero_partials") X(RENDER_BWD, "render_backward") X(BWD_PREPROCESS, "backward_preprocess")                \
     X(WDIST, "weighted_distance") X(VQ_ACC, "vq_accumulate") X(VQ_APPLY, "vq_apply") X(LOSS_FWD, "l1_ssim_forward")            \
     X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
@@ -603,6 +605,65 @@ int c3dgs_contrib_accumulate(int32_t P_model, int32_t P_rows, const uint8_t* vis
     launch_contrib_accumulate(P_model, P_rows, visible, rank, weight_sum, weight_max, hits, acc_sum, acc_max, acc_hits, acc_views,
                               (hipStream_t)stream);
     C3DGS_STAGE("contrib_accumulate", 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
+size_t c3dgs_error_workspace_bytes(int32_t P, int32_t R) { return error_layout(P, R).total_bytes; }
+
+int c3dgs_render_error(int32_t P, int32_t W, int32_t H, int32_t R, const void* geom_buffer, const void* binning_buffer,
+                       const void* image_buffer, void* workspace, const float* pixel_map, float* out_err_sum, void* stream)
+{
+    if (W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, "render_error: W and H must be positive");
+    if (P < 0 || R < 0) return fail(C3DGS_E_INVALID, "render_error: P and R must be >= 0");
+    if (!out_err_sum) return fail(C3DGS_E_INVALID, "render_error: the output is required");
+    if (!pixel_map) return fail(C3DGS_E_INVALID, "render_error: the pixel map is required");
+    if (R > 0 && P == 0) return fail(C3DGS_E_INVALID, "render_error: R > 0 instances cannot come from P = 0");
+    if (R > 0 && (!geom_buffer || !binning_buffer || !image_buffer || !workspace))
+        return fail(C3DGS_E_INVALID, "render_error: the forward's geometry, binning and image buffers and a workspace are required");
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0 || R == 0) {            // nothing was blended anywhere
+        if (P > 0) C3DGS_HIP_TRY(hipMemsetAsync(out_err_sum, 0, (size_t)P * sizeof(float), s));
+        return C3DGS_OK;
+    }
+    uint32_t* sort_err = onesweep_error_word();
+    if (!sort_err) return fail(C3DGS_E_HIP, "cannot resolve the sort error word");
+    const GeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
+    const ImgPtrs img = img_ptrs(const_cast<void*>(image_buffer), W, H);
+    const BinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), R, W, H);
+    const ErrorPtrs w = error_ptrs(workspace, P, R);
+    {
+        StageTimer t_(ST_RENDER_ERROR, s);
+        // only the 1-byte "written" flags are cleared, as c3dgs_render_contrib clears its own
+        launch_backward_prep(0, H, img, w.touched, w.touched_bytes / 16, nullptr, 0, s);
+        { StageTimer a_(ST_RENDER_ERROR_BLEND, s); launch_render_error(W, H, img, compact_ptrs(b, R), g, w, pixel_map, sort_err, s); }
+        { StageTimer b_(ST_RENDER_ERROR_SUM, s); launch_error_sum(P, g, w, out_err_sum, sort_err, s); }
+    }
+    C3DGS_STAGE_CHECK(ST_RENDER_ERROR, 0, s);
+    return C3DGS_OK;
+}
+
+int c3dgs_error_map_l1(int32_t C, int32_t H, int32_t W, const float* img, const float* gt, float* out, void* stream)
+{
+    if (C <= 0 || H <= 0 || W <= 0) return fail(C3DGS_E_INVALID, "error_map_l1: C, H and W must be positive");
+    if (!img || !gt || !out) return fail(C3DGS_E_INVALID, "error_map_l1: both images and the output are required");
+    {
+        StageTimer t_(ST_ERROR_MAP_L1, (hipStream_t)stream);
+        launch_error_map_l1(C, H, W, img, gt, out, (hipStream_t)stream);
+    }
+    C3DGS_STAGE_CHECK(ST_ERROR_MAP_L1, 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
+int c3dgs_error_accumulate(int32_t P_model, int32_t P_rows, const uint8_t* visible, const int32_t* rank, const float* err_sum,
+                           float* acc_max, float* acc_sum, void* stream)
+{
+    if (P_model < 0 || P_rows < 0) return fail(C3DGS_E_INVALID, "error_accumulate: P_model and P_rows must be >= 0");
+    if ((visible == nullptr) != (rank == nullptr)) return fail(C3DGS_E_INVALID, "error_accumulate: visible and rank come as a pair");
+    if (!visible && P_rows != P_model) return fail(C3DGS_E_INVALID, "error_accumulate: without visible / rank the rows are the model's");
+    if (P_model == 0 || P_rows == 0) return C3DGS_OK;
+    if (!err_sum || !acc_max || !acc_sum) return fail(C3DGS_E_INVALID, "error_accumulate: the row and the two accumulators are required");
+    launch_error_accumulate(P_model, P_rows, visible, rank, err_sum, acc_max, acc_sum, (hipStream_t)stream);
+    C3DGS_STAGE("error_accumulate", 0, (hipStream_t)stream);
     return C3DGS_OK;
 }
 

@@ -187,6 +187,21 @@ inline ContribLayout contrib_layout(int P, int R)
     return L;
 }
 
+// Error-score workspace (render_error.hip): one float per backward slot, f32 [R] | their 1-byte "written" flags. Same slot
+// numbering as the backward's partials; only the flags are cleared per call.
+struct ErrorLayout { size_t slots, touched, touched_bytes, total_bytes; };
+inline ErrorLayout error_layout(int P, int R)
+{
+    (void)P;
+    size_t o = 0, r = (size_t)(R > 0 ? R : 1);
+    ErrorLayout L;
+    L.slots = o;   o = align_up(o + r * sizeof(float));
+    L.touched = o; o = align_up(o + r);
+    L.touched_bytes = o - L.touched;
+    L.total_bytes = o;
+    return L;
+}
+
 // ---------------------------------------------------------------- kernel launchers (one per .hip file)
 struct GeomPtrs {
     float4* splat; uint32_t* depth_keys; uint32_t* depth_keys_sorted;
@@ -204,6 +219,7 @@ struct CompactPtrs { uint8_t* cqm; uint32_t* cid; };   // inside BinPtrs::sort_t
 struct BwdPtrs { float* partials; uint8_t* touched; size_t touched_bytes;   // the flags' whole region: what a call clears
                  uint32_t* live_ids; uint32_t* live_slots; uint32_t* live_count; };
 struct ContribPtrs { ContribSlot* slots; uint8_t* touched; size_t touched_bytes; };
+struct ErrorPtrs { float* slots; uint8_t* touched; size_t touched_bytes; };
 
 inline GeomPtrs geom_ptrs(void* base, int P)
 {
@@ -246,6 +262,13 @@ inline ContribPtrs contrib_ptrs(void* base, int P, int R)
     const ContribLayout L = contrib_layout(P, R);
     char* b = (char*)base;
     return { (ContribSlot*)(b + L.slots), (uint8_t*)(b + L.touched), L.touched_bytes };
+}
+
+inline ErrorPtrs error_ptrs(void* base, int P, int R)
+{
+    const ErrorLayout L = error_layout(P, R);
+    char* b = (char*)base;
+    return { (float*)(b + L.slots), (uint8_t*)(b + L.touched), L.touched_bytes };
 }
 
 // preprocess.hip
@@ -317,6 +340,15 @@ void launch_contrib_sum(int P, const GeomPtrs& g, const ContribPtrs& w, float* o
 void launch_contrib_accumulate(int P_model, int P_rows, const uint8_t* visible, const int32_t* rank, const float* weight_sum,
                                const float* weight_max, const uint32_t* hits, float* acc_sum, float* acc_max, int64_t* acc_hits,
                                uint32_t* acc_views, hipStream_t s);
+// render_error.hip (forward-only replay of the blend: per-Gaussian sum of alpha T x a per-pixel map): the blend replay into the
+// slots (the caller has cleared w.touched on the stream), the per-Gaussian fold of the slots, the fold of one view's row into
+// model-sized accumulators, and the mean-absolute-difference map of two planar images.
+void launch_render_error(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const ErrorPtrs& w,
+                         const float* pixel_map, const uint32_t* sort_err, hipStream_t s);
+void launch_error_sum(int P, const GeomPtrs& g, const ErrorPtrs& w, float* out_sum, const uint32_t* sort_err, hipStream_t s);
+void launch_error_accumulate(int P_model, int P_rows, const uint8_t* visible, const int32_t* rank, const float* err_sum,
+                             float* acc_max, float* acc_sum, hipStream_t s);
+void launch_error_map_l1(int C, int H, int W, const float* img, const float* gt, float* out, hipStream_t s);
 // backward_preprocess.hip
 void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,
                                 const c3dgs_raster_grads& gr, hipStream_t s);

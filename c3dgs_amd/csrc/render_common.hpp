@@ -1,6 +1,7 @@
 // render_common.hpp -- what the blend kernels of render.hip (forward, backward) and render_depth.hip (depth / alpha / median
 // replay) must share to take the same decisions bit for bit: the staged batch size, the pre-scaled conic, the alpha
-// expression, the quadrant cull and the workgroup -> tile banding. One owner; device code only.
+// expression, the quadrant cull and the workgroup -> tile banding; and the transposing butterfly that render_contrib.hip and
+// render_error.hip reduce with, so that both sum in the same order. One owner; device code only.
 #pragma once
 #include "common.hpp"
 
@@ -85,6 +86,49 @@ __device__ __forceinline__ int tile_of_block(int b, int T)
 {
     const int chunk = (T + 7) >> 3;
     return (b & 7) * chunk + (b >> 3);
+}
+
+// ---- the transposing butterfly of the per-Gaussian passes (render_contrib.hip, render_error.hip): one network, so that both
+// reduce in the same order
+template <int CTRL>
+__device__ __forceinline__ float dpp_get(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+
+struct OpAdd { __device__ __forceinline__ float operator()(float a, float b) const { return a + b; } };
+struct OpMax { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
+
+// One level of the transposing butterfly: a lane pair (lane, its DPP partner) exchanges halves. Each lane keeps half of the N
+// values it held and combines its partner's copy of that half into them.
+template <int N, int CTRL, class Op>
+__device__ __forceinline__ void transpose_step(float* v, bool hi, Op op)
+{
+#pragma unroll
+    for (int k = 0; k < N / 2; k++) {
+        const float keep = hi ? v[k + N / 2] : v[k];
+        const float send = hi ? v[k] : v[k + N / 2];
+        v[k] = op(keep, dpp_get<CTRL>(send));
+    }
+}
+
+// v[0..7] = this pixel's value for the row's 8 candidates -> the reduction over the wave's 64 pixels of candidate
+// beta(lane) = 4 * bit2 + 2 * bit0 + bit1 (render_backward's lane -> Gaussian map), in every lane.
+//   8 -> 4  row_half_mirror (i <-> 7 - i), 4 -> 2  quad_perm [1,0,3,2], 2 -> 1  quad_perm [2,3,0,1]: 8 lanes per value
+//   then three plain levels over the 8 pixel rows: row_ror:8, v_permlane16_swap, v_permlane32_swap
+// Both operands of every combination are the same in the two lanes of a pair and op is commutative: all lanes that hold a
+// candidate hold the same bits, and the order of the float sum is the network's, not the timing's.
+template <class Op>
+__device__ __forceinline__ float reduce_row_of_8(float* v, int lane, Op op)
+{
+    transpose_step<8, 0x141>(v, (lane & 4) != 0, op);
+    transpose_step<4, 0xB1>(v, (lane & 1) != 0, op);
+    transpose_step<2, 0x4E>(v, (lane & 2) != 0, op);
+    float r = op(v[0], dpp_get<0x128>(v[0]));
+    auto s0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(r), __float_as_uint(r), false, false);
+    r = op(__uint_as_float(s0[0]), __uint_as_float(s0[1]));
+    auto s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(r), __float_as_uint(r), false, false);
+    return op(__uint_as_float(s1[0]), __uint_as_float(s1[1]));
 }
 
 } // namespace c3dgs

@@ -903,18 +903,27 @@ class GaussianModel:
                             self.optimizer.state[param] = st
             setattr(self, attr, param)
 
-    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, draws=None, N=2):
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, draws=None, N=2, scores=None):
         """:1336-1349 fused: the reference's clone stage, split stage and final prune decided per row in one classification
         pass, the scene rebuilt in one pass. Every decision is taken on the values the staged sequence would have seen and the
         three observers (scaling, scaling_factor, opacity) are left as it leaves them (DESIGN.md "Density control").
         `draws`: [N*S,3] unit normals for the S split parents (default torch.randn). Returns the plan (src, kind, draw_row,
-        (kept, clones, S, parents with surviving children))."""
+        (kept, clones, S, parents with surviving children)).
+        `scores`: f32 [P], e.g. error_max of add_error_stats / error_stats. It takes the place of xyz_gradient_accum / denom in
+        the classification (handed over as the accumulator with a denominator of ones: the kernel is the same), `max_grad` is
+        then the score threshold; every other decision and the rebuild are unchanged, and the error accumulators are zeroed
+        behind the rebuild."""
         self._dense_only("densify_and_prune")
         lib = _lib.lib()
         dev = self.device
         with torch.no_grad():
             P = self._xyz.shape[0]
             accum, denom, _ = self._density_stats()
+            if scores is not None:
+                if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.numel() != P:
+                    raise RuntimeError(f"densify_and_prune: scores must be a float32 tensor of {P} elements")
+                accum = _lib.gpu_tensor(scores.detach().reshape(P), "scores")
+                denom = torch.ones(P, dtype=torch.float32, device=dev)
             raw_s = self._scaling.detach()
             raw_f = self._scaling_factor.detach() if self._scaling_factor is not None else None
             dense_extent, big_extent = self.percent_dense * extent, 0.1 * extent
@@ -946,7 +955,11 @@ class GaussianModel:
                 sp_self, sp_child = s3[:P], s3[P:]
             if P > 0:
                 classify(min_opacity)
-            return self._rebuild(code, N, std=s2, draws=draws)
+            plan = self._rebuild(code, N, std=s2, draws=draws)
+            if scores is not None:
+                self.error_max = self.error_sum_acc = None        # zeros at the new length on the next add_error_stats
+                self._error_accumulators()
+            return plan
 
     def _append_clones(self, rows, new_xyz=None):
         """Every original, then a copy of each row of `rows` (int32, in the order given; moments zero), through the one apply
@@ -1246,19 +1259,23 @@ class GaussianModel:
 
     # ---- render (gaussian_model.py:766-886)
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, clamp_color=True,
-               cov3d=None, gather_visible=True, return_depth=False, return_contrib=False):
+               cov3d=None, gather_visible=True, return_depth=False, return_contrib=False, error_target=None):
         """return_depth=True: the dict also carries "depth" (sum of alpha T z, not normalised), "alpha" (accumulated opacity)
         and "median_depth", each [H, W] (rasterizer._C.render_depth); forward-only, no gradient flows through them.
         return_contrib=True: the dict also carries "contrib_sum", "contrib_max" (sum / max of alpha T over the (pixel, entry)
         pairs the forward blended) and "contrib_hits" (their number), indexed like "radii" (rasterizer._C.render_contrib), and
-        "contrib_rank" (see _extra_keys); forward-only as well."""
+        "contrib_rank" (see _extra_keys); forward-only as well.
+        error_target=[3, H, W] fp32 device tensor (the view's ground truth): the dict also carries "error_sum", per Gaussian the
+        sum of alpha T x mean |render - target| over the pairs the forward blended (rasterizer._C.render_error), indexed like
+        "radii", and "error_rank" (the same convention as "contrib_rank"); forward-only as well."""
         if pipe.convert_SHs_python and override_color is None:
             raise NotImplementedError("convert_SHs_python: SH evaluation in Python is outside the mirrored render path")
         dev = self.device
         settings = GaussianRasterizationSettings(
             intrinsic=viewpoint_camera.intrinsic.to(dev), extrinsic_vector=viewpoint_camera.extrinsic_vector.to(dev),
             bg=bg_color.to(dev), scale_modifier=scaling_modifier, sh_degree=self.active_sh_degree, prefiltered=False,
-            debug=pipe.debug, clamp_color=clamp_color, depth=bool(return_depth), contrib=bool(return_contrib))
+            debug=pipe.debug, clamp_color=clamp_color, depth=bool(return_depth), contrib=bool(return_contrib),
+            error_target=error_target)
         indexed = self.color_index_mode == ColorMode.ALL_INDEXED and self.is_gaussian_indexed
         fused = indexed and self.use_factor_scaling and cov3d is None and override_color is None and \
             not pipe.compute_cov3D_python
@@ -1315,14 +1332,70 @@ class GaussianModel:
     def _extra_keys(settings, extras, rank):
         """the rasterizer's extra outputs -> the keys render() adds: the three maps under settings.depth, then under
         settings.contrib the three per-Gaussian rows and "contrib_rank" (int32 [P]: the row of a visible Gaussian in them, or
-        None when they are indexed by Gaussian)"""
+        None when they are indexed by Gaussian), then under settings.error_target "error_sum" and "error_rank" (the same rank)"""
+        scored = settings.error_target is not None
         names = (("depth", "alpha", "median_depth") if settings.depth else ()) + \
-            (("contrib_sum", "contrib_max", "contrib_hits") if settings.contrib else ())
+            (("contrib_sum", "contrib_max", "contrib_hits") if settings.contrib else ()) + (("error_sum",) if scored else ())
         assert len(names) == len(extras)
         out = dict(zip(names, extras))
         if settings.contrib:
             out["contrib_rank"] = rank
+        if scored:
+            out["error_rank"] = rank
         return out
+
+    # ---- error scores over a set of views, the signal of densify_and_prune(scores=) (csrc/render_error.hip; not in the reference)
+    def _error_accumulators(self):
+        """error_max / error_sum_acc of the current length: zeros when absent or of another length, like _density_stats"""
+        n = self._xyz.shape[0]
+        for name in ("error_max", "error_sum_acc"):
+            t = getattr(self, name, None)
+            if t is None or tuple(t.shape) != (n,) or t.device != self._xyz.device:
+                setattr(self, name, torch.zeros((n,), dtype=torch.float32, device=self.device))
+        return self.error_max, self.error_sum_acc
+
+    def add_error_stats(self, error_sum, visible=None, rank=None):
+        """One view's "error_sum" of render(error_target=) into the model-sized accumulators: error_max[i] = max(error_max[i], e),
+        error_sum_acc[i] += e with e = error_sum[rank[i]] for the rows with visible[i] (render()'s "visible" and "error_rank"),
+        or e = error_sum[i] when both are None. One c3dgs_error_accumulate launch that neither allocates nor synchronises (the
+        accumulators are created as zeros on the first call at a length)."""
+        acc_max, acc_sum = self._error_accumulators()
+        P = self._xyz.shape[0]
+        if (visible is None) != (rank is None):
+            raise RuntimeError("add_error_stats: visible and rank come as a pair")
+        if error_sum.dtype != torch.float32 or error_sum.dim() != 1 or not error_sum.is_contiguous():
+            raise RuntimeError("add_error_stats: error_sum must be the rasterizer's contiguous float32 row")
+        if visible is not None:
+            if visible.shape[0] != P or rank.shape[0] != P or rank.dtype != torch.int32 or visible.dtype not in (torch.bool, torch.uint8):
+                raise RuntimeError("add_error_stats: visible bool [P] and rank int32 [P] of the model's length are needed")
+        elif error_sum.shape[0] != P:
+            raise RuntimeError(f"add_error_stats: {error_sum.shape[0]} rows for {P} Gaussians and no visible / rank")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().c3dgs_error_accumulate(P, int(error_sum.shape[0]), _ptr(visible), _ptr(rank), error_sum.data_ptr(),
+                                                         acc_max.data_ptr(), acc_sum.data_ptr(), _stream(self.device)))
+
+    def error_stats(self, cameras, pipe, bg_color):
+        """-> dict(error_max f32 [P], error_sum f32 [P]) over `cameras`: per Gaussian the maximum and the sum over the views of
+        its error score against `cam.original_image`. One render(error_target=) per camera under no_grad and one
+        c3dgs_error_accumulate launch per view; no host read of its own. The model's own accumulators (add_error_stats) are not
+        touched. As in contribution_stats the observer / quantiser state is saved in front of the pass and put back behind it."""
+        dev = self.device
+        P = self._xyz.shape[0]
+        acc = dict(error_max=torch.zeros(P, dtype=torch.float32, device=dev), error_sum=torch.zeros(P, dtype=torch.float32, device=dev))
+        lib = _lib.lib()
+        with torch.no_grad():
+            fq_saved = self._fq_state.clone()
+            for cam in cameras:
+                target = cam.original_image.to(dev)
+                out = self.render(cam, pipe, bg_color, error_target=target)
+                visible, rank, es = out["visible"], out["error_rank"], out["error_sum"]
+                if rank is None:
+                    visible = None
+                with torch.cuda.device(dev):
+                    _lib.check(lib.c3dgs_error_accumulate(P, int(es.shape[0]), _ptr(visible), _ptr(rank), _ptr(es),
+                                                          acc["error_max"].data_ptr(), acc["error_sum"].data_ptr(), _stream(dev)))
+            self._fq_state.copy_(fq_saved)
+        return acc
 
     # ---- contribution statistics over a set of views, and pruning by them (csrc/render_contrib.hip; not in the reference)
     def contribution_stats(self, cameras, pipe, bg_color):
@@ -1398,7 +1471,7 @@ class GaussianModel:
         rank = None
         if gather_visible:
             rows = visible.nonzero(as_tuple=False).squeeze(1)
-            if settings.contrib:                                # model row -> row of the gathered tensors: the exclusive scan of the flags
+            if settings.contrib or settings.error_target is not None:   # model row -> row of the gathered tensors: the exclusive scan of the flags
                 rank = torch.cumsum(visible, 0, dtype=torch.int32) - visible.to(torch.int32)
             pick = lambda t: None if t is None else (_MaskGather.apply(t, rows) if t.requires_grad else t.index_select(0, rows))  # noqa: E731
         else:

@@ -178,7 +178,8 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
     return ema_loss_for_log
 
 
-def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, degree_up_iter=1000):
+def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, degree_up_iter=1000, *, densify_by="grad",
+          error_threshold=None):
     """train.py:15-173 without its disabled compression-statistics branch: optimise a non-indexed model (usually
     GaussianModel.load_ply of a point cloud) with adaptive density control.
 
@@ -194,7 +195,19 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     `scene`: as for finetune(), plus `cameras_extent` (or pass `extent`). The model's `spatial_lr_scale` is the caller's to set
     (the reference's scene loader sets it to the camera extent). `log(epoch, info)` is called after every epoch with
     {"iteration", "ema_loss", "N", "densified": None | (rows before, (kept, clones, S, parents with children)), "reset_opacity"}.
-    Returns the number of iterations run."""
+    Returns the number of iterations run.
+
+    `densify_by` = "grad" is the loop above. "error" (not in the reference) densifies by image error instead of the view-space
+    gradient: every view renders with error_target=gt_image, GaussianModel.add_error_stats keeps each Gaussian's largest score
+    E = sum over its blended pixels of alpha T x mean |render - gt| over the epoch's views in place of the gradient
+    accumulation, and the epoch's densification is densify_and_prune(error_threshold, ..., scores=error_max).
+    add_densification_stats still runs with `radii`, so max_radii2D and the screen-size prune work as before. `error_threshold`
+    is required in that mode and has no default: its scale grows with the resolution, and nobody has tuned it."""
+    if densify_by not in ("grad", "error"):
+        raise ValueError(f"train: densify_by must be 'grad' or 'error', not {densify_by!r}")
+    by_error = densify_by == "error"
+    if by_error and error_threshold is None:
+        raise ValueError("train: densify_by='error' needs an error_threshold (there is no default)")
     gaussians = scene.gaussians if hasattr(scene, "gaussians") else dataset.gaussians
     cameras = _train_cameras(scene)
     if extent is None:
@@ -223,9 +236,15 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             cov3d = (cov3d_scaled / coeff).requires_grad_(True)
             # every row goes to the rasterizer (it culls them itself): radii and the screen-space gradient are then indexed
             # by Gaussian, which is what the reference scatters them back to (train.py:103-105)
-            render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False)
+            if by_error:
+                gt_image = viewpoint_cam.original_image.to(dev)
+                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False,
+                                              error_target=gt_image)
+            else:
+                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False)
             image, viewspace_point_tensor, radii = render_pkg["render"], render_pkg["viewspace_points"], render_pkg["radii"]
-            gt_image = viewpoint_cam.original_image.to(image.device)
+            if not by_error:
+                gt_image = viewpoint_cam.original_image.to(image.device)
             loss = _loss.l1_ssim_loss(image, gt_image, opt.lambda_dssim)
             loss.backward()
             pending.append(loss.detach())
@@ -234,6 +253,8 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             if epoch < densify_until_epoch:
                 with torch.no_grad():
                     gaussians.add_densification_stats(viewspace_point_tensor, render_pkg["visibility_filter"], radii)
+                    if by_error:
+                        gaussians.add_error_stats(render_pkg["error_sum"])
             iteration += 1
         for v in torch.stack(pending).tolist():                   # one host read per epoch
             ema_loss_for_log = 0.4 * v + 0.6 * ema_loss_for_log
@@ -243,7 +264,11 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
                 if epoch > densify_from_epoch and epoch % densification_interval == 0:
                     size_threshold = 20 if epoch > opacity_reset_interval else None
                     rows = gaussians._xyz.shape[0]
-                    plan = gaussians.densify_and_prune(opt.densify_grad_threshold, 0.005, extent, size_threshold)
+                    if by_error:
+                        plan = gaussians.densify_and_prune(float(error_threshold), 0.005, extent, size_threshold,
+                                                           scores=gaussians._error_accumulators()[0])
+                    else:
+                        plan = gaussians.densify_and_prune(opt.densify_grad_threshold, 0.005, extent, size_threshold)
                     info["densified"] = (rows, plan[3])
                 if epoch > 0 and epoch % opacity_reset_interval == 0:
                     gaussians.reset_opacity()

@@ -5,12 +5,14 @@ on top of the MI355X C-ABI library.  Same names, argument order and error behavi
     GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,
     rasterize_gaussians, rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,
     getProjectionMatrix, quat_to_mat, mat_to_quat, and `_C` with the five pybind entry points
-    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth` and `render_contrib`.
+    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`, `render_contrib`, `render_error` and `error_map_l1`.
 
 Beyond the reference: `GaussianRasterizationSettings(depth=True)` / `_C.render_depth` add depth, accumulated-opacity and
 median-depth maps of a forward (forward-only, csrc/render_depth.hip); `GaussianRasterizationSettings(contrib=True)` /
 `_C.render_contrib` add every Gaussian's blend statistics: sum and max of alpha T and the number of (pixel, entry) pairs the
-forward blended (forward-only, csrc/render_contrib.hip).
+forward blended (forward-only, csrc/render_contrib.hip); `GaussianRasterizationSettings(error_target=gt)` / `_C.render_error` /
+`_C.error_map_l1` add every Gaussian's error score, the sum of alpha T x a per-pixel error map (forward-only,
+csrc/render_error.hip).
 
 PyTorch is plumbing only here (device memory, streams, autograd bookkeeping); every numeric stage
 runs in libc3dgs_hip.so.  There is no CPU path: tensors must live on the GPU.
@@ -503,9 +505,65 @@ def _c_render_contrib(P, W, H, R, geomBuffer, binningBuffer, imgBuffer):
     return out[0], out[1], hits
 
 
+_error_workspace = _GrowOnly()
+
+
+def _c_render_error(P, W, H, R, geomBuffer, binningBuffer, imgBuffer, pixel_map):
+    """Error scores of the forward that filled the three buffers (c3dgs_render_error): -> err_sum f32 [P] on the current stream:
+    per Gaussian, over the (pixel, entry) pairs the forward blended, the sum of fl(alpha T x pixel_map[pixel]). `pixel_map` is
+    any finite fp32 [H, W] device tensor. Rows of culled or never-blended Gaussians are exact zeros; a map of ones gives
+    _C.render_contrib's weight_sum bit for bit. Forward-only. Valid before or after the matching backward. Its workspace
+    (R x 5 bytes, grow-only) is its own."""
+    if not imgBuffer.is_cuda:
+        raise RuntimeError("c3dgs_amd: render_error needs the forward's GPU buffers (there is no CPU path)")
+    dev = imgBuffer.device
+    P, W, H, R = int(P), int(W), int(H), int(R)
+    _check_map(pixel_map, (H, W), dev, "render_error: pixel_map")
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        out = torch.empty((max(P, 0),), dtype=torch.float32, device=dev)
+        if P == 0:
+            return out
+        ws = _error_workspace.get(dev, L.c3dgs_error_workspace_bytes(P, R))
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        rc = L.c3dgs_render_error(P, W, H, R, ptr(geomBuffer), ptr(binningBuffer), ptr(imgBuffer), ws.data_ptr(),
+                                  pixel_map.data_ptr(), out.data_ptr(), _stream(dev))
+    _lib.check(rc)
+    return out
+
+
+def _check_map(t, shape, dev, what):
+    """the usual RuntimeError for a map or image of the wrong kind"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev:
+        raise RuntimeError(f"c3dgs_amd: {what} must be a tensor on {dev}")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"c3dgs_amd: {what} must be float32, not {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"c3dgs_amd: {what} must have shape {tuple(shape)}, not {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"c3dgs_amd: {what} must be contiguous")
+
+
+def _c_error_map_l1(img, gt):
+    """planar fp32 [C, H, W] image and target on one device -> [H, W]: the mean over the channels of |img - gt|, channels added
+    in ascending order, then one division by C (c3dgs_error_map_l1), on the current stream."""
+    if not isinstance(img, torch.Tensor) or img.dim() != 3 or not img.is_cuda:
+        raise RuntimeError("c3dgs_amd: error_map_l1: img must be a [C, H, W] tensor on the GPU (there is no CPU path)")
+    _check_map(img, img.shape, img.device, "error_map_l1: img")
+    _check_map(gt, img.shape, img.device, "error_map_l1: gt")
+    C, H, W = (int(v) for v in img.shape)
+    with torch.cuda.device(img.device):
+        out = torch.empty((H, W), dtype=torch.float32, device=img.device)
+        rc = _lib.lib().c3dgs_error_map_l1(C, H, W, img.data_ptr(), gt.data_ptr(), out.data_ptr(), _stream(img.device))
+    _lib.check(rc)
+    return out
+
+
 _C = SimpleNamespace(
     render_depth=_c_render_depth,
     render_contrib=_c_render_contrib,
+    render_error=_c_render_error,
+    error_map_l1=_c_error_map_l1,
     rasterize_gaussians=_c_rasterize_gaussians,
     rasterize_gaussians_backward=_c_rasterize_gaussians_backward,
     rasterize_gaussians_indexed=_c_rasterize_gaussians_indexed,
@@ -557,6 +615,12 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     # with `raster_settings.contrib`: (weight_sum, weight_max, hits) per Gaussian, behind whatever `depth` added
     if getattr(rs, "contrib", False):
         extras = tuple(extras) + _C.render_contrib(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer)
+    # with `raster_settings.error_target`: err_sum per Gaussian under the map mean |color - target|, behind the others
+    target = getattr(rs, "error_target", None)
+    if target is not None:
+        _check_map(target, color.shape, color.device, "error_target")
+        emap = _C.error_map_l1(color.detach(), target)
+        extras = tuple(extras) + (_C.render_error(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer, emap),)
     ctx.raster_settings = rs
     ctx.indexed = indexed
     ctx.num_rendered = num_rendered
@@ -758,21 +822,29 @@ class GaussianRasterizationSettings(_SettingsFields):
     `contrib` is an attribute beside the tuple's elements, not one of them: the tuple keeps the length, order and `_fields` that
     callers who unpack or index it rely on (`depth` stays its last element). `_replace` carries it (and accepts it); what
     works on the tuple's elements alone does not see it: `==`, `hash`, `_asdict`, `_make` and pickling compare, list or rebuild the
-    nine elements only, and two settings that differ in `contrib` alone compare equal."""
+    nine elements only, and two settings that differ in `contrib` alone compare equal.
+    `error_target` (keyword only, default None) is a second such attribute: a [3, H, W] fp32 tensor on the device, the view's
+    ground truth. With it the rasterizers queue _C.error_map_l1(color, error_target) and _C.render_error behind the forward and
+    append (err_sum,), [P], behind whatever `depth` and `contrib` added; forward-only and non-differentiable, the backward is
+    unchanged. A wrong shape, dtype or device raises RuntimeError. None: no launch."""
     contrib = False
+    error_target = None
 
-    def __new__(cls, *args, contrib=False, **kwargs):
+    def __new__(cls, *args, contrib=False, error_target=None, **kwargs):
         n = len(cls._fields)
         if len(args) == n + 1:
             args, contrib = args[:n], args[n]
         self = super().__new__(cls, *args, **kwargs)
         self.contrib = bool(contrib)
+        self.error_target = error_target
         return self
 
     def _replace(self, **kwargs):
         contrib = kwargs.pop("contrib", self.contrib)
+        error_target = kwargs.pop("error_target", self.error_target)
         new = super()._replace(**kwargs)
         new.contrib = bool(contrib)
+        new.error_target = error_target
         return new
 
 

@@ -185,6 +185,39 @@ int c3dgs_contrib_accumulate(int32_t P_model, int32_t P_rows, const uint8_t* vis
                              const uint32_t* hits, float* acc_sum, float* acc_max, int64_t* acc_hits, uint32_t* acc_views,
                              void* stream);
 
+/* ---- per-Gaussian error scores of a finished forward (csrc/render_error.hip; no reference counterpart) ----
+ * geom/binning/image buffers are the ones a forward of the same P, W, H filled; R is its num_rendered; pixel_map is any finite
+ * fp32 [H,W] map e. For every Gaussian g, over the (pixel, entry) pairs the forward BLENDED, with w = alpha T in fp32 as
+ * c3dgs_render_contrib forms it:
+ *   out_err_sum[g] = sum fl(w * e[pixel])
+ * (two roundings per pair; the product is not fused into the sum). Rows of culled or never-blended Gaussians are exact zeros;
+ * every row is written. The call reads what c3dgs_render_contrib reads, plus the map, once per pixel. It replays the forward's
+ * own decisions, reduces with c3dgs_render_contrib's network, merges its waves and folds each Gaussian's run in that call's
+ * order: a map of ones gives out_weight_sum's bits, and the result is bitwise reproducible (no float atomics). Per-(Gaussian,
+ * tile) sums go with plain stores to `workspace` (c3dgs_error_workspace_bytes(P, R) bytes: R floats + R flag bytes, each region
+ * 256-byte aligned; the base 256-byte aligned; only the flag bytes are cleared, inside the call). It writes nothing but the
+ * workspace and its output: valid before or after the matching backward, with the same result; the backward's workspace and
+ * c3dgs_render_contrib's are not touched.
+ * Sort time-out word set: every row is NaN. P == 0 or R == 0: zeros, no blend launch. Argument errors (a NULL map, output,
+ * buffer or workspace, negative sizes) return C3DGS_E_INVALID before any device work. Stage name: "render_error" (the clear and
+ * both kernels; "render_error_blend" / "render_error_sum" are the two kernels alone). */
+size_t c3dgs_error_workspace_bytes(int32_t P, int32_t R);
+int c3dgs_render_error(int32_t P, int32_t W, int32_t H, int32_t R,
+                       const void* geom_buffer, const void* binning_buffer, const void* image_buffer, void* workspace,
+                       const float* pixel_map /*[H,W]*/, float* out_err_sum /*[P]*/, void* stream);
+/* The usual map, one launch: out[y][x] = (|img[0][y][x] - gt[0][y][x]| + ... + |img[C-1][y][x] - gt[C-1][y][x]|) / (float)C
+ * in fp32, channels added in ascending order, a correctly rounded division. img and gt are planar [C,H,W], contiguous; out is
+ * [H,W]. Reads the two images, writes out and nothing else. C, H, W <= 0 or a NULL pointer: C3DGS_E_INVALID before any device
+ * work. Stage name: "error_map_l1". */
+int c3dgs_error_map_l1(int32_t C, int32_t H, int32_t W, const float* img, const float* gt, float* out /*[H,W]*/, void* stream);
+/* One view's row into model-sized accumulators, one launch: for model row i, r = rank[i] if visible[i] (the pair
+ * c3dgs_qat_visible produces; rows not visible are left alone), or r = i when both are NULL (then P_rows == P_model):
+ *   acc_max[i] = max(acc_max[i], err_sum[r]); acc_sum[i] += err_sum[r]
+ * A NaN row of a timed-out view propagates into acc_max and acc_sum. */
+int c3dgs_error_accumulate(int32_t P_model, int32_t P_rows, const uint8_t* visible /*[P_model] | NULL*/,
+                           const int32_t* rank /*[P_model] | NULL*/, const float* err_sum, float* acc_max, float* acc_sum,
+                           void* stream);
+
 /* ---- weighted_distance._C.weightedDistance (weighted_distance.cu:46-93) ----
  * coefs [N,K], codebook [C,K] row-major fp32 -> min squared distance [N] and argmin [N] (int64).
  * Exact reference semantics: fp32 k-ordered FMA chain, strict '<' (lowest index wins ties).
