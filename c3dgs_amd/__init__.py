@@ -25,7 +25,8 @@ import types
 from . import encode, knn, loss, metrics, model, optim, ply, rasterizer, rasterizer_matrix, sensitivity, vq  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,  # noqa: F401
                          getProjectionMatrix, mat_to_quat, quat_to_mat, rasterize_gaussians,
-                         rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera)
+                         rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,
+                         rasterize_gaussians_camera_exact, rasterize_gaussians_indexed_camera_exact)
 from .vq import (CompressionSettings, VectorQuantize, compress_color, compress_covariance, compress_gaussians,  # noqa: F401
                  join_features, vq_features, weightedDistance)
 

@@ -37,6 +37,8 @@ SOURCES = {
     "render_error.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # MFMA accumulators in VGPRs (no v_accvgpr_read per value in the top-2 update of the search kernel)
     "vq.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + os.environ.get("C3DGS_VQ_FLAGS", "").split(),
+    # the exact pose gradient rebuilds Sigma and the SH direction term with preprocess's / backward_preprocess's expressions (csrc/gsmath.hpp)
+    "pose_grad.hip": ["-ffp-contract=off"],
     "draws.hip": [],
     "loss.hip": [],
     "metrics.hip": [],

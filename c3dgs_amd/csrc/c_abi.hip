@@ -26,6 +26,7 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(RENDER_CONTRIB, "render_contrib") X(RENDER_CONTRIB_BLEND, "render_contrib_blend") X(RENDER_CONTRIB_SUM, "render_contrib_sum") \
     X(RENDER_ERROR, "render_error") X(RENDER_ERROR_BLEND, "render_error_blend") X(RENDER_ERROR_SUM, "render_error_sum")           \
     X(ERROR_MAP_L1, "error_map_l1")                                                                                            \
+    X(POSE_GRAD, "pose_grad") X(POSE_GRAD_SUMS, "pose_grad_sums") X(POSE_GRAD_FOLD, "pose_grad_fold")                          \
     X(ZERO_PARTIALS, "zero_partials") X(RENDER_BWD, "render_backward") X(BWD_PREPROCESS, "backward_preprocess")                \
     X(WDIST, "weighted_distance") X(VQ_ACC, "vq_accumulate") X(VQ_APPLY, "vq_apply") X(LOSS_FWD, "l1_ssim_forward")            \
     X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
@@ -639,6 +640,49 @@ int c3dgs_render_error(int32_t P, int32_t W, int32_t H, int32_t R, const void* g
         { StageTimer b_(ST_RENDER_ERROR_SUM, s); launch_error_sum(P, g, w, out_err_sum, sort_err, s); }
     }
     C3DGS_STAGE_CHECK(ST_RENDER_ERROR, 0, s);
+    return C3DGS_OK;
+}
+
+size_t c3dgs_pose_grad_workspace_bytes(int32_t P) { return pose_grad_workspace_bytes(P); }
+
+int c3dgs_pose_grad(int32_t P, int32_t D, int32_t M, float scale_modifier, const float* means3D, const float* dL_dmeans3D,
+                    const float* dL_dcov3D, const float* dL_dcolors, const float* sh, const int64_t* sh_indices,
+                    const float* cov3D_precomp, const float* scales, const float* rotations, const float* scale_factors,
+                    const int64_t* g_indices, const void* geom_buffer, const int32_t* radii, const float* pose, void* workspace,
+                    float* out, void* stream)
+{
+    if (P < 0) return fail(C3DGS_E_INVALID, "pose_grad: P must be >= 0");
+    if (D < 0 || D > 3 || M < 0) return fail(C3DGS_E_INVALID, "pose_grad: the SH degree must be 0..3 and M >= 0");
+    if (!pose || !out) return fail(C3DGS_E_INVALID, "pose_grad: the pose and the output are required");
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0) {                      // nothing to sum
+        C3DGS_HIP_TRY(hipMemsetAsync(out, 0, 7 * sizeof(float), s));
+        return C3DGS_OK;
+    }
+    if (!means3D || !dL_dmeans3D || !dL_dcov3D || !radii)
+        return fail(C3DGS_E_INVALID, "pose_grad: means3D, dL_dmeans3D, dL_dcov3D and radii are required");
+    if (!geom_buffer || !workspace) return fail(C3DGS_E_INVALID, "pose_grad: the forward's geometry buffer and a workspace are required");
+    if ((scales == nullptr) != (rotations == nullptr)) return fail(C3DGS_E_INVALID, "pose_grad: scales and rotations come as a pair");
+    if ((cov3D_precomp != nullptr) == (scales != nullptr))
+        return fail(C3DGS_E_INVALID, "pose_grad: exactly one of cov3D_precomp and the scale / rotation pair is required");
+    if ((g_indices == nullptr) != (scale_factors == nullptr))
+        return fail(C3DGS_E_INVALID, "pose_grad: g_indices and scale_factors come as a pair");
+    if (g_indices && !scales) return fail(C3DGS_E_INVALID, "pose_grad: g_indices need the scale / rotation codebooks");
+    if (sh_indices && !sh) return fail(C3DGS_E_INVALID, "pose_grad: sh_indices need sh");
+    if (sh && !dL_dcolors) return fail(C3DGS_E_INVALID, "pose_grad: with sh, dL_dcolors is required");
+    if (sh && M < (D + 1) * (D + 1)) return fail(C3DGS_E_INVALID, "pose_grad: M must hold the (D + 1)^2 coefficients of degree D");
+    const GeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
+    PoseGradIn in;
+    in.P = P; in.D = D; in.M = M; in.scale_modifier = scale_modifier;
+    in.means3D = means3D; in.dL_dmeans3D = dL_dmeans3D; in.dL_dcov3D = dL_dcov3D; in.dL_dcolors = dL_dcolors;
+    in.sh = sh; in.sh_indices = sh_indices; in.cov3D_precomp = cov3D_precomp; in.scales = scales; in.rotations = rotations;
+    in.scale_factors = scale_factors; in.g_indices = g_indices; in.clamped = g.clamped; in.radii = radii; in.pose = pose;
+    {
+        StageTimer t_(ST_POSE_GRAD, s);
+        { StageTimer a_(ST_POSE_GRAD_SUMS, s); launch_pose_sums(in, (float*)workspace, s); }
+        { StageTimer b_(ST_POSE_GRAD_FOLD, s); launch_pose_fold(P, (const float*)workspace, pose, out, s); }
+    }
+    C3DGS_STAGE_CHECK(ST_POSE_GRAD, 0, s);
     return C3DGS_OK;
 }
 

@@ -349,6 +349,18 @@ void launch_error_sum(int P, const GeomPtrs& g, const ErrorPtrs& w, float* out_s
 void launch_error_accumulate(int P_model, int P_rows, const uint8_t* visible, const int32_t* rank, const float* err_sum,
                              float* acc_max, float* acc_sum, hipStream_t s);
 void launch_error_map_l1(int C, int H, int W, const float* img, const float* gt, float* out, hipStream_t s);
+// pose_grad.hip (exact gradient with respect to the camera's 7-element pose, behind a finished backward): the 24 per-workgroup
+// sums into `rows` (pose_grad_workspace_bytes(P) bytes), then their fold and the pose-dependent epilogue into out[7]. P > 0.
+struct PoseGradIn {
+    int P, D, M; float scale_modifier;
+    const float* means3D; const float* dL_dmeans3D; const float* dL_dcov3D; const float* dL_dcolors;
+    const float* sh; const int64_t* sh_indices;
+    const float* cov3D_precomp; const float* scales; const float* rotations; const float* scale_factors; const int64_t* g_indices;
+    const uint8_t* clamped; const int32_t* radii; const float* pose;
+};
+size_t pose_grad_workspace_bytes(int P);
+void launch_pose_sums(const PoseGradIn& in, float* rows, hipStream_t s);
+void launch_pose_fold(int P, const float* rows, const float* pose, float* out, hipStream_t s);
 // backward_preprocess.hip
 void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,
                                 const c3dgs_raster_grads& gr, hipStream_t s);

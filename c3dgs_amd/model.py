@@ -1259,8 +1259,12 @@ class GaussianModel:
 
     # ---- render (gaussian_model.py:766-886)
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, clamp_color=True,
-               cov3d=None, gather_visible=True, return_depth=False, return_contrib=False, error_target=None):
-        """return_depth=True: the dict also carries "depth" (sum of alpha T z, not normalised), "alpha" (accumulated opacity)
+               cov3d=None, gather_visible=True, return_depth=False, return_contrib=False, error_target=None,
+               pose_grad="reference"):
+        """pose_grad: what a camera pose that requires grad receives. "reference" (the default): the reference's formula on the
+        indexed rasterizer (rasterizer.camera_pose_jacobian_sum), nothing on the other. "exact": the gradient of the render itself
+        on both (rasterizer._C.pose_grad, one pass behind the backward). A pose that does not require grad costs nothing either way.
+        return_depth=True: the dict also carries "depth" (sum of alpha T z, not normalised), "alpha" (accumulated opacity)
         and "median_depth", each [H, W] (rasterizer._C.render_depth); forward-only, no gradient flows through them.
         return_contrib=True: the dict also carries "contrib_sum", "contrib_max" (sum / max of alpha T over the (pixel, entry)
         pairs the forward blended) and "contrib_hits" (their number), indexed like "radii" (rasterizer._C.render_contrib), and
@@ -1270,6 +1274,8 @@ class GaussianModel:
         "radii", and "error_rank" (the same convention as "contrib_rank"); forward-only as well."""
         if pipe.convert_SHs_python and override_color is None:
             raise NotImplementedError("convert_SHs_python: SH evaluation in Python is outside the mirrored render path")
+        if pose_grad not in ("reference", "exact"):
+            raise ValueError(f'pose_grad must be "reference" or "exact", not {pose_grad!r}')
         dev = self.device
         settings = GaussianRasterizationSettings(
             intrinsic=viewpoint_camera.intrinsic.to(dev), extrinsic_vector=viewpoint_camera.extrinsic_vector.to(dev),
@@ -1281,9 +1287,9 @@ class GaussianModel:
             not pipe.compute_cov3D_python
         screenspace_points = torch.zeros(self._xyz.shape, dtype=torch.float32, device=dev, requires_grad=True)
         if fused:
-            return self._render_indexed_fused(settings, screenspace_points)
+            return self._render_indexed_fused(settings, screenspace_points, pose_grad)
         return self._render_composed(settings, screenspace_points, indexed, pipe, scaling_modifier, override_color, cov3d,
-                                     gather_visible)
+                                     gather_visible, pose_grad)
 
     def _visible(self, settings):
         """visible flags, their exclusive scan and a deferred host read of the count."""
@@ -1314,7 +1320,7 @@ class GaussianModel:
             return int(self._count_host[0])
         return visible, rank, read
 
-    def _render_indexed_fused(self, settings, screenspace_points):
+    def _render_indexed_fused(self, settings, screenspace_points, pose_grad="reference"):
         visible, rank, read = self._visible(settings)
         (means3D, means2D, opac, sfac, scales_n, rotations, shs, sh_idx, g_idx) = _QatGetters.apply(
             self, (visible, rank, read), self._feature_indices, self._gaussian_indices, self._xyz, screenspace_points,
@@ -1322,9 +1328,9 @@ class GaussianModel:
         # what GaussianRasterizerIndexed(settings, optimize_camera=True)(...) calls, without building an nn.Module per view
         # (the host has ~0.2 ms of Python between the visible count's arrival and the rasterizer's first launch, and the GPU
         # idles for the part of it the getter kernels do not cover)
-        image, radii, *extras = _rz.rasterize_gaussians_indexed_camera(means3D, means2D, shs, sh_idx, g_idx, _rz._empty(), opac,
-                                                                       scales_n, sfac, rotations, _rz._empty(), settings,
-                                                                       settings.extrinsic_vector)
+        rasterize = _rz.rasterize_gaussians_indexed_camera_exact if pose_grad == "exact" else _rz.rasterize_gaussians_indexed_camera
+        image, radii, *extras = rasterize(means3D, means2D, shs, sh_idx, g_idx, _rz._empty(), opac, scales_n, sfac, rotations,
+                                          _rz._empty(), settings, settings.extrinsic_vector)
         return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
                 "visible": visible.bool(), **self._extra_keys(settings, extras, rank)}
 
@@ -1441,15 +1447,16 @@ class GaussianModel:
         return n
 
     def _render_composed(self, settings, screenspace_points, indexed, pipe, scaling_modifier, override_color, cov3d,
-                         gather_visible=True):
+                         gather_visible=True, pose_grad="reference"):
         """Every other configuration of render(): the same getters, composed with torch gathers like the reference.
         gather_visible=False (the sensitivity pass) hands all rows to the rasterizer instead of the reference's `t[visible]`
         copies: the rasterizer culls the same Gaussians itself (mark_visible is its own frustum test), so image and gradients
         are the same, `radii` / `viewspace_points` are then indexed by Gaussian rather than by visible row."""
         means3D = self.get_xyz
         opacity = self.get_opacity
-        rasterizer = GaussianRasterizerIndexed(raster_settings=settings, optimize_camera=True) if indexed \
-            else GaussianRasterizer(raster_settings=settings)
+        exact = pose_grad == "exact"
+        rasterizer = GaussianRasterizerIndexed(raster_settings=settings, optimize_camera="exact" if exact else True) if indexed \
+            else GaussianRasterizer(raster_settings=settings, optimize_camera="exact" if exact else False)
         scales = rotations = None
         cov3D_precomp = cov3d
         if cov3D_precomp is None:

@@ -281,6 +281,63 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     return iteration
 
 
+def refine_poses(scene_or_cameras, gaussians, pipe, background, iterations, lr=1e-3, lambda_dssim=0.2, cameras=None, log=None,
+                 pose_grad="exact"):
+    """train_camera.py:56-112 without its plotting: optimise camera poses against a FROZEN model. One torch.optim.Adam over the
+    chosen cameras' `extrinsic_vector` (one parameter group per camera, as the reference builds them); `iterations` passes over
+    them, per camera and pass: render -> fused (1 - l) L1 + l (1 - SSIM) against `cam.original_image` -> backward -> step.
+
+    `scene_or_cameras`: a scene with getTrainCameras() or a list of cameras; `cameras`: indices into it (None: all). Each
+    chosen camera's `extrinsic_vector` becomes a leaf on the model's device that requires grad (the same tensor when it already
+    lives there, so the caller sees the refined pose in place); nothing else about the cameras changes. The model's
+    parameters have `requires_grad` switched off for the run and put back on exit, its optimizer is not touched, and as in
+    GaussianModel.contribution_stats the QAT observer / quantiser state is saved in front and put back behind.
+    `pose_grad`: "exact" (the default), the gradient of the render itself (csrc/pose_grad.hip); "reference", the reference's
+    formula, which exists on the indexed rasterizer only.
+    The losses stay on the device: one host read per 10 passes, where `log(pass, [loss per camera])` is called.
+    -> [(first loss, last loss) per chosen camera]."""
+    cams = _train_cameras(scene_or_cameras)
+    if cameras is not None:
+        cams = [cams[i] for i in cameras]
+    if not cams:
+        return []
+    dev = gaussians.device
+    params = gaussians.parameters()
+    was = [t.requires_grad for t in params]
+    fq_saved = gaussians._fq_state.clone()
+    groups = []
+    for i, cam in enumerate(cams):
+        cam.extrinsic_vector = cam.extrinsic_vector.detach().to(dev, torch.float32).requires_grad_(True)
+        groups.append({"params": [cam.extrinsic_vector], "lr": lr, "name": f"extr{i}"})
+    optimizer = torch.optim.Adam(groups)
+    history, pending = [], []
+    try:
+        for t in params:
+            t.requires_grad_(False)
+        for it in range(1, int(iterations) + 1):
+            row = []
+            for cam in cams:
+                image = gaussians.render(cam, pipe, background, pose_grad=pose_grad)["render"]
+                loss = _loss.l1_ssim_loss(image, cam.original_image.to(dev), lambda_dssim)
+                loss.backward()
+                optimizer.step()
+                optimizer.zero_grad(set_to_none=True)
+                row.append(loss.detach())
+            pending.append(torch.stack(row))
+            if it % 10 == 0 or it == iterations:
+                vals = torch.stack(pending).tolist()                # one host read per 10 passes
+                history.extend(vals)
+                pending = []
+                if log is not None:
+                    log(it, vals[-1])
+    finally:
+        for t, r in zip(params, was):
+            t.requires_grad_(r)
+        with torch.no_grad():
+            gaussians._fq_state.copy_(fq_saved)
+    return [(history[0][k], history[-1][k]) for k in range(len(cams))] if history else [(float("nan"),) * 2 for _ in cams]
+
+
 def run_vq(gaussians, scene, optim_params, pipeline_params, comp_params, dataset=None, group=None, silent=True,
            out_file: Optional[str] = None, eval_cameras=None, eval_name="test", background=None):
     """compress.py:202-303 on an already constructed model and camera set: sensitivity (use_gt) -> prune + colour /

@@ -5,14 +5,17 @@ on top of the MI355X C-ABI library.  Same names, argument order and error behavi
     GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,
     rasterize_gaussians, rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,
     getProjectionMatrix, quat_to_mat, mat_to_quat, and `_C` with the five pybind entry points
-    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`, `render_contrib`, `render_error` and `error_map_l1`.
+    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`, `render_contrib`, `render_error`, `error_map_l1`
+    and `pose_grad`.
 
 Beyond the reference: `GaussianRasterizationSettings(depth=True)` / `_C.render_depth` add depth, accumulated-opacity and
 median-depth maps of a forward (forward-only, csrc/render_depth.hip); `GaussianRasterizationSettings(contrib=True)` /
 `_C.render_contrib` add every Gaussian's blend statistics: sum and max of alpha T and the number of (pixel, entry) pairs the
 forward blended (forward-only, csrc/render_contrib.hip); `GaussianRasterizationSettings(error_target=gt)` / `_C.render_error` /
 `_C.error_map_l1` add every Gaussian's error score, the sum of alpha T x a per-pixel error map (forward-only,
-csrc/render_error.hip).
+csrc/render_error.hip); `GaussianRasterizer(rs, optimize_camera="exact")` / `GaussianRasterizerIndexed(rs, optimize_camera="exact")`
+/ `_C.pose_grad` give the exact gradient of the render with respect to the 7-element pose (csrc/pose_grad.hip, one pass behind
+the backward), where `optimize_camera=True` keeps the reference's formula.
 
 PyTorch is plumbing only here (device memory, streams, autograd bookkeeping); every numeric stage
 runs in libc3dgs_hip.so.  There is no CPU path: tensors must live on the GPU.
@@ -532,6 +535,50 @@ def _c_render_error(P, W, H, R, geomBuffer, binningBuffer, imgBuffer, pixel_map)
     return out
 
 
+_pose_workspace = _GrowOnly()
+
+
+def _c_pose_grad(means3D, dL_dmeans3D, dL_dcov3D, dL_dcolors, sh, degree, sh_indices, cov3D_precomp, scales, rotations,
+                 scale_factors, g_indices, scale_modifier, geomBuffer, radii, extrinsic_vector):
+    """Exact dL/dpose [7] (qx, qy, qz, qw, tx, ty, tz) from a finished backward's outputs (c3dgs_pose_grad), on the current stream:
+    two launches, no float atomics, bitwise reproducible. `dL_dmeans3D`, `dL_dcov3D` and (with `sh`) `dL_dcolors` are the backward's
+    own tensors, not skipped; the other arguments are the forward's inputs, absent ones None or empty; `geomBuffer` and `radii`
+    are the forward's. The pose is read on the device by the kernels: nothing about it is cached on the host. Its workspace
+    (96 bytes per 256 Gaussians, grow-only) is its own."""
+    if not means3D.is_cuda:
+        raise RuntimeError("c3dgs_amd: pose_grad needs GPU tensors (there is no CPU path)")
+    dev = means3D.device
+    P = int(means3D.size(0))
+    pose = extrinsic_vector.detach()
+    if pose.device != dev or pose.dtype != torch.float32 or not pose.is_contiguous():
+        pose = pose.to(device=dev, dtype=torch.float32).contiguous()
+    if pose.dim() != 1 or pose.numel() != 7:
+        raise RuntimeError("pose_grad: extrinsic_vector must have 7 elements (qx, qy, qz, qw, tx, ty, tz)")
+    t = dict(means3D=_optional(means3D, "means3D"), dL_dmeans3D=_optional(dL_dmeans3D, "dL_dmeans3D"),
+             dL_dcov3D=_optional(dL_dcov3D, "dL_dcov3D"), dL_dcolors=_optional(dL_dcolors, "dL_dcolors"), sh=_optional(sh, "sh"),
+             sh_indices=_optional(sh_indices, "sh_indices", torch.int64), cov3D_precomp=_optional(cov3D_precomp, "cov3D_precomp"),
+             scales=_optional(scales, "scales"), rotations=_optional(rotations, "rotations"),
+             scale_factors=_optional(scale_factors, "scale_factors"), g_indices=_optional(g_indices, "g_indices", torch.int64),
+             radii=_optional(radii, "radii", torch.int32))
+    for name, width in (("dL_dmeans3D", 3), ("dL_dcov3D", 6), ("dL_dcolors", 3), ("cov3D_precomp", 6), ("scale_factors", 1),
+                        ("sh_indices", 1), ("g_indices", 1), ("radii", 1)):
+        if t[name] is not None and t[name].numel() != P * width:
+            raise RuntimeError(f"pose_grad: {name} must have {P} x {width} elements, not {t[name].numel()}")
+    shp = t["sh"]
+    M = int(shp.size(1)) if shp is not None else 0
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        out = torch.empty(7, dtype=torch.float32, device=dev)
+        ws = _pose_workspace.get(dev, L.c3dgs_pose_grad_workspace_bytes(P))
+        rc = L.c3dgs_pose_grad(P, int(degree), M, float(scale_modifier), _ptr(t["means3D"]), _ptr(t["dL_dmeans3D"]),
+                               _ptr(t["dL_dcov3D"]), _ptr(t["dL_dcolors"]), _ptr(shp), _ptr(t["sh_indices"]),
+                               _ptr(t["cov3D_precomp"]), _ptr(t["scales"]), _ptr(t["rotations"]), _ptr(t["scale_factors"]),
+                               _ptr(t["g_indices"]), geomBuffer.data_ptr() if geomBuffer.numel() else None, _ptr(t["radii"]),
+                               pose.data_ptr(), ws.data_ptr(), out.data_ptr(), _stream(dev))
+    _lib.check(rc)
+    return out
+
+
 def _check_map(t, shape, dev, what):
     """the usual RuntimeError for a map or image of the wrong kind"""
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev:
@@ -564,6 +611,7 @@ _C = SimpleNamespace(
     render_contrib=_c_render_contrib,
     render_error=_c_render_error,
     error_map_l1=_c_error_map_l1,
+    pose_grad=_c_pose_grad,
     rasterize_gaussians=_c_rasterize_gaussians,
     rasterize_gaussians_backward=_c_rasterize_gaussians_backward,
     rasterize_gaussians_indexed=_c_rasterize_gaussians_indexed,
@@ -643,9 +691,12 @@ def _fit(grad, inp):
     return grad
 
 
-def _autograd_backward(ctx, grad_out_color):
-    """backward of the three Functions -> the gradients BY THE NAME OF THE forward INPUT they belong to (None for an absent
-    input); each Function lays them out in its own input order. `args`: pybind order again (snapshot_bw.dump)."""
+def _autograd_backward(ctx, grad_out_color, exact_pose=False):
+    """backward of the Functions -> the gradients BY THE NAME OF THE forward INPUT they belong to (None for an absent
+    input); each Function lays them out in its own input order. `args`: pybind order again (snapshot_bw.dump).
+    `exact_pose`: the pose requires grad in exact mode. Then dL_dcov3D (and, with SH, dL_dcolors) are not skipped, _C.pose_grad is
+    queued behind the backward on the same stream and its 7-vector comes back as `.pose`; the caller-visible gradients of absent
+    inputs stay None (_fit). False: exactly the launches and stores of a backward without it, `.pose` is None."""
     rs = ctx.raster_settings
     (extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
      binningBuffer, imgBuffer, sh_indices, g_indices) = ctx.saved_tensors
@@ -655,6 +706,9 @@ def _autograd_backward(ctx, grad_out_color):
         grad_out_color = torch.zeros(ctx.image_shape, dtype=torch.float32, device=means3D.device)
     view, proj, campos, tanfovx, tanfovy = ctx.camera
     skip = tuple(n for n, t in (("dL_dcolors", colors_precomp), ("dL_dcov3D", cov3Ds_precomp)) if t is None or t.numel() == 0)
+    sh_used = sh is not None and sh.numel() != 0
+    if exact_pose:
+        skip = tuple(n for n in skip if n != "dL_dcov3D" and not (n == "dL_dcolors" and sh_used))
     grad_scale_factors = None
     if ctx.indexed:
         args = (rs.bg, means3D, radii, colors_precomp, scales, scale_factors, rotations, rs.scale_modifier, cov3Ds_precomp, view,
@@ -669,7 +723,15 @@ def _autograd_backward(ctx, grad_out_color):
                 imgBuffer, rs.debug)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations) = _call_debug(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump", skip=skip)
-    return SimpleNamespace(means3D=grad_means3D, means2D=grad_means2D, sh=_fit(grad_sh, sh),
+    grad_pose = None
+    if exact_pose:
+        # the indexed entry always carries both index tensors; the library wants each only with what it indexes
+        by_codebook = ctx.indexed and scales is not None and scales.numel() != 0
+        grad_pose = _C.pose_grad(means3D, grad_means3D, grad_cov3Ds_precomp, grad_colors_precomp if sh_used else None, sh,
+                                 rs.sh_degree, sh_indices if sh_used else None, cov3Ds_precomp, scales, rotations,
+                                 scale_factors if by_codebook else None, g_indices if by_codebook else None,
+                                 rs.scale_modifier, geomBuffer, radii, extrinsic_vector).to(extrinsic_vector.device)
+    return SimpleNamespace(pose=grad_pose, means3D=grad_means3D, means2D=grad_means2D, sh=_fit(grad_sh, sh),
                            colors_precomp=_fit(grad_colors_precomp, colors_precomp), opacities=grad_opacities,
                            scales=_fit(grad_scales, scales), scale_factors=_fit(grad_scale_factors, scale_factors),
                            rotations=_fit(grad_rotations, rotations), cov3Ds_precomp=_fit(grad_cov3Ds_precomp, cov3Ds_precomp))
@@ -779,6 +841,38 @@ class _RasterizeGaussiansIndexedCamera(torch.autograd.Function):
                 g.cov3Ds_precomp, None, grad_mat)
 
 
+class _RasterizeGaussiansCameraExact(torch.autograd.Function):
+    """_RasterizeGaussians plus the exact pose gradient (csrc/pose_grad.hip); no reference counterpart. Evaluated only when
+    extrinsic_vector requires grad: otherwise the backward is _RasterizeGaussians', launch for launch."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                extrinsic_vector):
+        return _autograd_forward(ctx, False, means3D, sh, None, None, colors_precomp, opacities, scales, None, rotations,
+                                 cov3Ds_precomp, raster_settings, extrinsic_vector)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, *params):
+        g = _autograd_backward(ctx, grad_out_color, exact_pose=ctx.needs_input_grad[9])
+        return (g.means3D, g.means2D, g.sh, g.colors_precomp, g.opacities, g.scales, g.rotations, g.cov3Ds_precomp, None, g.pose)
+
+
+class _RasterizeGaussiansIndexedCameraExact(torch.autograd.Function):
+    """_RasterizeGaussiansIndexedCamera with the exact pose gradient in place of the reference's formula."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities, scales, scale_factors, rotations,
+                cov3Ds_precomp, raster_settings, extrinsic_vector):
+        return _autograd_forward(ctx, True, means3D, sh, sh_indices, g_indices, colors_precomp, opacities, scales,
+                                 scale_factors, rotations, cov3Ds_precomp, raster_settings, extrinsic_vector)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, *params):
+        g = _autograd_backward(ctx, grad_out_color, exact_pose=ctx.needs_input_grad[12])
+        return (g.means3D, g.means2D, g.sh, None, None, g.colors_precomp, g.opacities, g.scales, g.scale_factors, g.rotations,
+                g.cov3Ds_precomp, None, g.pose)
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                         extrinsic_vector):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -796,6 +890,26 @@ def rasterize_gaussians_indexed_camera(means3D, means2D, sh, sh_indices, g_indic
     return _RasterizeGaussiansIndexedCamera.apply(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities,
                                                   scales, scale_factors, rotations, cov3Ds_precomp, raster_settings,
                                                   extrinsic_vector)
+
+
+def rasterize_gaussians_camera_exact(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                     raster_settings, extrinsic_vector):
+    return _RasterizeGaussiansCameraExact.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                                cov3Ds_precomp, raster_settings, extrinsic_vector)
+
+
+def rasterize_gaussians_indexed_camera_exact(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities, scales,
+                                             scale_factors, rotations, cov3Ds_precomp, raster_settings, extrinsic_vector):
+    return _RasterizeGaussiansIndexedCameraExact.apply(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities,
+                                                       scales, scale_factors, rotations, cov3Ds_precomp, raster_settings,
+                                                       extrinsic_vector)
+
+
+def _check_optimize_camera(value):
+    """False | True (the reference's pose gradient) | "exact" (csrc/pose_grad.hip)"""
+    if value is True or value is False or value == "exact":
+        return value
+    raise ValueError(f'optimize_camera must be False, True or "exact", not {value!r}')
 
 
 # ----------------------------------------------------------------------------- public modules
@@ -884,7 +998,17 @@ class _Rasterizer(nn.Module):
 
 class GaussianRasterizer(_Rasterizer):
     """reference __init__.py:881-948. `forward` accepts the pose as `extrinsic_vector=` (what the reference's own
-    caller passes, scene/gaussian_model.py:874) and, for compatibility with the declared signature, `extrinsic=`."""
+    caller passes, scene/gaussian_model.py:874) and, for compatibility with the declared signature, `extrinsic=`.
+    `optimize_camera="exact"`: a 7-element pose that requires grad receives the exact gradient of the render
+    (rasterize_gaussians_camera_exact). False (the default, the reference's behaviour): no pose gradient. The reference has no
+    pose formula for this path, so True is not accepted."""
+
+    def __init__(self, raster_settings, optimize_camera=False):
+        super().__init__(raster_settings)
+        if optimize_camera is True:
+            raise ValueError('GaussianRasterizer: optimize_camera must be False or "exact" (the reference formula exists for '
+                             'the indexed rasterizer only)')
+        self.optimize_camera = _check_optimize_camera(optimize_camera)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, extrinsic_vector=None, extrinsic=None):
@@ -893,12 +1017,14 @@ class GaussianRasterizer(_Rasterizer):
             extrinsic_vector = extrinsic if extrinsic is not None else self.raster_settings.extrinsic_vector
         shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_to_empty(shs, colors_precomp, scales, rotations,
                                                                                  cov3D_precomp)
-        return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings, extrinsic_vector)
+        fn = rasterize_gaussians_camera_exact if self.optimize_camera == "exact" else rasterize_gaussians
+        return fn(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, self.raster_settings,
+                  extrinsic_vector)
 
 
 class GaussianRasterizerIndexed(_Rasterizer):
-    """reference __init__.py:951-1046."""
+    """reference __init__.py:951-1046. `optimize_camera`: False; True, the reference's pose gradient (camera_pose_jacobian_sum,
+    dL/dmeans2D through a projection formula); or "exact", the gradient of the render itself (rasterize_gaussians_indexed_camera_exact)."""
 
     def __init__(self, raster_settings, optimize_camera=False):
         super().__init__(raster_settings)
@@ -911,6 +1037,7 @@ class GaussianRasterizerIndexed(_Rasterizer):
             extrinsic_vector = self.raster_settings.extrinsic_vector
         shs, colors_precomp, scales, scale_factors, rotations, cov3D_precomp = _absent_to_empty(
             shs, colors_precomp, scales, scale_factors, rotations, cov3D_precomp)
-        fn = rasterize_gaussians_indexed_camera if self.optimize_camera else rasterize_gaussians_indexed
+        fn = (rasterize_gaussians_indexed_camera_exact if self.optimize_camera == "exact" else
+              rasterize_gaussians_indexed_camera if self.optimize_camera else rasterize_gaussians_indexed)
         return fn(means3D, means2D, shs, sh_indices, g_indices, colors_precomp, opacities, scales, scale_factors, rotations,
                   cov3D_precomp, self.raster_settings, extrinsic_vector)

@@ -218,6 +218,32 @@ int c3dgs_error_accumulate(int32_t P_model, int32_t P_rows, const uint8_t* visib
                            const int32_t* rank /*[P_model] | NULL*/, const float* err_sum, float* acc_max, float* acc_sum,
                            void* stream);
 
+/* ---- exact gradient with respect to the camera's 7-element pose, behind a finished backward (csrc/pose_grad.hip; no reference
+ * counterpart: the reference's pose gradient chains dL/dmeans2D alone through a projection formula) ----
+ * pose = (qx, qy, qz, qw, tx, ty, tz) on the device, read by the call's kernels on the stream (nothing about it is cached on
+ * the host); R, t, c = -R^-1 t are formed from it as c3dgs_camera_from_pose forms them, R is not assumed orthonormal. With
+ * g_i = dL_dmeans3D[i], G_i = dL_dcov3D[i] as a full matrix (an off-diagonal entry of the six counts both symmetric positions),
+ * gdir_i = the part of g_i that arrived through the SH view direction (recomputed from dL_dcolors, the forward's clamp flags in
+ * the geometry buffer and the SH row; zero without SH or at degree 0), Sigma_i rebuilt as the forward built it:
+ *   dL/dt = R^-T sum_i g_i
+ *   dL/dR = R^-T [ sum_i (g_i - gdir_i) mu_i^T + sum_i (G_i + G_i^T) Sigma_i + (sum_i gdir_i) c^T ]
+ * and out[7] = dL/dpose through the entries of the unnormalised-quaternion matrix. Rows with radii <= 0 are skipped. Inputs
+ * are those of the forward / the outputs of its backward (dL_dcov3D and, with SH, dL_dcolors must have been written, not
+ * skipped). Exactly one of cov3D_precomp and the pair (scales, rotations); g_indices and scale_factors come together (the indexed
+ * path: codebook rows, scale = scale_factors x scale_modifier); sh_indices needs sh; sh needs dL_dcolors and M >= (D + 1)^2.
+ * `workspace`: c3dgs_pose_grad_workspace_bytes(P) bytes (24 floats per 256 Gaussians), every word the call reads is written by
+ * it first. No float atomics: bitwise reproducible. P == 0: seven zeros, no kernel. Argument errors return C3DGS_E_INVALID before
+ * any device work. Stage name: "pose_grad" (both kernels; "pose_grad_sums" / "pose_grad_fold" alone). */
+size_t c3dgs_pose_grad_workspace_bytes(int32_t P);
+int c3dgs_pose_grad(int32_t P, int32_t D, int32_t M, float scale_modifier,
+                    const float* means3D /*[P,3]*/, const float* dL_dmeans3D /*[P,3]*/, const float* dL_dcov3D /*[P,6]*/,
+                    const float* dL_dcolors /*[P,3] | NULL without sh*/, const float* sh /*[SHS,M,3] | NULL*/,
+                    const int64_t* sh_indices /*[P] | NULL*/, const float* cov3D_precomp /*[P,6] | NULL*/,
+                    const float* scales /*[GS,3] | NULL*/, const float* rotations /*[GS,4] | NULL*/,
+                    const float* scale_factors /*[P] | NULL*/, const int64_t* g_indices /*[P] | NULL*/,
+                    const void* geom_buffer, const int32_t* radii /*[P]*/, const float* pose /*[7]*/, void* workspace,
+                    float* out /*[7]*/, void* stream);
+
 /* ---- weighted_distance._C.weightedDistance (weighted_distance.cu:46-93) ----
  * coefs [N,K], codebook [C,K] row-major fp32 -> min squared distance [N] and argmin [N] (int64).
  * Exact reference semantics: fp32 k-ordered FMA chain, strict '<' (lowest index wins ties).
