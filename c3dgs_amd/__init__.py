@@ -14,7 +14,8 @@ Drop-in for the reference's two native extensions and the Python directly around
     c3dgs_amd.model       <->  GaussianModel getters + FakeQuantize modules + render() glue + adaptive density control
                                (scene/gaussian_model.py)
     c3dgs_amd.pipeline    <->  train.py / finetune.py / compress.py drivers
-    c3dgs_amd.optim       <->  the torch.optim.Adam step of the QAT loop (finetune.py:65-66), one fused launch
+    c3dgs_amd.optim       <->  the torch.optim.Adam step of the QAT loop (finetune.py:65-66), one fused launch; beyond the
+                               reference, SparseGaussianAdam: the same step over the Gaussians a view saw only
 
 The numeric work runs in c3dgs_amd/libc3dgs_hip.so (include/c3dgs_hip.h); build it with
 `python -m c3dgs_amd.build`.  There is no CPU fallback.

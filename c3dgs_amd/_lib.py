@@ -76,6 +76,10 @@ class AdamTensor(C.Structure):
                 ("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float)]
 
 
+class SparseAdamTensor(C.Structure):    # c3dgs_sparse_adam_tensor: AdamTensor's fields (n = P * row_len) + row_len
+    _fields_ = AdamTensor._fields_ + [("row_len", C.c_int32)]
+
+
 class RowsTensor(C.Structure):          # c3dgs_rows_tensor
     _fields_ = [("in_param", C.c_void_p), ("in_exp_avg", C.c_void_p), ("in_exp_avg_sq", C.c_void_p), ("out_param", C.c_void_p),
                 ("out_exp_avg", C.c_void_p), ("out_exp_avg_sq", C.c_void_p), ("row_floats", C.c_int32), ("role", C.c_int32)]
@@ -142,6 +146,10 @@ PROTOTYPES = {
     "c3dgs_ray_fill_xyz": (C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_float, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "c3dgs_image_from_u8": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     "c3dgs_adam_step": (C.c_int, [C.c_int32, C.POINTER(AdamTensor), C.c_double, C.c_double, C.c_double, _vp]),
+    "c3dgs_sparse_adam_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "c3dgs_sparse_adam_select": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp]),
+    "c3dgs_sparse_adam_step": (C.c_int, [C.c_int32, C.POINTER(SparseAdamTensor), C.c_int64, _vp, C.c_double, C.c_double, C.c_double,
+                                         _vp]),
     "c3dgs_densify_classify": (C.c_int, [C.c_int32] + [_vp] * 7 + [C.c_float] * 4 + [_vp, _vp]),
     "c3dgs_rows_plan_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "c3dgs_rows_plan": (C.c_int, [C.c_int32, _vp, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),

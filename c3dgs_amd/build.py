@@ -45,6 +45,7 @@ SOURCES = {
     "encode.hip": [],
     "knn.hip": ["-ffp-contract=off"],       # the distances and box bounds are bit-exact fp32 expressions (csrc/knn.hip)
     "adam.hip": ["-ffp-contract=off"],
+    "sparse_adam.hip": ["-ffp-contract=off"],   # adam.hip's arithmetic (csrc/adam_common.hpp), rounded as adam.hip rounds it
     "qat.hip": ["-ffp-contract=off"],
     "densify.hip": ["-ffp-contract=off"],   # sqrt(gx*gx + gy*gy) of the densification stats is torch's two-rounding sum
     "index_plan.hip": [],
@@ -52,7 +53,7 @@ SOURCES = {
     "image_io.hip": ["-ffp-contract=off"],  # t0 * (1 - f) + t1 * f of the bilinear taps is separately rounded (csrc/image_io.hip)
 }
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), os.path.join(CSRC, "render_diag.hpp"),
-           os.path.join(CSRC, "render_common.hpp"), os.path.join(CSRC, "scan_blocks.hpp"),
+           os.path.join(CSRC, "render_common.hpp"), os.path.join(CSRC, "scan_blocks.hpp"), os.path.join(CSRC, "adam_common.hpp"),
            os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h")]
 
 

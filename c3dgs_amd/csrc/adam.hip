@@ -10,6 +10,7 @@
 //     p <- p - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // HBM-bound streaming.
 #include "common.hpp"
+#include "adam_common.hpp"      // adam_one: the per-element arithmetic, shared with sparse_adam.hip
 
 namespace c3dgs {
 
@@ -19,16 +20,6 @@ struct AdamJobs {
     int nblocks[C3DGS_ADAM_MAX_TENSORS];
     int n;
 };
-
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float w1, float beta2, float w2, float eps,
-                                         float neg_step, float bc2_sqrt)
-{
-    m = w1 < 0.5f ? m + w1 * (g - m) : g - (g - m) * (1.f - w1);          // at::lerp
-    v = v * beta2;
-    v = v + w2 * g * g;                                                    // addcmul: a + alpha * b * c
-    const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p = p + neg_step * (m / denom);                                        // addcdiv: a + alpha * (b / c)
-}
 
 __global__ void __launch_bounds__(256)
 adam_kernel(const AdamJobs jobs, float w1, float beta2, float w2, float eps)

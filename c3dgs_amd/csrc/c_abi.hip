@@ -32,7 +32,7 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
     X(QAT_VISIBLE, "qat_visible") X(QAT_POINTS, "qat_points") X(QAT_POINTS_BWD, "qat_points_backward")                         \
     X(QAT_CODEBOOKS_BWD, "qat_codebooks_backward") X(ADAM, "adam_step") X(KNN_SORT, "knn_sort") X(KNN_BOUNDS, "knn_bounds")    \
-    X(KNN_QUERY, "knn_query")
+    X(KNN_QUERY, "knn_query") X(SPARSE_ADAM_SELECT, "sparse_adam_select") X(SPARSE_ADAM_STEP, "sparse_adam_step")
 #define C3DGS_X(id, name) ST_##id,
 enum Stage { C3DGS_STAGE_TABLE(C3DGS_X) ST_COUNT };
 #undef C3DGS_X
@@ -881,6 +881,57 @@ int c3dgs_adam_step(int32_t n_tensors, const c3dgs_adam_tensor* tensors, double 
         if (tensors[k].n > 0 && (!tensors[k].param || !tensors[k].grad || !tensors[k].exp_avg || !tensors[k].exp_avg_sq))
             return fail(C3DGS_E_INVALID, "adam_step: NULL tensor pointer");
     C3DGS_TIMED_STAGE(ST_ADAM, 0, (hipStream_t)stream, launch_adam(n_tensors, tensors, beta1, beta2, eps, (hipStream_t)stream));
+    return C3DGS_OK;
+}
+
+// ---- sparse Adam (sparse_adam.hip)
+static const char* sparse_adam_bad_P(int64_t P)
+{
+    if (P < 0) return "P must be >= 0";
+    if (P >= (int64_t(1) << 31)) return "P must be below 2^31 (row ids are 32-bit)";
+    return nullptr;
+}
+
+int c3dgs_sparse_adam_workspace_bytes(int64_t P, size_t* bytes)
+{
+    if (!bytes) return fail(C3DGS_E_INVALID, "sparse_adam_workspace_bytes: bytes is NULL");
+    if (const char* bad = sparse_adam_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_workspace_bytes: ") + bad);
+    *bytes = sparse_adam_layout(P).total_bytes;
+    return C3DGS_OK;
+}
+
+int c3dgs_sparse_adam_select(int64_t P, const void* mask, int32_t mask_kind, void* workspace, void* stream)
+{
+    if (const char* bad = sparse_adam_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_select: ") + bad);
+    if (mask_kind != 0 && mask_kind != 1) return fail(C3DGS_E_INVALID, "sparse_adam_select: mask_kind must be 0 (uint8 != 0) or 1 (int32 > 0)");
+    if (P == 0) return C3DGS_OK;
+    if (!mask) return fail(C3DGS_E_INVALID, "sparse_adam_select: mask is NULL");
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(C3DGS_E_INVALID, "sparse_adam_select: the workspace must be non-NULL and 256-byte aligned");
+    C3DGS_TIMED_STAGE(ST_SPARSE_ADAM_SELECT, 0, (hipStream_t)stream, launch_sparse_adam_select(P, mask, mask_kind, workspace, (hipStream_t)stream));
+    return C3DGS_OK;
+}
+
+int c3dgs_sparse_adam_step(int32_t n_tensors, const c3dgs_sparse_adam_tensor* tensors, int64_t P, const void* workspace, double beta1,
+                           double beta2, double eps, void* stream)
+{
+    if (n_tensors < 0 || n_tensors > C3DGS_ADAM_MAX_TENSORS)
+        return fail(C3DGS_E_INVALID, "sparse_adam_step: between 0 and 16 tensors per call");
+    if (const char* bad = sparse_adam_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_step: ") + bad);
+    if (n_tensors == 0) return C3DGS_OK;
+    if (!tensors) return fail(C3DGS_E_INVALID, "sparse_adam_step: tensors is NULL");
+    for (int k = 0; k < n_tensors; k++) {
+        const c3dgs_sparse_adam_tensor& t = tensors[k];
+        if (t.row_len <= 0) return fail(C3DGS_E_INVALID, "sparse_adam_step: row_len must be > 0");
+        if (t.n != P * (int64_t)t.row_len) return fail(C3DGS_E_INVALID, "sparse_adam_step: n must be P * row_len");
+        if (t.n > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq))
+            return fail(C3DGS_E_INVALID, "sparse_adam_step: NULL tensor pointer");
+    }
+    if (P == 0) return C3DGS_OK;
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(C3DGS_E_INVALID, "sparse_adam_step: the workspace must be non-NULL and 256-byte aligned");
+    C3DGS_TIMED_STAGE(ST_SPARSE_ADAM_STEP, 0, (hipStream_t)stream,
+                      launch_sparse_adam_step(n_tensors, tensors, P, workspace, beta1, beta2, eps, (hipStream_t)stream));
     return C3DGS_OK;
 }
 

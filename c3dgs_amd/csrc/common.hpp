@@ -202,6 +202,23 @@ inline ErrorLayout error_layout(int P, int R)
     return L;
 }
 
+// Sparse-Adam workspace (sparse_adam.hip), caller-owned: count u32 (the number of listed rows) at offset 0 | rows u32[P], the
+// ascending ids of the listed rows, filled from the front | the exclusive scan of the listed rows per SPARSE_ADAM_SELECT_ROWS
+// rows, u32[ceil(P / 256) + 2] (scan_blocks.hpp's base[]: its last-but-one word is the total). Every region 256-byte aligned.
+constexpr int SPARSE_ADAM_SELECT_ROWS = 256;
+struct SparseAdamLayout { size_t count, rows, block_base, total_bytes; };
+inline SparseAdamLayout sparse_adam_layout(int64_t P)
+{
+    const size_t p = (size_t)(P > 0 ? P : 1);
+    SparseAdamLayout L;
+    size_t o = 0;
+    L.count = o;      o = align_up(o + 4);
+    L.rows = o;       o = align_up(o + p * 4);
+    L.block_base = o; o = align_up(o + ((p + SPARSE_ADAM_SELECT_ROWS - 1) / SPARSE_ADAM_SELECT_ROWS + 2) * 4);
+    L.total_bytes = o;
+    return L;
+}
+
 // ---------------------------------------------------------------- kernel launchers (one per .hip file)
 struct GeomPtrs {
     float4* splat; uint32_t* depth_keys; uint32_t* depth_keys_sorted;
@@ -403,6 +420,11 @@ void launch_image_from_u8(int Hs, int Ws, int C, const uint8_t* src, int flip, c
 // adam.hip
 void launch_adam(int n_tensors, const c3dgs_adam_tensor* tensors, double beta1, double beta2, double eps, hipStream_t s);
 void launch_abs_accumulate(int64_t n, const float* g, float* acc, hipStream_t s);
+// sparse_adam.hip: the list of the rows a mask names (mask_kind 0: u8 != 0, 1: i32 > 0) into the workspace, and the Adam step
+// over the listed rows of up to C3DGS_ADAM_MAX_TENSORS tensors. 0 < P < 2^31.
+void launch_sparse_adam_select(int64_t P, const void* mask, int mask_kind, void* workspace, hipStream_t s);
+void launch_sparse_adam_step(int n_tensors, const c3dgs_sparse_adam_tensor* tensors, int64_t P, const void* workspace, double beta1,
+                             double beta2, double eps, hipStream_t s);
 // densify.hip (adaptive density control): classify -> plan (scan + emit) -> apply, and the per-iteration stats
 void launch_densify_classify(int P, const float* accum, const float* denom, const float* scale_clone, const float* scale_split,
                              const float* scale_prune_self, const float* scale_prune_child, const float* opacity, float max_grad,

@@ -698,10 +698,22 @@ class GaussianModel:
         return self
 
     # ---- optimizer plumbing of the fine-tuning loop (gaussian_model.py:292-322)
-    def training_setup(self, training_args):
+    def training_setup(self, training_args, optimizer_type=None):
         """Same parameter groups, names and learning rates as the reference; the optimizer is the fused Adam
-        (c3dgs_amd.optim.Adam, one launch for all groups) instead of torch.optim.Adam(l, lr=0.0, eps=1e-15)."""
+        (c3dgs_amd.optim.Adam, one launch for all groups) instead of torch.optim.Adam(l, lr=0.0, eps=1e-15).
+
+        `optimizer_type` (None: training_args.optimizer_type, "default" where it has none): "sparse_adam" (not in the reference;
+        upstream 3DGS's accelerated optimizer) builds optim.SparseGaussianAdam over the same groups, each flagged per-Gaussian, so
+        that step(visibility) updates only the rows a view saw. Non-indexed models only: the rows of a codebook are shared
+        between Gaussians, there is no per-Gaussian row to skip."""
         from . import optim
+        if optimizer_type is None:
+            optimizer_type = getattr(training_args, "optimizer_type", "default")
+        if optimizer_type not in ("default", "sparse_adam"):
+            raise ValueError(f"training_setup: optimizer_type must be 'default' or 'sparse_adam', not {optimizer_type!r}")
+        if optimizer_type == "sparse_adam" and (self.is_color_indexed or self.is_gaussian_indexed):
+            raise NotImplementedError("training_setup: optimizer_type='sparse_adam' needs a non-indexed model (codebook rows are "
+                                      "shared between Gaussians)")
         self.percent_dense = training_args.percent_dense
         n = self._xyz.shape[0]
         self.xyz_gradient_accum = torch.zeros((n, 1), device=self.device)
@@ -716,7 +728,12 @@ class GaussianModel:
         ]
         if self._scaling_factor is not None:
             groups.append({"params": [self._scaling_factor], "lr": training_args.scaling_lr, "name": "scaling_factor"})
-        self.optimizer = optim.Adam(groups, lr=0.0, eps=1e-15)
+        if optimizer_type == "sparse_adam":
+            for g in groups:
+                g["per_gaussian"] = True
+            self.optimizer = optim.SparseGaussianAdam(groups, lr=0.0, eps=1e-15)
+        else:
+            self.optimizer = optim.Adam(groups, lr=0.0, eps=1e-15)
         self.xyz_scheduler_args = get_expon_lr_func(
             lr_init=training_args.position_lr_init * self.spatial_lr_scale,
             lr_final=training_args.position_lr_final * self.spatial_lr_scale,

@@ -21,6 +21,7 @@ import torch
 
 from . import loss as _loss
 from . import metrics as _metrics
+from . import optim as _optim
 from . import sensitivity as _sensitivity
 from .vq import CompressionSettings, compress_gaussians
 
@@ -47,6 +48,7 @@ class OptimizationParams:
         self.densify_grad_threshold = 0.0002
         self.random_background = False
         self.not_quantization_aware = False
+        self.optimizer_type = "default"      # "sparse_adam": GaussianModel.training_setup builds optim.SparseGaussianAdam (not in the reference)
         _apply(self, overrides)
 
 
@@ -179,7 +181,7 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
 
 
 def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, degree_up_iter=1000, *, densify_by="grad",
-          error_threshold=None):
+          error_threshold=None, optimizer_type=None, optimizer_visibility="radii"):
     """train.py:15-173 without its disabled compression-statistics branch: optimise a non-indexed model (usually
     GaussianModel.load_ply of a point cloud) with adaptive density control.
 
@@ -202,7 +204,16 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     E = sum over its blended pixels of alpha T x mean |render - gt| over the epoch's views in place of the gradient
     accumulation, and the epoch's densification is densify_and_prune(error_threshold, ..., scores=error_max).
     add_densification_stats still runs with `radii`, so max_radii2D and the screen-size prune work as before. `error_threshold`
-    is required in that mode and has no default: its scale grows with the resolution, and nobody has tuned it."""
+    is required in that mode and has no default: its scale grows with the resolution, and nobody has tuned it.
+
+    `optimizer_type` goes to GaussianModel.training_setup (None: opt.optimizer_type; "default" is the loop above).
+    "sparse_adam" (not in the reference; upstream 3DGS's accelerated optimizer) steps only the Gaussians the view saw and
+    leaves the parameters and moments of all others as they are. `optimizer_visibility` names what "saw" means and is used
+    with that optimizer only: "radii" (upstream's rule) lists the rows with radii > 0; "blended" lists the rows at least one
+    pixel blended, the `contrib_hits` of a render with return_contrib=True, which costs the contribution pass
+    (csrc/render_contrib.hip) in every view; None steps every row (the dense step through the sparse optimizer)."""
+    if optimizer_visibility not in ("radii", "blended", None):
+        raise ValueError(f"train: optimizer_visibility must be 'radii', 'blended' or None, not {optimizer_visibility!r}")
     if densify_by not in ("grad", "error"):
         raise ValueError(f"train: densify_by must be 'grad' or 'error', not {densify_by!r}")
     by_error = densify_by == "error"
@@ -212,8 +223,10 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     cameras = _train_cameras(scene)
     if extent is None:
         extent = scene.cameras_extent
-    gaussians.training_setup(opt)
+    gaussians.training_setup(opt, optimizer_type=optimizer_type)
     gaussians.update_learning_rate(0)
+    sparse = isinstance(gaussians.optimizer, _optim.SparseGaussianAdam) and optimizer_visibility is not None
+    extra = {"return_contrib": True} if sparse and optimizer_visibility == "blended" else {}
     dev = gaussians.device
     bg = torch.rand(3, device=dev) if opt.random_background else torch.tensor([0, 0, 0], dtype=torch.float32, device=dev)
     ema_loss_for_log = 0.0
@@ -239,16 +252,20 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             if by_error:
                 gt_image = viewpoint_cam.original_image.to(dev)
                 render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False,
-                                              error_target=gt_image)
+                                              error_target=gt_image, **extra)
             else:
-                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False)
+                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False,
+                                              **extra)
             image, viewspace_point_tensor, radii = render_pkg["render"], render_pkg["viewspace_points"], render_pkg["radii"]
             if not by_error:
                 gt_image = viewpoint_cam.original_image.to(image.device)
             loss = _loss.l1_ssim_loss(image, gt_image, opt.lambda_dssim)
             loss.backward()
             pending.append(loss.detach())
-            gaussians.optimizer.step()
+            if sparse:
+                gaussians.optimizer.step(render_pkg["contrib_hits"] if extra else radii)
+            else:
+                gaussians.optimizer.step()
             gaussians.optimizer.zero_grad(set_to_none=True)
             if epoch < densify_until_epoch:
                 with torch.no_grad():

@@ -395,6 +395,32 @@ typedef struct c3dgs_adam_tensor {
 } c3dgs_adam_tensor;
 int c3dgs_adam_step(int32_t n_tensors, const c3dgs_adam_tensor* tensors /*host*/, double beta1, double beta2, double eps, void* stream);
 
+/* ---- sparse Adam: the same step over the rows (Gaussians) a per-row mask lists, every other row untouched: neither loaded
+ * nor stored, in any of the four arrays (upstream 3DGS's optimizer_type="sparse_adam": rows with radii > 0). Beyond the
+ * reference, which has no sparse optimizer. Added without an ABI version bump: new entry points only.
+ *   select: the ascending list of the listed rows and its length, built on the device (block counts -> scan -> emit; stable,
+ *           no atomics, no host read). mask_kind 0: uint8, listed when != 0; 1: int32, listed when > 0 (radii as they are).
+ *   step:   ONE launch per call; lane i of a tensor handles element i % row_len of row rows[i / row_len]. The launch is
+ *           sized from P, the kernel reads the count from the workspace. Any row_len > 0; rows need 4-byte alignment only.
+ * The workspace is the caller's, 256-byte aligned, c3dgs_sparse_adam_workspace_bytes(P) bytes: count u32 at offset 0, rows
+ * u32[P] at offset 256, the select's block totals behind them. 0 <= P < 2^31. P == 0, n_tensors == 0 and a mask that lists
+ * nothing are no-ops; arguments are validated before any device work. */
+int c3dgs_sparse_adam_workspace_bytes(int64_t P, size_t* bytes);
+int c3dgs_sparse_adam_select(int64_t P, const void* mask /*[P]*/, int32_t mask_kind /* 0: u8 != 0, 1: i32 > 0 */, void* workspace,
+                             void* stream);
+typedef struct c3dgs_sparse_adam_tensor {
+    float* param;            /* [P, row_len] listed rows updated in place */
+    const float* grad;       /* [P, row_len]                              */
+    float* exp_avg;          /* [P, row_len] first moment                 */
+    float* exp_avg_sq;       /* [P, row_len] second moment                */
+    int64_t n;               /* P * row_len */
+    float step_size;
+    float bias_correction2_sqrt;
+    int32_t row_len;         /* elements per row */
+} c3dgs_sparse_adam_tensor;
+int c3dgs_sparse_adam_step(int32_t n_tensors, const c3dgs_sparse_adam_tensor* tensors /*host*/, int64_t P, const void* workspace,
+                           double beta1, double beta2, double eps, void* stream);
+
 /* ---- adaptive density control (scene/gaussian_model.py:1187-1403: densify_and_clone / densify_and_split / prune_points /
  * densify_and_prune / add_densification_stats), non-indexed models. The reference rebuilds the scene in four passes (clone
  * cat, split cat, the split's prune, the final prune); here: classify (one code byte per row) -> plan (one scan, the source

@@ -4,10 +4,12 @@ control and once with densify_until_iter = 0, and prints one JSON line: Gaussian
 before / after, and seconds per phase.
 
     python tools/run_train.py [--iterations 400] [--out profiles/r06_train_synth.json]
-                              [--densify-by grad|error] [--error-threshold T]
+                              [--densify-by grad|error] [--error-threshold T] [--optimizer default|sparse_adam]
 
 --densify-by error (with --error-threshold, which has no default) lets the run with density control densify by image error
-(pipeline.train(densify_by="error")); the JSON then carries "densify_by" and "error_threshold"."""
+(pipeline.train(densify_by="error")); the JSON then carries "densify_by" and "error_threshold".
+--optimizer sparse_adam runs both with optim.SparseGaussianAdam stepping only the rows with radii > 0
+(pipeline.train(optimizer_type="sparse_adam")); the JSON then carries "optimizer"."""
 import argparse
 import json
 import os
@@ -23,7 +25,7 @@ sys.path.insert(0, ROOT)
 from tests import train_scene  # noqa: E402
 
 
-def run(iterations, densify, densify_by="grad", error_threshold=None):
+def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer="default"):
     from c3dgs_amd import pipeline
     from c3dgs_amd.model import PipelineParams
     with tempfile.TemporaryDirectory() as tmp:
@@ -44,7 +46,8 @@ def run(iterations, densify, densify_by="grad", error_threshold=None):
     torch.manual_seed(0)
     t0 = time.perf_counter()
     n = pipeline.train(Scene(), None, train_scene.schedule(iterations, densify), PipelineParams(), camera_stride=1, degree_up_iter=80,
-                       log=lambda epoch, info: events.append((epoch, info)), densify_by=densify_by, error_threshold=error_threshold)
+                       log=lambda epoch, info: events.append((epoch, info)), densify_by=densify_by, error_threshold=error_threshold,
+                       optimizer_type=optimizer)
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -62,16 +65,19 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--densify-by", choices=("grad", "error"), default="grad")
     ap.add_argument("--error-threshold", type=float, default=None)
+    ap.add_argument("--optimizer", choices=("default", "sparse_adam"), default="default")
     args = ap.parse_args()
     if args.densify_by == "error" and args.error_threshold is None:
         ap.error("--densify-by error needs --error-threshold (there is no default)")
     if not torch.cuda.is_available():
         raise SystemExit("run_train.py needs the GPU; there is no CPU path")
     out = {"scene": "tests/train_scene.py: 4000-Gaussian synth-v1 teacher, 8 views 160x112, student = every 8th position as a point cloud",
-           "with_density_control": run(args.iterations, True, args.densify_by, args.error_threshold),
-           "densify_until_iter_0": run(args.iterations, False)}
+           "with_density_control": run(args.iterations, True, args.densify_by, args.error_threshold, args.optimizer),
+           "densify_until_iter_0": run(args.iterations, False, optimizer=args.optimizer)}
     if args.densify_by != "grad":
         out["densify_by"], out["error_threshold"] = args.densify_by, args.error_threshold
+    if args.optimizer != "default":
+        out["optimizer"] = args.optimizer
     print(json.dumps(out))
     if args.out:
         with open(args.out, "w") as f:
