@@ -17,6 +17,11 @@ Drop-in for the reference's two native extensions and the Python directly around
     c3dgs_amd.optim       <->  the torch.optim.Adam step of the QAT loop (finetune.py:65-66), one fused launch; beyond the
                                reference, SparseGaussianAdam: the same step over the Gaussians a view saw only
 
+Beyond the reference, the rasterizer also returns depth / accumulated-opacity / median-depth maps, per-Gaussian blend statistics and
+error scores and the exact pose gradient; with GaussianRasterizationSettings(depth_grad=True) the depth and alpha maps carry
+gradient (csrc/render_depth_backward.hip), which GaussianModel.render(depth_grad=True) and pipeline.train(lambda_depth=,
+lambda_alpha=) use for depth and silhouette losses.
+
 The numeric work runs in c3dgs_amd/libc3dgs_hip.so (include/c3dgs_hip.h); build it with
 `python -m c3dgs_amd.build`.  There is no CPU fallback.
 """

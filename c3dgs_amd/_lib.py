@@ -104,6 +104,13 @@ PROTOTYPES = {
     "c3dgs_rasterize_gaussians_backward_indexed": (C.c_int, [C.POINTER(RasterParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                                              C.c_void_p, C.c_int32, C.c_void_p, RESIZE_FN, C.c_void_p,
                                                              C.POINTER(RasterGrads), C.c_void_p]),
+    "c3dgs_rasterize_gaussians_backward_depth": (C.c_int, [C.POINTER(RasterParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, RESIZE_FN,
+                                                           C.c_void_p, C.POINTER(RasterGrads), C.c_void_p]),
+    "c3dgs_rasterize_gaussians_backward_depth_indexed": (C.c_int, [C.POINTER(RasterParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                   RESIZE_FN, C.c_void_p, C.POINTER(RasterGrads), C.c_void_p]),
+    "c3dgs_depth_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "c3dgs_render_depth": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "c3dgs_contrib_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "c3dgs_render_contrib": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8),

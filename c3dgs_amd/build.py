@@ -31,6 +31,8 @@ SOURCES = {
     "render.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the depth / alpha / median replay of the forward's blend: render.hip's flags, so that the shared alpha expression compiles alike
     "render_depth.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
+    # the gradients through the depth / alpha maps: the same replay, walked back to front with render.hip's backward recurrences
+    "render_depth_backward.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the per-Gaussian blend statistics: the same replay, the same flags
     "render_contrib.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the per-Gaussian error scores: the same replay and the same reduction network, the same flags

@@ -28,6 +28,7 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(ERROR_MAP_L1, "error_map_l1")                                                                                            \
     X(POSE_GRAD, "pose_grad") X(POSE_GRAD_SUMS, "pose_grad_sums") X(POSE_GRAD_FOLD, "pose_grad_fold")                          \
     X(ZERO_PARTIALS, "zero_partials") X(RENDER_BWD, "render_backward") X(BWD_PREPROCESS, "backward_preprocess")                \
+    X(RENDER_DEPTH_BWD, "render_depth_backward") X(DEPTH_BWD_FOLD, "depth_backward_fold")                                      \
     X(WDIST, "weighted_distance") X(VQ_ACC, "vq_accumulate") X(VQ_APPLY, "vq_apply") X(LOSS_FWD, "l1_ssim_forward")            \
     X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
     X(QAT_VISIBLE, "qat_visible") X(QAT_POINTS, "qat_points") X(QAT_POINTS_BWD, "qat_points_backward")                         \
@@ -303,8 +304,11 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
 
 static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int32_t* radii, const void* geom_buffer,
                          const void* binning_buffer, const void* image_buffer, int32_t R, const float* dL_dout_color,
-                         c3dgs_resize_fn ws_resize, void* ws_user, const c3dgs_raster_grads* grads, void* stream_)
+                         c3dgs_resize_fn ws_resize, void* ws_user, const c3dgs_raster_grads* grads, void* stream_,
+                         const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr)
 {
+    // gradients through the depth / alpha maps (render_depth_backward.hip): without a map, exactly the plain backward below
+    const bool maps = dL_ddepth != nullptr || dL_dalpha != nullptr;
     if (int rc = validate(pp, indexed, true)) return rc;
     if (!grads) return fail(C3DGS_E_INVALID, "grads is NULL");
     c3dgs_raster_params p = *pp;
@@ -336,16 +340,22 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
         }
     }
     if (P == 0) return C3DGS_OK;
-    if (!radii || !geom_buffer || !image_buffer || !dL_dout_color || (R > 0 && !binning_buffer))
+    if (!radii || !geom_buffer || !image_buffer || (!dL_dout_color && !maps) || (R > 0 && !binning_buffer))
         return fail(C3DGS_E_INVALID, "radii, forward buffers and dL_dout_color are required");
     if (!ws_resize) return fail(C3DGS_E_INVALID, "workspace callback is required");
     if (R < 0) return fail(C3DGS_E_INVALID, "R must be >= 0");
 
     const GeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
     const ImgPtrs img = img_ptrs(const_cast<void*>(image_buffer), W, H);
-    void* ws_base = ws_resize(ws_user, c3dgs_backward_workspace_bytes(P, R));
+    uint32_t* sort_err = maps ? onesweep_error_word() : nullptr;
+    if (maps && !sort_err) return fail(C3DGS_E_HIP, "cannot resolve the sort error word");
+    // with maps: the same layout and, behind it, the dL/dz plane
+    void* ws_base = ws_resize(ws_user, maps ? depth_backward_layout(P, R).total_bytes : c3dgs_backward_workspace_bytes(P, R));
     if (!ws_base) return fail(C3DGS_E_ALLOC, "backward workspace allocation failed");
     const BwdPtrs w = bwd_ptrs(ws_base, P, R);
+    float* dz_plane = maps ? (float*)((char*)ws_base + depth_backward_layout(P, R).dz) : nullptr;
+    // the colour blend launch: always without maps; with maps only where the loss uses the image
+    const bool blend = R > 0 && dL_dout_color != nullptr;
 
     // only the 1-byte "written" flags are cleared (R bytes, not 36 R): the blend kernel never visits the instances
     // behind each tile's saturation point (73 % of them on the bench scene) and the per-Gaussian kernel skips them.
@@ -354,14 +364,21 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
     // slice per tile workgroup: that kernel is bound by vector issue and leaves the memory system idle (without a blend launch
     // the clear stays here)
     { StageTimer t_(ST_ZERO_PARTIALS, s);
-      launch_backward_prep(R > 0 ? W : 0, H, img, w.touched, w.touched_bytes / 16, R > 0 ? nullptr : cb_zero, R > 0 ? 0 : cb_zero16, s); }
+      launch_backward_prep(blend ? W : 0, H, img, w.touched, w.touched_bytes / 16, blend ? nullptr : cb_zero, blend ? 0 : cb_zero16, s); }
     if (R > 0) {
-        const BinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), R, W, H);
-        C3DGS_TIMED_STAGE(ST_RENDER_BWD, p.debug, s,
-                          launch_render_backward(W, H, img, g.splat, g.block_base, p.background, dL_dout_color, w.partials, w.touched,
-                                                 compact_ptrs(b, R), cb_zero, cb_zero16, s)); // K10
+        const CompactPtrs cl = compact_ptrs(bin_ptrs(const_cast<void*>(binning_buffer), R, W, H), R);
+        if (blend)
+            C3DGS_TIMED_STAGE(ST_RENDER_BWD, p.debug, s,
+                              launch_render_backward(W, H, img, g.splat, g.block_base, p.background, dL_dout_color, w.partials, w.touched,
+                                                     cl, cb_zero, cb_zero16, s)); // K10
+        if (maps)
+            C3DGS_TIMED_STAGE(ST_RENDER_DEPTH_BWD, p.debug, s,
+                              launch_render_depth_backward(W, H, img, cl, g, w, dz_plane, dL_ddepth, dL_dalpha, sort_err, s));
     }
     C3DGS_TIMED_STAGE(ST_BWD_PREPROCESS, p.debug, s, launch_backward_preprocess(p, radii, g, w, *grads, s)); // K11 + K12(i)
+    if (maps && R > 0 && grads->dL_dmeans3D)
+        C3DGS_TIMED_STAGE(ST_DEPTH_BWD_FOLD, p.debug, s,
+                          launch_depth_backward_fold(P, g, w, dz_plane, p.viewmatrix, grads->dL_dmeans3D, sort_err, s));
     return C3DGS_OK;
 }
 
@@ -526,6 +543,28 @@ int c3dgs_rasterize_gaussians_backward_indexed(const c3dgs_raster_params* p, con
     return backward_impl(p, true, radii, geom_buffer, binning_buffer, image_buffer, R, dL_dout_color, workspace_resize,
                          workspace_user, grads, stream);
 }
+
+int c3dgs_rasterize_gaussians_backward_depth(const c3dgs_raster_params* p, const int32_t* radii, const void* geom_buffer,
+                                             const void* binning_buffer, const void* image_buffer, int32_t R,
+                                             const float* dL_dout_color, const float* dL_ddepth, const float* dL_dalpha,
+                                             c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                             const c3dgs_raster_grads* grads, void* stream)
+{
+    return backward_impl(p, false, radii, geom_buffer, binning_buffer, image_buffer, R, dL_dout_color, workspace_resize,
+                         workspace_user, grads, stream, dL_ddepth, dL_dalpha);
+}
+
+int c3dgs_rasterize_gaussians_backward_depth_indexed(const c3dgs_raster_params* p, const int32_t* radii, const void* geom_buffer,
+                                                     const void* binning_buffer, const void* image_buffer, int32_t R,
+                                                     const float* dL_dout_color, const float* dL_ddepth, const float* dL_dalpha,
+                                                     c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                                     const c3dgs_raster_grads* grads, void* stream)
+{
+    return backward_impl(p, true, radii, geom_buffer, binning_buffer, image_buffer, R, dL_dout_color, workspace_resize,
+                         workspace_user, grads, stream, dL_ddepth, dL_dalpha);
+}
+
+size_t c3dgs_depth_backward_workspace_bytes(int32_t P, int32_t R) { return depth_backward_layout(P, R).total_bytes; }
 
 int c3dgs_render_depth(int32_t P, int32_t W, int32_t H, int32_t R, const void* geom_buffer, const void* binning_buffer,
                        const void* image_buffer, float* out_depth, float* out_alpha, float* out_median, void* stream)

@@ -171,6 +171,20 @@ inline void backward_layout(int P, int R, c3dgs_backward_layout* L)
     L->total_bytes = o;
 }
 
+// Workspace of a backward with depth / alpha map gradients (render_depth_backward.hip): the backward's layout above, unchanged and
+// at the same offsets, and behind it the dL/dz plane, f32 [R], in the slot numbering of the partials. The plane is never cleared:
+// an element means something only where the slot's "written" flag is set behind render_depth_backward_kernel.
+struct DepthBackwardLayout { size_t dz, total_bytes; };
+inline DepthBackwardLayout depth_backward_layout(int P, int R)
+{
+    c3dgs_backward_layout B; backward_layout(P, R, &B);
+    const size_t r = (size_t)(R > 0 ? R : 1);
+    DepthBackwardLayout L;
+    L.dz = B.total_bytes;
+    L.total_bytes = align_up(L.dz + r * sizeof(float));
+    return L;
+}
+
 // Blend-statistics workspace (render_contrib.hip): one {sum, max, hits} record per backward slot, f32 f32 u32 [R] | their
 // 1-byte "written" flags. Same slot numbering as the backward's partials; only the flags are cleared per call.
 struct ContribSlot { float sum, max; uint32_t hits; };
@@ -347,6 +361,15 @@ void launch_render_backward(int W, int H, const ImgPtrs& img, const float4* spla
 // render_depth.hip (forward-only replay of the blend: depth / accumulated opacity / median depth; null outputs are skipped)
 void launch_render_depth(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const float4* splat, const uint32_t* depth_keys,
                          float* out_depth, float* out_alpha, float* out_median, const uint32_t* sort_err, hipStream_t s);
+// render_depth_backward.hip (gradients through the depth / alpha maps; either map may be null = zeros): the blend replay that adds
+// its six moments into the backward's partial-sum slots (behind render_backward or the flag clear, in front of
+// launch_backward_preprocess) and writes the dL/dz plane, and the fold of that plane into dL_dmeans3D behind
+// launch_backward_preprocess (it walks that launch's lists of blended Gaussians).
+void launch_render_depth_backward(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const BwdPtrs& w,
+                                  float* dz_plane, const float* dL_ddepth, const float* dL_dalpha, const uint32_t* sort_err,
+                                  hipStream_t s);
+void launch_depth_backward_fold(int P, const GeomPtrs& g, const BwdPtrs& w, const float* dz_plane, const float* view,
+                                float* dL_dmeans3D, const uint32_t* sort_err, hipStream_t s);
 // render_contrib.hip (forward-only replay of the blend: per-Gaussian sum / max of alpha T and blended-pair count; null outputs are
 // skipped): the blend replay into the slots (the caller has cleared w.touched on the stream), the per-Gaussian fold of the slots,
 // and the fold of one view's rows into model-sized accumulators.

@@ -118,17 +118,33 @@ __device__ __forceinline__ void transpose_step(float* v, bool hi, Op op)
 //   then three plain levels over the 8 pixel rows: row_ror:8, v_permlane16_swap, v_permlane32_swap
 // Both operands of every combination are the same in the two lanes of a pair and op is commutative: all lanes that hold a
 // candidate hold the same bits, and the order of the float sum is the network's, not the timing's.
+// The network's two halves are also used apart (render_depth_backward.hip forms the y-moments of a pixel row between them, as
+// render_backward_kernel does between its column and row levels: the same pairings, so the same sums).
+// columns: v[0..7] -> the reduction over the 8 pixels of this lane's pixel ROW of candidate beta(lane), in all 8 lanes of the row
 template <class Op>
-__device__ __forceinline__ float reduce_row_of_8(float* v, int lane, Op op)
+__device__ __forceinline__ float reduce_columns_of_8(float* v, int lane, Op op)
 {
     transpose_step<8, 0x141>(v, (lane & 4) != 0, op);
     transpose_step<4, 0xB1>(v, (lane & 1) != 0, op);
     transpose_step<2, 0x4E>(v, (lane & 2) != 0, op);
-    float r = op(v[0], dpp_get<0x128>(v[0]));
+    return v[0];
+}
+
+// rows: this lane's row value -> the reduction over the 8 pixel rows that share the lane's column
+template <class Op>
+__device__ __forceinline__ float reduce_rows_of_8(float r, Op op)
+{
+    r = op(r, dpp_get<0x128>(r));
     auto s0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(r), __float_as_uint(r), false, false);
     r = op(__uint_as_float(s0[0]), __uint_as_float(s0[1]));
     auto s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(r), __float_as_uint(r), false, false);
     return op(__uint_as_float(s1[0]), __uint_as_float(s1[1]));
+}
+
+template <class Op>
+__device__ __forceinline__ float reduce_row_of_8(float* v, int lane, Op op)
+{
+    return reduce_rows_of_8(reduce_columns_of_8(v, lane, op), op);
 }
 
 } // namespace c3dgs

@@ -1277,7 +1277,7 @@ class GaussianModel:
     # ---- render (gaussian_model.py:766-886)
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, clamp_color=True,
                cov3d=None, gather_visible=True, return_depth=False, return_contrib=False, error_target=None,
-               pose_grad="reference"):
+               pose_grad="reference", depth_grad=False):
         """pose_grad: what a camera pose that requires grad receives. "reference" (the default): the reference's formula on the
         indexed rasterizer (rasterizer.camera_pose_jacobian_sum), nothing on the other. "exact": the gradient of the render itself
         on both (rasterizer._C.pose_grad, one pass behind the backward). A pose that does not require grad costs nothing either way.
@@ -1288,7 +1288,13 @@ class GaussianModel:
         "contrib_rank" (see _extra_keys); forward-only as well.
         error_target=[3, H, W] fp32 device tensor (the view's ground truth): the dict also carries "error_sum", per Gaussian the
         sum of alpha T x mean |render - target| over the pairs the forward blended (rasterizer._C.render_error), indexed like
-        "radii", and "error_rank" (the same convention as "contrib_rank"); forward-only as well."""
+        "radii", and "error_rank" (the same convention as "contrib_rank"); forward-only as well.
+        depth_grad=True: the keys of return_depth, but "depth" and "alpha" carry gradient to the model's parameters, on the fused
+        indexed and the composed path alike (GaussianRasterizationSettings(depth_grad=True), csrc/render_depth_backward.hip);
+        "median_depth" stays non-differentiable. The pose receives no gradient on this path, whatever `pose_grad` says: a camera
+        pose that requires grad raises ValueError (not covered yet)."""
+        if depth_grad and viewpoint_camera.extrinsic_vector.requires_grad:
+            raise ValueError("render(depth_grad=True): the gradient to a camera pose that requires grad is not covered yet")
         if pipe.convert_SHs_python and override_color is None:
             raise NotImplementedError("convert_SHs_python: SH evaluation in Python is outside the mirrored render path")
         if pose_grad not in ("reference", "exact"):
@@ -1298,7 +1304,7 @@ class GaussianModel:
             intrinsic=viewpoint_camera.intrinsic.to(dev), extrinsic_vector=viewpoint_camera.extrinsic_vector.to(dev),
             bg=bg_color.to(dev), scale_modifier=scaling_modifier, sh_degree=self.active_sh_degree, prefiltered=False,
             debug=pipe.debug, clamp_color=clamp_color, depth=bool(return_depth), contrib=bool(return_contrib),
-            error_target=error_target)
+            error_target=error_target, depth_grad=bool(depth_grad))
         indexed = self.color_index_mode == ColorMode.ALL_INDEXED and self.is_gaussian_indexed
         fused = indexed and self.use_factor_scaling and cov3d is None and override_color is None and \
             not pipe.compute_cov3D_python
@@ -1346,6 +1352,8 @@ class GaussianModel:
         # (the host has ~0.2 ms of Python between the visible count's arrival and the rasterizer's first launch, and the GPU
         # idles for the part of it the getter kernels do not cover)
         rasterize = _rz.rasterize_gaussians_indexed_camera_exact if pose_grad == "exact" else _rz.rasterize_gaussians_indexed_camera
+        if settings.depth_grad:            # no pose gradient with the maps' gradient (render() has refused a pose that wants one)
+            rasterize = _rz.rasterize_gaussians_indexed
         image, radii, *extras = rasterize(means3D, means2D, shs, sh_idx, g_idx, _rz._empty(), opac, scales_n, sfac, rotations,
                                           _rz._empty(), settings, settings.extrinsic_vector)
         return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
@@ -1357,7 +1365,7 @@ class GaussianModel:
         settings.contrib the three per-Gaussian rows and "contrib_rank" (int32 [P]: the row of a visible Gaussian in them, or
         None when they are indexed by Gaussian), then under settings.error_target "error_sum" and "error_rank" (the same rank)"""
         scored = settings.error_target is not None
-        names = (("depth", "alpha", "median_depth") if settings.depth else ()) + \
+        names = (("depth", "alpha", "median_depth") if (settings.depth or settings.depth_grad) else ()) + \
             (("contrib_sum", "contrib_max", "contrib_hits") if settings.contrib else ()) + (("error_sum",) if scored else ())
         assert len(names) == len(extras)
         out = dict(zip(names, extras))
@@ -1472,8 +1480,11 @@ class GaussianModel:
         means3D = self.get_xyz
         opacity = self.get_opacity
         exact = pose_grad == "exact"
-        rasterizer = GaussianRasterizerIndexed(raster_settings=settings, optimize_camera="exact" if exact else True) if indexed \
-            else GaussianRasterizer(raster_settings=settings, optimize_camera="exact" if exact else False)
+        if settings.depth_grad:            # no pose gradient with the maps' gradient (render() has refused a pose that wants one)
+            rasterizer = (GaussianRasterizerIndexed if indexed else GaussianRasterizer)(raster_settings=settings, optimize_camera=False)
+        else:
+            rasterizer = GaussianRasterizerIndexed(raster_settings=settings, optimize_camera="exact" if exact else True) if indexed \
+                else GaussianRasterizer(raster_settings=settings, optimize_camera="exact" if exact else False)
         scales = rotations = None
         cov3D_precomp = cov3d
         if cov3D_precomp is None:

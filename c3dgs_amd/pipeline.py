@@ -181,7 +181,7 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
 
 
 def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, degree_up_iter=1000, *, densify_by="grad",
-          error_threshold=None, optimizer_type=None, optimizer_visibility="radii"):
+          error_threshold=None, optimizer_type=None, optimizer_visibility="radii", lambda_depth=0.0, lambda_alpha=0.0):
     """train.py:15-173 without its disabled compression-statistics branch: optimise a non-indexed model (usually
     GaussianModel.load_ply of a point cloud) with adaptive density control.
 
@@ -211,7 +211,16 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     leaves the parameters and moments of all others as they are. `optimizer_visibility` names what "saw" means and is used
     with that optimizer only: "radii" (upstream's rule) lists the rows with radii > 0; "blended" lists the rows at least one
     pixel blended, the `contrib_hits` of a render with return_contrib=True, which costs the contribution pass
-    (csrc/render_contrib.hip) in every view; None steps every row (the dense step through the sparse optimizer)."""
+    (csrc/render_contrib.hip) in every view; None steps every row (the dense step through the sparse optimizer).
+
+    `lambda_depth`, `lambda_alpha` (not in the reference) add losses on the depth and alpha maps of render(depth_grad=True)
+    (csrc/render_depth_backward.hip) for the views whose camera object carries a target, attached by the caller as [H, W] fp32:
+    `alpha_target` (a mask or silhouette) adds lambda_alpha x mean |alpha - alpha_target|; `depth_target` (0 = no measurement)
+    adds lambda_depth x the mean over the measured pixels of |depth - alpha x depth_target|, a residual in weight space (depth is
+    sum alpha T z, not normalised), so nothing is divided. Both at 0 (the default), and views without the attributes, run the
+    loop above with its launches."""
+    if lambda_depth < 0 or lambda_alpha < 0:
+        raise ValueError("train: lambda_depth and lambda_alpha must be >= 0")
     if optimizer_visibility not in ("radii", "blended", None):
         raise ValueError(f"train: optimizer_visibility must be 'radii', 'blended' or None, not {optimizer_visibility!r}")
     if densify_by not in ("grad", "error"):
@@ -226,7 +235,7 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     gaussians.training_setup(opt, optimizer_type=optimizer_type)
     gaussians.update_learning_rate(0)
     sparse = isinstance(gaussians.optimizer, _optim.SparseGaussianAdam) and optimizer_visibility is not None
-    extra = {"return_contrib": True} if sparse and optimizer_visibility == "blended" else {}
+    extra_base = {"return_contrib": True} if sparse and optimizer_visibility == "blended" else {}
     dev = gaussians.device
     bg = torch.rand(3, device=dev) if opt.random_background else torch.tensor([0, 0, 0], dtype=torch.float32, device=dev)
     ema_loss_for_log = 0.0
@@ -249,6 +258,9 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             cov3d = (cov3d_scaled / coeff).requires_grad_(True)
             # every row goes to the rasterizer (it culls them itself): radii and the screen-space gradient are then indexed
             # by Gaussian, which is what the reference scatters them back to (train.py:103-105)
+            alpha_target = getattr(viewpoint_cam, "alpha_target", None) if lambda_alpha > 0 else None
+            depth_target = getattr(viewpoint_cam, "depth_target", None) if lambda_depth > 0 else None
+            extra = dict(extra_base, depth_grad=True) if (alpha_target is not None or depth_target is not None) else extra_base
             if by_error:
                 gt_image = viewpoint_cam.original_image.to(dev)
                 render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False,
@@ -260,10 +272,17 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             if not by_error:
                 gt_image = viewpoint_cam.original_image.to(image.device)
             loss = _loss.l1_ssim_loss(image, gt_image, opt.lambda_dssim)
+            if alpha_target is not None:
+                loss = loss + lambda_alpha * (render_pkg["alpha"] - alpha_target.to(dev)).abs().mean()
+            if depth_target is not None:
+                target = depth_target.to(dev)
+                measured = target > 0
+                residual = ((render_pkg["depth"] - render_pkg["alpha"] * target).abs() * measured).sum()
+                loss = loss + lambda_depth * residual / measured.sum().clamp(min=1)
             loss.backward()
             pending.append(loss.detach())
             if sparse:
-                gaussians.optimizer.step(render_pkg["contrib_hits"] if extra else radii)
+                gaussians.optimizer.step(render_pkg["contrib_hits"] if extra_base else radii)
             else:
                 gaussians.optimizer.step()
             gaussians.optimizer.zero_grad(set_to_none=True)

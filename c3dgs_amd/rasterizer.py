@@ -15,7 +15,8 @@ forward blended (forward-only, csrc/render_contrib.hip); `GaussianRasterizationS
 `_C.error_map_l1` add every Gaussian's error score, the sum of alpha T x a per-pixel error map (forward-only,
 csrc/render_error.hip); `GaussianRasterizer(rs, optimize_camera="exact")` / `GaussianRasterizerIndexed(rs, optimize_camera="exact")`
 / `_C.pose_grad` give the exact gradient of the render with respect to the 7-element pose (csrc/pose_grad.hip, one pass behind
-the backward), where `optimize_camera=True` keeps the reference's formula.
+the backward), where `optimize_camera=True` keeps the reference's formula; `GaussianRasterizationSettings(depth_grad=True)` makes
+the depth and alpha maps differentiable outputs (csrc/render_depth_backward.hip, one blend replay and one fold in the backward).
 
 PyTorch is plumbing only here (device memory, streams, autograd bookkeeping); every numeric stage
 runs in libc3dgs_hip.so.  There is no CPU path: tensors must live on the GPU.
@@ -316,12 +317,25 @@ def _forward(indexed, background, means3D, colors, opacity, scales, scale_factor
 
 def _backward(indexed, background, means3D, radii, colors, scales, scale_factors, rotations, scale_modifier, cov3D_precomp,
               viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-              imageBuffer, debug, sh_indices, g_indices, skip=()):
-    """`skip`: names among ("dL_dcolors", "dL_dcov3D") that are neither allocated nor written and come back as None. The
+              imageBuffer, debug, sh_indices, g_indices, skip=(), dL_ddepth=None, dL_dalpha=None):
+    """`dL_ddepth` / `dL_dalpha`: [H, W] fp32 gradients of the depth / alpha maps of _C.render_depth, or None. With either, the call
+    goes to the library's *_backward_depth entry (csrc/render_depth_backward.hip: one blend replay in front of the per-Gaussian
+    kernels, one small fold behind them) and `dL_dout_color` may be None (the loss does not use the image: no colour blend
+    launch). With neither it is the plain backward, launch for launch.
+    `skip`: names among ("dL_dcolors", "dL_dcov3D") that are neither allocated nor written and come back as None. The
     autograd wrappers name the gradients of ABSENT optional inputs: dL_dcolors (12 B x P) and dL_dcov3D (24 B x P) are
     108 MB of stores per 3M-Gaussian backward. The pybind-order entry points (_C.*) skip nothing, like the reference."""
     L = _lib.lib()
-    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))               # rasterize_points.cu:143-145
+    maps = dL_ddepth is not None or dL_dalpha is not None
+    if dL_dout_color is not None:
+        H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))           # rasterize_points.cu:143-145
+    elif maps:
+        H, W = (int(v) for v in (dL_ddepth if dL_ddepth is not None else dL_dalpha).shape)
+    else:
+        raise RuntimeError("dL_dout_color is required")
+    for name, m in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha)):
+        if m is not None:
+            _check_map(m, (H, W), means3D.device, name)
     # opacities are not an input of the reference's backward either (they live in the geometry buffer)
     p, t = _params(background=background, means3D=means3D, colors=colors, opacity=None, scales=scales,
                    scale_factors=scale_factors, rotations=rotations, scale_modifier=scale_modifier,
@@ -364,11 +378,16 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
         radii_c = radii.contiguous()
         dpix = _optional(dL_dout_color, "dL_dout_color")
         scratch = _Scratch(dev)
-        fn = L.c3dgs_rasterize_gaussians_backward_indexed if indexed else L.c3dgs_rasterize_gaussians_backward
+        if maps:
+            fn = L.c3dgs_rasterize_gaussians_backward_depth_indexed if indexed else L.c3dgs_rasterize_gaussians_backward_depth
+            extra = (_ptr(dL_ddepth), _ptr(dL_dalpha))
+        else:
+            fn = L.c3dgs_rasterize_gaussians_backward_indexed if indexed else L.c3dgs_rasterize_gaussians_backward
+            extra = ()
         rc = fn(C.byref(p), radii_c.data_ptr() if P > 0 else None,
                 geomBuffer.data_ptr() if geomBuffer.numel() else None,
                 binningBuffer.data_ptr() if binningBuffer.numel() else None,
-                imageBuffer.data_ptr() if imageBuffer.numel() else None, int(R), _ptr(dpix),
+                imageBuffer.data_ptr() if imageBuffer.numel() else None, int(R), _ptr(dpix), *extra,
                 scratch.callback("ws"), None, C.byref(g), _stream(dev))
     scratch.release()       # the workspace goes back to the (stream-ordered) caching allocator right away
     _lib.check(rc)
@@ -399,19 +418,19 @@ def _c_rasterize_gaussians_indexed(background, means3D, colors, opacity, scales,
 
 def _c_rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                                    geomBuffer, R, binningBuffer, imageBuffer, debug, skip=()):
+                                    geomBuffer, R, binningBuffer, imageBuffer, debug, skip=(), dL_ddepth=None, dL_dalpha=None):
     return _backward(False, background, means3D, radii, colors, scales, None, rotations, scale_modifier, cov3D_precomp,
                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
-                     binningBuffer, imageBuffer, debug, None, None, skip)
+                     binningBuffer, imageBuffer, debug, None, None, skip, dL_ddepth, dL_dalpha)
 
 
 def _c_rasterize_gaussians_backward_indexed(background, means3D, radii, colors, scales, scale_factors, rotations,
                                             scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                                             dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-                                            debug, sh_indices, g_indices, skip=()):
+                                            debug, sh_indices, g_indices, skip=(), dL_ddepth=None, dL_dalpha=None):
     return _backward(True, background, means3D, radii, colors, scales, scale_factors, rotations, scale_modifier,
                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer,
-                     R, binningBuffer, imageBuffer, debug, sh_indices, g_indices, skip)
+                     R, binningBuffer, imageBuffer, debug, sh_indices, g_indices, skip, dL_ddepth, dL_dalpha)
 
 
 def _c_mark_visible(means3D, viewmatrix, projmatrix):
@@ -658,7 +677,8 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     # with `raster_settings.depth`: the (depth, alpha, median) maps, queued right behind the forward on the same stream;
     # otherwise no launch
     extras = ()
-    if getattr(rs, "depth", False):
+    depth_grad = bool(getattr(rs, "depth_grad", False))
+    if getattr(rs, "depth", False) or depth_grad:
         extras = _C.render_depth(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer)
     # with `raster_settings.contrib`: (weight_sum, weight_max, hits) per Gaussian, behind whatever `depth` added
     if getattr(rs, "contrib", False):
@@ -678,8 +698,10 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     ctx.image_shape = tuple(color.shape)
     # without this, autograd hands backward a zero-filled int32[P] "gradient" for radii on every call (a 12 MB fill at P = 3M)
     ctx.set_materialize_grads(False)
-    # the extras are forward-only: non-differentiable like radii, no gradient flows through them
-    ctx.mark_non_differentiable(radii, *extras)
+    # the extras are forward-only: non-differentiable like radii, no gradient flows through them -- except, with
+    # `raster_settings.depth_grad`, the depth and alpha maps (outputs 2 and 3), whose gradients the backward takes
+    ctx.depth_grad = depth_grad
+    ctx.mark_non_differentiable(radii, *(extras[2:] if depth_grad else extras))
     return (color, radii) + tuple(extras)
 
 
@@ -691,7 +713,15 @@ def _fit(grad, inp):
     return grad
 
 
-def _autograd_backward(ctx, grad_out_color, exact_pose=False):
+def _map_grads(ctx, params):
+    """(dL_ddepth, dL_dalpha) among the gradients of the outputs behind the image (radii, depth, alpha, median, ...): what the
+    loss sent through the two maps of a `depth_grad` forward, as contiguous fp32, or (None, None)."""
+    if not getattr(ctx, "depth_grad", False):
+        return None, None
+    return tuple(None if g is None else g.to(torch.float32).contiguous() for g in params[1:3])
+
+
+def _autograd_backward(ctx, grad_out_color, exact_pose=False, map_grads=(None, None)):
     """backward of the Functions -> the gradients BY THE NAME OF THE forward INPUT they belong to (None for an absent
     input); each Function lays them out in its own input order. `args`: pybind order again (snapshot_bw.dump).
     `exact_pose`: the pose requires grad in exact mode. Then dL_dcov3D (and, with SH, dL_dcolors) are not skipped, _C.pose_grad is
@@ -700,7 +730,9 @@ def _autograd_backward(ctx, grad_out_color, exact_pose=False):
     rs = ctx.raster_settings
     (extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
      binningBuffer, imgBuffer, sh_indices, g_indices) = ctx.saved_tensors
-    if grad_out_color is None:
+    grad_depth, grad_alpha = map_grads
+    maps = dict(dL_ddepth=grad_depth, dL_dalpha=grad_alpha) if (grad_depth is not None or grad_alpha is not None) else {}
+    if grad_out_color is None and not maps:
         # set_materialize_grads(False): an image nobody differentiated through arrives as None (backward still runs when only
         # `radii` was used downstream of a graph that needs grad); the library wants a dense dL/dC
         grad_out_color = torch.zeros(ctx.image_shape, dtype=torch.float32, device=means3D.device)
@@ -716,13 +748,13 @@ def _autograd_backward(ctx, grad_out_color, exact_pose=False):
                 imgBuffer, rs.debug, sh_indices, g_indices)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_scale_factors, grad_rotations) = _call_debug(_C.rasterize_gaussians_backward_indexed, args, rs.debug,
-                                                           "snapshot_bw.dump", skip=skip)
+                                                           "snapshot_bw.dump", skip=skip, **maps)
     else:
         args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
                 tanfovx, tanfovy, grad_out_color, sh, rs.sh_degree, campos, geomBuffer, ctx.num_rendered, binningBuffer,
                 imgBuffer, rs.debug)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _call_debug(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump", skip=skip)
+         grad_rotations) = _call_debug(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump", skip=skip, **maps)
     grad_pose = None
     if exact_pose:
         # the indexed entry always carries both index tensors; the library wants each only with what it indexes
@@ -748,7 +780,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, *params):
-        g = _autograd_backward(ctx, grad_out_color)
+        g = _autograd_backward(ctx, grad_out_color, map_grads=_map_grads(ctx, params))
         return (g.means3D, g.means2D, g.sh, g.colors_precomp, g.opacities, g.scales, g.rotations, g.cov3Ds_precomp, None, None)
 
 
@@ -763,7 +795,7 @@ class _RasterizeGaussiansIndexed(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, *params):
-        g = _autograd_backward(ctx, grad_out_color)
+        g = _autograd_backward(ctx, grad_out_color, map_grads=_map_grads(ctx, params))
         return (g.means3D, g.means2D, g.sh, None, None, g.colors_precomp, g.opacities, g.scales, g.scale_factors, g.rotations,
                 g.cov3Ds_precomp, None, None)
 
@@ -887,6 +919,7 @@ def rasterize_gaussians_indexed(means3D, means2D, sh, sh_indices, g_indices, col
 
 def rasterize_gaussians_indexed_camera(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities, scales,
                                        scale_factors, rotations, cov3Ds_precomp, raster_settings, extrinsic_vector):
+    _check_depth_grad_camera(raster_settings, True)
     return _RasterizeGaussiansIndexedCamera.apply(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities,
                                                   scales, scale_factors, rotations, cov3Ds_precomp, raster_settings,
                                                   extrinsic_vector)
@@ -894,15 +927,24 @@ def rasterize_gaussians_indexed_camera(means3D, means2D, sh, sh_indices, g_indic
 
 def rasterize_gaussians_camera_exact(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      raster_settings, extrinsic_vector):
+    _check_depth_grad_camera(raster_settings, True)
     return _RasterizeGaussiansCameraExact.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                                 cov3Ds_precomp, raster_settings, extrinsic_vector)
 
 
 def rasterize_gaussians_indexed_camera_exact(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities, scales,
                                              scale_factors, rotations, cov3Ds_precomp, raster_settings, extrinsic_vector):
+    _check_depth_grad_camera(raster_settings, True)
     return _RasterizeGaussiansIndexedCameraExact.apply(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities,
                                                        scales, scale_factors, rotations, cov3Ds_precomp, raster_settings,
                                                        extrinsic_vector)
+
+
+def _check_depth_grad_camera(raster_settings, optimize_camera):
+    """`depth_grad` with a pose gradient is not covered yet: the maps' gradient does not reach the pose"""
+    if optimize_camera is not False and getattr(raster_settings, "depth_grad", False):
+        raise ValueError("depth_grad=True cannot be combined with optimize_camera: the gradient to the camera pose through the "
+                         "depth and alpha maps is not implemented")
 
 
 def _check_optimize_camera(value):
@@ -940,25 +982,35 @@ class GaussianRasterizationSettings(_SettingsFields):
     `error_target` (keyword only, default None) is a second such attribute: a [3, H, W] fp32 tensor on the device, the view's
     ground truth. With it the rasterizers queue _C.error_map_l1(color, error_target) and _C.render_error behind the forward and
     append (err_sum,), [P], behind whatever `depth` and `contrib` added; forward-only and non-differentiable, the backward is
-    unchanged. A wrong shape, dtype or device raises RuntimeError. None: no launch."""
+    unchanged. A wrong shape, dtype or device raises RuntimeError. None: no launch.
+    `depth_grad` (keyword only, default False) is a third such attribute. True implies the outputs of `depth=True`, in the same
+    position -- (color, radii, depth, alpha, median, ...) with the forward's bits -- and makes `depth` and `alpha` differentiable
+    outputs: a loss on them reaches every input the image reaches (csrc/render_depth_backward.hip: one blend replay and one small
+    fold added to the backward). `median` (piecewise constant) and `radii` stay non-differentiable. When neither map receives a
+    gradient the backward issues the plain backward's launches. The gradient to the camera pose through the maps is not covered
+    yet: with `depth_grad`, `optimize_camera` other than False raises ValueError."""
     contrib = False
     error_target = None
+    depth_grad = False
 
-    def __new__(cls, *args, contrib=False, error_target=None, **kwargs):
+    def __new__(cls, *args, contrib=False, error_target=None, depth_grad=False, **kwargs):
         n = len(cls._fields)
         if len(args) == n + 1:
             args, contrib = args[:n], args[n]
         self = super().__new__(cls, *args, **kwargs)
         self.contrib = bool(contrib)
         self.error_target = error_target
+        self.depth_grad = bool(depth_grad)
         return self
 
     def _replace(self, **kwargs):
         contrib = kwargs.pop("contrib", self.contrib)
         error_target = kwargs.pop("error_target", self.error_target)
+        depth_grad = kwargs.pop("depth_grad", self.depth_grad)
         new = super()._replace(**kwargs)
         new.contrib = bool(contrib)
         new.error_target = error_target
+        new.depth_grad = bool(depth_grad)
         return new
 
 
@@ -1009,9 +1061,11 @@ class GaussianRasterizer(_Rasterizer):
             raise ValueError('GaussianRasterizer: optimize_camera must be False or "exact" (the reference formula exists for '
                              'the indexed rasterizer only)')
         self.optimize_camera = _check_optimize_camera(optimize_camera)
+        _check_depth_grad_camera(raster_settings, self.optimize_camera)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, extrinsic_vector=None, extrinsic=None):
+        _check_depth_grad_camera(self.raster_settings, self.optimize_camera)
         _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
         if extrinsic_vector is None:
             extrinsic_vector = extrinsic if extrinsic is not None else self.raster_settings.extrinsic_vector
@@ -1029,9 +1083,11 @@ class GaussianRasterizerIndexed(_Rasterizer):
     def __init__(self, raster_settings, optimize_camera=False):
         super().__init__(raster_settings)
         self.optimize_camera = optimize_camera
+        _check_depth_grad_camera(raster_settings, bool(optimize_camera))
 
     def forward(self, means3D, means2D, opacities, sh_indices, g_indices, shs=None, colors_precomp=None, scales=None,
                 scale_factors=None, rotations=None, cov3D_precomp=None, extrinsic_vector=None):
+        _check_depth_grad_camera(self.raster_settings, bool(self.optimize_camera))
         _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
         if extrinsic_vector is None:
             extrinsic_vector = self.raster_settings.extrinsic_vector

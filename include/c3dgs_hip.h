@@ -135,6 +135,35 @@ int c3dgs_rasterize_gaussians_backward_indexed(const c3dgs_raster_params* p, con
                                                c3dgs_resize_fn workspace_resize, void* workspace_user,
                                                const c3dgs_raster_grads* grads, void* stream);
 
+/* ---- the two backward entries with gradients through the depth and alpha maps of c3dgs_render_depth
+ * (csrc/render_depth_backward.hip; no reference counterpart) ----
+ * The arguments of the entries above plus dL_ddepth and dL_dalpha, [H,W] fp32 device maps: dL/d(out_depth) and dL/d(out_alpha)
+ * of the forward that filled the buffers. Either may be NULL (zeros). out_median is piecewise constant: no gradient.
+ * With both maps NULL the call IS the entry above: the same validation, workspace request, launches and bits.
+ * With a map, dL_dout_color may be NULL (the loss does not use the image): then the colour blend launch is left out. Per pixel,
+ * over the entries k the forward blended, with c_k = dL_ddepth z_k + dL_dalpha:
+ *   dL/dalpha_k = T_k c_k - (sum_{j>k} w_j c_j) / (1 - alpha_k),      dL/dz_g = sum over the pixels of w_k dL_ddepth
+ * and from dL/dalpha_k the chain of the colour backward (its clamp, skip and stop conventions; dL_dmeans2D in its units). One blend
+ * replay (stage "render_depth_backward") adds its sums into the colour backward's per-(Gaussian, tile) partial sums in front of
+ * "backward_preprocess", which then writes every gradient of `grads` as always; one small launch behind it (stage
+ * "depth_backward_fold") adds dL/dz_g x the depth row of p->viewmatrix into grads->dL_dmeans3D (skipped when that is NULL).
+ * No float atomics beyond the colour backward's own codebook scatter-adds; without those (non-indexed) bitwise reproducible.
+ * The workspace callback is asked for c3dgs_depth_backward_workspace_bytes(P, R): the backward's layout, unchanged, and behind it
+ * the dL/dz plane, f32 [max(R, 1)]. The sort's time-out word set: the replay walks nothing and the fold writes NaN. */
+int c3dgs_rasterize_gaussians_backward_depth(const c3dgs_raster_params* p, const int32_t* radii,
+                                             const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                                             int32_t R, const float* dL_dout_color /*[3,H,W] | NULL with a map*/,
+                                             const float* dL_ddepth /*[H,W] | NULL*/, const float* dL_dalpha /*[H,W] | NULL*/,
+                                             c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                             const c3dgs_raster_grads* grads, void* stream);
+int c3dgs_rasterize_gaussians_backward_depth_indexed(const c3dgs_raster_params* p, const int32_t* radii,
+                                                     const void* geom_buffer, const void* binning_buffer,
+                                                     const void* image_buffer, int32_t R, const float* dL_dout_color,
+                                                     const float* dL_ddepth, const float* dL_dalpha,
+                                                     c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                                     const c3dgs_raster_grads* grads, void* stream);
+size_t c3dgs_depth_backward_workspace_bytes(int32_t P, int32_t R);
+
 /* ---- depth, accumulated opacity and median depth of a finished forward (csrc/render_depth.hip; no reference counterpart) ----
  * geom/binning/image buffers are the ones a forward of the same P, W, H filled; R is its num_rendered. Per pixel, over the
  * entries k = 1..m the forward blended (w_k = alpha_k T_k, T_{k+1} = T_k (1 - alpha_k), T_1 = 1, z_k = the fp32 view-space
@@ -148,8 +177,8 @@ int c3dgs_rasterize_gaussians_backward_indexed(const c3dgs_raster_params* p, con
  * output is NaN, like the forward's image). It writes nothing but its outputs. The backward only reads those fields too (its
  * scratch in the image buffer is tile_order, which this call does not use), so the call is valid before or after the
  * matching backward, with the same result.
- * A NULL output is skipped; at least one must be non-NULL. P == 0 or R == 0: zeros, no blend launch. Forward-only: no
- * gradient flows through these maps. Stage name: "render_depth". */
+ * A NULL output is skipped; at least one must be non-NULL. P == 0 or R == 0: zeros, no blend launch. Forward-only: the
+ * gradients of out_depth and out_alpha are what c3dgs_rasterize_gaussians_backward_depth(_indexed) take. Stage name: "render_depth". */
 int c3dgs_render_depth(int32_t P, int32_t W, int32_t H, int32_t R,
                        const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
                        float* out_depth /*[H,W] | NULL*/, float* out_alpha /*[H,W] | NULL*/,
