@@ -119,6 +119,8 @@ PROTOTYPES = {
     "c3dgs_render_error": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_vp] * 7),
     "c3dgs_pose_grad_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "c3dgs_pose_grad": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [_vp] * 17),
+    "c3dgs_aa_opacity": (C.c_int, [C.POINTER(RasterParams), _vp, _vp, _vp]),
+    "c3dgs_aa_opacity_backward": (C.c_int, [C.POINTER(RasterParams), _vp, C.POINTER(RasterGrads), _vp]),
     "c3dgs_error_map_l1": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_vp] * 4),
     "c3dgs_error_accumulate": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 6),
     "c3dgs_weighted_distance": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -41,6 +41,8 @@ SOURCES = {
     "vq.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + os.environ.get("C3DGS_VQ_FLAGS", "").split(),
     # the exact pose gradient rebuilds Sigma and the SH direction term with preprocess's / backward_preprocess's expressions (csrc/gsmath.hpp)
     "pose_grad.hip": ["-ffp-contract=off"],
+    # the opacity compensation of the antialiased mode forms the 2D covariance with preprocess's expressions (csrc/gsmath.hpp)
+    "aa_opacity.hip": ["-ffp-contract=off"],
     "draws.hip": [],
     "loss.hip": [],
     "metrics.hip": [],

@@ -33,7 +33,8 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
     X(QAT_VISIBLE, "qat_visible") X(QAT_POINTS, "qat_points") X(QAT_POINTS_BWD, "qat_points_backward")                         \
     X(QAT_CODEBOOKS_BWD, "qat_codebooks_backward") X(ADAM, "adam_step") X(KNN_SORT, "knn_sort") X(KNN_BOUNDS, "knn_bounds")    \
-    X(KNN_QUERY, "knn_query") X(SPARSE_ADAM_SELECT, "sparse_adam_select") X(SPARSE_ADAM_STEP, "sparse_adam_step")
+    X(KNN_QUERY, "knn_query") X(SPARSE_ADAM_SELECT, "sparse_adam_select") X(SPARSE_ADAM_STEP, "sparse_adam_step")              \
+    X(AA_OPACITY, "aa_opacity") X(AA_OPACITY_BWD, "aa_opacity_backward")
 #define C3DGS_X(id, name) ST_##id,
 enum Stage { C3DGS_STAGE_TABLE(C3DGS_X) ST_COUNT };
 #undef C3DGS_X
@@ -722,6 +723,46 @@ int c3dgs_pose_grad(int32_t P, int32_t D, int32_t M, float scale_modifier, const
         { StageTimer b_(ST_POSE_GRAD_FOLD, s); launch_pose_fold(P, (const float*)workspace, pose, out, s); }
     }
     C3DGS_STAGE_CHECK(ST_POSE_GRAD, 0, s);
+    return C3DGS_OK;
+}
+
+// what c3dgs_aa_opacity and c3dgs_aa_opacity_backward both ask of the params: the per-Gaussian projection's inputs
+static int aa_validate(const char* who, const c3dgs_raster_params* p)
+{
+    const std::string w(who);
+    if (!p) return fail(C3DGS_E_INVALID, w + ": params is NULL");
+    if (p->P < 0) return fail(C3DGS_E_INVALID, w + ": P must be >= 0");
+    const bool has_sr = p->scales != nullptr && p->rotations != nullptr;
+    if ((p->scales != nullptr) != (p->rotations != nullptr) || has_sr == (p->cov3D_precomp != nullptr))
+        return fail(C3DGS_E_INVALID, w + ": exactly one of the scale / rotation pair and cov3D_precomp is required");
+    if (p->g_indices && !p->scale_factors) return fail(C3DGS_E_INVALID, w + ": g_indices need scale_factors");
+    if (p->P == 0) return C3DGS_OK;
+    if (p->W <= 0 || p->H <= 0) return fail(C3DGS_E_INVALID, w + ": W and H must be positive");
+    if (!p->means3D || !p->opacities || !p->viewmatrix)
+        return fail(C3DGS_E_INVALID, w + ": means3D, opacities (the raw ones) and viewmatrix are required");
+    return C3DGS_OK;
+}
+
+int c3dgs_aa_opacity(const c3dgs_raster_params* p, float* opacity_out, float* rho, void* stream)
+{
+    if (int rc = aa_validate("aa_opacity", p)) return rc;
+    if (!opacity_out) return fail(C3DGS_E_INVALID, "aa_opacity: opacity_out is required");
+    if (p->P == 0) return C3DGS_OK;
+    C3DGS_TIMED_STAGE(ST_AA_OPACITY, p->debug, (hipStream_t)stream, launch_aa_opacity(*p, opacity_out, rho, (hipStream_t)stream));
+    return C3DGS_OK;
+}
+
+int c3dgs_aa_opacity_backward(const c3dgs_raster_params* p, const int32_t* radii, const c3dgs_raster_grads* grads, void* stream)
+{
+    if (int rc = aa_validate("aa_opacity_backward", p)) return rc;
+    if (!grads) return fail(C3DGS_E_INVALID, "aa_opacity_backward: grads is NULL");
+    if (!grads->dL_dopacity) return fail(C3DGS_E_INVALID, "aa_opacity_backward: grads->dL_dopacity is required");
+    if (p->cov3D_precomp && !grads->dL_dcov3D)
+        return fail(C3DGS_E_INVALID, "aa_opacity_backward: with cov3D_precomp, grads->dL_dcov3D is required");
+    if (p->P == 0) return C3DGS_OK;
+    if (!radii) return fail(C3DGS_E_INVALID, "aa_opacity_backward: radii is required");
+    C3DGS_TIMED_STAGE(ST_AA_OPACITY_BWD, p->debug, (hipStream_t)stream,
+                      launch_aa_opacity_backward(*p, radii, *grads, (hipStream_t)stream));
     return C3DGS_OK;
 }
 

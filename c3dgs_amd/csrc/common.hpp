@@ -401,6 +401,9 @@ struct PoseGradIn {
 size_t pose_grad_workspace_bytes(int P);
 void launch_pose_sums(const PoseGradIn& in, float* rows, hipStream_t s);
 void launch_pose_fold(int P, const float* rows, const float* pose, float* out, hipStream_t s);
+// aa_opacity.hip (antialiased rasterization: o' = o rho in front of the forward, the chain through rho behind the backward)
+void launch_aa_opacity(const c3dgs_raster_params& p, float* opacity_out, float* rho, hipStream_t s);
+void launch_aa_opacity_backward(const c3dgs_raster_params& p, const int32_t* radii, const c3dgs_raster_grads& gr, hipStream_t s);
 // backward_preprocess.hip
 void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,
                                 const c3dgs_raster_grads& gr, hipStream_t s);

@@ -102,15 +102,16 @@ __device__ __forceinline__ void cov3d_from_scale_rot(const float sx, const float
 }
 
 struct Cov2D {
-    float a, b, c;   // cov2D (0,0) (0,1) (1,1), low-pass included
+    float a, b, c;   // cov2D (0,0) (0,1) (1,1): low-pass included from cov2d(), not from cov2d_raw()
     m3 T;            // glm T = W*J: T.c[i][j] = (J*R_w2c)[i][j]
     f3 t;            // view-space mean with clamped x,y
     float txtz, tytz;
 };
 
-// forward.cu:82-121
-__device__ __forceinline__ Cov2D cov2d(const f3 mean, float fx, float fy, float tan_fovx, float tan_fovy,
-                                       const float cov3D[6], const float* __restrict__ view)
+// forward.cu:82-121 up to the low-pass: a, b, c are the entries of T^T Sigma T themselves (what csrc/aa_opacity.hip compares
+// with the dilated ones)
+__device__ __forceinline__ Cov2D cov2d_raw(const f3 mean, float fx, float fy, float tan_fovx, float tan_fovy,
+                                           const float cov3D[6], const float* __restrict__ view)
 {
     Cov2D o;
     f3 t = xform4x3(mean, view);
@@ -127,10 +128,20 @@ __device__ __forceinline__ Cov2D cov2d(const f3 mean, float fx, float fy, float 
     o.T = m3_mul(Wm, J);
     m3 Vrk = m3_cols(cov3D[0], cov3D[1], cov3D[2], cov3D[1], cov3D[3], cov3D[4], cov3D[2], cov3D[4], cov3D[5]);
     m3 cov = m3_mul(m3_mul(m3_t(o.T), m3_t(Vrk)), o.T);
-    o.a = cov.c[0][0] + 0.3f;
+    o.a = cov.c[0][0];
     o.b = cov.c[0][1];
-    o.c = cov.c[1][1] + 0.3f;
+    o.c = cov.c[1][1];
     o.t = t;
+    return o;
+}
+
+// forward.cu:82-121: the same with the 0.3 px^2 low-pass on the diagonal
+__device__ __forceinline__ Cov2D cov2d(const f3 mean, float fx, float fy, float tan_fovx, float tan_fovy,
+                                       const float cov3D[6], const float* __restrict__ view)
+{
+    Cov2D o = cov2d_raw(mean, fx, fy, tan_fovx, tan_fovy, cov3D, view);
+    o.a = o.a + 0.3f;
+    o.c = o.c + 0.3f;
     return o;
 }
 

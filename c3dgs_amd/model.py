@@ -297,12 +297,13 @@ class _QatGetters(torch.autograd.Function):
 
 
 class PipelineParams:
-    """The three switches GaussianModel.render reads from the reference's arguments.PipelineParams."""
+    """The three switches GaussianModel.render reads from the reference's arguments.PipelineParams, and `antialiasing`."""
 
-    def __init__(self, convert_SHs_python=False, compute_cov3D_python=False, debug=False):
+    def __init__(self, convert_SHs_python=False, compute_cov3D_python=False, debug=False, antialiasing=False):
         self.convert_SHs_python = convert_SHs_python
         self.compute_cov3D_python = compute_cov3D_python
         self.debug = debug
+        self.antialiasing = antialiasing      # upstream 3DGS's switch (not in the reference): render(antialiasing=None) reads it
 
 
 class GaussianModel:
@@ -1277,7 +1278,7 @@ class GaussianModel:
     # ---- render (gaussian_model.py:766-886)
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, clamp_color=True,
                cov3d=None, gather_visible=True, return_depth=False, return_contrib=False, error_target=None,
-               pose_grad="reference", depth_grad=False):
+               pose_grad="reference", depth_grad=False, antialiasing=None):
         """pose_grad: what a camera pose that requires grad receives. "reference" (the default): the reference's formula on the
         indexed rasterizer (rasterizer.camera_pose_jacobian_sum), nothing on the other. "exact": the gradient of the render itself
         on both (rasterizer._C.pose_grad, one pass behind the backward). A pose that does not require grad costs nothing either way.
@@ -1292,9 +1293,17 @@ class GaussianModel:
         depth_grad=True: the keys of return_depth, but "depth" and "alpha" carry gradient to the model's parameters, on the fused
         indexed and the composed path alike (GaussianRasterizationSettings(depth_grad=True), csrc/render_depth_backward.hip);
         "median_depth" stays non-differentiable. The pose receives no gradient on this path, whatever `pose_grad` says: a camera
-        pose that requires grad raises ValueError (not covered yet)."""
+        pose that requires grad raises ValueError (not covered yet).
+        antialiasing: None (the default) reads `pipe.antialiasing`; True multiplies every opacity by the compensation factor of the
+        rasterizer's 0.3 px^2 low-pass (GaussianRasterizationSettings(antialiasing=True), csrc/aa_opacity.hip), on the fused indexed
+        and the composed path alike, with gradients to the model's parameters. As with depth_grad, the pose receives no gradient
+        and a camera pose that requires grad raises ValueError."""
+        if antialiasing is None:
+            antialiasing = getattr(pipe, "antialiasing", False)
         if depth_grad and viewpoint_camera.extrinsic_vector.requires_grad:
             raise ValueError("render(depth_grad=True): the gradient to a camera pose that requires grad is not covered yet")
+        if antialiasing and viewpoint_camera.extrinsic_vector.requires_grad:
+            raise ValueError("render(antialiasing=True): the gradient to a camera pose that requires grad is not covered")
         if pipe.convert_SHs_python and override_color is None:
             raise NotImplementedError("convert_SHs_python: SH evaluation in Python is outside the mirrored render path")
         if pose_grad not in ("reference", "exact"):
@@ -1304,7 +1313,7 @@ class GaussianModel:
             intrinsic=viewpoint_camera.intrinsic.to(dev), extrinsic_vector=viewpoint_camera.extrinsic_vector.to(dev),
             bg=bg_color.to(dev), scale_modifier=scaling_modifier, sh_degree=self.active_sh_degree, prefiltered=False,
             debug=pipe.debug, clamp_color=clamp_color, depth=bool(return_depth), contrib=bool(return_contrib),
-            error_target=error_target, depth_grad=bool(depth_grad))
+            error_target=error_target, depth_grad=bool(depth_grad), antialiasing=bool(antialiasing))
         indexed = self.color_index_mode == ColorMode.ALL_INDEXED and self.is_gaussian_indexed
         fused = indexed and self.use_factor_scaling and cov3d is None and override_color is None and \
             not pipe.compute_cov3D_python
@@ -1352,7 +1361,7 @@ class GaussianModel:
         # (the host has ~0.2 ms of Python between the visible count's arrival and the rasterizer's first launch, and the GPU
         # idles for the part of it the getter kernels do not cover)
         rasterize = _rz.rasterize_gaussians_indexed_camera_exact if pose_grad == "exact" else _rz.rasterize_gaussians_indexed_camera
-        if settings.depth_grad:            # no pose gradient with the maps' gradient (render() has refused a pose that wants one)
+        if settings.depth_grad or settings.antialiasing:   # no pose gradient in these modes (render() has refused a pose that wants one)
             rasterize = _rz.rasterize_gaussians_indexed
         image, radii, *extras = rasterize(means3D, means2D, shs, sh_idx, g_idx, _rz._empty(), opac, scales_n, sfac, rotations,
                                           _rz._empty(), settings, settings.extrinsic_vector)
@@ -1480,7 +1489,7 @@ class GaussianModel:
         means3D = self.get_xyz
         opacity = self.get_opacity
         exact = pose_grad == "exact"
-        if settings.depth_grad:            # no pose gradient with the maps' gradient (render() has refused a pose that wants one)
+        if settings.depth_grad or settings.antialiasing:   # no pose gradient in these modes (render() has refused a pose that wants one)
             rasterizer = (GaussianRasterizerIndexed if indexed else GaussianRasterizer)(raster_settings=settings, optimize_camera=False)
         else:
             rasterizer = GaussianRasterizerIndexed(raster_settings=settings, optimize_camera="exact" if exact else True) if indexed \

@@ -5,8 +5,8 @@ on top of the MI355X C-ABI library.  Same names, argument order and error behavi
     GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,
     rasterize_gaussians, rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,
     getProjectionMatrix, quat_to_mat, mat_to_quat, and `_C` with the five pybind entry points
-    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`, `render_contrib`, `render_error`, `error_map_l1`
-    and `pose_grad`.
+    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`, `render_contrib`, `render_error`, `error_map_l1`,
+    `pose_grad`, `aa_opacity` and `aa_opacity_backward`.
 
 Beyond the reference: `GaussianRasterizationSettings(depth=True)` / `_C.render_depth` add depth, accumulated-opacity and
 median-depth maps of a forward (forward-only, csrc/render_depth.hip); `GaussianRasterizationSettings(contrib=True)` /
@@ -16,7 +16,9 @@ forward blended (forward-only, csrc/render_contrib.hip); `GaussianRasterizationS
 csrc/render_error.hip); `GaussianRasterizer(rs, optimize_camera="exact")` / `GaussianRasterizerIndexed(rs, optimize_camera="exact")`
 / `_C.pose_grad` give the exact gradient of the render with respect to the 7-element pose (csrc/pose_grad.hip, one pass behind
 the backward), where `optimize_camera=True` keeps the reference's formula; `GaussianRasterizationSettings(depth_grad=True)` makes
-the depth and alpha maps differentiable outputs (csrc/render_depth_backward.hip, one blend replay and one fold in the backward).
+the depth and alpha maps differentiable outputs (csrc/render_depth_backward.hip, one blend replay and one fold in the backward);
+`GaussianRasterizationSettings(antialiasing=True)` / `_C.aa_opacity` / `_C.aa_opacity_backward` compensate every opacity for the
+0.3 px^2 low-pass (csrc/aa_opacity.hip, one per-Gaussian launch in front of the forward and one behind the backward).
 
 PyTorch is plumbing only here (device memory, streams, autograd bookkeeping); every numeric stage
 runs in libc3dgs_hip.so.  There is no CPU path: tensors must live on the GPU.
@@ -598,6 +600,75 @@ def _c_pose_grad(means3D, dL_dmeans3D, dL_dcov3D, dL_dcolors, sh, degree, sh_ind
     return out
 
 
+def _aa_params(means3D, opacities, scales, rotations, scale_factors, g_indices, cov3D_precomp, scale_modifier, viewmatrix,
+               tan_fovx, tan_fovy, image_height, image_width, prefiltered, debug):
+    """the RasterParams of the two aa_opacity entries: the projection's inputs alone; the index pair only with its codebooks"""
+    if not means3D.is_cuda:
+        raise RuntimeError("c3dgs_amd: aa_opacity needs GPU tensors (there is no CPU path)")
+    by_codebook = scales is not None and scales.numel() != 0 and g_indices is not None and g_indices.numel() != 0
+    p, t = _params(background=None, means3D=means3D, colors=None, opacity=opacities, scales=scales,
+                   scale_factors=scale_factors if by_codebook else None, rotations=rotations, scale_modifier=scale_modifier,
+                   cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix, projmatrix=None, tan_fovx=tan_fovx, tan_fovy=tan_fovy,
+                   H=image_height, W=image_width, sh=None, degree=0, campos=None, sh_indices=None,
+                   g_indices=g_indices if by_codebook else None, prefiltered=prefiltered, debug=debug, clamp_color=False)
+    P = p.P
+    for name, width in (("opacities", 1), ("cov3D_precomp", 6), ("scale_factors", 1), ("g_indices", 1)):
+        if t[name] is not None and t[name].numel() != P * width:
+            raise RuntimeError(f"aa_opacity: {name} must have {P} x {width} elements, not {t[name].numel()}")
+    if P > 0 and t["opacities"] is None:
+        raise RuntimeError("aa_opacity: opacities is required")
+    return p, t
+
+
+def _c_aa_opacity(means3D, opacities, scales, rotations, scale_factors, g_indices, cov3D_precomp, scale_modifier, viewmatrix,
+                  tan_fovx, tan_fovy, image_height, image_width, prefiltered=False, debug=False, rho=True):
+    """Opacity compensation of the antialiased mode (c3dgs_aa_opacity), one launch on the current stream: -> (o', rho) with
+    o' = opacities * rho shaped like `opacities` and rho f32 [P] (None with rho=False). Absent inputs None or empty; `g_indices`
+    and `scale_factors` count only with `scales` / `rotations`. Forward-only: its gradient is _C.aa_opacity_backward."""
+    p, t = _aa_params(means3D, opacities, scales, rotations, scale_factors, g_indices, cov3D_precomp, scale_modifier, viewmatrix,
+                      tan_fovx, tan_fovy, image_height, image_width, prefiltered, debug)
+    dev = means3D.device
+    with torch.cuda.device(dev):
+        out = torch.empty_like(t["opacities"]) if t["opacities"] is not None else torch.empty((0, 1), dtype=torch.float32, device=dev)
+        rho_t = torch.empty((p.P,), dtype=torch.float32, device=dev) if rho else None
+        if p.P > 0:                                 # an empty tensor has no address to hand over, and nothing would be launched
+            _lib.check(_lib.lib().c3dgs_aa_opacity(C.byref(p), out.data_ptr(), _ptr(rho_t), _stream(dev)))
+    return out, rho_t
+
+
+def _c_aa_opacity_backward(means3D, opacities, radii, scales, rotations, scale_factors, g_indices, cov3D_precomp, scale_modifier,
+                           viewmatrix, tan_fovx, tan_fovy, image_height, image_width, dL_dopacity, dL_dmeans3D=None,
+                           dL_dcov3D=None, dL_dscales=None, dL_drotations=None, dL_dscale_factors=None, prefiltered=False,
+                           debug=False):
+    """The chain through rho behind a finished backward (c3dgs_aa_opacity_backward), one launch on the current stream, IN PLACE:
+    `dL_dopacity` holds the rasterizer's gradient with respect to o' and becomes rho times it; the terms through rho are added into
+    the other gradient tensors given (contiguous fp32, the backward's own; None is skipped). `opacities` are the raw ones."""
+    p, t = _aa_params(means3D, opacities, scales, rotations, scale_factors, g_indices, cov3D_precomp, scale_modifier, viewmatrix,
+                      tan_fovx, tan_fovy, image_height, image_width, prefiltered, debug)
+    dev = means3D.device
+    g = RasterGrads()
+    P = p.P
+    widths = dict(dL_dopacity=P, dL_dmeans3D=3 * P, dL_dcov3D=6 * P, dL_dscale_factors=P,
+                  dL_dscales=3 * (p.GS if p.g_indices else P), dL_drotations=4 * (p.GS if p.g_indices else P))
+    for name, gt in (("dL_dopacity", dL_dopacity), ("dL_dmeans3D", dL_dmeans3D), ("dL_dcov3D", dL_dcov3D), ("dL_dscales", dL_dscales),
+                     ("dL_drotations", dL_drotations), ("dL_dscale_factors", dL_dscale_factors)):
+        if gt is None or gt.numel() == 0:
+            continue
+        if not gt.is_cuda or gt.device != dev or gt.dtype != torch.float32 or not gt.is_contiguous():
+            raise RuntimeError(f"aa_opacity_backward: {name} must be a contiguous float32 tensor on {dev}")
+        if gt.numel() != widths[name]:
+            raise RuntimeError(f"aa_opacity_backward: {name} must have {widths[name]} elements, not {gt.numel()}")
+        setattr(g, name, gt.data_ptr())
+    radii_c = _optional(radii, "radii", torch.int32)
+    if radii_c is not None and radii_c.numel() != P:
+        raise RuntimeError(f"aa_opacity_backward: radii must have {P} elements, not {radii_c.numel()}")
+    if P == 0:                                      # empty tensors have no address to hand over, and nothing would be launched
+        return
+    with torch.cuda.device(dev):
+        rc = _lib.lib().c3dgs_aa_opacity_backward(C.byref(p), _ptr(radii_c), C.byref(g), _stream(dev))
+    _lib.check(rc)
+
+
 def _check_map(t, shape, dev, what):
     """the usual RuntimeError for a map or image of the wrong kind"""
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev:
@@ -631,6 +702,8 @@ _C = SimpleNamespace(
     render_error=_c_render_error,
     error_map_l1=_c_error_map_l1,
     pose_grad=_c_pose_grad,
+    aa_opacity=_c_aa_opacity,
+    aa_opacity_backward=_c_aa_opacity_backward,
     rasterize_gaussians=_c_rasterize_gaussians,
     rasterize_gaussians_backward=_c_rasterize_gaussians_backward,
     rasterize_gaussians_indexed=_c_rasterize_gaussians_indexed,
@@ -659,9 +732,15 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     and scale_factors are None. `args` is the pybind order of the entry it goes to (what snapshot_fw.dump holds)."""
     rs = raster_settings
     dev = means3D.device
+    antialiasing = bool(getattr(rs, "antialiasing", False))
+    raw_opacities = opacities
     for _attempt in range(2):          # a second pass only if the cached intrinsic scalars turn out stale (_IntrinsicGuard)
         guard = []
         view, proj, campos, tanfovx, tanfovy, H, W = camera_matrices(rs.intrinsic, extrinsic_vector, dev, guard)
+        if antialiasing:
+            # one per-Gaussian launch in front of the forward: the rasterizer runs on o' = o rho (csrc/aa_opacity.hip)
+            opacities = _C.aa_opacity(means3D, raw_opacities, scales, rotations, scale_factors, g_indices, cov3Ds_precomp,
+                                      rs.scale_modifier, view, tanfovx, tanfovy, H, W, rs.prefiltered, rs.debug, rho=False)[0]
         if indexed:
             fn = _C.rasterize_gaussians_indexed
             args = (rs.bg, means3D, colors_precomp, opacities, scales, scale_factors, rotations, rs.scale_modifier, cov3Ds_precomp,
@@ -693,8 +772,11 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     ctx.indexed = indexed
     ctx.num_rendered = num_rendered
     ctx.camera = (view, proj, campos, tanfovx, tanfovy)
+    # the raw opacities are an input of the backward in the antialiased mode only (the plain backward reads o' from the geometry buffer)
+    ctx.antialiasing = antialiasing
+    ctx.image_size = (H, W)
     ctx.save_for_backward(extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii, sh,
-                          geomBuffer, binningBuffer, imgBuffer, sh_indices, g_indices)
+                          geomBuffer, binningBuffer, imgBuffer, sh_indices, g_indices, *((raw_opacities,) if antialiasing else ()))
     ctx.image_shape = tuple(color.shape)
     # without this, autograd hands backward a zero-filled int32[P] "gradient" for radii on every call (a 12 MB fill at P = 3M)
     ctx.set_materialize_grads(False)
@@ -729,7 +811,7 @@ def _autograd_backward(ctx, grad_out_color, exact_pose=False, map_grads=(None, N
     inputs stay None (_fit). False: exactly the launches and stores of a backward without it, `.pose` is None."""
     rs = ctx.raster_settings
     (extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-     binningBuffer, imgBuffer, sh_indices, g_indices) = ctx.saved_tensors
+     binningBuffer, imgBuffer, sh_indices, g_indices) = ctx.saved_tensors[:14]
     grad_depth, grad_alpha = map_grads
     maps = dict(dL_ddepth=grad_depth, dL_dalpha=grad_alpha) if (grad_depth is not None or grad_alpha is not None) else {}
     if grad_out_color is None and not maps:
@@ -755,6 +837,18 @@ def _autograd_backward(ctx, grad_out_color, exact_pose=False, map_grads=(None, N
                 imgBuffer, rs.debug)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations) = _call_debug(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump", skip=skip, **maps)
+    if getattr(ctx, "antialiasing", False):
+        # behind the whole backward (the depth maps' part included) on the same stream: dL/do' becomes dL/do and the terms through
+        # rho are added to the gradients the backward has just written (csrc/aa_opacity.hip)
+        present = lambda g, inp: g if (g is not None and inp is not None and inp.numel() != 0) else None
+        H, W = ctx.image_size
+        by_codebook = present(grad_scales, scales) is not None         # scale factors count only with the codebooks
+        _C.aa_opacity_backward(means3D, ctx.saved_tensors[14], radii, scales, rotations, scale_factors, g_indices, cov3Ds_precomp,
+                               rs.scale_modifier, view, tanfovx, tanfovy, H, W, grad_opacities, dL_dmeans3D=grad_means3D,
+                               dL_dcov3D=present(grad_cov3Ds_precomp, cov3Ds_precomp), dL_dscales=present(grad_scales, scales),
+                               dL_drotations=present(grad_rotations, rotations),
+                               dL_dscale_factors=present(grad_scale_factors, scale_factors) if by_codebook else None,
+                               prefiltered=rs.prefiltered, debug=rs.debug)
     grad_pose = None
     if exact_pose:
         # the indexed entry always carries both index tensors; the library wants each only with what it indexes
@@ -920,6 +1014,7 @@ def rasterize_gaussians_indexed(means3D, means2D, sh, sh_indices, g_indices, col
 def rasterize_gaussians_indexed_camera(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities, scales,
                                        scale_factors, rotations, cov3Ds_precomp, raster_settings, extrinsic_vector):
     _check_depth_grad_camera(raster_settings, True)
+    _check_antialiasing_camera(raster_settings, True)
     return _RasterizeGaussiansIndexedCamera.apply(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities,
                                                   scales, scale_factors, rotations, cov3Ds_precomp, raster_settings,
                                                   extrinsic_vector)
@@ -928,6 +1023,7 @@ def rasterize_gaussians_indexed_camera(means3D, means2D, sh, sh_indices, g_indic
 def rasterize_gaussians_camera_exact(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                      raster_settings, extrinsic_vector):
     _check_depth_grad_camera(raster_settings, True)
+    _check_antialiasing_camera(raster_settings, True)
     return _RasterizeGaussiansCameraExact.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                                 cov3Ds_precomp, raster_settings, extrinsic_vector)
 
@@ -935,6 +1031,7 @@ def rasterize_gaussians_camera_exact(means3D, means2D, sh, colors_precomp, opaci
 def rasterize_gaussians_indexed_camera_exact(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities, scales,
                                              scale_factors, rotations, cov3Ds_precomp, raster_settings, extrinsic_vector):
     _check_depth_grad_camera(raster_settings, True)
+    _check_antialiasing_camera(raster_settings, True)
     return _RasterizeGaussiansIndexedCameraExact.apply(means3D, means2D, sh, sh_indices, g_indices, colors_precomp, opacities,
                                                        scales, scale_factors, rotations, cov3Ds_precomp, raster_settings,
                                                        extrinsic_vector)
@@ -945,6 +1042,13 @@ def _check_depth_grad_camera(raster_settings, optimize_camera):
     if optimize_camera is not False and getattr(raster_settings, "depth_grad", False):
         raise ValueError("depth_grad=True cannot be combined with optimize_camera: the gradient to the camera pose through the "
                          "depth and alpha maps is not implemented")
+
+
+def _check_antialiasing_camera(raster_settings, optimize_camera):
+    """`antialiasing` with a pose gradient is not covered: the opacity factor's dependence on the pose is not differentiated"""
+    if optimize_camera is not False and getattr(raster_settings, "antialiasing", False):
+        raise ValueError("antialiasing=True cannot be combined with optimize_camera: the gradient to the camera pose through the "
+                         "opacity compensation is not implemented")
 
 
 def _check_optimize_camera(value):
@@ -988,12 +1092,20 @@ class GaussianRasterizationSettings(_SettingsFields):
     outputs: a loss on them reaches every input the image reaches (csrc/render_depth_backward.hip: one blend replay and one small
     fold added to the backward). `median` (piecewise constant) and `radii` stay non-differentiable. When neither map receives a
     gradient the backward issues the plain backward's launches. The gradient to the camera pose through the maps is not covered
-    yet: with `depth_grad`, `optimize_camera` other than False raises ValueError."""
+    yet: with `depth_grad`, `optimize_camera` other than False raises ValueError.
+    `antialiasing` (keyword only, default False) is a fourth such attribute. True: every Gaussian's opacity is multiplied by
+    rho = sqrt(max(0.000025, det Sigma2D / det(Sigma2D + 0.3 I))) in front of the rasterizer (csrc/aa_opacity.hip: one
+    per-Gaussian launch in front of the forward, one behind the backward, which chains dL/d(opacity rho) to the opacity, the mean,
+    the covariance, scales, rotations and scale factors), so that a splat smaller than a pixel is not drawn with the energy of
+    the low-passed one. Radii, tile keys and conics are the plain render's; every output, the extra ones included, sees the
+    compensated opacity. False: the plain rasterizer's launches and bits. The gradient to the camera pose through rho is not
+    covered: with `antialiasing`, `optimize_camera` other than False raises ValueError."""
     contrib = False
     error_target = None
     depth_grad = False
+    antialiasing = False
 
-    def __new__(cls, *args, contrib=False, error_target=None, depth_grad=False, **kwargs):
+    def __new__(cls, *args, contrib=False, error_target=None, depth_grad=False, antialiasing=False, **kwargs):
         n = len(cls._fields)
         if len(args) == n + 1:
             args, contrib = args[:n], args[n]
@@ -1001,16 +1113,19 @@ class GaussianRasterizationSettings(_SettingsFields):
         self.contrib = bool(contrib)
         self.error_target = error_target
         self.depth_grad = bool(depth_grad)
+        self.antialiasing = bool(antialiasing)
         return self
 
     def _replace(self, **kwargs):
         contrib = kwargs.pop("contrib", self.contrib)
         error_target = kwargs.pop("error_target", self.error_target)
         depth_grad = kwargs.pop("depth_grad", self.depth_grad)
+        antialiasing = kwargs.pop("antialiasing", self.antialiasing)
         new = super()._replace(**kwargs)
         new.contrib = bool(contrib)
         new.error_target = error_target
         new.depth_grad = bool(depth_grad)
+        new.antialiasing = bool(antialiasing)
         return new
 
 
@@ -1062,10 +1177,12 @@ class GaussianRasterizer(_Rasterizer):
                              'the indexed rasterizer only)')
         self.optimize_camera = _check_optimize_camera(optimize_camera)
         _check_depth_grad_camera(raster_settings, self.optimize_camera)
+        _check_antialiasing_camera(raster_settings, self.optimize_camera)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, extrinsic_vector=None, extrinsic=None):
         _check_depth_grad_camera(self.raster_settings, self.optimize_camera)
+        _check_antialiasing_camera(self.raster_settings, self.optimize_camera)
         _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
         if extrinsic_vector is None:
             extrinsic_vector = extrinsic if extrinsic is not None else self.raster_settings.extrinsic_vector
@@ -1084,10 +1201,12 @@ class GaussianRasterizerIndexed(_Rasterizer):
         super().__init__(raster_settings)
         self.optimize_camera = optimize_camera
         _check_depth_grad_camera(raster_settings, bool(optimize_camera))
+        _check_antialiasing_camera(raster_settings, bool(optimize_camera))
 
     def forward(self, means3D, means2D, opacities, sh_indices, g_indices, shs=None, colors_precomp=None, scales=None,
                 scale_factors=None, rotations=None, cov3D_precomp=None, extrinsic_vector=None):
         _check_depth_grad_camera(self.raster_settings, bool(self.optimize_camera))
+        _check_antialiasing_camera(self.raster_settings, bool(self.optimize_camera))
         _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
         if extrinsic_vector is None:
             extrinsic_vector = self.raster_settings.extrinsic_vector

@@ -273,6 +273,38 @@ int c3dgs_pose_grad(int32_t P, int32_t D, int32_t M, float scale_modifier,
                     const void* geom_buffer, const int32_t* radii /*[P]*/, const float* pose /*[7]*/, void* workspace,
                     float* out /*[7]*/, void* stream);
 
+/* ---- antialiased rasterization: opacity compensation of the 0.3 px^2 low-pass (csrc/aa_opacity.hip; no reference counterpart:
+ * upstream 3DGS `antialiasing`, Mip-Splatting, gsplat rasterize_mode="antialiased") ----
+ * With (a0, b, c0) the 2D covariance the forward forms BEFORE it adds h = 0.3 to the diagonal (same T = W J, same clamp of
+ * t.x, t.y at 1.3 tan_fov), in fp32, every operation rounded as the forward rounds it:
+ *   D0 = a0 c0 - b b,  D1 = (a0 + h)(c0 + h) - b b,  r = D0 / D1,  rho = sqrt(max(0.000025f, r)),  opacity_out = opacity * rho
+ * and the rasterizer is then called with opacity_out as p->opacities: radii, tile keys and conics are the plain render's.
+ * rho is finite for every row: a row that fails the forward's near-plane test (view z <= 0.01 unless p->prefiltered), a row with
+ * D1 == 0 and a row with a non-finite D0, D1 or r get rho = 1.
+ * Both calls read of `p`: P, W, H, means3D, opacities (the RAW ones, also in the backward), tan_fovx, tan_fovy, scale_modifier,
+ * viewmatrix, prefiltered, debug and either cov3D_precomp or scales + rotations -- rows of the latter two through g_indices,
+ * multiplied by scale_factors x scale_modifier, when g_indices is not NULL (scale_factors without g_indices is ignored). SH,
+ * colours, background, projmatrix and campos are ignored and may be NULL.
+ * c3dgs_aa_opacity: one launch, one lane per Gaussian; writes opacity_out [P] and, when not NULL, rho [P].
+ * c3dgs_aa_opacity_backward: one launch, queued BEHIND the whole backward (and its depth-map part) on the same stream, with that
+ * backward's `grads` and the forward's radii. For every row with radii > 0 (the others' gradients are zero already), with g' the
+ * value found in grads->dL_dopacity (the rasterizer's dL/d opacity_out): dL_dopacity is rewritten as rho g', and the terms through
+ * rho -- dL/drho = opacity g', through sqrt and r to (a0, b, c0) and from there with the backward's own chain for the conic (T and
+ * J, the clamped t.x, t.y held constant) -- are ADDED into whichever of dL_dmeans3D, dL_dcov3D, dL_dscales, dL_drotations and
+ * dL_dscale_factors are not NULL; these are exact derivatives (scale_modifier included). No such terms where rho = 1 by the rule
+ * above or r <= 0.000025f. rho and these decisions are the fp32 values of c3dgs_aa_opacity; the terms through rho are evaluated in
+ * double from the fp32 inputs and rounded once when added. A row whose g' is zero is left as it is (every term is a multiple of
+ * g'). The covariance is recomputed: nothing is handed over from c3dgs_aa_opacity. P-sized outputs are plain
+ * read-modify-writes; with g_indices, dL_dscales [GS,3] and dL_drotations [GS,4] are added with fp32 atomics (not reproducible
+ * run to run, like the indexed backward's own). The other members of `grads` are not touched.
+ * C3DGS_E_INVALID before any device work: P < 0; not exactly one of scales + rotations / cov3D_precomp; g_indices without
+ * scale_factors; opacity_out NULL; grads or grads->dL_dopacity NULL; with cov3D_precomp a NULL grads->dL_dcov3D; and, for P > 0,
+ * W or H <= 0 or a NULL means3D, opacities, viewmatrix or radii. P == 0 launches nothing. Stage names: "aa_opacity",
+ * "aa_opacity_backward". */
+int c3dgs_aa_opacity(const c3dgs_raster_params* p, float* opacity_out /*[P]*/, float* rho /*[P] | NULL*/, void* stream);
+int c3dgs_aa_opacity_backward(const c3dgs_raster_params* p, const int32_t* radii /*[P]*/, const c3dgs_raster_grads* grads,
+                              void* stream);
+
 /* ---- weighted_distance._C.weightedDistance (weighted_distance.cu:46-93) ----
  * coefs [N,K], codebook [C,K] row-major fp32 -> min squared distance [N] and argmin [N] (int64).
  * Exact reference semantics: fp32 k-ordered FMA chain, strict '<' (lowest index wins ties).

@@ -5,7 +5,7 @@ before / after, and seconds per phase.
 
     python tools/run_train.py [--iterations 400] [--out profiles/r06_train_synth.json]
                               [--densify-by grad|error] [--error-threshold T] [--optimizer default|sparse_adam]
-                              [--lambda-depth X] [--lambda-alpha Y]
+                              [--lambda-depth X] [--lambda-alpha Y] [--antialiasing]
 
 --densify-by error (with --error-threshold, which has no default) lets the run with density control densify by image error
 (pipeline.train(densify_by="error")); the JSON then carries "densify_by" and "error_threshold".
@@ -14,7 +14,12 @@ before / after, and seconds per phase.
 --lambda-depth X / --lambda-alpha Y (either positive) attach the teacher's own maps to the cameras -- alpha_target = its alpha,
 depth_target = its depth / alpha where alpha > 0.5, else 0 -- and run pipeline.train(lambda_depth=X, lambda_alpha=Y); both runs
 are then also made WITHOUT the two terms ("without_map_terms"), and every run carries "depth_l1" and "alpha_l1": the mean over
-the views of mean |depth - teacher depth| and mean |alpha - teacher alpha| of the trained student (sum alpha T z, not normalised)."""
+the views of mean |depth - teacher depth| and mean |alpha - teacher alpha| of the trained student (sum alpha T z, not normalised).
+--antialiasing makes the run without density control twice, with PipelineParams(antialiasing=False) and (True), at the scene's
+resolution, and scores each trained student with metrics.render_and_eval (under the pipe it was trained with) at 0.5x, 1x and 2x
+that resolution, same poses, focal length scaled. The targets there are the teacher rendered at 4x the evaluated resolution by
+the plain rasterizer and box-filtered down 4 x 4 ("resolution_eval"); "train_views_1x" is the score against the training images
+themselves. One run each, nothing tuned; the JSON then carries "antialiasing" in place of the two default runs."""
 import argparse
 import json
 import os
@@ -52,8 +57,32 @@ def map_l1(student, cams, maps):
     return sum(d) / len(d), sum(a) / len(a)
 
 
+def resolution_eval(student, cams, pipe):
+    """-> {"0.5x" | "1x" | "2x": render_and_eval's dict against the 4x supersampled, box-filtered teacher, "train_views_1x": against
+    the training images}"""
+    from c3dgs_amd import metrics
+    from c3dgs_amd.model import PipelineParams
+    from tests import synth
+    W, H, focal = 160, 112, 150.0
+    teacher, _ = train_scene.teacher_model(4000, W, H, focal, "cuda")
+    bg = torch.zeros(3, device="cuda")
+    out = {"train_views_1x": metrics.render_and_eval(student, cams, pipe, bg)}
+    for label, s in (("0.5x", 0.5), ("1x", 1.0), ("2x", 2.0)):
+        views = []
+        for cam in cams:
+            ev = tuple(cam.extrinsic_vector.detach().cpu().tolist())
+            view = train_scene.Cam(*synth.camera(int(W * s), int(H * s), focal * s, extrinsic_vector=ev), "cuda")
+            fine = train_scene.Cam(*synth.camera(int(W * s) * 4, int(H * s) * 4, focal * s * 4, extrinsic_vector=ev), "cuda")
+            with torch.no_grad():
+                big = teacher.render(fine, PipelineParams(), bg)["render"].clamp(0, 1)
+                view.original_image = torch.nn.functional.avg_pool2d(big[None], 4)[0].contiguous()
+            views.append(view)
+        out[label] = metrics.render_and_eval(student, views, pipe, bg)
+    return out
+
+
 def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer="default", lambda_depth=0.0, lambda_alpha=0.0,
-        with_maps=False):
+        with_maps=False, antialiasing=None):
     from c3dgs_amd import pipeline
     from c3dgs_amd.model import PipelineParams
     with tempfile.TemporaryDirectory() as tmp:
@@ -79,7 +108,8 @@ def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer=
 
     torch.manual_seed(0)
     t0 = time.perf_counter()
-    n = pipeline.train(Scene(), None, train_scene.schedule(iterations, densify), PipelineParams(), camera_stride=1, degree_up_iter=80,
+    pipe = PipelineParams(antialiasing=bool(antialiasing))
+    n = pipeline.train(Scene(), None, train_scene.schedule(iterations, densify), pipe, camera_stride=1, degree_up_iter=80,
                        log=lambda epoch, info: events.append((epoch, info)), densify_by=densify_by, error_threshold=error_threshold,
                        optimizer_type=optimizer, **extra)
     torch.cuda.synchronize()
@@ -93,6 +123,8 @@ def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer=
            "seconds": {"setup": t_setup, "train": t_train, "eval": t_eval}}
     if with_maps:
         out["depth_l1"], out["alpha_l1"] = map_l1(student, cams, maps)
+    if antialiasing is not None:
+        out["resolution_eval"] = resolution_eval(student, cams, pipe)
     return out
 
 
@@ -105,12 +137,21 @@ def main():
     ap.add_argument("--optimizer", choices=("default", "sparse_adam"), default="default")
     ap.add_argument("--lambda-depth", type=float, default=0.0)
     ap.add_argument("--lambda-alpha", type=float, default=0.0)
+    ap.add_argument("--antialiasing", action="store_true")
     args = ap.parse_args()
     if args.densify_by == "error" and args.error_threshold is None:
         ap.error("--densify-by error needs --error-threshold (there is no default)")
     if not torch.cuda.is_available():
         raise SystemExit("run_train.py needs the GPU; there is no CPU path")
     out = {"scene": "tests/train_scene.py: 4000-Gaussian synth-v1 teacher, 8 views 160x112, student = every 8th position as a point cloud"}
+    if args.antialiasing:
+        out["antialiasing"] = {"off": run(args.iterations, False, optimizer=args.optimizer, antialiasing=False),
+                               "on": run(args.iterations, False, optimizer=args.optimizer, antialiasing=True)}
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     terms = args.lambda_depth > 0 or args.lambda_alpha > 0
     kw = dict(lambda_depth=args.lambda_depth, lambda_alpha=args.lambda_alpha, with_maps=True) if terms else {}
     out["with_density_control"] = run(args.iterations, True, args.densify_by, args.error_threshold, args.optimizer, **kw)
