@@ -86,6 +86,7 @@ class RowsTensor(C.Structure):          # c3dgs_rows_tensor
 
 
 ROLE_COPY, ROLE_XYZ, ROLE_SCALING = 0, 1, 2
+MCMC_ROLE_OPACITY, MCMC_ROLE_SCALE = 3, 4             # c3dgs_mcmc_apply
 ROW_KEEP, ROW_CLONE, ROW_SPLIT, ROW_CHILD_KEPT = 1, 2, 4, 8
 
 _vp = C.c_void_p
@@ -165,6 +166,12 @@ PROTOTYPES = {
     "c3dgs_rows_apply": (C.c_int, [C.c_int32, C.c_int64, _vp, _vp, _vp, C.c_int32, C.POINTER(RowsTensor), C.c_int32, C.c_int64,
                                    _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
     "c3dgs_densify_stats": (C.c_int, [C.c_int32] + [_vp] * 7),
+    "c3dgs_mcmc_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "c3dgs_mcmc_sample": (C.c_int, [C.c_int64, _vp, _vp, C.c_int32, C.c_float, _vp, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, _vp,
+                                    _vp, _vp]),
+    "c3dgs_mcmc_apply": (C.c_int, [C.c_int64, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int32, C.POINTER(RowsTensor), C.c_int32,
+                                   C.c_float, _vp, _vp]),
+    "c3dgs_mcmc_noise": (C.c_int, [C.c_int64] + [_vp] * 6 + [C.c_float, C.c_float, _vp]),
     "c3dgs_index_plan_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "c3dgs_index_plan": (C.c_int, [C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64] + [_vp] * 8),
     "c3dgs_extract_rot_scale": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),

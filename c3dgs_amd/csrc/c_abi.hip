@@ -2,6 +2,7 @@
 // Stage order follows the reference's Rasterizer::forward / backward (cuda_rasterizer/rasterizer_impl.cu:194-334,
 // 338-435, 440-586, 590-697); the stages themselves are the gfx950 kernels in this directory.
 #include "common.hpp"
+#include "mcmc.hpp"
 #include <cfloat>
 #include <climits>
 #include <cstdlib>
@@ -34,7 +35,9 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(QAT_VISIBLE, "qat_visible") X(QAT_POINTS, "qat_points") X(QAT_POINTS_BWD, "qat_points_backward")                         \
     X(QAT_CODEBOOKS_BWD, "qat_codebooks_backward") X(ADAM, "adam_step") X(KNN_SORT, "knn_sort") X(KNN_BOUNDS, "knn_bounds")    \
     X(KNN_QUERY, "knn_query") X(SPARSE_ADAM_SELECT, "sparse_adam_select") X(SPARSE_ADAM_STEP, "sparse_adam_step")              \
-    X(AA_OPACITY, "aa_opacity") X(AA_OPACITY_BWD, "aa_opacity_backward")
+    X(AA_OPACITY, "aa_opacity") X(AA_OPACITY_BWD, "aa_opacity_backward")                                                       \
+    X(MCMC_WEIGHTS, "mcmc_weights") X(MCMC_SEARCH, "mcmc_search") X(MCMC_VALUES, "mcmc_values") X(MCMC_APPLY, "mcmc_apply")    \
+    X(MCMC_NOISE, "mcmc_noise")
 #define C3DGS_X(id, name) ST_##id,
 enum Stage { C3DGS_STAGE_TABLE(C3DGS_X) ST_COUNT };
 #undef C3DGS_X
@@ -1091,6 +1094,96 @@ int c3dgs_densify_stats(int32_t P, const float* grad, const uint8_t* filter, con
     if ((radii == nullptr) != (max_radii == nullptr)) return fail(C3DGS_E_INVALID, "densify_stats: radii and max_radii go together");
     launch_densify_stats(P, grad, filter, radii, accum, denom, max_radii, (hipStream_t)stream);
     C3DGS_STAGE("densify_stats", 0, (hipStream_t)stream);
+    return C3DGS_OK;
+}
+
+// ---- MCMC density control (mcmc.hip)
+static const char* mcmc_bad_P(int64_t P)
+{
+    if (P < 0) return "P must be >= 0";
+    if (P >= (int64_t(1) << 31)) return "P must be below 2^31 (row ids are 32-bit)";
+    return nullptr;
+}
+static bool mcmc_bad_workspace(const void* w) { return !w || (reinterpret_cast<uintptr_t>(w) & 255u); }
+
+int c3dgs_mcmc_workspace_bytes(int64_t P, size_t* bytes)
+{
+    if (!bytes) return fail(C3DGS_E_INVALID, "mcmc_workspace_bytes: bytes is NULL");
+    if (const char* bad = mcmc_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_workspace_bytes: ") + bad);
+    *bytes = mcmc_layout(P).total_bytes;
+    return C3DGS_OK;
+}
+
+int c3dgs_mcmc_sample(int64_t P, const float* raw_opacity, const uint8_t* dead, int32_t derive_dead, float min_opacity,
+                      uint8_t* dead_out, int64_t n, const double* draws, int32_t reuse_weights, uint32_t* q, int32_t* sources,
+                      int32_t* counts, uint64_t* T, void* workspace, void* stream)
+{
+    if (const char* bad = mcmc_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_sample: ") + bad);
+    if (n < 0) return fail(C3DGS_E_INVALID, "mcmc_sample: n must be >= 0");
+    if (n >= (int64_t(1) << 31)) return fail(C3DGS_E_INVALID, "mcmc_sample: n must be below 2^31");
+    if (dead && derive_dead) return fail(C3DGS_E_INVALID, "mcmc_sample: a dead mask and derive_dead exclude each other");
+    if (P == 0) return C3DGS_OK;
+    if (!counts) return fail(C3DGS_E_INVALID, "mcmc_sample: counts is NULL");
+    if (!reuse_weights) {
+        if (!raw_opacity || !q || !T) return fail(C3DGS_E_INVALID, "mcmc_sample: raw_opacity, q and T are required");
+        if (derive_dead && !dead_out) return fail(C3DGS_E_INVALID, "mcmc_sample: derive_dead needs dead_out");
+        if (derive_dead && !(min_opacity >= 0.f)) return fail(C3DGS_E_INVALID, "mcmc_sample: min_opacity must be >= 0");
+    }
+    if (n > 0 && (!draws || !sources)) return fail(C3DGS_E_INVALID, "mcmc_sample: n > 0 needs draws and sources");
+    if (mcmc_bad_workspace(workspace)) return fail(C3DGS_E_INVALID, "mcmc_sample: the workspace must be non-NULL and 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (reuse_weights) C3DGS_HIP_TRY(hipMemsetAsync(counts, 0, (size_t)P * sizeof(int32_t), s));
+    else
+        C3DGS_TIMED_STAGE(ST_MCMC_WEIGHTS, 0, s, launch_mcmc_weights(P, raw_opacity, dead, derive_dead, min_opacity, dead_out, q, counts,
+                                                                     (unsigned long long*)T, workspace, s));
+    if (n > 0) C3DGS_TIMED_STAGE(ST_MCMC_SEARCH, 0, s, launch_mcmc_search(P, n, draws, sources, counts, workspace, s));
+    return C3DGS_OK;
+}
+
+int c3dgs_mcmc_apply(int64_t P, int64_t n, const int32_t* dst, int64_t dst_base, const int32_t* sources, const int32_t* counts,
+                     int32_t n_tensors, const c3dgs_rows_tensor* tensors, int32_t copy_rows, float min_opacity, void* workspace,
+                     void* stream)
+{
+    if (const char* bad = mcmc_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_apply: ") + bad);
+    if (n < 0) return fail(C3DGS_E_INVALID, "mcmc_apply: n must be >= 0");
+    if (n >= (int64_t(1) << 31)) return fail(C3DGS_E_INVALID, "mcmc_apply: n must be below 2^31");
+    if (n_tensors < 0 || n_tensors > C3DGS_ROWS_MAX_TENSORS) return fail(C3DGS_E_INVALID, "mcmc_apply: between 0 and 16 tensors per call");
+    if (!(min_opacity >= 0.f && min_opacity < 1.f)) return fail(C3DGS_E_INVALID, "mcmc_apply: min_opacity must be in [0, 1)");
+    if (P == 0 || n == 0) return C3DGS_OK;
+    if (!sources || !counts || !tensors) return fail(C3DGS_E_INVALID, "mcmc_apply: NULL buffer");
+    if (!dst && (dst_base < 0 || dst_base + n > P)) return fail(C3DGS_E_INVALID, "mcmc_apply: dst_base + n must lie inside [0, P]");
+    const c3dgs_rows_tensor* opacity = nullptr;
+    const c3dgs_rows_tensor* scale = nullptr;
+    for (int k = 0; k < n_tensors; k++) {
+        const c3dgs_rows_tensor& t = tensors[k];
+        if (t.row_floats < 1 || t.row_floats > 4096) return fail(C3DGS_E_INVALID, "mcmc_apply: row_floats must be between 1 and 4096");
+        if (!t.out_param || t.in_param != t.out_param) return fail(C3DGS_E_INVALID, "mcmc_apply: the step is in place (in_param == out_param, not NULL)");
+        if (t.in_exp_avg != t.out_exp_avg || t.in_exp_avg_sq != t.out_exp_avg_sq || (t.out_exp_avg == nullptr) != (t.out_exp_avg_sq == nullptr))
+            return fail(C3DGS_E_INVALID, "mcmc_apply: the moment pointers go together and are in place");
+        if (t.role == C3DGS_MCMC_ROLE_OPACITY) {
+            if (opacity || t.row_floats != 1) return fail(C3DGS_E_INVALID, "mcmc_apply: one opacity tensor of 1 float per row");
+            opacity = &t;
+        } else if (t.role == C3DGS_MCMC_ROLE_SCALE) {
+            if (scale || t.row_floats > 3) return fail(C3DGS_E_INVALID, "mcmc_apply: one scale tensor of 1 to 3 floats per row");
+            scale = &t;
+        } else if (t.role != C3DGS_ROLE_COPY) return fail(C3DGS_E_INVALID, "mcmc_apply: unknown role");
+    }
+    if (!opacity || !scale) return fail(C3DGS_E_INVALID, "mcmc_apply: the table needs the opacity and the scale tensor");
+    if (mcmc_bad_workspace(workspace)) return fail(C3DGS_E_INVALID, "mcmc_apply: the workspace must be non-NULL and 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_MCMC_VALUES, 0, s, launch_mcmc_values(P, counts, opacity->in_param, scale->in_param, scale->row_floats, min_opacity, workspace, s));
+    C3DGS_TIMED_STAGE(ST_MCMC_APPLY, 0, s, launch_mcmc_apply(P, n, dst, dst_base, sources, n_tensors, tensors, copy_rows, workspace, s));
+    return C3DGS_OK;
+}
+
+int c3dgs_mcmc_noise(int64_t P, float* xyz, const float* rotation, const float* scaling, const float* scaling_factor,
+                     const float* raw_opacity, const float* xi, float noise_lr, float xyz_lr, void* stream)
+{
+    if (const char* bad = mcmc_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_noise: ") + bad);
+    if (P == 0) return C3DGS_OK;
+    if (!xyz || !rotation || !scaling || !raw_opacity || !xi) return fail(C3DGS_E_INVALID, "mcmc_noise: NULL buffer");
+    C3DGS_TIMED_STAGE(ST_MCMC_NOISE, 0, (hipStream_t)stream,
+                      launch_mcmc_noise(P, xyz, rotation, scaling, scaling_factor, raw_opacity, xi, noise_lr, xyz_lr, (hipStream_t)stream));
     return C3DGS_OK;
 }
 

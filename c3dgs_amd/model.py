@@ -991,6 +991,114 @@ class GaussianModel:
         self._apply_plan(src, kind, draw_row, P + n, new_xyz=new_xyz)
         return src, kind, draw_row
 
+    # ---- MCMC density control (not in the reference: "3D Gaussian Splatting as Markov Chain Monte Carlo", gsplat's MCMCStrategy);
+    # non-indexed models; csrc/mcmc.hip, DESIGN.md "MCMC density control"
+    def _mcmc_table(self):
+        """The in-place tensor table of c3dgs_mcmc_apply: every parameter with its moments (where the optimizer has them), the raw
+        opacity and the tensor that carries the log scale flagged (the factor when the model has one, its activation being exp)."""
+        scale_attr = "_scaling_factor" if self._scaling_factor is not None else "_scaling"
+        table = []
+        for name, attr, _ in self._GROUPS:
+            p = getattr(self, attr)
+            if p is None:
+                continue
+            tensors = [p]
+            st = self.optimizer.state.get(p) if self.optimizer is not None else None
+            if st is not None and "exp_avg" in st:
+                tensors += [st["exp_avg"], st["exp_avg_sq"]]
+            for x in tensors:
+                if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+                    raise RuntimeError(f"c3dgs_amd: {attr} and its moments must be contiguous float32 GPU tensors (the MCMC step is in place)")
+            t = _lib.RowsTensor()
+            t.in_param = t.out_param = p.data_ptr()
+            if len(tensors) == 3:
+                t.in_exp_avg = t.out_exp_avg = tensors[1].data_ptr()
+                t.in_exp_avg_sq = t.out_exp_avg_sq = tensors[2].data_ptr()
+            t.row_floats = int(torch.Size(p.shape[1:]).numel())
+            t.role = _lib.MCMC_ROLE_OPACITY if attr == "_opacity" else _lib.MCMC_ROLE_SCALE if attr == scale_attr else _lib.ROLE_COPY
+            table.append(t)
+        return table
+
+    def _read_pair(self, a, b):
+        """Two device scalars in one device->host read (pinned memory and an event, as _read_totals)."""
+        host = getattr(self, "_pair_host", None)
+        if host is None:
+            host = self._pair_host = torch.empty(2, dtype=torch.int64).pin_memory()
+        host.copy_(torch.cat((a.reshape(1).to(torch.int64), b.reshape(1).to(torch.int64))), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        ev.synchronize()
+        return host.tolist()
+
+    def relocate_gs(self, dead_mask=None, min_opacity=0.005, draws=None):
+        """Move every dead Gaussian onto a live one sampled by opacity; opacity and scale of the source and of its copies are
+        corrected so that together they composite to what the single Gaussian did (the paper's eq. 9, N = min(copies + 1, 51),
+        evaluated in double). In place: P and the parameter tensors stay, `step` stays. -> the number relocated.
+
+        `dead_mask`: bool / uint8 [P]; None: sigmoid(_opacity) <= min_opacity, derived by the kernel on the raw parameter (the
+        opacity observer is not touched). `draws`: float64 uniforms in [0, 1), at least one per dead row (default torch.rand in
+        float64); the j-th dead row in ascending row order uses draws[j]. All dead, none dead or no live row with weight: nothing
+        changes, returns 0. exp_avg / exp_avg_sq of every source AND every destination row become zero: gsplat zeroes only the
+        sources, but a destination's moments describe a Gaussian that is no longer there. One device->host read."""
+        self._dense_only("relocate_gs")
+        from . import mcmc, optim
+        with torch.no_grad():
+            P = self._xyz.shape[0]
+            if P == 0:
+                return 0
+            w = mcmc.weights(self._opacity, dead_mask, None if dead_mask is not None else min_opacity)
+            rows, count = optim.visible_rows(w.dead)                # the stable device-side selection of sparse Adam
+            n, T = self._read_pair(count, w.T)
+            if n == 0 or n == P or T == 0:
+                return 0
+            if draws is None:
+                draws = torch.rand(n, dtype=torch.float64, device=self.device)
+            sources = mcmc.draw(w, draws, n)
+            mcmc.apply(P, n, rows, 0, sources, w.counts, self._mcmc_table(), True, min_opacity, w.ws, self.device)
+            return n
+
+    def add_new_gs(self, cap_max, draws=None, min_opacity=0.005):
+        """Grow the scene by 5 % up to `cap_max` rows: n_new = max(0, min(cap_max, int(1.05 P)) - P) sources sampled by opacity
+        over all rows, appended as copies (_append_clones: moments of the originals kept, zero for the new rows), then every
+        source and its copies take the relocation opacity and scale, and the moments of the sources and the new rows are
+        zeroed, as in relocate_gs. `draws`: float64 [>= n_new] uniforms (default torch.rand). -> the number added. No
+        device->host read. (A scene without any opacity above 2^-20 has nothing to sample from: the new rows are zero.)"""
+        self._dense_only("add_new_gs")
+        from . import mcmc
+        with torch.no_grad():
+            P = self._xyz.shape[0]
+            n_new = max(0, min(int(cap_max), int(1.05 * P)) - P)
+            if n_new == 0 or P == 0:
+                return 0
+            if draws is None:
+                draws = torch.rand(n_new, dtype=torch.float64, device=self.device)
+            w = mcmc.weights(self._opacity, None, None, counts_rows=P + n_new)
+            sources = mcmc.draw(w, draws, n_new)
+            self._append_clones(sources)
+            mcmc.apply(P + n_new, n_new, None, P, sources, w.counts, self._mcmc_table(), False, min_opacity, w.ws, self.device)
+            return n_new
+
+    def add_position_noise(self, noise_lr, xyz_lr=None, draws=None):
+        """The per-iteration perturbation of MCMC training, in place on _xyz, one launch:
+            xyz += Sigma xi g(o) noise_lr xyz_lr,   Sigma = R diag(s^2) R^T,   g(o) = 1 / (1 + exp(-100 ((1 - o) - 0.995)))
+        from the RAW parameters through the model's activations (normalised quaternion; exp, or normalize(relu(.)) * exp(factor);
+        sigmoid). FakeQuantize is NOT applied and the observers are not touched: the noise is a property of the optimisation,
+        not of the quantised render. `xyz_lr`: None takes the current learning rate of the "xyz" group. `draws`: [P,3] unit
+        normals (default torch.randn)."""
+        self._dense_only("add_position_noise")
+        from . import mcmc
+        with torch.no_grad():
+            P = self._xyz.shape[0]
+            if xyz_lr is None:
+                if self.optimizer is None:
+                    raise RuntimeError("add_position_noise: xyz_lr=None needs training_setup (the learning rate of the xyz group)")
+                xyz_lr = next(g["lr"] for g in self.optimizer.param_groups if g.get("name") == "xyz")
+            if draws is None:
+                draws = torch.randn((P, 3), device=self.device)
+            mcmc.noise(self._xyz.detach(), self._rotation.detach(), self._scaling.detach(),
+                       None if self._scaling_factor is None else self._scaling_factor.detach(), self._opacity.detach(), draws,
+                       noise_lr, xyz_lr)
+
     def densify_and_clone(self, grads=None, grad_threshold=None, scene_extent=None, selected_pts_mask=None, new_xyz=None):
         """:1279-1330. The gradient-mask form: row order every original, then the clones; returns (src, kind, draw_row,
         totals). The explicit form (`selected_pts_mask`: a bool mask or an index tensor; `new_xyz`: [n,3] positions that

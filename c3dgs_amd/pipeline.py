@@ -181,7 +181,8 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
 
 
 def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, degree_up_iter=1000, *, densify_by="grad",
-          error_threshold=None, optimizer_type=None, optimizer_visibility="radii", lambda_depth=0.0, lambda_alpha=0.0):
+          error_threshold=None, optimizer_type=None, optimizer_visibility="radii", lambda_depth=0.0, lambda_alpha=0.0,
+          strategy="default", cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01, min_opacity=0.005):
     """train.py:15-173 without its disabled compression-statistics branch: optimise a non-indexed model (usually
     GaussianModel.load_ply of a point cloud) with adaptive density control.
 
@@ -218,7 +219,29 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     `alpha_target` (a mask or silhouette) adds lambda_alpha x mean |alpha - alpha_target|; `depth_target` (0 = no measurement)
     adds lambda_depth x the mean over the measured pixels of |depth - alpha x depth_target|, a residual in weight space (depth is
     sum alpha T z, not normalised), so nothing is divided. Both at 0 (the default), and views without the attributes, run the
-    loop above with its launches."""
+    loop above with its launches.
+
+    `strategy` = "default" is the loop above, launch for launch. "mcmc" (not in the reference: "3D Gaussian Splatting as Markov
+    Chain Monte Carlo", gsplat's MCMCStrategy; csrc/mcmc.hip) trains towards a hard budget of `cap_max` Gaussians (required):
+      - it renders WITHOUT the precomputed covariance, so scale and rotation are learnable, which the method presumes (moving
+        a Gaussian rescales it); the reference's loop, and the default strategy here, freeze them between densifications;
+      - the loss gains opacity_reg x mean sigmoid(_opacity) + scale_reg x mean get_scaling;
+      - GaussianModel.add_position_noise(noise_lr) follows every optimizer step;
+      - after an epoch, on the default loop's densification schedule (the same densify_from / until / interval conversion), it
+        calls relocate_gs(min_opacity=min_opacity) and then add_new_gs(cap_max): dead Gaussians move onto live ones, the scene
+        grows by 5 % up to the cap. The schedule INCLUDES epoch densify_from_epoch itself (epoch >= densify_from_epoch, where the
+        default loop asks >): that epoch already ends past densify_from_iter, and a refinement reads the opacities as they are,
+        it has no gradient statistics to gather over an interval first. tests/train_scene.py's schedule(400) thus refines at
+        epochs 5, 10, ... 35, seven times. No densify_and_prune, no reset_opacity, no add_densification_stats.
+    `info` keeps "densified": None and "reset_opacity": False and gains "mcmc": None | (relocated, added). Both optimizer types
+    work. densify_by="error" with it raises ValueError, as does an unknown strategy."""
+    if strategy not in ("default", "mcmc"):
+        raise ValueError(f"train: strategy must be 'default' or 'mcmc', not {strategy!r}")
+    mcmc = strategy == "mcmc"
+    if mcmc and densify_by != "grad":
+        raise ValueError("train: strategy='mcmc' has its own density control; densify_by must stay 'grad'")
+    if mcmc and cap_max is None:
+        raise ValueError("train: strategy='mcmc' needs cap_max, the budget of Gaussians (there is no default)")
     if lambda_depth < 0 or lambda_alpha < 0:
         raise ValueError("train: lambda_depth and lambda_alpha must be >= 0")
     if optimizer_visibility not in ("radii", "blended", None):
@@ -229,8 +252,10 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     if by_error and error_threshold is None:
         raise ValueError("train: densify_by='error' needs an error_threshold (there is no default)")
     gaussians = scene.gaussians if hasattr(scene, "gaussians") else dataset.gaussians
+    if mcmc:
+        gaussians._dense_only("train(strategy='mcmc')")
     cameras = _train_cameras(scene)
-    if extent is None:
+    if extent is None and not mcmc:
         extent = scene.cameras_extent
     gaussians.training_setup(opt, optimizer_type=optimizer_type)
     gaussians.update_learning_rate(0)
@@ -252,16 +277,19 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
         pending = []
         for viewpoint_cam in cameras[::camera_stride]:
             gaussians.update_learning_rate(iteration)
-            cov3d_scaled = gaussians.get_covariance().detach()
-            scaling_factor = gaussians.get_scaling_factor
-            coeff = scaling_factor.detach().square() if torch.is_tensor(scaling_factor) else 1.0
-            cov3d = (cov3d_scaled / coeff).requires_grad_(True)
+            if not mcmc:
+                cov3d_scaled = gaussians.get_covariance().detach()
+                scaling_factor = gaussians.get_scaling_factor
+                coeff = scaling_factor.detach().square() if torch.is_tensor(scaling_factor) else 1.0
+                cov3d = (cov3d_scaled / coeff).requires_grad_(True)
             # every row goes to the rasterizer (it culls them itself): radii and the screen-space gradient are then indexed
             # by Gaussian, which is what the reference scatters them back to (train.py:103-105)
             alpha_target = getattr(viewpoint_cam, "alpha_target", None) if lambda_alpha > 0 else None
             depth_target = getattr(viewpoint_cam, "depth_target", None) if lambda_depth > 0 else None
             extra = dict(extra_base, depth_grad=True) if (alpha_target is not None or depth_target is not None) else extra_base
-            if by_error:
+            if mcmc:
+                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, gather_visible=False, **extra)
+            elif by_error:
                 gt_image = viewpoint_cam.original_image.to(dev)
                 render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False,
                                               error_target=gt_image, **extra)
@@ -279,6 +307,8 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
                 measured = target > 0
                 residual = ((render_pkg["depth"] - render_pkg["alpha"] * target).abs() * measured).sum()
                 loss = loss + lambda_depth * residual / measured.sum().clamp(min=1)
+            if mcmc:
+                loss = loss + opacity_reg * torch.sigmoid(gaussians._opacity).mean() + scale_reg * gaussians.get_scaling.mean()
             loss.backward()
             pending.append(loss.detach())
             if sparse:
@@ -286,7 +316,9 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             else:
                 gaussians.optimizer.step()
             gaussians.optimizer.zero_grad(set_to_none=True)
-            if epoch < densify_until_epoch:
+            if mcmc:
+                gaussians.add_position_noise(noise_lr)
+            elif epoch < densify_until_epoch:
                 with torch.no_grad():
                     gaussians.add_densification_stats(viewspace_point_tensor, render_pkg["visibility_filter"], radii)
                     if by_error:
@@ -295,8 +327,13 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
         for v in torch.stack(pending).tolist():                   # one host read per epoch
             ema_loss_for_log = 0.4 * v + 0.6 * ema_loss_for_log
         info = {"iteration": iteration, "ema_loss": ema_loss_for_log, "densified": None, "reset_opacity": False}
+        if mcmc:
+            info["mcmc"] = None
+            if densify_from_epoch <= epoch < densify_until_epoch and epoch % densification_interval == 0:
+                relocated = gaussians.relocate_gs(min_opacity=min_opacity)
+                info["mcmc"] = (relocated, gaussians.add_new_gs(cap_max, min_opacity=min_opacity))
         with torch.no_grad():
-            if epoch < densify_until_epoch:
+            if epoch < densify_until_epoch and not mcmc:
                 if epoch > densify_from_epoch and epoch % densification_interval == 0:
                     size_threshold = 20 if epoch > opacity_reset_interval else None
                     rows = gaussians._xyz.shape[0]

@@ -550,6 +550,54 @@ int c3dgs_rows_apply(int32_t P, int64_t P_new, const int32_t* src /*[P_new]*/, c
 int c3dgs_densify_stats(int32_t P, const float* grad /*[P,3]*/, const uint8_t* filter /*[P]*/, const int32_t* radii /*[P] or NULL*/,
                         float* accum /*[P]*/, float* denom /*[P]*/, float* max_radii /*[P] or NULL*/, void* stream);
 
+/* ---- MCMC density control ("3D Gaussian Splatting as Markov Chain Monte Carlo", gsplat's MCMCStrategy), non-indexed models.
+ * Beyond the reference, which has threshold-driven density control only. Added without an ABI version bump: new entry points
+ * only. csrc/mcmc.hip. 0 <= P < 2^31; P == 0 and n == 0 are no-ops; arguments are validated before any device work.
+ *
+ * sample: n draws over P rows by opacity. o_i = sigmoid(raw_opacity_i) in fp32 and the INTEGER weight q_i = floor(o_i 2^20),
+ *   q_i = 0 for an excluded row: the rows `dead` marks (non-zero), or, with dead == NULL and derive_dead != 0, the rows with
+ *   o_i <= min_opacity, whose mask is then written to dead_out; with dead == NULL and derive_dead == 0 every row takes part.
+ *   With C_i the inclusive 64-bit prefix of q and T its total, draw j (a float64 uniform in [0, 1)) has the target
+ *   t_j = min(T - 1, (uint64) floor(draws[j] * (double) T)), one IEEE multiply, and sources[j] is the smallest i with
+ *   C_i > t_j: a row of weight 0 is never chosen. counts[i] = the number of draws that chose i (integer atomics). The
+ *   prefix is exact and independent of the scan order, so q, sources and counts are bitwise reproducible.
+ *   Outputs: q u32[P], counts i32[P] (zeroed first), *T u64 (device), sources i32[n]. With T == 0 nothing has weight: every
+ *   source is -1, counts stay 0 and *T == 0 reports it.
+ *   reuse_weights != 0: the workspace still holds the weights and prefix of a previous call with the same P and opacities
+ *   (q, *T and dead_out are not written again); counts are zeroed and the n draws are taken. A call with n == 0 and
+ *   reuse_weights == 0 computes the weights alone, so that the caller can size n from the mask it derived.
+ * apply: n pairs (dst_j, src_j = sources[j]), in place, P unchanged. dst_j = dst[j], or dst_base + j with dst == NULL. For
+ *   a row with count > 0 and N = min(count + 1, 51):
+ *     o' = 1 - (1 - o)^(1/N), clamped to [min_opacity, 1 - FLT_EPSILON]
+ *     c  = o / sum_{i=1..N} sum_{k=0..i-1} C(i-1,k) (-1)^k o'^(k+1) / sqrt(k+1)
+ *   evaluated in double from the raw fp32 opacity (o itself included: near o = 1 the fp32 sigmoid has lost 1 - o; in fp32
+ *   the sums are off by 1e-4 relative) and written in raw space, each value rounded once: the C3DGS_MCMC_ROLE_OPACITY tensor (row_floats 1) takes
+ *   logit(o'), every float of the C3DGS_MCMC_ROLE_SCALE tensor's row (row_floats 1..3: the raw log scale, or the raw log
+ *   scale factor) takes += log c. Each source gets its own values; each destination gets its source's, and with copy_rows != 0
+ *   also its source's row of every C3DGS_ROLE_COPY tensor (copy_rows == 0: the caller has copied the rows already). exp_avg
+ *   and exp_avg_sq of every source and destination row become zero in every tensor that has moments. All values are those
+ *   from before the call: the relocation values are staged in the workspace first, the row launch reads nothing it writes.
+ *   Sources and destinations must be disjoint (a destination's count is 0), which holds for dead rows (weight 0) and for
+ *   appended rows. The table is c3dgs_rows_apply's: in place, so in_* == out_*; exactly one opacity and one scale tensor.
+ *   Pairs with a source or destination outside [0, P) are skipped.
+ * noise: xyz += Sigma xi g(o) noise_lr xyz_lr, per row, in place, with Sigma = R diag(s^2) R^T formed as R (s^2 * (R^T xi)),
+ *   R of the normalised raw quaternion (r, x, y, z), s = exp(scaling), or normalize(relu(scaling)) * exp(scaling_factor) when
+ *   scaling_factor is given, o = sigmoid(raw_opacity), g(o) = 1 / (1 + exp(-100 ((1 - o) - 0.995))), xi [P,3] unit normals.
+ * The workspace is the caller's, 256-byte aligned, c3dgs_mcmc_workspace_bytes(P) bytes, shared by sample and apply. */
+#define C3DGS_MCMC_ROLE_OPACITY 3
+#define C3DGS_MCMC_ROLE_SCALE 4
+int c3dgs_mcmc_workspace_bytes(int64_t P, size_t* bytes);
+int c3dgs_mcmc_sample(int64_t P, const float* raw_opacity /*[P]*/, const uint8_t* dead /*[P] or NULL*/, int32_t derive_dead,
+                      float min_opacity, uint8_t* dead_out /*[P], with derive_dead*/, int64_t n, const double* draws /*[n]*/,
+                      int32_t reuse_weights, uint32_t* q /*[P]*/, int32_t* sources /*[n]*/, int32_t* counts /*[P]*/,
+                      uint64_t* T /*device*/, void* workspace, void* stream);
+int c3dgs_mcmc_apply(int64_t P, int64_t n, const int32_t* dst /*[n] or NULL*/, int64_t dst_base, const int32_t* sources /*[n]*/,
+                     const int32_t* counts /*[P]*/, int32_t n_tensors, const c3dgs_rows_tensor* tensors /*host*/,
+                     int32_t copy_rows, float min_opacity, void* workspace, void* stream);
+int c3dgs_mcmc_noise(int64_t P, float* xyz /*[P,3]*/, const float* rotation /*[P,4]*/, const float* scaling /*[P,3]*/,
+                     const float* scaling_factor /*[P] or NULL*/, const float* raw_opacity /*[P]*/, const float* xi /*[P,3]*/,
+                     float noise_lr, float xyz_lr, void* stream);
+
 /* ---- initial densification (GaussianModel.densify_initial, scene/gaussian_model.py:1352-1389): new points one `step` apart
  * on the ray from every point to each of its three nearest neighbours, planned in one pass from the neighbour table of
  * c3dgs_knn_neighbours instead of the reference's loop over levels (DESIGN.md "Initial densification"). With

@@ -6,6 +6,7 @@ before / after, and seconds per phase.
     python tools/run_train.py [--iterations 400] [--out profiles/r06_train_synth.json]
                               [--densify-by grad|error] [--error-threshold T] [--optimizer default|sparse_adam]
                               [--lambda-depth X] [--lambda-alpha Y] [--antialiasing]
+                              [--strategy default|mcmc] [--cap-max N] [--noise-lr X]
 
 --densify-by error (with --error-threshold, which has no default) lets the run with density control densify by image error
 (pipeline.train(densify_by="error")); the JSON then carries "densify_by" and "error_threshold".
@@ -19,7 +20,10 @@ the views of mean |depth - teacher depth| and mean |alpha - teacher alpha| of th
 resolution, and scores each trained student with metrics.render_and_eval (under the pipe it was trained with) at 0.5x, 1x and 2x
 that resolution, same poses, focal length scaled. The targets there are the teacher rendered at 4x the evaluated resolution by
 the plain rasterizer and box-filtered down 4 x 4 ("resolution_eval"); "train_views_1x" is the score against the training images
-themselves. One run each, nothing tuned; the JSON then carries "antialiasing" in place of the two default runs."""
+themselves. One run each, nothing tuned; the JSON then carries "antialiasing" in place of the two default runs.
+--strategy mcmc --cap-max N [--noise-lr X] makes ONE run with pipeline.train(strategy="mcmc", cap_max=N) (relocation, growth
+by 5 % up to N rows, position noise; csrc/mcmc.hip) in place of the two default runs; the JSON carries "strategy", "cap_max",
+"noise_lr" and under "mcmc" the run with its (epoch, relocated, added) refinements."""
 import argparse
 import json
 import os
@@ -82,7 +86,7 @@ def resolution_eval(student, cams, pipe):
 
 
 def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer="default", lambda_depth=0.0, lambda_alpha=0.0,
-        with_maps=False, antialiasing=None):
+        with_maps=False, antialiasing=None, mcmc=None):
     from c3dgs_amd import pipeline
     from c3dgs_amd.model import PipelineParams
     with tempfile.TemporaryDirectory() as tmp:
@@ -111,7 +115,7 @@ def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer=
     pipe = PipelineParams(antialiasing=bool(antialiasing))
     n = pipeline.train(Scene(), None, train_scene.schedule(iterations, densify), pipe, camera_stride=1, degree_up_iter=80,
                        log=lambda epoch, info: events.append((epoch, info)), densify_by=densify_by, error_threshold=error_threshold,
-                       optimizer_type=optimizer, **extra)
+                       optimizer_type=optimizer, **extra, **(mcmc or {}))
     torch.cuda.synchronize()
     t_train = time.perf_counter() - t0
     t0 = time.perf_counter()
@@ -121,6 +125,8 @@ def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer=
            "psnr_after": after, "densifications": [[e, i["densified"][0], list(i["densified"][1])] for e, i in events if i["densified"]],
            "opacity_resets": [e for e, i in events if i["reset_opacity"]],
            "seconds": {"setup": t_setup, "train": t_train, "eval": t_eval}}
+    if mcmc:
+        out["refinements"] = [[e, i["mcmc"][0], i["mcmc"][1]] for e, i in events if i.get("mcmc")]
     if with_maps:
         out["depth_l1"], out["alpha_l1"] = map_l1(student, cams, maps)
     if antialiasing is not None:
@@ -138,15 +144,31 @@ def main():
     ap.add_argument("--lambda-depth", type=float, default=0.0)
     ap.add_argument("--lambda-alpha", type=float, default=0.0)
     ap.add_argument("--antialiasing", action="store_true")
+    ap.add_argument("--strategy", choices=("default", "mcmc"), default="default")
+    ap.add_argument("--cap-max", type=int, default=None)
+    ap.add_argument("--noise-lr", type=float, default=5e5)
     args = ap.parse_args()
     if args.densify_by == "error" and args.error_threshold is None:
         ap.error("--densify-by error needs --error-threshold (there is no default)")
+    if args.strategy == "mcmc" and args.cap_max is None:
+        ap.error("--strategy mcmc needs --cap-max (there is no default)")
     if not torch.cuda.is_available():
         raise SystemExit("run_train.py needs the GPU; there is no CPU path")
     out = {"scene": "tests/train_scene.py: 4000-Gaussian synth-v1 teacher, 8 views 160x112, student = every 8th position as a point cloud"}
     if args.antialiasing:
         out["antialiasing"] = {"off": run(args.iterations, False, optimizer=args.optimizer, antialiasing=False),
                                "on": run(args.iterations, False, optimizer=args.optimizer, antialiasing=True)}
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
+    if args.strategy == "mcmc":
+        out["strategy"], out["cap_max"], out["noise_lr"] = "mcmc", args.cap_max, args.noise_lr
+        out["mcmc"] = run(args.iterations, True, optimizer=args.optimizer,
+                          mcmc=dict(strategy="mcmc", cap_max=args.cap_max, noise_lr=args.noise_lr))
+        if args.optimizer != "default":
+            out["optimizer"] = args.optimizer
         print(json.dumps(out))
         if args.out:
             with open(args.out, "w") as f:
