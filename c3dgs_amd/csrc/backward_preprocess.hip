@@ -16,6 +16,7 @@
 // 3D covariances are recomputed from scale/rotation instead of being stored by the forward.
 #include "common.hpp"
 #include "gsmath.hpp"
+#include "render_common.hpp" // slot_run
 
 #ifndef C3DGS_BWD_CH
 #define C3DGS_BWD_CH 128
@@ -166,9 +167,9 @@ __global__ void __launch_bounds__(BWD_LIST) __attribute__((amdgpu_waves_per_eu(8
     uint32_t start_;
     {
         const int ic = min(i, a.P - 1);                       // lanes past P clamp to the last Gaussian (empty run)
-        // global slot offsets = per-workgroup inclusive offsets of the forward + block_base[] (preprocess.hip)
-        const uint32_t end_ = a.inst_offset[ic] + a.block_base[ic >> 8];
-        start_ = (ic == 0) ? 0u : a.inst_offset[ic - 1] + a.block_base[(ic - 1) >> 8];
+        const SlotRun run = slot_run(ic, a.inst_offset, a.block_base);
+        const uint32_t end_ = run.end;
+        start_ = run.start;
         if (i >= a.P) start_ = end_;
         const uint32_t w_begin = __builtin_amdgcn_readfirstlane(start_);
         const uint32_t w_end = __builtin_amdgcn_readlane(end_, 63);

@@ -251,8 +251,7 @@ void launch_render_forward(int W, int H, const ImgPtrs& img, const uint32_t* poi
                            const float* bg, float* out_color, const CompactPtrs& cl, const uint32_t* sort_err, hipStream_t s)
 {
     const int gx = tiles_x(W), T = gx * tiles_y(H);
-    const int grid = ((T + 7) / 8) * 8;
-    render_forward_kernel<<<grid, 256, 0, s>>>(W, H, gx, T, img.ranges, point_list, splat, bg, out_color, img.final_T,
+    render_forward_kernel<<<banded_grid(T), 256, 0, s>>>(W, H, gx, T, img.ranges, point_list, splat, bg, out_color, img.final_T,
                                                img.n_contrib, img.tile_used, img.n_contrib_c, img.tile_used_c, cl.cqm, cl.cid, sort_err);
 }
 
@@ -424,7 +423,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
     for (int o = 32; o > 0; o >>= 1) wave_last = max(wave_last, __shfl_xor(wave_last, o));
     wave_last = __builtin_amdgcn_readfirstlane(wave_last);      // tell the compiler it is wave-uniform (scalar loop control)
     // where this lane's reduced values belong: Gaussian slot beta of the group, term my_m of the nine (see the network above)
-    const int beta = ((lane >> 2) & 1) * 4 + (lane & 1) * 2 + ((lane >> 1) & 1);
+    const int beta = candidate_of_lane(lane);
     const int my_m = ((lane >> 3) & 1) * 4 + ((lane >> 4) & 1) * 2 + ((lane >> 5) & 1);
     LaneCount lc;
 
@@ -448,9 +447,7 @@ render_backward_kernel(int W, int H, int gx, int T, const uint2* __restrict__ ra
             float4 a = splat[3 * (size_t)id], b = splat[3 * (size_t)id + 1];
             const float4 c = splat[3 * (size_t)id + 2];
             prescale_conic(a, b);
-            const uint32_t off = __float_as_uint(c.y), lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
-            const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
-            s_slot[tid] = block_base[id >> 8] + off + (uint32_t)((ty - y0) * (x1 - x0) + (tx - x0));
+            s_slot[tid] = entry_slot(c, block_base, id, tx, ty);
             s_ab[tid][0] = a; s_ab[tid][1] = b; s_c[tid] = c.x;
         }
         {   // next round's ids / masks: in flight behind this round's blending (two registers)
@@ -623,8 +620,7 @@ void launch_render_backward(int W, int H, const ImgPtrs& img, const float4* spla
                             uint8_t* touched, const CompactPtrs& cl, void* zero_span, size_t zero_n16, hipStream_t s)
 {
     const int gx = tiles_x(W), T = gx * tiles_y(H);
-    const int grid = ((T + 7) / 8) * 8;
-    render_backward_kernel<<<grid, 256, 0, s>>>(W, H, gx, T, img.ranges, img.tile_used_c, cl.cid, splat, block_base, bg, img.final_T,
+    render_backward_kernel<<<banded_grid(T), 256, 0, s>>>(W, H, gx, T, img.ranges, img.tile_used_c, cl.cid, splat, block_base, bg, img.final_T,
                                                 img.n_contrib_c, dL_dpix, partials, touched, cl.cqm, img.tile_order, (uint4*)zero_span,
                                                 zero_span ? zero_n16 : 0);
 }

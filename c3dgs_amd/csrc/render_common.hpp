@@ -1,7 +1,8 @@
 // render_common.hpp -- what the blend kernels of render.hip (forward, backward) and render_depth.hip (depth / alpha / median
 // replay) must share to take the same decisions bit for bit: the staged batch size, the pre-scaled conic, the alpha
-// expression, the quadrant cull and the workgroup -> tile banding; and the transposing butterfly that render_contrib.hip and
-// render_error.hip reduce with, so that both sum in the same order. One owner; device code only.
+// expression, the quadrant cull and the workgroup -> tile banding; the slot numbering of the (Gaussian, tile) entries; and the
+// transposing butterfly that the per-Gaussian passes reduce with, so that they sum in the same order. One owner; device code
+// only (but for banded_grid). The skeleton of the passes that replay a finished forward is replay.hpp.
 #pragma once
 #include "common.hpp"
 
@@ -87,6 +88,33 @@ __device__ __forceinline__ int tile_of_block(int b, int T)
     const int chunk = (T + 7) >> 3;
     return (b & 7) * chunk + (b >> 3);
 }
+// the grid of that order: 8 bands of ceil(T / 8) workgroups; those that fall off the end of a band, or past T, have no tile
+inline int banded_grid(int T) { return ((T + 7) / 8) * 8; }
+__device__ __forceinline__ bool block_has_no_tile(uint32_t b, int T)
+{
+    return tile_of_block((int)b, T) >= T || (b >> 3) >= (uint32_t)((T + 7) >> 3);
+}
+
+// ---- the slots of the (Gaussian, tile) entries: the numbering of the backward's partial sums, which the per-Gaussian passes share
+// The slot of Gaussian `id` in tile (tx, ty): first slot of the Gaussian + the tile's place in its rectangle. c = the third
+// float4 of the Gaussian's splat record {-, first slot relative to block_base[id >> 8], y0 << 16 | x0, y1 << 16 | x1}.
+__device__ __forceinline__ uint32_t entry_slot(const float4 c, const uint32_t* __restrict__ block_base, uint32_t id, int tx, int ty)
+{
+    const uint32_t off = __float_as_uint(c.y), lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
+    const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
+    return block_base[id >> 8] + off + (uint32_t)((ty - y0) * (x1 - x0) + (tx - x0));
+}
+
+// Gaussian i's slots [start, end): the id-order scan of tiles_touched = per-workgroup inclusive offsets of the forward +
+// block_base[] (preprocess.hip); the run's length is the rectangle's area
+struct SlotRun { uint32_t start, end; };
+__device__ __forceinline__ SlotRun slot_run(int i, const uint32_t* __restrict__ inst_offset, const uint32_t* __restrict__ block_base)
+{
+    SlotRun r;
+    r.end = inst_offset[i] + block_base[i >> 8];
+    r.start = (i == 0) ? 0u : inst_offset[i - 1] + block_base[(i - 1) >> 8];
+    return r;
+}
 
 // ---- the transposing butterfly of the per-Gaussian passes (render_contrib.hip, render_error.hip): one network, so that both
 // reduce in the same order
@@ -120,6 +148,11 @@ __device__ __forceinline__ void transpose_step(float* v, bool hi, Op op)
 // candidate hold the same bits, and the order of the float sum is the network's, not the timing's.
 // The network's two halves are also used apart (render_depth_backward.hip forms the y-moments of a pixel row between them, as
 // render_backward_kernel does between its column and row levels: the same pairings, so the same sums).
+__device__ __forceinline__ int candidate_of_lane(int lane)      // beta(lane): where this lane's reduced values belong
+{
+    return ((lane >> 2) & 1) * 4 + (lane & 1) * 2 + ((lane >> 1) & 1);
+}
+
 // columns: v[0..7] -> the reduction over the 8 pixels of this lane's pixel ROW of candidate beta(lane), in all 8 lanes of the row
 template <class Op>
 __device__ __forceinline__ float reduce_columns_of_8(float* v, int lane, Op op)

@@ -10,25 +10,25 @@
 //
 // Two launches behind render_backward (or behind the flag clear alone, when the loss does not use the image), no float
 // atomics, bitwise reproducible:
-//   A  render_depth_backward_kernel: a replay of the finished forward with render_contrib_kernel's structure (one 16x16 tile per
-//      workgroup, one 8x8 quadrant per wave, batches of 256 compact entries in double-buffered LDS, per-wave candidate lists from
-//      the cqm ballots, the forward's cuts tile_used_c / n_contrib_c, the shared gaussian_alpha() on the pre-scaled conic: it
-//      decides nothing again), walked BACK TO FRONT with render_backward_kernel's recurrences: T starts at the forward's final_T
-//      and is divided by (1 - alpha) on the way to the front, the "what lies behind" sum grows from 0. Per row of 8 candidates the
+//   A  render_depth_backward_kernel: a replay of the finished forward (replay.hpp: the tile walk, the staging, the candidate
+//      lists and the forward's cuts tile_used_c / n_contrib_c; it decides nothing again), walked BACK TO FRONT with
+//      render_backward_kernel's recurrences: T starts at the forward's final_T and is divided by (1 - alpha) on the way to the
+//      front, the "what lies behind" sum grows from 0. Per row of 8 candidates the
 //      per-pixel terms {w, w dx, w dx^2, alpha T gD} are reduced over a pixel row with the column levels of render_common.hpp's
 //      transposing butterfly, the row's dy gives the y-moments, the row levels add the seven sums over the 8 rows (the pairings
 //      and roundings of render_backward_kernel's network, so the sums are that kernel's for a colour channel), the four
 //      waves meet in LDS, and one thread per entry merges them, (0 + 1) + (2 + 3), and ADDS the six moments into the entry's
-//      36-byte slot of the product backward's partial sums (read-add-store where the slot's flag byte is set, a store that sets
-//      the byte otherwise; the colour components stay as they are). A slot belongs to one (Gaussian, tile), i.e. to one
-//      workgroup of this grid, and render_backward has finished on the stream: no race. dL/dz goes to a 4-byte plane of its own
-//      in the same slot numbering; it is written for every slot whose flag is set afterwards.
+//      36-byte slot of the product backward's partial sums (entry_slot(); read-add-store where the slot's flag byte is set, a
+//      store that sets the byte otherwise; the colour components stay as they are). A slot belongs to one (Gaussian, tile), i.e.
+//      to one workgroup of this grid, and render_backward has finished on the stream: no race. dL/dz goes to a 4-byte plane of
+//      its own in the same slot numbering; it is written for every slot whose flag is set afterwards.
 //   B  depth_backward_fold_kernel, behind backward_preprocess: one lane per LISTED Gaussian folds the flagged slots of its run of
-//      the dL/dz plane in slot order (the whole wave a long run, as contrib_sum_kernel does) and adds dL/dz x the depth row of
-//      the view matrix -- the row preprocess forms the stored depth from, xform4x3's z -- into dL_dmeans3D.
-// Both honour the sort's time-out word as the other replays do: set -> A walks nothing, B poisons the listed rows with NaN.
+//      the dL/dz plane with fold_slot_run() and adds dL/dz x the depth row of the view matrix -- the row preprocess forms the
+//      stored depth from, xform4x3's z -- into dL_dmeans3D.
+// Both honour the sort's time-out word: set -> A walks nothing, B poisons the listed rows with NaN.
 #include "common.hpp"
 #include "render_common.hpp"
+#include "replay.hpp"
 
 namespace c3dgs {
 
@@ -49,77 +49,45 @@ render_depth_backward_kernel(int W, int H, int gx, int T, const uint2* __restric
     // every product below is rounded on its own, as in render_backward_kernel, whose terms feed hand-placed DPP adds: the sums are
     // then that kernel's bits for a colour channel (explicit fmaf calls are not affected)
 #pragma clang fp contract(off)
-    const int tile = tile_of_block(blockIdx.x, T);
-    if (tile >= T || (blockIdx.x >> 3) >= ((T + 7) >> 3)) return;
+    if (block_has_no_tile(blockIdx.x, T)) return;
     // the sort's time-out word, as in the forward: set -> the lists are not to be trusted, walk nothing (stage B writes NaN)
     if (*sort_err != 0u) return;
-    __shared__ float4 s_ab[2][BATCH + 1][2];          // {x, y, ka, kb | kc, opacity, z, -}; entry BATCH: sentinel, opacity 0
-    __shared__ uint32_t s_list[4][BATCH + 8];        // per wave: its candidates of the batch, padded to a multiple of 8
-    __shared__ unsigned long long s_mask[2][4][4];   // [buf][quadrant][staging wave]
+    __shared__ ReplayStage st;                       // the staged record carries z in place of the red
     __shared__ float s_stat[4][BATCH][DEPTH_BWD_TERMS];   // [wave][batch entry] the seven sums over the wave's 64 pixels
     __shared__ uint8_t s_hits[4][BATCH];             // ... and whether any of them blended it
-    static_assert(sizeof(s_ab) + sizeof(s_list) + sizeof(s_mask) + sizeof(s_stat) + sizeof(s_hits) <= 41 * 1280,
+    static_assert(sizeof(st) + sizeof(s_stat) + sizeof(s_hits) <= 41 * 1280,
                   "render_depth_backward: more than 41 LDS granules = two workgroups per CU instead of three");
-    constexpr uint32_t REC_BYTES = 32, BUF_BYTES = (BATCH + 1) * REC_BYTES;
 
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int tx = tile % gx, ty = tile / gx;
-    const int px = tx * TILE + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const size_t pix = (size_t)W * py + px;
-    if (tid < 2) { s_ab[tid][BATCH][0] = make_float4(0, 0, 0, 0); s_ab[tid][BATCH][1] = make_float4(0, 0, 0, 0); }
-
-    const uint2 range = ranges[tile];
-    const int n = (int)(range.y - range.x);
-    const int used = min(n, (int)tile_used_c[tile]);            // compact entries the forward wrote and some pixel blended
-    const int rounds = (used + BATCH - 1) / BATCH;
-
-    // 1-based compact index of the pixel's last blended entry = where this pixel's walk starts; per wave the deepest of its 64
-    const int last = inside ? min((int)n_contrib_c[pix], used) : 0;
-    float Tr = inside ? final_Ts[pix] : 0.f;                    // transmittance behind the pixel's last blended entry
-    const float gD = (inside && dL_ddepth) ? dL_ddepth[pix] : 0.f;
-    const float gA = (inside && dL_dalpha_map) ? dL_dalpha_map[pix] : 0.f;
+    // t.last is where this pixel's walk starts
+    const ReplayTile t = replay_tile(blockIdx.x, W, H, gx, T, ranges, tile_used_c, n_contrib_c, false, st);
+    const int tid = t.tid, wave = t.wave, lane = t.lane;
+    float Tr = t.inside ? final_Ts[t.pix] : 0.f;                // transmittance behind the pixel's last blended entry
+    const float gD = (t.inside && dL_ddepth) ? dL_ddepth[t.pix] : 0.f;
+    const float gA = (t.inside && dL_dalpha_map) ? dL_dalpha_map[t.pix] : 0.f;
     float Sd = 0.f;                                             // sum_{j behind} w_j c_j
-    int wave_last = last;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) wave_last = max(wave_last, __shfl_xor(wave_last, o));
-    wave_last = __builtin_amdgcn_readfirstlane(wave_last);
 
-    const char* rec_base = reinterpret_cast<const char*>(&s_ab[0][0][0]);
-    // where this lane's reduced values belong: candidate beta of the row
-    const int beta = ((lane >> 2) & 1) * 4 + (lane & 1) * 2 + ((lane >> 1) & 1);
+    const int beta = candidate_of_lane(lane);
 
     float4 ra = make_float4(0, 0, 0, 0), rb = ra;
     uint32_t qm = 0u, slot_next = 0u;
     // batch entry j of round r is compact entry used - 1 - (r * BATCH + j): back to front, as render_backward walks
     auto gather = [&](int back) {                               // `back`-th entry from the end -> this thread's staging registers
         qm = 0u;
-        const int pos = used - 1 - back;
+        const int pos = t.used - 1 - back;
         if (pos >= 0) {
-            const uint32_t id = cid[range.x + pos];
-            qm = cqm[range.x + pos];
+            const uint32_t id = cid[t.range.x + pos];
+            qm = cqm[t.range.x + pos];
             ra = splat[3 * (size_t)id]; rb = splat[3 * (size_t)id + 1];
-            rb.z = __uint_as_float(depth_keys[id]);             // in place of the record's red, as render_depth stages it
-            // the entry's slot, as render_backward forms it: first slot of the Gaussian + the tile's place in its rectangle
-            const float4 c = splat[3 * (size_t)id + 2];
-            const uint32_t off = __float_as_uint(c.y), lo = __float_as_uint(c.z), hi = __float_as_uint(c.w);
-            const int x0 = lo & 0xffff, y0 = lo >> 16, x1 = hi & 0xffff;
-            slot_next = block_base[id >> 8] + off + (uint32_t)((ty - y0) * (x1 - x0) + (tx - x0));
+            rb.z = __uint_as_float(depth_keys[id]);             // in place of the record's red
+            slot_next = entry_slot(splat[3 * (size_t)id + 2], block_base, id, t.tx, t.ty);
         }
     };
     gather(tid);
-    for (int r = 0; r < rounds; r++) {
+    for (int r = 0; r < t.rounds; r++) {
         const int buf = r & 1;
         const uint32_t slot = slot_next;                        // of batch entry `tid`, which this thread stages and later merges
-        prescale_conic(ra, rb);
-        s_ab[buf][tid][0] = ra; s_ab[buf][tid][1] = rb;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const unsigned long long bm = __ballot((qm >> q) & 1u);
-            if (lane == 0) s_mask[buf][q][wave] = bm;
-        }
+        stage_batch(st, buf, tid, ra, rb);
+        publish_quadrant_masks(st, buf, wave, lane, qm);
         // a wave only writes the entries of its own candidate list: the others read as "nothing blended". This thread read
         // its entry's words of the previous batch behind that batch's second barrier, so it may clear them here.
 #pragma unroll
@@ -130,41 +98,25 @@ render_depth_backward_kernel(int W, int H, int gx, int T, const uint2* __restric
         }
         __syncthreads();
         gather((r + 1) * BATCH + tid);                          // the next batch, behind this batch's blending
-        const int pos0 = used - 1 - r * BATCH;                  // 0-based compact position of batch entry j is pos0 - j
+        const int pos0 = t.used - 1 - r * BATCH;                // 0-based compact position of batch entry j is pos0 - j
         // entries at position >= wave_last (j <= pos0 - wave_last) lie behind every pixel of this wave
-        if (pos0 - wave_last + 1 < BATCH) {
-            int nw = 0;
-            const uint32_t buf_off = (uint32_t)buf * BUF_BYTES;
-            {
-                const unsigned long long lt = (1ull << lane) - 1ull;
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    unsigned long long m = uniform_u64(s_mask[buf][wave][c]);
-                    const int jmin = pos0 - wave_last + 1 - c * 64;   // first entry of this staging wave in front of the cut
-                    if (jmin >= 64) m = 0; else if (jmin > 0) m &= ~0ull << jmin;
-                    if ((m >> lane) & 1ull) s_list[wave][nw + (int)__popcll(m & lt)] = buf_off + (uint32_t)(c * 64 + lane) * REC_BYTES;
-                    nw += (int)__popcll(m);
-                }
-                if (lane < 8) s_list[wave][nw + lane] = buf_off + (uint32_t)BATCH * REC_BYTES;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
+        const int jmin = pos0 - t.wave_last + 1;
+        if (jmin < BATCH) {
+            const int nw = build_candidate_list(st, buf, wave, lane,
+                                                [&](unsigned long long m, int c) { return drop_behind(m, jmin - c * 64); });
             // a pixel takes entry j only if pos0 - j < last, i.e. record offset > thr (the sentinel's opacity is 0: never a hit)
-            const int thr = (int)buf_off + min(max(pos0 - last, -1), BATCH) * (int)REC_BYTES;
+            const int thr = (int)((uint32_t)buf * REPLAY_BUF_BYTES) + min(max(pos0 - t.last, -1), BATCH) * (int)REPLAY_REC_BYTES;
             for (int k = 0; k < nw; k += 8) {
-                const uint4 row0 = *reinterpret_cast<const uint4*>(&s_list[wave][k]);
-                const uint4 row1 = *reinterpret_cast<const uint4*>(&s_list[wave][k + 4]);
-                const uint32_t e[8] = { row0.x, row0.y, row0.z, row0.w, row1.x, row1.y, row1.z, row1.w };
-                const uint32_t my_off = s_list[wave][k + beta];  // the candidate this lane reports on
+                uint32_t e[8];
+                load_row(st, wave, k, e);
+                const uint32_t my_off = st.list[wave][k + beta];  // the candidate this lane reports on
                 float v0[8], vx[8], vxx[8], vz[8];
                 uint32_t my_hit = 0u;
 #pragma unroll
                 for (int g = 0; g < 8; g++) {
-                    const float4 a = *reinterpret_cast<const float4*>(rec_base + e[g]);
-                    const float4 b = *reinterpret_cast<const float4*>(rec_base + e[g] + 16);
+                    const StagedRecord s = staged_record(st, e[g]);
                     float dx, dy, G, alpha;
-                    bool hit = gaussian_alpha(a.x, a.y, a.z, a.w, b.x, b.y, pxf, pyf, dx, dy, G, alpha);
+                    bool hit = gaussian_alpha(s.a.x, s.a.y, s.a.z, s.a.w, s.b.x, s.b.y, t.pxf, t.pyf, dx, dy, G, alpha);
                     // in front of the pixel's last contributor every hit was blended by the forward (its stop lies behind it)
                     hit = hit && ((int)e[g] > thr);
                     // branch-free, as render_backward: a pixel that does not blend the entry runs the same instructions with
@@ -173,7 +125,7 @@ render_depth_backward_kernel(int W, int H, int gx, int T, const uint2* __restric
                     const float rinv = __builtin_amdgcn_rcpf(1.f - a_eff);   // 1 - alpha is in [0.01, 1]; rcp(1) == 1
                     Tr = Tr * rinv;                              // transmittance in front of this entry
                     const float wgt = a_eff * Tr;                // alpha_k T_k
-                    const float cd = b.z * gD + gA;              // two roundings: the colour backward's (z, 1, 0) . (gD, gA, 0)
+                    const float cd = s.b.z * gD + gA;            // two roundings: the colour backward's (z, 1, 0) . (gD, gA, 0)
                     const float dL_dalpha = fmaf(Tr, cd, -(rinv * Sd));
                     Sd = fmaf(wgt, cd, Sd);
                     // w = G * dL/dalpha and its first two x-moments about the mean; the y-moments follow from the row sums
@@ -188,7 +140,7 @@ render_depth_backward_kernel(int W, int H, int gx, int T, const uint2* __restric
                 // render_backward_kernel's pairings and roundings, term for term
                 const float c0 = reduce_columns_of_8(v0, lane, OpAdd()), cx = reduce_columns_of_8(vx, lane, OpAdd());
                 const float cxx = reduce_columns_of_8(vxx, lane, OpAdd()), cz = reduce_columns_of_8(vz, lane, OpAdd());
-                const float dyb = *reinterpret_cast<const float*>(rec_base + my_off + 4) - pyf;
+                const float dyb = staged_mean_y(st, my_off) - t.pyf;
                 float sum[DEPTH_BWD_TERMS];
                 sum[0] = reduce_rows_of_8(c0, OpAdd());
                 sum[1] = reduce_rows_of_8(cx, OpAdd());
@@ -197,9 +149,8 @@ render_depth_backward_kernel(int W, int H, int gx, int T, const uint2* __restric
                 sum[4] = reduce_rows_of_8(dyb * cx, OpAdd());
                 sum[5] = reduce_rows_of_8((dyb * dyb) * c0, OpAdd());
                 sum[6] = reduce_rows_of_8(cz, OpAdd());
-                // lanes 0..7 hold the row's 8 candidates (beta is a permutation of them); the row's padding is the sentinel.
-                // Each (wave, entry) pair occurs once: plain LDS stores into the wave's own plane.
-                const int myj = (int)((my_off - buf_off) / REC_BYTES);
+                // each (wave, entry) pair occurs once: plain LDS stores into the wave's own plane
+                const int myj = batch_entry_of(my_off, buf);
                 if (lane < 8 && myj < BATCH) {
 #pragma unroll
                     for (int q = 0; q < DEPTH_BWD_TERMS; q++) s_stat[wave][myj][q] = sum[q];
@@ -209,7 +160,7 @@ render_depth_backward_kernel(int W, int H, int gx, int T, const uint2* __restric
         }
         __syncthreads();
         // one thread per batch entry merges the four waves, (0 + 1) + (2 + 3) as render_backward_kernel's flush, and owns the slot
-        if (r * BATCH + tid < used) {
+        if (r * BATCH + tid < t.used) {
             const uint32_t h = (uint32_t)s_hits[0][tid] | s_hits[1][tid] | s_hits[2][tid] | s_hits[3][tid];
             const bool was = touched[slot] != 0;
             if (h || was) {
@@ -236,11 +187,8 @@ render_depth_backward_kernel(int W, int H, int gx, int T, const uint2* __restric
 }
 
 // ---- stage B: one lane per listed Gaussian (sum_partials_kernel's lists: BWD_LIST entries per list, filled from the front, the
-// grid and the workgroup -> (list, quarter) map of backward_preprocess_kernel) folds the flagged slots of its run
-// [start, end) of the dL/dz plane in slot order; a run longer than DEPTH_FOLD_LONG_RUN slots is folded by the whole wave, lane l
-// taking slots start + l, start + l + 64, ... and the 64 partial results meeting in an xor butterfly, as contrib_sum_kernel does.
-// Which lane adds what follows from the run alone, so the result is the same bits whoever the neighbours are.
-constexpr uint32_t DEPTH_FOLD_LONG_RUN = 64;
+// grid and the workgroup -> (list, quarter) map of backward_preprocess_kernel) folds the flagged slots of its run of the dL/dz
+// plane (replay.hpp)
 __global__ void __launch_bounds__(256)
 depth_backward_fold_kernel(int P, const uint32_t* __restrict__ live_count, const uint32_t* __restrict__ live_ids,
                            const uint32_t* __restrict__ inst_offset, const uint32_t* __restrict__ block_base,
@@ -259,38 +207,9 @@ depth_backward_fold_kernel(int P, const uint32_t* __restrict__ live_count, const
     if (*sort_err != 0u) {
         sum = __uint_as_float(0x7fc00000u);
     } else {
-        uint32_t start = 0u, end = 0u;
-        if (live && i < P) {
-            end = inst_offset[i] + block_base[i >> 8];
-            start = (i == 0) ? 0u : inst_offset[i - 1] + block_base[(i - 1) >> 8];
-        }
-        const bool long_run = end - start > DEPTH_FOLD_LONG_RUN;
-        if (!long_run)
-            for (uint32_t s = start; s < end; s++) {
-                if (!touched[s]) continue;
-                sum += dz_plane[s];
-            }
-        for (unsigned long long m = __ballot(long_run); m; m &= m - 1ull) {
-            const int src = (int)__ffsll((long long)m) - 1;
-            const uint32_t s0 = __shfl(start, src), s1 = __shfl(end, src);
-            float ps = 0.f;
-            for (uint32_t s = s0 + (uint32_t)lane; s < s1; s += 256) {
-                uint8_t f[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) f[k] = (s + 64u * k < s1) ? touched[s + 64u * k] : (uint8_t)0;
-                float c[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    c[k] = 0.f;
-                    if (f[k]) c[k] = dz_plane[s + 64u * k];
-                }
-#pragma unroll
-                for (int k = 0; k < 4; k++) ps += c[k];         // ascending slots; an unwritten one adds +0
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) ps += __shfl_xor(ps, o);
-            if (lane == src) sum = ps;
-        }
+        SlotRun run = { 0u, 0u };
+        if (live && i < P) run = slot_run(i, inst_offset, block_base);
+        sum = fold_slot_run(run, dz_plane, touched, lane);
     }
     if (!live || i >= P) return;
     // z = view[2] x + view[6] y + view[10] z + view[14] (gsmath.hpp: xform4x3, what preprocess stores as the depth)
@@ -305,10 +224,9 @@ void launch_render_depth_backward(int W, int H, const ImgPtrs& img, const Compac
                                   hipStream_t s)
 {
     const int gx = tiles_x(W), T = gx * tiles_y(H);
-    const int grid = ((T + 7) / 8) * 8;
-    render_depth_backward_kernel<<<grid, 256, 0, s>>>(W, H, gx, T, img.ranges, img.tile_used_c, img.n_contrib_c, img.final_T, cl.cid,
-                                                      cl.cqm, g.splat, g.depth_keys, g.block_base, dL_ddepth, dL_dalpha, w.partials,
-                                                      dz_plane, w.touched, sort_err);
+    render_depth_backward_kernel<<<banded_grid(T), 256, 0, s>>>(W, H, gx, T, img.ranges, img.tile_used_c, img.n_contrib_c, img.final_T,
+                                                                cl.cid, cl.cqm, g.splat, g.depth_keys, g.block_base, dL_ddepth,
+                                                                dL_dalpha, w.partials, dz_plane, w.touched, sort_err);
 }
 
 void launch_depth_backward_fold(int P, const GeomPtrs& g, const BwdPtrs& w, const float* dz_plane, const float* view,

@@ -28,12 +28,12 @@ import numpy as np
 import pytest
 import torch
 
-from tests import cases, depth_grad_ref as dgr, depth_ref, gpu_util, synth
+from tests import cases, depth_grad_ref as dgr, depth_ref, error_ref, gpu_util, synth
 
 pytestmark = pytest.mark.gpu
 
 IDENTITY_MEASURED = ("worst tensor, both maps or one, plain and indexed alike: indexed 8.1e-8, odd_size 1.5e-8, opaque_big 5.3e-8, "
-                     "needles_long 2.2e-8, huge_faint 1.2e-7, deep 0, one_pixel 0, one_tile (signed maps) 1.2e-8")
+                     "needles_long 2.2e-8, huge_faint 1.2e-7, deep 0, one_pixel 0, one_tile (signed maps) 1.2e-8, long_run 0")
 TRUTH_MEASURED = ("tiny 6.0e-7, indexed 4.6e-6 (one pair replayed; 7.3e-4 under the other decision of its one ambiguous pair), "
                   "odd_size 6.8e-6 (one pair replayed; 1.9e-3 against the float64 reference's own decision), cov_precomp 5.1e-6, "
                   "colors_precomp 6.1e-6")
@@ -119,11 +119,13 @@ def _worst(got, ref, names, bar, label):
 
 
 CASES = [(name, ix) for name in depth_ref.SCENES for ix in ((True,) if name == "indexed" else (False, True))]
+# tests/error_ref.py's scene: a Gaussian over 17 x 17 tiles, i.e. a run of 289 slots (two trips of the fold's whole-wave path)
+CASES += [("long_run", False), ("long_run", True)]
 
 
 @pytest.mark.parametrize("name,as_indexed", CASES, ids=[f"{n}-{'indexed' if i else 'plain'}" for n, i in CASES])
 def test_identity_with_the_colour_coded_product_backward(hip, name, as_indexed):
-    inp, cam, indexed = depth_ref.scene(name)
+    inp, cam, indexed = error_ref.long_run_scene() if name == "long_run" else depth_ref.scene(name)
     if as_indexed and not indexed:
         inp = _lift(inp)
     W, H = cam["W"], cam["H"]

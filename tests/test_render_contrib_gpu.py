@@ -2,7 +2,7 @@
 c3dgs_contrib_accumulate) and what is built on them (settings.contrib, GaussianModel.render(return_contrib=True),
 contribution_stats, prune_by_contribution, finetune(prune_min_views=...)).
 
-On every scene of tests/depth_ref.py:
+On every scene of tests/depth_ref.py and on tests/error_ref.py's `long_run`:
   1. against the float64 walk of tests/contrib_ref.py: a Gaussian is exempt if its `hits` differs from the walk's, at most
      max(2, 2e-5 P) are (tests/test_contrib_ref_cpu.py: the reference side needs none); every other row has equal hits and
      weight_sum, weight_max within 1e-4 relative (the project's gradient bar; about 9x the spread between the walk and an
@@ -29,7 +29,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import cases, contrib_ref, depth_ref, gpu_util, synth
+from tests import cases, contrib_ref, depth_ref, error_ref, gpu_util, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -72,19 +72,27 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+def _scene(name):
+    """-> (inputs, cam, indexed); computed once per process, not to be modified."""
+    return error_ref.long_run_scene() if name == "long_run" else depth_ref.scene(name)
+
+
 @functools.lru_cache(maxsize=None)
 def _reference(name):
-    st = depth_ref.oracle_state(name)
+    st = error_ref.long_run_state() if name == "long_run" else depth_ref.oracle_state(name)
     return contrib_ref.walk(st, st.W, st.H)
 
 
-@pytest.mark.parametrize("name", depth_ref.SCENES)
+@pytest.mark.parametrize("name", list(depth_ref.SCENES) + ["long_run"])
 def test_statistics_replay_the_forward(hip, orc, name):
-    """Measured on an MI355X, over the seven scenes: 0 Gaussians exempt; largest relative difference against the walk 1.15e-5 for
-    weight_sum (`needles_long`; 2.5e-6 on `huge_faint`, 1.5e-6 on `deep`) and 4.3e-6 for weight_max; weight_sum against
-    dL_dcolors[:, 0] of the product backward rel-inf 6.2e-7 at most (`huge_faint`; 5.7e-7 on `deep`, 1.2e-7 elsewhere);
-    conservation within 8.7e-9. The test prints each figure before it asserts."""
-    inp, cam, indexed = depth_ref.scene(name)
+    """Measured on an MI355X, over the seven scenes of tests/depth_ref.py: 0 Gaussians exempt; largest relative difference against
+    the walk 1.15e-5 for weight_sum (`needles_long`; 2.5e-6 on `huge_faint`, 1.5e-6 on `deep`) and 4.3e-6 for weight_max;
+    weight_sum against dL_dcolors[:, 0] of the product backward rel-inf 6.2e-7 at most (`huge_faint`; 5.7e-7 on `deep`, 1.2e-7
+    elsewhere); conservation within 8.7e-9. `long_run` (tests/error_ref.py: the one scene with a blended Gaussian over more than
+    256 slots, i.e. two trips of stage B's whole-wave fold) puts weight_max and hits through that fold: 0 of 301 exempt, 2.8e-7 and 2.6e-7 against
+    the walk, 1.1e-9 against the product backward.
+    The test prints each figure before it asserts."""
+    inp, cam, indexed = _scene(name)
     W, H = cam["W"], cam["H"]
     fw = gpu_util.hip_forward(inp, cam, indexed)
     u = gpu_util.unpack(fw)
@@ -94,6 +102,8 @@ def test_statistics_replay_the_forward(hip, orc, name):
     assert np.isfinite(wsum).all() and np.isfinite(wmax).all()
     if name in ("indexed", "odd_size", "huge_faint", "deep"):
         assert (hits[256:] > 0).any(), "no blended Gaussian beyond the first 256-Gaussian scan group"
+    if name == "long_run":
+        assert ((u["tiles_touched"] > 256) & (hits > 0)).any(), "no blended Gaussian whose run takes two trips of the whole-wave fold"
 
     # 1. against the float64 walk
     ref = _reference(name)
