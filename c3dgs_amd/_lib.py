@@ -266,6 +266,20 @@ def gpu_tensor(t, name, dtype=torch.float32):
     return t.contiguous()
 
 
+_workspaces = {}      # (key, device) -> the cached workspace (uint8), grown on demand
+
+
+def workspace(key, device, nbytes, zeroed=False):
+    """The workspace that module `key` ("optim", "mcmc") keeps per device: at least `nbytes`, reallocated (zero-filled if
+    `zeroed`) only to grow, and 256-byte aligned as the library demands."""
+    ws = _workspaces.get((key, device))
+    if ws is None or ws.numel() < nbytes:
+        ws = _workspaces[key, device] = (torch.zeros if zeroed else torch.empty)(nbytes, dtype=torch.uint8, device=device)
+    if ws.data_ptr() % 256:
+        raise RuntimeError(f"c3dgs_amd.{key}: the allocator returned a workspace that is not 256-byte aligned")
+    return ws
+
+
 def profile_enable(on=True, only=None):
     """Bracket stage launches with HIP events; `only` = one stage name to keep the queue cost to that kernel."""
     check(lib().c3dgs_profile_only(only.encode() if only else None))

@@ -59,7 +59,7 @@ SOURCES = {
     "image_io.hip": ["-ffp-contract=off"],  # t0 * (1 - f) + t1 * f of the bilinear taps is separately rounded (csrc/image_io.hip)
 }
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), os.path.join(CSRC, "render_diag.hpp"),
-           os.path.join(CSRC, "render_common.hpp"), os.path.join(CSRC, "replay.hpp"), os.path.join(CSRC, "scan_blocks.hpp"), os.path.join(CSRC, "adam_common.hpp"), os.path.join(CSRC, "mcmc.hpp"),
+           os.path.join(CSRC, "render_common.hpp"), os.path.join(CSRC, "replay.hpp"), os.path.join(CSRC, "scan_blocks.hpp"), os.path.join(CSRC, "adam_common.hpp"), os.path.join(CSRC, "mcmc.hpp"), os.path.join(CSRC, "jobs.hpp"),
            os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h")]
 
 

@@ -11,23 +11,16 @@
 // HBM-bound streaming.
 #include "common.hpp"
 #include "adam_common.hpp"      // adam_one: the per-element arithmetic, shared with sparse_adam.hip
+#include "jobs.hpp"
 
 namespace c3dgs {
 
-struct AdamJobs {
-    c3dgs_adam_tensor t[C3DGS_ADAM_MAX_TENSORS];
-    int first_block[C3DGS_ADAM_MAX_TENSORS];
-    int nblocks[C3DGS_ADAM_MAX_TENSORS];
-    int n;
-};
+using AdamJobs = JobTable<c3dgs_adam_tensor, C3DGS_ADAM_MAX_TENSORS>;
 
 __global__ void __launch_bounds__(256)
 adam_kernel(const AdamJobs jobs, float w1, float beta2, float w2, float eps)
 {
-    int j = 0;
-#pragma unroll
-    for (int k = 1; k < C3DGS_ADAM_MAX_TENSORS; k++)
-        if (k < jobs.n && (int)blockIdx.x >= jobs.first_block[k]) j = k;
+    const int j = job_of_block(jobs);
     const c3dgs_adam_tensor t = jobs.t[j];
     const float neg_step = -t.step_size;
     const long long stride = (long long)jobs.nblocks[j] * 256, i0 = (long long)(blockIdx.x - jobs.first_block[j]) * 256 + threadIdx.x;
@@ -56,20 +49,12 @@ adam_kernel(const AdamJobs jobs, float w1, float beta2, float w2, float eps)
 
 void launch_adam(int n_tensors, const c3dgs_adam_tensor* tensors, double beta1, double beta2, double eps, hipStream_t s)
 {
-    AdamJobs J; J.n = 0;
-    int nb = 0;
-    for (int k = 0; k < n_tensors; k++) {
-        if (tensors[k].n <= 0) continue;
-        J.t[J.n] = tensors[k];
-        J.first_block[J.n] = nb;
-        long long want = (tensors[k].n / 4 + 256 * 4 - 1) / (256 * 4);
-        J.nblocks[J.n] = (int)(want < 1 ? 1 : (want > 16384 ? 16384 : want));
-        nb += J.nblocks[J.n];
-        J.n++;
-    }
+    AdamJobs J;
+    for (int k = 0; k < n_tensors; k++)
+        if (tensors[k].n > 0) J.add(tensors[k], (tensors[k].n / 4 + 256 * 4 - 1) / (256 * 4), 16384);
     if (J.n == 0) return;
     // 1 - beta is formed in double and rounded once, as torch's Python side does (1.f - 0.999f is off by 1.3e-5 relative)
-    adam_kernel<<<nb, 256, 0, s>>>(J, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
+    adam_kernel<<<J.grid(), 256, 0, s>>>(J, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
 }
 
 // acc += |g| (the accumulation step of the sensitivity pass, compress.py:110-113): one read of g, one read-modify-write of

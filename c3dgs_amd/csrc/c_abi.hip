@@ -967,30 +967,46 @@ int c3dgs_adam_step(int32_t n_tensors, const c3dgs_adam_tensor* tensors, double 
     return C3DGS_OK;
 }
 
-// ---- sparse Adam (sparse_adam.hip)
-static const char* sparse_adam_bad_P(int64_t P)
+// ---- what the entries of sparse Adam, density control and MCMC check alike; each returns the message behind the entry's name
+static const char* bad_row_count(int64_t P)
 {
     if (P < 0) return "P must be >= 0";
     if (P >= (int64_t(1) << 31)) return "P must be below 2^31 (row ids are 32-bit)";
     return nullptr;
 }
+static const char* bad_workspace(const void* w)
+{
+    return !w || (reinterpret_cast<uintptr_t>(w) & 255u) ? "the workspace must be non-NULL and 256-byte aligned" : nullptr;
+}
+// the c3dgs_rows_tensor table of c3dgs_rows_apply / c3dgs_mcmc_apply. `rows`: how many rows the call writes; a call that
+// writes none returns before it reads the table, so only the count is checked then.
+static const char* bad_rows_table(int32_t n_tensors, const c3dgs_rows_tensor* tensors, int64_t rows)
+{
+    if (n_tensors < 0 || n_tensors > C3DGS_ROWS_MAX_TENSORS) return "between 0 and 16 tensors per call";
+    if (rows == 0 || n_tensors == 0) return nullptr;
+    if (!tensors) return "NULL buffer";
+    for (int k = 0; k < n_tensors; k++)
+        if (tensors[k].row_floats < 1 || tensors[k].row_floats > 4096) return "row_floats must be between 1 and 4096";
+    return nullptr;
+}
+
+// ---- sparse Adam (sparse_adam.hip)
 
 int c3dgs_sparse_adam_workspace_bytes(int64_t P, size_t* bytes)
 {
     if (!bytes) return fail(C3DGS_E_INVALID, "sparse_adam_workspace_bytes: bytes is NULL");
-    if (const char* bad = sparse_adam_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_workspace_bytes: ") + bad);
+    if (const char* bad = bad_row_count(P)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_workspace_bytes: ") + bad);
     *bytes = sparse_adam_layout(P).total_bytes;
     return C3DGS_OK;
 }
 
 int c3dgs_sparse_adam_select(int64_t P, const void* mask, int32_t mask_kind, void* workspace, void* stream)
 {
-    if (const char* bad = sparse_adam_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_select: ") + bad);
+    if (const char* bad = bad_row_count(P)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_select: ") + bad);
     if (mask_kind != 0 && mask_kind != 1) return fail(C3DGS_E_INVALID, "sparse_adam_select: mask_kind must be 0 (uint8 != 0) or 1 (int32 > 0)");
     if (P == 0) return C3DGS_OK;
     if (!mask) return fail(C3DGS_E_INVALID, "sparse_adam_select: mask is NULL");
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return fail(C3DGS_E_INVALID, "sparse_adam_select: the workspace must be non-NULL and 256-byte aligned");
+    if (const char* bad = bad_workspace(workspace)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_select: ") + bad);
     C3DGS_TIMED_STAGE(ST_SPARSE_ADAM_SELECT, 0, (hipStream_t)stream, launch_sparse_adam_select(P, mask, mask_kind, workspace, (hipStream_t)stream));
     return C3DGS_OK;
 }
@@ -1000,7 +1016,7 @@ int c3dgs_sparse_adam_step(int32_t n_tensors, const c3dgs_sparse_adam_tensor* te
 {
     if (n_tensors < 0 || n_tensors > C3DGS_ADAM_MAX_TENSORS)
         return fail(C3DGS_E_INVALID, "sparse_adam_step: between 0 and 16 tensors per call");
-    if (const char* bad = sparse_adam_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_step: ") + bad);
+    if (const char* bad = bad_row_count(P)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_step: ") + bad);
     if (n_tensors == 0) return C3DGS_OK;
     if (!tensors) return fail(C3DGS_E_INVALID, "sparse_adam_step: tensors is NULL");
     for (int k = 0; k < n_tensors; k++) {
@@ -1011,8 +1027,7 @@ int c3dgs_sparse_adam_step(int32_t n_tensors, const c3dgs_sparse_adam_tensor* te
             return fail(C3DGS_E_INVALID, "sparse_adam_step: NULL tensor pointer");
     }
     if (P == 0) return C3DGS_OK;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return fail(C3DGS_E_INVALID, "sparse_adam_step: the workspace must be non-NULL and 256-byte aligned");
+    if (const char* bad = bad_workspace(workspace)) return fail(C3DGS_E_INVALID, std::string("sparse_adam_step: ") + bad);
     C3DGS_TIMED_STAGE(ST_SPARSE_ADAM_STEP, 0, (hipStream_t)stream,
                       launch_sparse_adam_step(n_tensors, tensors, P, workspace, beta1, beta2, eps, (hipStream_t)stream));
     return C3DGS_OK;
@@ -1063,14 +1078,13 @@ int c3dgs_rows_apply(int32_t P, int64_t P_new, const int32_t* src, const uint8_t
 {
     if (P < 0 || P_new < 0 || n_draws < 0) return fail(C3DGS_E_INVALID, "rows_apply: sizes must be >= 0");
     if (N < 1 || N > kRowsMaxCopies) return fail(C3DGS_E_INVALID, "rows_apply: N must be between 1 and 250");
-    if (n_tensors < 0 || n_tensors > C3DGS_ROWS_MAX_TENSORS) return fail(C3DGS_E_INVALID, "rows_apply: between 0 and 16 tensors per call");
+    if (const char* bad = bad_rows_table(n_tensors, tensors, P_new)) return fail(C3DGS_E_INVALID, std::string("rows_apply: ") + bad);
     if (P_new >= ((int64_t)1 << 31)) return fail(C3DGS_E_INVALID, "rows_apply: P_new must fit 31 bits");
     if (P_new == 0 || n_tensors == 0) return C3DGS_OK;
     if (P == 0) return fail(C3DGS_E_INVALID, "rows_apply: P_new > 0 rows cannot come from P = 0");
-    if (!src || !kind || !draw_row || !tensors) return fail(C3DGS_E_INVALID, "rows_apply: NULL buffer");
+    if (!src || !kind || !draw_row) return fail(C3DGS_E_INVALID, "rows_apply: NULL buffer");
     for (int k = 0; k < n_tensors; k++) {
         const c3dgs_rows_tensor& t = tensors[k];
-        if (t.row_floats < 1 || t.row_floats > 4096) return fail(C3DGS_E_INVALID, "rows_apply: row_floats must be between 1 and 4096");
         if (!t.in_param || !t.out_param) return fail(C3DGS_E_INVALID, "rows_apply: NULL tensor pointer");
         const int nm = (t.in_exp_avg != nullptr) + (t.in_exp_avg_sq != nullptr) + (t.out_exp_avg != nullptr) + (t.out_exp_avg_sq != nullptr);
         if (nm != 0 && nm != 4) return fail(C3DGS_E_INVALID, "rows_apply: the four moment pointers go together");
@@ -1098,18 +1112,10 @@ int c3dgs_densify_stats(int32_t P, const float* grad, const uint8_t* filter, con
 }
 
 // ---- MCMC density control (mcmc.hip)
-static const char* mcmc_bad_P(int64_t P)
-{
-    if (P < 0) return "P must be >= 0";
-    if (P >= (int64_t(1) << 31)) return "P must be below 2^31 (row ids are 32-bit)";
-    return nullptr;
-}
-static bool mcmc_bad_workspace(const void* w) { return !w || (reinterpret_cast<uintptr_t>(w) & 255u); }
-
 int c3dgs_mcmc_workspace_bytes(int64_t P, size_t* bytes)
 {
     if (!bytes) return fail(C3DGS_E_INVALID, "mcmc_workspace_bytes: bytes is NULL");
-    if (const char* bad = mcmc_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_workspace_bytes: ") + bad);
+    if (const char* bad = bad_row_count(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_workspace_bytes: ") + bad);
     *bytes = mcmc_layout(P).total_bytes;
     return C3DGS_OK;
 }
@@ -1118,7 +1124,7 @@ int c3dgs_mcmc_sample(int64_t P, const float* raw_opacity, const uint8_t* dead, 
                       uint8_t* dead_out, int64_t n, const double* draws, int32_t reuse_weights, uint32_t* q, int32_t* sources,
                       int32_t* counts, uint64_t* T, void* workspace, void* stream)
 {
-    if (const char* bad = mcmc_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_sample: ") + bad);
+    if (const char* bad = bad_row_count(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_sample: ") + bad);
     if (n < 0) return fail(C3DGS_E_INVALID, "mcmc_sample: n must be >= 0");
     if (n >= (int64_t(1) << 31)) return fail(C3DGS_E_INVALID, "mcmc_sample: n must be below 2^31");
     if (dead && derive_dead) return fail(C3DGS_E_INVALID, "mcmc_sample: a dead mask and derive_dead exclude each other");
@@ -1130,7 +1136,7 @@ int c3dgs_mcmc_sample(int64_t P, const float* raw_opacity, const uint8_t* dead, 
         if (derive_dead && !(min_opacity >= 0.f)) return fail(C3DGS_E_INVALID, "mcmc_sample: min_opacity must be >= 0");
     }
     if (n > 0 && (!draws || !sources)) return fail(C3DGS_E_INVALID, "mcmc_sample: n > 0 needs draws and sources");
-    if (mcmc_bad_workspace(workspace)) return fail(C3DGS_E_INVALID, "mcmc_sample: the workspace must be non-NULL and 256-byte aligned");
+    if (const char* bad = bad_workspace(workspace)) return fail(C3DGS_E_INVALID, std::string("mcmc_sample: ") + bad);
     hipStream_t s = (hipStream_t)stream;
     if (reuse_weights) C3DGS_HIP_TRY(hipMemsetAsync(counts, 0, (size_t)P * sizeof(int32_t), s));
     else
@@ -1144,19 +1150,18 @@ int c3dgs_mcmc_apply(int64_t P, int64_t n, const int32_t* dst, int64_t dst_base,
                      int32_t n_tensors, const c3dgs_rows_tensor* tensors, int32_t copy_rows, float min_opacity, void* workspace,
                      void* stream)
 {
-    if (const char* bad = mcmc_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_apply: ") + bad);
+    if (const char* bad = bad_row_count(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_apply: ") + bad);
     if (n < 0) return fail(C3DGS_E_INVALID, "mcmc_apply: n must be >= 0");
     if (n >= (int64_t(1) << 31)) return fail(C3DGS_E_INVALID, "mcmc_apply: n must be below 2^31");
-    if (n_tensors < 0 || n_tensors > C3DGS_ROWS_MAX_TENSORS) return fail(C3DGS_E_INVALID, "mcmc_apply: between 0 and 16 tensors per call");
+    if (const char* bad = bad_rows_table(n_tensors, tensors, P ? n : 0)) return fail(C3DGS_E_INVALID, std::string("mcmc_apply: ") + bad);
     if (!(min_opacity >= 0.f && min_opacity < 1.f)) return fail(C3DGS_E_INVALID, "mcmc_apply: min_opacity must be in [0, 1)");
     if (P == 0 || n == 0) return C3DGS_OK;
-    if (!sources || !counts || !tensors) return fail(C3DGS_E_INVALID, "mcmc_apply: NULL buffer");
+    if (!sources || !counts) return fail(C3DGS_E_INVALID, "mcmc_apply: NULL buffer");
     if (!dst && (dst_base < 0 || dst_base + n > P)) return fail(C3DGS_E_INVALID, "mcmc_apply: dst_base + n must lie inside [0, P]");
     const c3dgs_rows_tensor* opacity = nullptr;
     const c3dgs_rows_tensor* scale = nullptr;
     for (int k = 0; k < n_tensors; k++) {
         const c3dgs_rows_tensor& t = tensors[k];
-        if (t.row_floats < 1 || t.row_floats > 4096) return fail(C3DGS_E_INVALID, "mcmc_apply: row_floats must be between 1 and 4096");
         if (!t.out_param || t.in_param != t.out_param) return fail(C3DGS_E_INVALID, "mcmc_apply: the step is in place (in_param == out_param, not NULL)");
         if (t.in_exp_avg != t.out_exp_avg || t.in_exp_avg_sq != t.out_exp_avg_sq || (t.out_exp_avg == nullptr) != (t.out_exp_avg_sq == nullptr))
             return fail(C3DGS_E_INVALID, "mcmc_apply: the moment pointers go together and are in place");
@@ -1169,7 +1174,7 @@ int c3dgs_mcmc_apply(int64_t P, int64_t n, const int32_t* dst, int64_t dst_base,
         } else if (t.role != C3DGS_ROLE_COPY) return fail(C3DGS_E_INVALID, "mcmc_apply: unknown role");
     }
     if (!opacity || !scale) return fail(C3DGS_E_INVALID, "mcmc_apply: the table needs the opacity and the scale tensor");
-    if (mcmc_bad_workspace(workspace)) return fail(C3DGS_E_INVALID, "mcmc_apply: the workspace must be non-NULL and 256-byte aligned");
+    if (const char* bad = bad_workspace(workspace)) return fail(C3DGS_E_INVALID, std::string("mcmc_apply: ") + bad);
     hipStream_t s = (hipStream_t)stream;
     C3DGS_TIMED_STAGE(ST_MCMC_VALUES, 0, s, launch_mcmc_values(P, counts, opacity->in_param, scale->in_param, scale->row_floats, min_opacity, workspace, s));
     C3DGS_TIMED_STAGE(ST_MCMC_APPLY, 0, s, launch_mcmc_apply(P, n, dst, dst_base, sources, n_tensors, tensors, copy_rows, workspace, s));
@@ -1179,7 +1184,7 @@ int c3dgs_mcmc_apply(int64_t P, int64_t n, const int32_t* dst, int64_t dst_base,
 int c3dgs_mcmc_noise(int64_t P, float* xyz, const float* rotation, const float* scaling, const float* scaling_factor,
                      const float* raw_opacity, const float* xi, float noise_lr, float xyz_lr, void* stream)
 {
-    if (const char* bad = mcmc_bad_P(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_noise: ") + bad);
+    if (const char* bad = bad_row_count(P)) return fail(C3DGS_E_INVALID, std::string("mcmc_noise: ") + bad);
     if (P == 0) return C3DGS_OK;
     if (!xyz || !rotation || !scaling || !raw_opacity || !xi) return fail(C3DGS_E_INVALID, "mcmc_noise: NULL buffer");
     C3DGS_TIMED_STAGE(ST_MCMC_NOISE, 0, (hipStream_t)stream,

@@ -15,6 +15,7 @@
 // HBM-bound streaming: no LDS, no atomics. Compiled with -ffp-contract=off (sqrt(gx*gx + gy*gy) and sqrt(g*g) are the
 // two-rounding expressions torch evaluates).
 #include "common.hpp"
+#include "jobs.hpp"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 #include <hip/hip_fp16.h>
@@ -140,12 +141,6 @@ hipError_t run_rows_plan(int P, const uint8_t* code, int N, long long capacity, 
 
 // ------------------------------------------------------------------------------------------------ apply
 constexpr int ROWS_BLOCK_CAP = 16384;      // workgroups per tensor, the grid stride covers the rest
-struct RowsJobs {
-    c3dgs_rows_tensor t[C3DGS_ROWS_MAX_TENSORS];
-    int first_block[C3DGS_ROWS_MAX_TENSORS];
-    int nblocks[C3DGS_ROWS_MAX_TENSORS];
-    int n;
-};
 
 struct ChildArgs {
     const float* rotation_raw;
@@ -180,10 +175,7 @@ __global__ void __launch_bounds__(256)
 rows_apply_kernel(const RowsJobs jobs, int P, long long P_new, const int32_t* __restrict__ src, const uint8_t* __restrict__ kind,
                   const int32_t* __restrict__ draw_row, const ChildArgs ca)
 {
-    int jb = 0;
-#pragma unroll
-    for (int k = 1; k < C3DGS_ROWS_MAX_TENSORS; k++)
-        if (k < jobs.n && (int)blockIdx.x >= jobs.first_block[k]) jb = k;
+    const int jb = job_of_block(jobs);
     const c3dgs_rows_tensor t = jobs.t[jb];
     const int rf = t.row_floats;
     const long long total = P_new * rf;
@@ -233,21 +225,15 @@ void launch_rows_apply(int P, long long P_new, const int32_t* src, const uint8_t
                        const c3dgs_rows_tensor* tensors, int N, long long n_draws, const float* rotation_raw, const float* std,
                        const float* z, int log_scaling, int half_xyz, hipStream_t s)
 {
-    RowsJobs J; J.n = 0;
-    int nb = 0;
+    RowsJobs J;
     for (int k = 0; k < n_tensors; k++) {
         if (!tensors[k].out_param) continue;
-        J.t[J.n] = tensors[k];
-        J.first_block[J.n] = nb;
         const long long steps = (P_new * tensors[k].row_floats + 1023) / 1024;     // 1024 floats per workgroup step
-        long long want = (steps + 1) / 2;
-        J.nblocks[J.n] = (int)(want < 1 ? 1 : (want > ROWS_BLOCK_CAP ? ROWS_BLOCK_CAP : want));
-        nb += J.nblocks[J.n];
-        J.n++;
+        J.add(tensors[k], (steps + 1) / 2, ROWS_BLOCK_CAP);
     }
     if (J.n == 0 || P_new <= 0) return;
     const ChildArgs ca = { rotation_raw, std, z, n_draws, (float)(0.8 * N), log_scaling, half_xyz };
-    rows_apply_kernel<<<nb, 256, 0, s>>>(J, P, P_new, src, kind, draw_row, ca);
+    rows_apply_kernel<<<J.grid(), 256, 0, s>>>(J, P, P_new, src, kind, draw_row, ca);
 }
 
 // ------------------------------------------------------------------------------------------------ stats

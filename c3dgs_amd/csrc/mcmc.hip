@@ -18,6 +18,7 @@
 //            is never formed in memory. fp32, no LDS, no atomics, about 72 bytes per row.
 // Compiled with -ffp-contract=off: t = floor(u * T) is ONE IEEE multiply, which the host restatement repeats bit for bit.
 #include "mcmc.hpp"
+#include "jobs.hpp"
 #include <cfloat>
 
 namespace c3dgs {
@@ -199,25 +200,16 @@ void launch_mcmc_values(int64_t P, const int32_t* counts, const float* raw_opaci
 
 // ------------------------------------------------------------------------------------------------ apply
 constexpr int MCMC_APPLY_BLOCK_CAP = 8192;     // workgroups per tensor, the grid stride covers the rest
-struct McmcJobs {
-    c3dgs_rows_tensor t[C3DGS_ROWS_MAX_TENSORS];
-    int first_block[C3DGS_ROWS_MAX_TENSORS];
-    int nblocks[C3DGS_ROWS_MAX_TENSORS];
-    int n;
-};
 
 // A tensor's lanes run over 2 n row_floats elements: the first half are the destination rows, the second half the source of
 // every pair (a source drawn k times is written k times with the same staged words). Reads: sources[], dst[], the staged
 // values, and with copy_rows the source's row of a COPY tensor, which no lane writes (a source is never a destination).
 __global__ void __launch_bounds__(256)
-mcmc_apply_kernel(const McmcJobs jobs, long long P, long long n, const int32_t* __restrict__ dst, long long dst_base,
+mcmc_apply_kernel(const RowsJobs jobs, long long P, long long n, const int32_t* __restrict__ dst, long long dst_base,
                   const int32_t* __restrict__ sources, int copy_rows, const float* __restrict__ new_opacity,
                   const float* __restrict__ new_scale)
 {
-    int jb = 0;
-#pragma unroll
-    for (int k = 1; k < C3DGS_ROWS_MAX_TENSORS; k++)
-        if (k < jobs.n && (int)blockIdx.x >= jobs.first_block[k]) jb = k;
+    const int jb = job_of_block(jobs);
     const c3dgs_rows_tensor t = jobs.t[jb];
     const int rf = t.row_floats;
     const long long half = n * rf, total = 2 * half;
@@ -245,18 +237,10 @@ void launch_mcmc_apply(int64_t P, int64_t n, const int32_t* dst, int64_t dst_bas
 {
     const McmcLayout L = mcmc_layout(P);
     const char* w = (const char*)workspace;
-    McmcJobs J; J.n = 0;
-    int nb = 0;
-    for (int k = 0; k < n_tensors; k++) {
-        J.t[J.n] = tensors[k];
-        J.first_block[J.n] = nb;
-        const long long want = (2 * n * tensors[k].row_floats + 255) / 256;
-        J.nblocks[J.n] = (int)(want < 1 ? 1 : (want > MCMC_APPLY_BLOCK_CAP ? MCMC_APPLY_BLOCK_CAP : want));
-        nb += J.nblocks[J.n];
-        J.n++;
-    }
+    RowsJobs J;
+    for (int k = 0; k < n_tensors; k++) J.add(tensors[k], (2 * n * tensors[k].row_floats + 255) / 256, MCMC_APPLY_BLOCK_CAP);
     if (J.n == 0 || n <= 0) return;
-    mcmc_apply_kernel<<<nb, 256, 0, s>>>(J, P, n, dst, dst_base, sources, copy_rows, (const float*)(w + L.new_opacity),
+    mcmc_apply_kernel<<<J.grid(), 256, 0, s>>>(J, P, n, dst, dst_base, sources, copy_rows, (const float*)(w + L.new_opacity),
                                          (const float*)(w + L.new_scale));
 }
 

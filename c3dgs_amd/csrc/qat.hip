@@ -20,6 +20,7 @@
 // Compiled with -ffp-contract=off: every expression is evaluated as written (torch's kernels do not fuse either).
 #include "common.hpp"
 #include "gsmath.hpp"
+#include "jobs.hpp"
 #include <hip/hip_fp16.h>
 #include <cfloat>
 #include <rocprim/device/device_scan.hpp>
@@ -32,8 +33,8 @@ constexpr float NORM_EPS = 1e-12f; // torch.nn.functional.normalize default eps
 
 enum { ACT_IDENT = 0, ACT_SIGMOID = 1, ACT_NORMRELU3 = 2 };
 
-struct ObsJob { const float* x; long long units; int act; int first_block; int nblocks; int slot; };
-struct ObsJobs { ObsJob j[C3DGS_FQ_COUNT]; int n; };
+struct ObsJob { const float* x; long long units; int act; int slot; };
+using ObsJobs = JobTable<ObsJob, C3DGS_FQ_COUNT>;
 
 // torch.sigmoid: 1 / (1 + exp(-x)) in fp32
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -74,13 +75,10 @@ __device__ __forceinline__ float half_round(float v) { return __half2float(__flo
 __global__ void __launch_bounds__(256)
 qat_observe_kernel(const ObsJobs jobs, float* __restrict__ ws)
 {
-    int t = 0;
-#pragma unroll
-    for (int k = 1; k < C3DGS_FQ_COUNT; k++)
-        if (k < jobs.n && (int)blockIdx.x >= jobs.j[k].first_block) t = k;
-    const ObsJob job = jobs.j[t];
-    const int b = blockIdx.x - job.first_block;
-    const long long stride = (long long)job.nblocks * 256;
+    const int t = job_of_block(jobs);
+    const ObsJob job = jobs.t[t];
+    const int b = blockIdx.x - jobs.first_block[t];
+    const long long stride = (long long)jobs.nblocks[t] * 256;
     float lo = INFINITY, hi = -INFINITY;
     if (job.act == ACT_NORMRELU3) {
         for (long long r = (long long)b * 256 + threadIdx.x; r < job.units; r += stride) {
@@ -123,9 +121,9 @@ qat_finalize_kernel(const ObsJobs jobs, const float* __restrict__ ws, c3dgs_fq_s
 {
     const int t = threadIdx.x >> 6, lane = threadIdx.x & 63;          // one wave per observed module
     if (t >= jobs.n) return;
-    const ObsJob job = jobs.j[t];
+    const ObsJob job = jobs.t[t];
     float lo = INFINITY, hi = -INFINITY;
-    for (int b = lane; b < job.nblocks; b += 64) {
+    for (int b = lane; b < jobs.nblocks[t]; b += 64) {
         lo = fminf(lo, ws[(job.slot * OBS_MAXB + b) * 2]);
         hi = fmaxf(hi, ws[(job.slot * OBS_MAXB + b) * 2 + 1]);
     }
@@ -149,33 +147,28 @@ qat_finalize_kernel(const ObsJobs jobs, const float* __restrict__ ws, c3dgs_fq_s
     }
 }
 
-static void add_job(ObsJobs& J, int& nb, const float* x, long long units, int act, int slot, int per_thread)
+static void add_job(ObsJobs& J, const float* x, long long units, int act, int slot, int per_thread)
 {
     if (!x || units <= 0) return;
-    ObsJob& j = J.j[J.n++];
-    j.x = x; j.units = units; j.act = act; j.slot = slot; j.first_block = nb;
     const long long work = act == ACT_NORMRELU3 ? units : (units + 3) / 4;
-    long long want = (work + 256LL * per_thread - 1) / (256LL * per_thread);
-    j.nblocks = (int)(want < 1 ? 1 : (want > OBS_MAXB ? OBS_MAXB : want));
-    nb += j.nblocks;
+    J.add(ObsJob{ x, units, act, slot }, (work + 256LL * per_thread - 1) / (256LL * per_thread), OBS_MAXB);
 }
 
 size_t qat_workspace_bytes() { return (size_t)C3DGS_FQ_COUNT * OBS_MAXB * 2 * sizeof(float); }
 
 void launch_qat_observe(const c3dgs_qat_params& q, void* workspace, hipStream_t s)
 {
-    ObsJobs J; J.n = 0;
-    int nb = 0;
+    ObsJobs J;
     const long long P = q.P, GS = q.GS, SHS = q.SHS;
-    if (q.observer_enabled[C3DGS_FQ_OPACITY]) add_job(J, nb, q.opacity, P, ACT_SIGMOID, C3DGS_FQ_OPACITY, 4);
-    if (q.observer_enabled[C3DGS_FQ_SCALING]) add_job(J, nb, q.scaling, GS, ACT_NORMRELU3, C3DGS_FQ_SCALING, 4);
-    if (q.observer_enabled[C3DGS_FQ_SCALING_FACTOR]) add_job(J, nb, q.scaling_factor, P, ACT_IDENT, C3DGS_FQ_SCALING_FACTOR, 4);
-    if (q.observer_enabled[C3DGS_FQ_ROTATION]) add_job(J, nb, q.rotation, GS * 4, ACT_IDENT, C3DGS_FQ_ROTATION, 4);
-    if (q.observer_enabled[C3DGS_FQ_FEATURES_DC]) add_job(J, nb, q.features_dc, SHS * 3, ACT_IDENT, C3DGS_FQ_FEATURES_DC, 4);
+    if (q.observer_enabled[C3DGS_FQ_OPACITY]) add_job(J, q.opacity, P, ACT_SIGMOID, C3DGS_FQ_OPACITY, 4);
+    if (q.observer_enabled[C3DGS_FQ_SCALING]) add_job(J, q.scaling, GS, ACT_NORMRELU3, C3DGS_FQ_SCALING, 4);
+    if (q.observer_enabled[C3DGS_FQ_SCALING_FACTOR]) add_job(J, q.scaling_factor, P, ACT_IDENT, C3DGS_FQ_SCALING_FACTOR, 4);
+    if (q.observer_enabled[C3DGS_FQ_ROTATION]) add_job(J, q.rotation, GS * 4, ACT_IDENT, C3DGS_FQ_ROTATION, 4);
+    if (q.observer_enabled[C3DGS_FQ_FEATURES_DC]) add_job(J, q.features_dc, SHS * 3, ACT_IDENT, C3DGS_FQ_FEATURES_DC, 4);
     if (q.observer_enabled[C3DGS_FQ_FEATURES_REST])
-        add_job(J, nb, q.features_rest, SHS * 3 * (q.M - 1), ACT_IDENT, C3DGS_FQ_FEATURES_REST, 4);
+        add_job(J, q.features_rest, SHS * 3 * (q.M - 1), ACT_IDENT, C3DGS_FQ_FEATURES_REST, 4);
     if (J.n == 0) return;
-    qat_observe_kernel<<<nb, 256, 0, s>>>(J, (float*)workspace);
+    qat_observe_kernel<<<J.grid(), 256, 0, s>>>(J, (float*)workspace);
     qat_finalize_kernel<<<1, 64 * C3DGS_FQ_COUNT, 0, s>>>(J, (const float*)workspace, q.state, q.averaging_constant);
 }
 
@@ -462,8 +455,8 @@ void launch_qat_points_backward(const c3dgs_qat_params& q, const uint8_t* visibl
 // kernel of torch evaluates nearbyint(double(x) / double(scale)) + zero_point (checked against torch on the MI355X box:
 // bit-identical codes; the fp32 multiply-by-reciprocal of torch's CPU path differs at rounding ties), so does this one.
 enum { QACT_IDENT = 0, QACT_SIGMOID = 1, QACT_NORMRELU3 = 2, QACT_NORM4 = 3, QACT_EXP = 4 };
-struct QuantJob { const float* x; int8_t* out; long long units; int act; int slot; int first_block; int nblocks; };
-struct QuantJobs { QuantJob j[C3DGS_FQ_COUNT]; int n; };
+struct QuantJob { const float* x; int8_t* out; long long units; int act; int slot; };
+using QuantJobs = JobTable<QuantJob, C3DGS_FQ_COUNT>;
 
 __device__ __forceinline__ int8_t quant_code(float v, double scale, int zp)
 {
@@ -474,14 +467,11 @@ __device__ __forceinline__ int8_t quant_code(float v, double scale, int zp)
 __global__ void __launch_bounds__(256)
 qat_quantize_kernel(const QuantJobs jobs, const c3dgs_fq_state* __restrict__ state)
 {
-    int t = 0;
-#pragma unroll
-    for (int k = 1; k < C3DGS_FQ_COUNT; k++)
-        if (k < jobs.n && (int)blockIdx.x >= jobs.j[k].first_block) t = k;
-    const QuantJob job = jobs.j[t];
+    const int t = job_of_block(jobs);
+    const QuantJob job = jobs.t[t];
     const double scale = (double)state[job.slot].scale;
     const int zp = state[job.slot].zero_point;
-    const long long stride = (long long)job.nblocks * 256, i0 = (long long)(blockIdx.x - job.first_block) * 256 + threadIdx.x;
+    const long long stride = (long long)jobs.nblocks[t] * 256, i0 = (long long)(blockIdx.x - jobs.first_block[t]) * 256 + threadIdx.x;
     if (job.act == QACT_NORMRELU3) {
         for (long long r = i0; r < job.units; r += stride) {
             const float x[3] = { job.x[3 * r], job.x[3 * r + 1], job.x[3 * r + 2] };
@@ -512,15 +502,9 @@ qat_quantize_kernel(const QuantJobs jobs, const c3dgs_fq_state* __restrict__ sta
 void launch_qat_quantize(const c3dgs_qat_params& q, int scaling_exp, int8_t* opacity, int8_t* scaling, int8_t* scaling_factor,
                          int8_t* rotation, int8_t* features_dc, int8_t* features_rest, hipStream_t s)
 {
-    QuantJobs J; J.n = 0;
-    int nb = 0;
+    QuantJobs J;
     auto add = [&](const float* x, int8_t* out, long long units, int act, int slot) {
-        if (!x || !out || units <= 0) return;
-        QuantJob& j = J.j[J.n++];
-        j.x = x; j.out = out; j.units = units; j.act = act; j.slot = slot; j.first_block = nb;
-        const long long want = (units + 1023) / 1024;
-        j.nblocks = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
-        nb += j.nblocks;
+        if (x && out && units > 0) J.add(QuantJob{ x, out, units, act, slot }, (units + 1023) / 1024, 4096);
     };
     const long long P = q.P, GS = q.GS, SHS = q.SHS;
     add(q.opacity, opacity, P, QACT_SIGMOID, C3DGS_FQ_OPACITY);
@@ -531,7 +515,7 @@ void launch_qat_quantize(const c3dgs_qat_params& q, int scaling_exp, int8_t* opa
     add(q.features_dc, features_dc, SHS * 3, QACT_IDENT, C3DGS_FQ_FEATURES_DC);
     add(q.features_rest, features_rest, SHS * 3 * (q.M - 1), QACT_IDENT, C3DGS_FQ_FEATURES_REST);
     if (J.n == 0) return;
-    qat_quantize_kernel<<<nb, 256, 0, s>>>(J, q.state);
+    qat_quantize_kernel<<<J.grid(), 256, 0, s>>>(J, q.state);
 }
 
 // ------------------------------------------------------------------------------------------- stand-alone module
@@ -553,10 +537,9 @@ void launch_fake_quantize(long long n, const float* x, c3dgs_fq_state* state, in
 {
     if (n <= 0) return;
     if (observe) {
-        ObsJobs J; J.n = 0;
-        int nb = 0;
-        add_job(J, nb, x, n, ACT_IDENT, 0, 4);
-        qat_observe_kernel<<<nb, 256, 0, s>>>(J, (float*)workspace);
+        ObsJobs J;
+        add_job(J, x, n, ACT_IDENT, 0, 4);
+        qat_observe_kernel<<<J.grid(), 256, 0, s>>>(J, (float*)workspace);
         qat_finalize_kernel<<<1, 64 * C3DGS_FQ_COUNT, 0, s>>>(J, (const float*)workspace, state, c);
     }
     const long long want = (n + 1023) / 1024;

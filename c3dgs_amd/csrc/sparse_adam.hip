@@ -13,6 +13,7 @@
 // Rows are disjoint and nothing is accumulated across lanes: results are bitwise reproducible.
 #include "common.hpp"
 #include "adam_common.hpp"
+#include "jobs.hpp"
 #include "scan_blocks.hpp"
 
 namespace c3dgs {
@@ -86,12 +87,7 @@ void launch_sparse_adam_select(int64_t P, const void* mask, int mask_kind, void*
     else sa_emit_kernel<1><<<nb, SA_SEL, 0, s>>>(P, mask, base, nb, rows, count);
 }
 
-struct SparseAdamJobs {
-    c3dgs_sparse_adam_tensor t[C3DGS_ADAM_MAX_TENSORS];
-    int first_block[C3DGS_ADAM_MAX_TENSORS];
-    int nblocks[C3DGS_ADAM_MAX_TENSORS];
-    int n;
-};
+using SparseAdamJobs = JobTable<c3dgs_sparse_adam_tensor, C3DGS_ADAM_MAX_TENSORS>;
 
 // RL: the row length as a constant (the divisions below become multiplies), 0: t.row_len at run time
 template <int RL>
@@ -139,10 +135,7 @@ sparse_adam_kernel(const SparseAdamJobs jobs, const uint32_t* __restrict__ count
 {
     const uint32_t count = *count_ptr;
     if (count == 0) return;
-    int j = 0;
-#pragma unroll
-    for (int k = 1; k < C3DGS_ADAM_MAX_TENSORS; k++)
-        if (k < jobs.n && (int)blockIdx.x >= jobs.first_block[k]) j = k;
+    const int j = job_of_block(jobs);
     const c3dgs_sparse_adam_tensor t = jobs.t[j];
     const uint32_t block = blockIdx.x - (uint32_t)jobs.first_block[j], nblocks = (uint32_t)jobs.nblocks[j];
     switch (t.row_len) {                                 // the row lengths of a Gaussian model at SH degree 3, and 48 of its SH block
@@ -160,20 +153,12 @@ void launch_sparse_adam_step(int n_tensors, const c3dgs_sparse_adam_tensor* tens
 {
     const SparseAdamLayout L = sparse_adam_layout(P);
     const char* w = (const char*)workspace;
-    SparseAdamJobs J; J.n = 0;
-    int nb = 0;
-    for (int k = 0; k < n_tensors; k++) {
-        if (tensors[k].n <= 0) continue;
-        J.t[J.n] = tensors[k];
-        J.first_block[J.n] = nb;
-        const long long want = (tensors[k].n + SA_STEP_CHUNK - 1) / SA_STEP_CHUNK;    // every row listed: one trip per workgroup
-        J.nblocks[J.n] = (int)(want > SA_STEP_MAX_BLOCKS ? SA_STEP_MAX_BLOCKS : want);
-        nb += J.nblocks[J.n];
-        J.n++;
-    }
+    SparseAdamJobs J;
+    for (int k = 0; k < n_tensors; k++)                    // every row listed: one trip per workgroup
+        if (tensors[k].n > 0) J.add(tensors[k], (tensors[k].n + SA_STEP_CHUNK - 1) / SA_STEP_CHUNK, SA_STEP_MAX_BLOCKS);
     if (J.n == 0) return;
     // 1 - beta is formed in double and rounded once, as launch_adam does
-    sparse_adam_kernel<<<nb, 256, 0, s>>>(J, (const uint32_t*)(w + L.count), (const uint32_t*)(w + L.rows), (float)(1.0 - beta1),
+    sparse_adam_kernel<<<J.grid(), 256, 0, s>>>(J, (const uint32_t*)(w + L.count), (const uint32_t*)(w + L.rows), (float)(1.0 - beta1),
                                           (float)beta2, (float)(1.0 - beta2), (float)eps);
 }
 

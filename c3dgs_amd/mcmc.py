@@ -9,18 +9,12 @@ from . import _lib
 
 WEIGHT_ONE = 1 << 20          # the integer weight of opacity 1
 MAX_N = 51                    # relocation: N = min(count + 1, MAX_N)
-_workspaces = {}              # device -> the cached workspace (uint8), grown on demand
 
 
 def workspace(P, device):
     need = C.c_size_t(0)
     _lib.check(_lib.lib().c3dgs_mcmc_workspace_bytes(P, C.byref(need)))
-    ws = _workspaces.get(device)
-    if ws is None or ws.numel() < need.value:
-        ws = _workspaces[device] = torch.empty(need.value, dtype=torch.uint8, device=device)
-    if ws.data_ptr() % 256:
-        raise RuntimeError("c3dgs_amd.mcmc: the allocator returned a workspace that is not 256-byte aligned")
-    return ws
+    return _lib.workspace("mcmc", device, need.value)
 
 
 def _mask_u8(mask, P):

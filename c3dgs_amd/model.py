@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from . import rasterizer as _rz
+from . import rows as _rows
 from ._lib import ptr as _ptr, stream as _stream
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed
 
@@ -802,16 +803,30 @@ class GaussianModel:
             return self._get(scaling_factor=factor)[3] * scaling_n
         return self.scaling_qa(self.scaling_activation(raw))
 
-    def _read_totals(self, totals):
-        """The one device->host read of a rebuild: four int32 through pinned memory and an event."""
-        host = getattr(self, "_totals_host", None)
-        if host is None:
-            host = self._totals_host = torch.empty(4, dtype=torch.int32).pin_memory()
-        host.copy_(totals, non_blocking=True)
+    def _read_host(self, t):
+        """The one blocking device->host read of a rebuild: a small integer tensor (the four int32 totals of a plan, the two
+        int64 of relocate_gs) -> its Python ints, through a pinned buffer per dtype (kept on the model), a non-blocking copy and
+        an event."""
+        bufs = self.__dict__.setdefault("_host_bufs", {})
+        host = bufs.get(t.dtype)
+        if host is None or host.numel() < t.numel():
+            host = bufs[t.dtype] = torch.empty(t.numel(), dtype=t.dtype).pin_memory()
+        host = host[:t.numel()]
+        host.copy_(t, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         ev.synchronize()
         return host.tolist()
+
+    def _row_table(self, n_out, attrs, roles):
+        """A rows.RowTable (out of place to `n_out` rows; None: in place) over the parameters named by `attrs`, each with the
+        moments the optimizer holds for it; roles: {attr: role}, copy where it has none."""
+        tab = _rows.RowTable(self.device, n_out)
+        for attr in attrs:
+            old = getattr(self, attr)
+            if old is not None:
+                tab.add(old, roles.get(attr, _lib.ROLE_COPY), attr, self.optimizer.state.get(old) if self.optimizer is not None else None)
+        return tab
 
     def plan_rows(self, code, N=2):
         """code uint8[P] (bits: include/c3dgs_hip.h C3DGS_ROW_*) -> (src int32[P_new], kind uint8[P_new], draw_row int32[P_new],
@@ -823,7 +838,7 @@ class GaussianModel:
         ws = torch.empty(max(int(lib.c3dgs_rows_plan_workspace_bytes(P)), 256), dtype=torch.uint8, device=dev)
         totals = torch.empty(4, dtype=torch.int32, device=dev)
         _lib.check(lib.c3dgs_rows_plan(P, _ptr(code), N, 0, None, None, None, totals.data_ptr(), ws.data_ptr(), s))
-        K, Cn, S, CK = self._read_totals(totals)
+        K, Cn, S, CK = self._read_host(totals)
         P_new = K + Cn + N * CK
         src = torch.empty(P_new, dtype=torch.int32, device=dev)
         kind = torch.empty(P_new, dtype=torch.uint8, device=dev)
@@ -858,44 +873,18 @@ class GaussianModel:
         draws = _lib.gpu_tensor(draws, "draws")
         std = None if std is None else _lib.gpu_tensor(std, "std")
         rotation = _lib.gpu_tensor(self._rotation.detach(), "rotation")
-        table, new, moments = [], {}, {}
-        for name, attr, role in self._GROUPS:
-            old = getattr(self, attr)
-            if old is None:
-                continue
-            old_c = _lib.gpu_tensor(old.detach(), attr)
-            out = torch.empty((P_new,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
-            st = self.optimizer.state.get(old) if self.optimizer is not None else None
-            t = _lib.RowsTensor()
-            t.in_param, t.out_param = old_c.data_ptr(), out.data_ptr()
-            t.row_floats, t.role = int(torch.Size(old.shape[1:]).numel()), role
-            keep = [old_c]
-            if st is not None and "exp_avg" in st:
-                m, v = st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous()
-                om, ov = torch.empty_like(out), torch.empty_like(out)
-                t.in_exp_avg, t.in_exp_avg_sq, t.out_exp_avg, t.out_exp_avg_sq = m.data_ptr(), v.data_ptr(), om.data_ptr(), ov.data_ptr()
-                moments[attr] = (om, ov)
-                keep += [m, v]
-            table.append((t, keep))
-            new[attr] = out
+        tab = self._row_table(P_new, [attr for _, attr, _ in self._GROUPS], {attr: role for _, attr, role in self._GROUPS})
         stats_new = None
         if carry_stats:                                       # prune_points gathers the accumulators (:1150-1152)
-            stats_new = []
-            for old in (accum, denom, max_radii):
-                out = torch.empty((P_new,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
-                t = _lib.RowsTensor()
-                t.in_param, t.out_param, t.row_floats, t.role = old.data_ptr(), out.data_ptr(), 1, 0
-                table.append((t, [old]))
-                stats_new.append(out)
+            stats_new = [tab.add(old) for old in (accum, denom, max_radii)]
         if P_new > 0 and P > 0:
-            arr = (_lib.RowsTensor * len(table))(*[t for t, _ in table])
-            _lib.check(lib.c3dgs_rows_apply(P, P_new, src.data_ptr(), kind.data_ptr(), draw_row.data_ptr(), len(table), arr, N,
-                                            N * S, rotation.data_ptr(), _ptr(std),
+            _lib.check(lib.c3dgs_rows_apply(P, P_new, src.data_ptr(), kind.data_ptr(), draw_row.data_ptr(), len(tab.jobs), tab.array(),
+                                            N, N * S, rotation.data_ptr(), _ptr(std),
                                             draws.data_ptr() if draws.numel() else None,
                                             int(not self.use_factor_scaling), int(self.quantization), _stream(dev)))
         if new_xyz is not None:
-            new_xyz(new["_xyz"])
-        self._install(new, moments)
+            new_xyz(tab.new["_xyz"])
+        self._install(tab.new, tab.moments)
         if stats_new is not None:
             self.xyz_gradient_accum, self.denom, self.max_radii2D = stats_new
         else:                                                 # densification_postfix, :1209-1211
@@ -997,38 +986,8 @@ class GaussianModel:
         """The in-place tensor table of c3dgs_mcmc_apply: every parameter with its moments (where the optimizer has them), the raw
         opacity and the tensor that carries the log scale flagged (the factor when the model has one, its activation being exp)."""
         scale_attr = "_scaling_factor" if self._scaling_factor is not None else "_scaling"
-        table = []
-        for name, attr, _ in self._GROUPS:
-            p = getattr(self, attr)
-            if p is None:
-                continue
-            tensors = [p]
-            st = self.optimizer.state.get(p) if self.optimizer is not None else None
-            if st is not None and "exp_avg" in st:
-                tensors += [st["exp_avg"], st["exp_avg_sq"]]
-            for x in tensors:
-                if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
-                    raise RuntimeError(f"c3dgs_amd: {attr} and its moments must be contiguous float32 GPU tensors (the MCMC step is in place)")
-            t = _lib.RowsTensor()
-            t.in_param = t.out_param = p.data_ptr()
-            if len(tensors) == 3:
-                t.in_exp_avg = t.out_exp_avg = tensors[1].data_ptr()
-                t.in_exp_avg_sq = t.out_exp_avg_sq = tensors[2].data_ptr()
-            t.row_floats = int(torch.Size(p.shape[1:]).numel())
-            t.role = _lib.MCMC_ROLE_OPACITY if attr == "_opacity" else _lib.MCMC_ROLE_SCALE if attr == scale_attr else _lib.ROLE_COPY
-            table.append(t)
-        return table
-
-    def _read_pair(self, a, b):
-        """Two device scalars in one device->host read (pinned memory and an event, as _read_totals)."""
-        host = getattr(self, "_pair_host", None)
-        if host is None:
-            host = self._pair_host = torch.empty(2, dtype=torch.int64).pin_memory()
-        host.copy_(torch.cat((a.reshape(1).to(torch.int64), b.reshape(1).to(torch.int64))), non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        ev.synchronize()
-        return host.tolist()
+        return self._row_table(None, [attr for _, attr, _ in self._GROUPS],
+                               {"_opacity": _lib.MCMC_ROLE_OPACITY, scale_attr: _lib.MCMC_ROLE_SCALE}).jobs
 
     def relocate_gs(self, dead_mask=None, min_opacity=0.005, draws=None):
         """Move every dead Gaussian onto a live one sampled by opacity; opacity and scale of the source and of its copies are
@@ -1048,7 +1007,7 @@ class GaussianModel:
                 return 0
             w = mcmc.weights(self._opacity, dead_mask, None if dead_mask is not None else min_opacity)
             rows, count = optim.visible_rows(w.dead)                # the stable device-side selection of sparse Adam
-            n, T = self._read_pair(count, w.T)
+            n, T = self._read_host(torch.cat((count.reshape(1).to(torch.int64), w.T.reshape(1).to(torch.int64))))
             if n == 0 or n == P or T == 0:
                 return 0
             if draws is None:
@@ -1167,7 +1126,7 @@ class GaussianModel:
             ws = torch.empty(int(lib.c3dgs_ray_fill_plan_workspace_bytes(P, 0)), dtype=torch.uint8, device=dev)
             _lib.check(lib.c3dgs_ray_fill_plan(P, d2.data_ptr(), step, 0, None, None, None, totals.data_ptr(), ws.data_ptr(),
                                                ws.numel(), s))
-            n0, n1, n2, overflow = self._read_totals(totals)
+            n0, n1, n2, overflow = self._read_host(totals)
             n = n0 + n1 + n2
             if overflow:
                 raise ValueError(f"densify_initial: more than {2**31 - 256 - P} new rows (at least {n} counted) for {P} points "
@@ -1219,40 +1178,14 @@ class GaussianModel:
         -> ({attr: new tensor}, {attr: (exp_avg, exp_avg_sq)}, [new extra tensors]); nothing is installed."""
         dev = self.device
         n_out = int(src.shape[0])
-        table, new, moments, extra_new = [], {}, {}, []
-
-        def job(old, st=None):
-            old_c = _lib.gpu_tensor(old.detach(), "tensor")
-            out = torch.empty((n_out,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
-            t = _lib.RowsTensor()
-            t.in_param, t.out_param = old_c.data_ptr(), out.data_ptr()
-            t.row_floats, t.role = int(torch.Size(old.shape[1:]).numel()), _lib.ROLE_COPY
-            keep, mom = [old_c], None
-            if st is not None and "exp_avg" in st:
-                m, v = st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous()
-                mom = (torch.empty_like(out), torch.empty_like(out))
-                t.in_exp_avg, t.in_exp_avg_sq, t.out_exp_avg, t.out_exp_avg_sq = m.data_ptr(), v.data_ptr(), mom[0].data_ptr(), mom[1].data_ptr()
-                keep += [m, v]
-            if t.row_floats > 0:
-                table.append((t, keep))
-            return out, mom
-
-        for attr in attrs:
-            old = getattr(self, attr)
-            if old is None:
-                continue
-            new[attr], mom = job(old, self.optimizer.state.get(old) if self.optimizer is not None else None)
-            if mom is not None:
-                moments[attr] = mom
-        for old in extra:
-            extra_new.append(job(old)[0])
-        if n_out > 0 and n_in > 0 and table:
+        tab = self._row_table(n_out, attrs, {})
+        extra_new = [tab.add(old) for old in extra]
+        if n_out > 0 and n_in > 0 and tab.jobs:
             kind = torch.zeros(n_out, dtype=torch.uint8, device=dev)            # C3DGS_KIND_ORIGINAL
-            arr = (_lib.RowsTensor * len(table))(*[t for t, _ in table])
             # draw_row is read for child rows only: any [n_out] int32 buffer serves
-            _lib.check(_lib.lib().c3dgs_rows_apply(n_in, n_out, src.data_ptr(), kind.data_ptr(), src.data_ptr(), len(table), arr, 1, 0,
-                                                   None, None, None, 0, 0, _stream(dev)))
-        return new, moments, extra_new
+            _lib.check(_lib.lib().c3dgs_rows_apply(n_in, n_out, src.data_ptr(), kind.data_ptr(), src.data_ptr(), len(tab.jobs),
+                                                   tab.array(), 1, 0, None, None, None, 0, 0, _stream(dev)))
+        return tab.new, tab.moments, extra_new
 
     def plan_index_prune(self, keep, idx0, K0, idx1, K1):
         """c3dgs_index_plan in its two calls around the one host read. keep: uint8 [P] or None; idx: int64 [P] or None.
@@ -1267,7 +1200,7 @@ class GaussianModel:
         totals = torch.empty(4, dtype=torch.int32, device=dev)
         args = (P, _ptr(keep), _ptr(idx0), K0, _ptr(idx1), K1)
         _lib.check(lib.c3dgs_index_plan(*args, 0, 0, 0, None, None, None, None, None, totals.data_ptr(), ws.data_ptr(), s))
-        tot = tuple(self._read_totals(totals))
+        tot = tuple(self._read_host(totals))
         P_new, K0n, K1n, bad = tot
         if bad:
             raise RuntimeError(f"{bad} codebook indices lie outside their codebook ({K0} colour rows, {K1} geometry rows)")

@@ -18,7 +18,6 @@ import torch
 from . import _lib
 
 _MASK_KINDS = {torch.bool: 0, torch.uint8: 0, torch.int32: 1}      # c3dgs_sparse_adam_select's mask_kind
-_workspaces = {}                                                   # device -> the cached select workspace (uint8), grown on demand
 
 
 def _check_mask(mask):
@@ -36,11 +35,7 @@ def _select(mask):
     P, dev = mask.shape[0], mask.device
     need = C.c_size_t(0)
     _lib.check(L.c3dgs_sparse_adam_workspace_bytes(P, C.byref(need)))
-    ws = _workspaces.get(dev)
-    if ws is None or ws.numel() < need.value:
-        ws = _workspaces[dev] = torch.zeros(need.value, dtype=torch.uint8, device=dev)
-    if ws.data_ptr() % 256:
-        raise RuntimeError("c3dgs_amd.optim: the allocator returned a workspace that is not 256-byte aligned")
+    ws = _lib.workspace("optim", dev, need.value, zeroed=True)
     if P == 0:
         ws[:4].zero_()                                 # the library does nothing for P == 0: the count is this side's to clear
         return ws

@@ -439,7 +439,7 @@ def test_one_host_read_per_rebuild():
     warm = _model(1000, 50, 50, _indices(1000, 50, "uniform", g).to(DEV), _indices(1000, 50, "uniform", g).to(DEV), True, seed=18)
     warm.compact_codebooks()
     m = _model(P, K0, K1, idx0, idx1, True, seed=19)
-    _ = m._read_totals(torch.zeros(4, dtype=torch.int32, device=DEV))               # the pinned buffer exists
+    _ = m._read_host(torch.zeros(4, dtype=torch.int32, device=DEV))               # the pinned buffer exists
     mask = (torch.rand(P, generator=g) < 0.6).to(DEV)
     torch.cuda.synchronize()
     for call in (lambda: m.prune_points_indexed(mask), lambda: m.compact_codebooks(), lambda: m.to_unindexed()):
