@@ -24,6 +24,8 @@ lambda_alpha=) use for depth and silhouette losses; GaussianRasterizationSetting
 compensate every opacity for the rasterizer's 0.3 px^2 low-pass (csrc/aa_opacity.hip), upstream 3DGS's `antialiasing`.
 pipeline.train(strategy="mcmc", cap_max=N) trains towards a hard budget of Gaussians ("3DGS as Markov Chain Monte Carlo":
 GaussianModel.relocate_gs / add_new_gs / add_position_noise on csrc/mcmc.hip; thin entries in c3dgs_amd.mcmc).
+c3dgs_amd.bilagrid (BilateralGrid, ExposureModel on csrc/bilagrid.hip) is a per-image colour model, gsplat's bilateral grid and
+upstream 3DGS's `exposure`, which pipeline.train(bilagrid=...) trains and pipeline.finetune(bilagrid=...) applies frozen.
 
 The numeric work runs in c3dgs_amd/libc3dgs_hip.so (include/c3dgs_hip.h); build it with
 `python -m c3dgs_amd.build`.  There is no CPU fallback.
@@ -31,7 +33,7 @@ The numeric work runs in c3dgs_amd/libc3dgs_hip.so (include/c3dgs_hip.h); build 
 import sys
 import types
 
-from . import encode, knn, loss, mcmc, metrics, model, optim, ply, rasterizer, rasterizer_matrix, sensitivity, vq  # noqa: F401
+from . import bilagrid, encode, knn, loss, mcmc, metrics, model, optim, ply, rasterizer, rasterizer_matrix, sensitivity, vq  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,  # noqa: F401
                          getProjectionMatrix, mat_to_quat, quat_to_mat, rasterize_gaussians,
                          rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,

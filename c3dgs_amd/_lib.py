@@ -172,6 +172,11 @@ PROTOTYPES = {
     "c3dgs_mcmc_apply": (C.c_int, [C.c_int64, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int32, C.POINTER(RowsTensor), C.c_int32,
                                    C.c_float, _vp, _vp]),
     "c3dgs_mcmc_noise": (C.c_int, [C.c_int64] + [_vp] * 6 + [C.c_float, C.c_float, _vp]),
+    "c3dgs_bilagrid_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "c3dgs_bilagrid_slice": (C.c_int, [C.c_int32] * 5 + [_vp] * 4),
+    "c3dgs_bilagrid_slice_backward": (C.c_int, [C.c_int32] * 5 + [_vp] * 7),
+    "c3dgs_bilagrid_tv": (C.c_int, [C.c_int32] * 4 + [_vp] * 4),
+    "c3dgs_bilagrid_tv_backward": (C.c_int, [C.c_int32] * 4 + [_vp] * 4),
     "c3dgs_index_plan_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "c3dgs_index_plan": (C.c_int, [C.c_int32, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64] + [_vp] * 8),
     "c3dgs_extract_rot_scale": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
@@ -288,6 +293,6 @@ def profile_enable(on=True, only=None):
 
 def profile_read():
     """-> {stage: (total_ms, count)} since the last read (synchronises the recorded events)."""
-    arr = (StageTime * 48)()
-    n = lib().c3dgs_profile_read(arr, 48)
+    arr = (StageTime * 64)()
+    n = lib().c3dgs_profile_read(arr, 64)
     return {arr[i].name.decode(): (float(arr[i].total_ms), int(arr[i].count)) for i in range(n)}

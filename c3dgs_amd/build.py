@@ -54,12 +54,15 @@ SOURCES = {
     "densify.hip": ["-ffp-contract=off"],   # sqrt(gx*gx + gy*gy) of the densification stats is torch's two-rounding sum
     # MCMC density control: t = floor(u * T) of the sampler is one IEEE multiply that the host restatement repeats (csrc/mcmc.hip)
     "mcmc.hip": ["-ffp-contract=off"],
+    # per-image colour correction (bilateral grids): no test needs separately rounded operations, so contraction stays on
+    "bilagrid.hip": [],
     "index_plan.hip": [],
     "ray_fill.hip": ["-ffp-contract=off"],  # x * (1 - a) + a * y of the new positions is four separately rounded operations
     "image_io.hip": ["-ffp-contract=off"],  # t0 * (1 - f) + t1 * f of the bilinear taps is separately rounded (csrc/image_io.hip)
 }
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), os.path.join(CSRC, "render_diag.hpp"),
            os.path.join(CSRC, "render_common.hpp"), os.path.join(CSRC, "replay.hpp"), os.path.join(CSRC, "scan_blocks.hpp"), os.path.join(CSRC, "adam_common.hpp"), os.path.join(CSRC, "mcmc.hpp"), os.path.join(CSRC, "jobs.hpp"),
+           os.path.join(CSRC, "bilagrid.hpp"),
            os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h")]
 
 

@@ -3,6 +3,7 @@
 // 338-435, 440-586, 590-697); the stages themselves are the gfx950 kernels in this directory.
 #include "common.hpp"
 #include "mcmc.hpp"
+#include "bilagrid.hpp"
 #include <cfloat>
 #include <climits>
 #include <cstdlib>
@@ -37,7 +38,10 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(KNN_QUERY, "knn_query") X(SPARSE_ADAM_SELECT, "sparse_adam_select") X(SPARSE_ADAM_STEP, "sparse_adam_step")              \
     X(AA_OPACITY, "aa_opacity") X(AA_OPACITY_BWD, "aa_opacity_backward")                                                       \
     X(MCMC_WEIGHTS, "mcmc_weights") X(MCMC_SEARCH, "mcmc_search") X(MCMC_VALUES, "mcmc_values") X(MCMC_APPLY, "mcmc_apply")    \
-    X(MCMC_NOISE, "mcmc_noise")
+    X(MCMC_NOISE, "mcmc_noise")                                                                                                \
+    X(BILAGRID_SLICE, "bilagrid_slice") X(BILAGRID_SLICE_BWD, "bilagrid_slice_backward") X(BILAGRID_GATHER, "bilagrid_gather") \
+    X(BILAGRID_FOLD, "bilagrid_fold") X(BILAGRID_RGB_BWD, "bilagrid_rgb_backward") X(BILAGRID_TV, "bilagrid_tv")               \
+    X(BILAGRID_TV_BWD, "bilagrid_tv_backward")
 #define C3DGS_X(id, name) ST_##id,
 enum Stage { C3DGS_STAGE_TABLE(C3DGS_X) ST_COUNT };
 #undef C3DGS_X
@@ -1189,6 +1193,89 @@ int c3dgs_mcmc_noise(int64_t P, float* xyz, const float* rotation, const float* 
     if (!xyz || !rotation || !scaling || !raw_opacity || !xi) return fail(C3DGS_E_INVALID, "mcmc_noise: NULL buffer");
     C3DGS_TIMED_STAGE(ST_MCMC_NOISE, 0, (hipStream_t)stream,
                       launch_mcmc_noise(P, xyz, rotation, scaling, scaling_factor, raw_opacity, xi, noise_lr, xyz_lr, (hipStream_t)stream));
+    return C3DGS_OK;
+}
+
+// ---- per-image colour correction: bilateral grids (bilagrid.hip)
+// the sizes every bilagrid entry takes; H = W = 1 where there is no image. -> the message, or null
+static const char* bilagrid_bad_sizes(int32_t H, int32_t W, int32_t L, int32_t Hg, int32_t Wg)
+{
+    if (H <= 0 || W <= 0 || L <= 0 || Hg <= 0 || Wg <= 0) return "every size must be positive";
+    const int64_t lim = int64_t(1) << 31;
+    const int64_t lh = (int64_t)L * Hg;
+    if (lh >= lim || lh * Wg >= lim || 12 * lh * Wg >= lim) return "12 * L * Hg * Wg must be below 2^31";
+    if (3 * (int64_t)H * W >= lim) return "3 * H * W must be below 2^31";
+    return nullptr;
+}
+// the launch limits of the gather: vertices x slabs workgroups along x, level chunks along y
+static const char* bilagrid_bad_plan(const BilagridPlan& plan)
+{
+    if (plan.groups >= (int64_t(1) << 31) || plan.chunks > 65535) return "the gather's launch does not fit (vertices x slabs >= 2^31 or L > 524280)";
+    return nullptr;
+}
+
+size_t c3dgs_bilagrid_workspace_bytes(int32_t H, int32_t W, int32_t L, int32_t Hg, int32_t Wg)
+{
+    if (const char* bad = bilagrid_bad_sizes(H, W, L, Hg, Wg)) { set_error(std::string("bilagrid_workspace_bytes: ") + bad); return 0; }
+    return bilagrid_plan(H, W, L, Hg, Wg).total_bytes;
+}
+
+int c3dgs_bilagrid_slice(int32_t H, int32_t W, int32_t L, int32_t Hg, int32_t Wg, const float* grid, const float* rgb, float* out,
+                         void* stream)
+{
+    if (const char* bad = bilagrid_bad_sizes(H, W, L, Hg, Wg)) return fail(C3DGS_E_INVALID, std::string("bilagrid_slice: ") + bad);
+    if (!grid || !rgb || !out) return fail(C3DGS_E_INVALID, "bilagrid_slice: grid, rgb and out are required");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_BILAGRID_SLICE, 0, s, launch_bilagrid_slice(H, W, L, Hg, Wg, grid, rgb, out, s));
+    return C3DGS_OK;
+}
+
+int c3dgs_bilagrid_slice_backward(int32_t H, int32_t W, int32_t L, int32_t Hg, int32_t Wg, const float* grid, const float* rgb,
+                                  const float* dL_dout, float* dL_dgrid, float* dL_drgb, void* workspace, void* stream)
+{
+    if (const char* bad = bilagrid_bad_sizes(H, W, L, Hg, Wg)) return fail(C3DGS_E_INVALID, std::string("bilagrid_slice_backward: ") + bad);
+    if (!grid || !rgb || !dL_dout || !dL_dgrid)
+        return fail(C3DGS_E_INVALID, "bilagrid_slice_backward: grid, rgb, dL_dout and dL_dgrid are required");
+    if (!workspace) return fail(C3DGS_E_INVALID, "bilagrid_slice_backward: the workspace is NULL (c3dgs_bilagrid_workspace_bytes)");
+    const BilagridPlan plan = bilagrid_plan(H, W, L, Hg, Wg);
+    if (const char* bad = bilagrid_bad_plan(plan)) return fail(C3DGS_E_INVALID, std::string("bilagrid_slice_backward: ") + bad);
+    hipStream_t s = (hipStream_t)stream;
+    {
+        StageTimer t_(ST_BILAGRID_SLICE_BWD, s);
+        { StageTimer a_(ST_BILAGRID_GATHER, s); launch_bilagrid_gather(H, W, L, Hg, Wg, plan, rgb, dL_dout, (float*)workspace, s); }
+        { StageTimer b_(ST_BILAGRID_FOLD, s); launch_bilagrid_fold(L, Hg, Wg, plan, (const float*)workspace, dL_dgrid, s); }
+        if (dL_drgb) { StageTimer c_(ST_BILAGRID_RGB_BWD, s); launch_bilagrid_rgb_backward(H, W, L, Hg, Wg, grid, rgb, dL_dout, dL_drgb, s); }
+    }
+    C3DGS_STAGE_CHECK(ST_BILAGRID_SLICE_BWD, 0, s);
+    return C3DGS_OK;
+}
+
+// what the two total-variation entries ask of their sizes
+static const char* bilagrid_bad_tv_sizes(int32_t C, int32_t L, int32_t Hg, int32_t Wg)
+{
+    if (C <= 0) return "every size must be positive";
+    if (const char* bad = bilagrid_bad_sizes(1, 1, L, Hg, Wg)) return bad;
+    if ((int64_t)C * 12 * L * Hg * Wg >= (int64_t(1) << 31)) return "C * 12 * L * Hg * Wg must be below 2^31";
+    return nullptr;
+}
+
+int c3dgs_bilagrid_tv(int32_t C, int32_t L, int32_t Hg, int32_t Wg, const float* grids, void* workspace, float* out, void* stream)
+{
+    if (const char* bad = bilagrid_bad_tv_sizes(C, L, Hg, Wg)) return fail(C3DGS_E_INVALID, std::string("bilagrid_tv: ") + bad);
+    if (!grids || !out) return fail(C3DGS_E_INVALID, "bilagrid_tv: grids and out are required");
+    if (!workspace) return fail(C3DGS_E_INVALID, "bilagrid_tv: the workspace is NULL (c3dgs_bilagrid_workspace_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_BILAGRID_TV, 0, s, launch_bilagrid_tv(C, L, Hg, Wg, grids, (double*)workspace, out, s));
+    return C3DGS_OK;
+}
+
+int c3dgs_bilagrid_tv_backward(int32_t C, int32_t L, int32_t Hg, int32_t Wg, const float* grids, const float* dL_dtv,
+                               float* dL_dgrids, void* stream)
+{
+    if (const char* bad = bilagrid_bad_tv_sizes(C, L, Hg, Wg)) return fail(C3DGS_E_INVALID, std::string("bilagrid_tv_backward: ") + bad);
+    if (!grids || !dL_dtv || !dL_dgrids) return fail(C3DGS_E_INVALID, "bilagrid_tv_backward: grids, dL_dtv and dL_dgrids are required");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_BILAGRID_TV_BWD, 0, s, launch_bilagrid_tv_backward(C, L, Hg, Wg, grids, dL_dtv, dL_dgrids, s));
     return C3DGS_OK;
 }
 

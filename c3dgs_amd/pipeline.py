@@ -19,6 +19,7 @@ from typing import Optional
 
 import torch
 
+from . import bilagrid as _bilagrid
 from . import loss as _loss
 from . import metrics as _metrics
 from . import optim as _optim
@@ -112,7 +113,7 @@ def _train_cameras(scene):
 
 
 def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_interval=0, prune_min_opacity=0.005,
-             prune_min_views=0):
+             prune_min_views=0, bilagrid=None):
     """finetune.py:10-66. One camera per iteration, drawn without replacement from a stack that is refilled when empty
     (`pop(randint(0, len - 1))` on Python's `random`, like the reference); render -> (1 - l) L1 + l (1 - SSIM) ->
     backward -> learning-rate update -> Adam step (not after the last iteration).
@@ -129,8 +130,33 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
     `prune_min_views` = V > 0 (0 changes nothing): when `prune_interval` fires, the Gaussians that
     GaussianModel.contribution_stats over the training cameras sees blended in fewer than V views go as well
     (prune_by_contribution): what no training view blends costs sort, list and codebook space in every view. The statistics
-    pass renders every training camera once but leaves the QAT observers as it found them (contribution_stats restores them)."""
+    pass renders every training camera once but leaves the QAT observers as it found them (contribution_stats restores them).
+    `bilagrid` (not in the reference; None changes nothing): a trained bilagrid.BilateralGrid whose row k belongs to camera k of
+    the training list. The loss then sees bilagrid.slice(render, k), so the fine-tuning does not fight the exposure differences
+    the grids had absorbed. The grids are frozen: no optimizer, requires_grad is switched off for the call and restored."""
     gaussians = scene.gaussians if hasattr(scene, "gaussians") else dataset.gaussians
+    if bilagrid is not None:
+        camera_index = _camera_indices(_train_cameras(scene), bilagrid)
+        grids_required_grad = bilagrid.grids.requires_grad
+        bilagrid.grids.requires_grad_(False)
+        try:
+            return _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, prune_min_opacity, prune_min_views,
+                             gaussians, bilagrid, camera_index)
+        finally:
+            bilagrid.grids.requires_grad_(grids_required_grad)
+    return _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, prune_min_opacity, prune_min_views, gaussians,
+                     None, None)
+
+
+def _camera_indices(cameras, bilagrid):
+    """{id(camera): its index in the training list}, the row of `bilagrid` it owns"""
+    if bilagrid.num_cameras != len(cameras):
+        raise ValueError(f"bilagrid: {bilagrid.num_cameras} grids for {len(cameras)} training cameras")
+    return {id(cam): k for k, cam in enumerate(cameras)}
+
+
+def _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, prune_min_opacity, prune_min_views, gaussians,
+              bilagrid, camera_index):
     first_iter = int(getattr(scene, "loaded_iter", 0) or 0)
     max_iter = first_iter + comp.finetune_iterations
     bg_color = [1, 1, 1] if getattr(dataset, "white_background", False) else [0, 0, 0]
@@ -151,6 +177,8 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
             pipe.debug = True
         render_pkg = gaussians.render(viewpoint_cam, pipe, background)
         image = render_pkg["render"]
+        if bilagrid is not None:
+            image = bilagrid.slice(image, camera_index[id(viewpoint_cam)])
         gt_image = viewpoint_cam.original_image.to(image.device)
         loss = _loss.l1_ssim_loss(image, gt_image, opt.lambda_dssim)
         loss.backward()
@@ -182,7 +210,8 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
 
 def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, degree_up_iter=1000, *, densify_by="grad",
           error_threshold=None, optimizer_type=None, optimizer_visibility="radii", lambda_depth=0.0, lambda_alpha=0.0,
-          strategy="default", cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01, min_opacity=0.005):
+          strategy="default", cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01, min_opacity=0.005,
+          bilagrid=None, bilagrid_lr=2e-3, bilagrid_tv=10.0):
     """train.py:15-173 without its disabled compression-statistics branch: optimise a non-indexed model (usually
     GaussianModel.load_ply of a point cloud) with adaptive density control.
 
@@ -234,7 +263,20 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
         it has no gradient statistics to gather over an interval first. tests/train_scene.py's schedule(400) thus refines at
         epochs 5, 10, ... 35, seven times. No densify_and_prune, no reset_opacity, no add_densification_stats.
     `info` keeps "densified": None and "reset_opacity": False and gains "mcmc": None | (relocated, added). Both optimizer types
-    work. densify_by="error" with it raises ValueError, as does an unknown strategy."""
+    work. densify_by="error" with it raises ValueError, as does an unknown strategy.
+
+    `bilagrid` (not in the reference: gsplat's bilateral grid; shape (1, 1, 1) is upstream 3DGS's per-image `exposure`;
+    csrc/bilagrid.hip) = None is the loop above, launch for launch. A shape (L, Hg, Wg) builds a bilagrid.BilateralGrid with one
+    identity grid per training camera and hands it out as info["bilagrid"] on the first log call; a BilateralGrid is trained in
+    place. Row k belongs to camera k of the training list (all of them, whatever `camera_stride` visits). The loss then sees
+    bilagrid.slice(render, k) in place of the render, plus `bilagrid_tv` x bilagrid.tv_loss() when the shape has more than one
+    vertex and bilagrid_tv > 0. The grids get an optim.Adam of their own at `bilagrid_lr`, stepped and zeroed next to the model's:
+    they stay out of the model's optimizer, so densification and MCMC never see their moments. The defaults (2e-3, 10.0) are
+    gsplat's, quoted from memory; nobody has tuned them here. densify_by="error" with a grid raises ValueError: the error map
+    inside render() would compare the uncorrected image. Every epoch's `info` also carries "epoch_loss", the mean of the epoch's
+    losses (the values the moving average is fed)."""
+    if bilagrid is not None and densify_by == "error":
+        raise ValueError("train: densify_by='error' compares the uncorrected render inside render(); it cannot be combined with bilagrid")
     if strategy not in ("default", "mcmc"):
         raise ValueError(f"train: strategy must be 'default' or 'mcmc', not {strategy!r}")
     mcmc = strategy == "mcmc"
@@ -257,6 +299,13 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     cameras = _train_cameras(scene)
     if extent is None and not mcmc:
         extent = scene.cameras_extent
+    grid_optimizer = None
+    if bilagrid is not None:
+        if not isinstance(bilagrid, _bilagrid.BilateralGrid):
+            bilagrid = _bilagrid.BilateralGrid(len(cameras), bilagrid, device=gaussians.device).set_cameras(cameras)
+        camera_index = _camera_indices(cameras, bilagrid)
+        grid_optimizer = _optim.Adam([bilagrid.grids], lr=bilagrid_lr, eps=1e-15)
+        grid_tv = float(bilagrid_tv) if bilagrid_tv and max(bilagrid.shape) > 1 else 0.0
     gaussians.training_setup(opt, optimizer_type=optimizer_type)
     gaussians.update_learning_rate(0)
     sparse = isinstance(gaussians.optimizer, _optim.SparseGaussianAdam) and optimizer_visibility is not None
@@ -299,7 +348,11 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             image, viewspace_point_tensor, radii = render_pkg["render"], render_pkg["viewspace_points"], render_pkg["radii"]
             if not by_error:
                 gt_image = viewpoint_cam.original_image.to(image.device)
+            if bilagrid is not None:
+                image = bilagrid.slice(image, camera_index[id(viewpoint_cam)])
             loss = _loss.l1_ssim_loss(image, gt_image, opt.lambda_dssim)
+            if grid_optimizer is not None and grid_tv > 0:
+                loss = loss + grid_tv * bilagrid.tv_loss()
             if alpha_target is not None:
                 loss = loss + lambda_alpha * (render_pkg["alpha"] - alpha_target.to(dev)).abs().mean()
             if depth_target is not None:
@@ -316,6 +369,9 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             else:
                 gaussians.optimizer.step()
             gaussians.optimizer.zero_grad(set_to_none=True)
+            if grid_optimizer is not None:
+                grid_optimizer.step()
+                grid_optimizer.zero_grad(set_to_none=True)
             if mcmc:
                 gaussians.add_position_noise(noise_lr)
             elif epoch < densify_until_epoch:
@@ -324,9 +380,13 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
                     if by_error:
                         gaussians.add_error_stats(render_pkg["error_sum"])
             iteration += 1
-        for v in torch.stack(pending).tolist():                   # one host read per epoch
+        epoch_losses = torch.stack(pending).tolist()               # one host read per epoch
+        for v in epoch_losses:
             ema_loss_for_log = 0.4 * v + 0.6 * ema_loss_for_log
-        info = {"iteration": iteration, "ema_loss": ema_loss_for_log, "densified": None, "reset_opacity": False}
+        info = {"iteration": iteration, "ema_loss": ema_loss_for_log, "densified": None, "reset_opacity": False,
+                "epoch_loss": sum(epoch_losses) / len(epoch_losses)}
+        if bilagrid is not None and epoch == 0:
+            info["bilagrid"] = bilagrid
         if mcmc:
             info["mcmc"] = None
             if densify_from_epoch <= epoch < densify_until_epoch and epoch % densification_interval == 0:

@@ -598,6 +598,40 @@ int c3dgs_mcmc_noise(int64_t P, float* xyz /*[P,3]*/, const float* rotation /*[P
                      const float* scaling_factor /*[P] or NULL*/, const float* raw_opacity /*[P]*/, const float* xi /*[P,3]*/,
                      float noise_lr, float xyz_lr, void* stream);
 
+/* ---- per-image colour correction by a bilateral grid (csrc/bilagrid.hip; no reference counterpart: gsplat's lib_bilagrid /
+ * fused_bilagrid; a grid of shape (1, 1, 1) is upstream 3DGS's per-image 3x4 `exposure`) ----
+ * Added without an ABI version bump: new entry points only. One camera's grid G is fp32 [12, L, Hg, Wg], the 12 rows a row-major
+ * 3x4 matrix per lattice vertex; rgb, out, dL_dout, dL_drgb are planar fp32 [3, H, W]. For pixel (x, y) with colour c = (r, g, b):
+ *   gx = (x + 0.5) / W (Wg - 1),  gy = (y + 0.5) / H (Hg - 1),  z = clamp(0.299 r + 0.587 g + 0.114 b, 0, 1) (L - 1)
+ *   A = the trilinear interpolation of the 12 rows at (z, gy, gx), hat weights max(0, 1 - |coordinate - index|) per axis, an
+ *       axis of size 1 weighing 1;   out = A[:, :3] c + A[:, 3]
+ * which is grid_sample(G[None], (2 xs - 1, 2 ys - 1, 2 luma - 1), "bilinear", "border", align_corners=True) followed by the affine.
+ * An identity grid of shape (1, 1, 1) returns rgb bit for bit. A NaN luma reads level 0.
+ * slice_backward: dL_dgrid (every element written; a vertex no pixel touches receives exactly 0) and, unless dL_drgb is NULL,
+ *   dL_drgb = A[:, :3]^T dL_dout + (dL/dz)(L - 1)(0.299, 0.587, 0.114), the second term zero where the luma was clamped and for
+ *   L == 1. dL_dgrid is gathered by vertex into `workspace` (c3dgs_bilagrid_workspace_bytes(H, W, L, Hg, Wg) bytes, never 0,
+ *   8-byte aligned, every word read is written first) and folded in a fixed order: no float atomics, bitwise
+ *   reproducible, and the same bits with and without dL_drgb.
+ * tv: out[0] = (1 / C) sum over the lattice axes of size >= 2 of sum((X[i + 1] - X[i])^2 along the axis) / (12 x the lattice
+ *   positions of one camera's differences along it), for X = grids [C, 12, L, Hg, Wg]; summed in double in a fixed order.
+ *   `workspace`: the same query with H = W = 1 (8 KiB suffice). tv_backward: dL_dgrids = dL_dtv[0] x d tv / dX, every element
+ *   written, each from its up to six neighbours; dL_dtv is one fp32 on the device.
+ * Every entry returns C3DGS_E_INVALID with a message before any device work for a non-positive size, 12 L Hg Wg (for tv also
+ * C 12 L Hg Wg) or 3 H W not below 2^31, a NULL required pointer or workspace, and a gather launch that does not fit
+ * (Hg Wg x slabs >= 2^31 or L > 524280); c3dgs_bilagrid_workspace_bytes returns 0 then and leaves the message in
+ * c3dgs_last_error. Stage names: "bilagrid_slice"; "bilagrid_slice_backward" (all of its launches; "bilagrid_gather",
+ * "bilagrid_fold", "bilagrid_rgb_backward" alone); "bilagrid_tv" (both launches); "bilagrid_tv_backward". */
+size_t c3dgs_bilagrid_workspace_bytes(int32_t H, int32_t W, int32_t L, int32_t Hg, int32_t Wg);
+int c3dgs_bilagrid_slice(int32_t H, int32_t W, int32_t L, int32_t Hg, int32_t Wg, const float* grid, const float* rgb,
+                         float* out, void* stream);
+int c3dgs_bilagrid_slice_backward(int32_t H, int32_t W, int32_t L, int32_t Hg, int32_t Wg, const float* grid, const float* rgb,
+                                  const float* dL_dout, float* dL_dgrid /*written*/, float* dL_drgb /*| NULL*/, void* workspace,
+                                  void* stream);
+int c3dgs_bilagrid_tv(int32_t C, int32_t L, int32_t Hg, int32_t Wg, const float* grids, void* workspace, float* out /*[1]*/,
+                      void* stream);
+int c3dgs_bilagrid_tv_backward(int32_t C, int32_t L, int32_t Hg, int32_t Wg, const float* grids, const float* dL_dtv /*[1], device*/,
+                               float* dL_dgrids /*written*/, void* stream);
+
 /* ---- initial densification (GaussianModel.densify_initial, scene/gaussian_model.py:1352-1389): new points one `step` apart
  * on the ray from every point to each of its three nearest neighbours, planned in one pass from the neighbour table of
  * c3dgs_knn_neighbours instead of the reference's loop over levels (DESIGN.md "Initial densification"). With

@@ -7,6 +7,7 @@ before / after, and seconds per phase.
                               [--densify-by grad|error] [--error-threshold T] [--optimizer default|sparse_adam]
                               [--lambda-depth X] [--lambda-alpha Y] [--antialiasing]
                               [--strategy default|mcmc] [--cap-max N] [--noise-lr X]
+                              [--bilagrid L HG WG | --exposure] [--bilagrid-lr X] [--bilagrid-tv Y] [--exposure-jitter S]
 
 --densify-by error (with --error-threshold, which has no default) lets the run with density control densify by image error
 (pipeline.train(densify_by="error")); the JSON then carries "densify_by" and "error_threshold".
@@ -23,7 +24,15 @@ the plain rasterizer and box-filtered down 4 x 4 ("resolution_eval"); "train_vie
 themselves. One run each, nothing tuned; the JSON then carries "antialiasing" in place of the two default runs.
 --strategy mcmc --cap-max N [--noise-lr X] makes ONE run with pipeline.train(strategy="mcmc", cap_max=N) (relocation, growth
 by 5 % up to N rows, position noise; csrc/mcmc.hip) in place of the two default runs; the JSON carries "strategy", "cap_max",
-"noise_lr" and under "mcmc" the run with its (epoch, relocated, added) refinements."""
+"noise_lr" and under "mcmc" the run with its (epoch, relocated, added) refinements.
+--bilagrid L HG WG (or --exposure, which is --bilagrid 1 1 1) [--bilagrid-lr X] [--bilagrid-tv Y] trains one bilateral grid per
+camera next to the model (pipeline.train(bilagrid=(L, HG, WG)); csrc/bilagrid.hip). --exposure-jitter S, for the demonstration
+only, replaces every training image by a_k * image + b_k with per-camera, per-channel a in [1 - S, 1 + S] and b in
+[-S / 4, S / 4] from a seeded generator (tests/bilagrid_ref.py jitter_exposure). With any of them ONE run is made, without
+density control, in place of the two default runs; the JSON carries "bilagrid" (the shape or null), "exposure_jitter" and under
+"run" the run: "final_loss" (the mean loss over the last epoch, which every run reports), "psnr_after" as always (the RAW render against the
+training images as they were trained on, jittered or not) and, here only, "psnr_vs_clean_images" (the raw render against the
+teacher's own images; it carries a global gain ambiguity that only a colour-corrected metric would remove)."""
 import argparse
 import json
 import os
@@ -86,7 +95,7 @@ def resolution_eval(student, cams, pipe):
 
 
 def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer="default", lambda_depth=0.0, lambda_alpha=0.0,
-        with_maps=False, antialiasing=None, mcmc=None):
+        with_maps=False, antialiasing=None, mcmc=None, bilagrid=None, jitter=0.0):
     from c3dgs_amd import pipeline
     from c3dgs_amd.model import PipelineParams
     with tempfile.TemporaryDirectory() as tmp:
@@ -94,12 +103,16 @@ def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer=
         student, cams, extent = train_scene.make(tmp)
         torch.cuda.synchronize()
         t_setup = time.perf_counter() - t0
-    extra = {}
+    extra = dict(bilagrid or {})
+    clean = [cam.original_image.clone() for cam in cams]
+    if jitter:
+        from tests import bilagrid_ref
+        bilagrid_ref.jitter_exposure(cams, jitter)
     if with_maps:
         maps = teacher_maps(cams)
         for cam, (depth, alpha) in zip(cams, maps):
             cam.alpha_target, cam.depth_target = alpha, (depth / alpha.clamp(min=1e-6)) * (alpha > 0.5)
-        extra = dict(lambda_depth=lambda_depth, lambda_alpha=lambda_alpha)
+        extra.update(lambda_depth=lambda_depth, lambda_alpha=lambda_alpha)
     rows0, before = student._xyz.shape[0], train_scene.mean_psnr(student, cams)
     events = []
 
@@ -125,6 +138,14 @@ def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer=
            "psnr_after": after, "densifications": [[e, i["densified"][0], list(i["densified"][1])] for e, i in events if i["densified"]],
            "opacity_resets": [e for e, i in events if i["reset_opacity"]],
            "seconds": {"setup": t_setup, "train": t_train, "eval": t_eval}}
+    out["final_loss"] = events[-1][1]["epoch_loss"]           # the mean loss over the last epoch
+    if bilagrid is not None or jitter:
+        trained_on = [cam.original_image for cam in cams]
+        for cam, img in zip(cams, clean):
+            cam.original_image = img
+        out["psnr_vs_clean_images"] = train_scene.mean_psnr(student, cams)
+        for cam, img in zip(cams, trained_on):
+            cam.original_image = img
     if mcmc:
         out["refinements"] = [[e, i["mcmc"][0], i["mcmc"][1]] for e, i in events if i.get("mcmc")]
     if with_maps:
@@ -147,7 +168,14 @@ def main():
     ap.add_argument("--strategy", choices=("default", "mcmc"), default="default")
     ap.add_argument("--cap-max", type=int, default=None)
     ap.add_argument("--noise-lr", type=float, default=5e5)
+    ap.add_argument("--bilagrid", type=int, nargs=3, metavar=("L", "HG", "WG"), default=None)
+    ap.add_argument("--exposure", action="store_true")
+    ap.add_argument("--bilagrid-lr", type=float, default=2e-3)
+    ap.add_argument("--bilagrid-tv", type=float, default=10.0)
+    ap.add_argument("--exposure-jitter", type=float, default=0.0)
     args = ap.parse_args()
+    if args.exposure and args.bilagrid is not None:
+        ap.error("--exposure is --bilagrid 1 1 1; give one of the two")
     if args.densify_by == "error" and args.error_threshold is None:
         ap.error("--densify-by error needs --error-threshold (there is no default)")
     if args.strategy == "mcmc" and args.cap_max is None:
@@ -158,6 +186,18 @@ def main():
     if args.antialiasing:
         out["antialiasing"] = {"off": run(args.iterations, False, optimizer=args.optimizer, antialiasing=False),
                                "on": run(args.iterations, False, optimizer=args.optimizer, antialiasing=True)}
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
+    shape = (1, 1, 1) if args.exposure else (tuple(args.bilagrid) if args.bilagrid is not None else None)
+    if shape is not None or args.exposure_jitter:
+        grid = None if shape is None else dict(bilagrid=shape, bilagrid_lr=args.bilagrid_lr, bilagrid_tv=args.bilagrid_tv)
+        out["bilagrid"], out["exposure_jitter"] = shape, args.exposure_jitter
+        if shape is not None:
+            out["bilagrid_lr"], out["bilagrid_tv"] = args.bilagrid_lr, args.bilagrid_tv
+        out["run"] = run(args.iterations, False, optimizer=args.optimizer, bilagrid=grid, jitter=args.exposure_jitter)
         print(json.dumps(out))
         if args.out:
             with open(args.out, "w") as f:
