@@ -26,6 +26,8 @@ pipeline.train(strategy="mcmc", cap_max=N) trains towards a hard budget of Gauss
 GaussianModel.relocate_gs / add_new_gs / add_position_noise on csrc/mcmc.hip; thin entries in c3dgs_amd.mcmc).
 c3dgs_amd.bilagrid (BilateralGrid, ExposureModel on csrc/bilagrid.hip) is a per-image colour model, gsplat's bilateral grid and
 upstream 3DGS's `exposure`, which pipeline.train(bilagrid=...) trains and pipeline.finetune(bilagrid=...) applies frozen.
+GaussianModel.compute_3D_filter(cameras) / pipeline.train(filter_3d=True) give every Gaussian Mip-Splatting's 3D smoothing filter,
+a minimum world-space size from the training cameras' sampling rates that render() applies (c3dgs_amd.filter3d on csrc/filter3d.hip).
 
 The numeric work runs in c3dgs_amd/libc3dgs_hip.so (include/c3dgs_hip.h); build it with
 `python -m c3dgs_amd.build`.  There is no CPU fallback.
@@ -33,7 +35,7 @@ The numeric work runs in c3dgs_amd/libc3dgs_hip.so (include/c3dgs_hip.h); build 
 import sys
 import types
 
-from . import bilagrid, encode, knn, loss, mcmc, metrics, model, optim, ply, rasterizer, rasterizer_matrix, sensitivity, vq  # noqa: F401
+from . import bilagrid, encode, filter3d, knn, loss, mcmc, metrics, model, optim, ply, rasterizer, rasterizer_matrix, sensitivity, vq  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,  # noqa: F401
                          getProjectionMatrix, mat_to_quat, quat_to_mat, rasterize_gaussians,
                          rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,

@@ -85,6 +85,18 @@ class RowsTensor(C.Structure):          # c3dgs_rows_tensor
                 ("out_exp_avg", C.c_void_p), ("out_exp_avg_sq", C.c_void_p), ("row_floats", C.c_int32), ("role", C.c_int32)]
 
 
+class Filter3DRows(C.Structure):        # c3dgs_filter3d_rows
+    _fields_ = [("n", C.c_int32), ("P_model", C.c_int32), ("opacities", C.c_void_p), ("scales", C.c_void_p), ("rotations", C.c_void_p),
+                ("scale_factors", C.c_void_p), ("g_indices", C.c_void_p), ("cov3D_precomp", C.c_void_p), ("filter_3D", C.c_void_p),
+                ("visible", C.c_void_p),
+                ("rank", C.c_void_p), ("scale_modifier", C.c_float)]
+
+
+class Filter3DGrads(C.Structure):       # c3dgs_filter3d_grads
+    _fields_ = [(n, C.c_void_p) for n in ("dL_dcov3D", "dL_dopacity_out", "dL_dopacity", "dL_dscales", "dL_drotations",
+                                          "dL_dscale_factors")]
+
+
 ROLE_COPY, ROLE_XYZ, ROLE_SCALING = 0, 1, 2
 MCMC_ROLE_OPACITY, MCMC_ROLE_SCALE = 3, 4             # c3dgs_mcmc_apply
 ROW_KEEP, ROW_CLONE, ROW_SPLIT, ROW_CHILD_KEPT = 1, 2, 4, 8
@@ -122,6 +134,10 @@ PROTOTYPES = {
     "c3dgs_pose_grad": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_float] + [_vp] * 17),
     "c3dgs_aa_opacity": (C.c_int, [C.POINTER(RasterParams), _vp, _vp, _vp]),
     "c3dgs_aa_opacity_backward": (C.c_int, [C.POINTER(RasterParams), _vp, C.POINTER(RasterGrads), _vp]),
+    "c3dgs_filter3d_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "c3dgs_filter3d_compute": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "c3dgs_filter3d_apply": (C.c_int, [C.POINTER(Filter3DRows), _vp, _vp, _vp]),
+    "c3dgs_filter3d_apply_backward": (C.c_int, [C.POINTER(Filter3DRows), C.POINTER(Filter3DGrads), _vp]),
     "c3dgs_error_map_l1": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_vp] * 4),
     "c3dgs_error_accumulate": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 6),
     "c3dgs_weighted_distance": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -43,6 +43,9 @@ SOURCES = {
     "pose_grad.hip": ["-ffp-contract=off"],
     # the opacity compensation of the antialiased mode forms the 2D covariance with preprocess's expressions (csrc/gsmath.hpp)
     "aa_opacity.hip": ["-ffp-contract=off"],
+    # the 3D smoothing filter: its projections are single fp32 operations a NumPy restatement repeats bit for bit, and its
+    # covariance is preprocess's (csrc/gsmath.hpp)
+    "filter3d.hip": ["-ffp-contract=off"],
     "draws.hip": [],
     "loss.hip": [],
     "metrics.hip": [],

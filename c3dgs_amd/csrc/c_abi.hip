@@ -41,7 +41,8 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(MCMC_NOISE, "mcmc_noise")                                                                                                \
     X(BILAGRID_SLICE, "bilagrid_slice") X(BILAGRID_SLICE_BWD, "bilagrid_slice_backward") X(BILAGRID_GATHER, "bilagrid_gather") \
     X(BILAGRID_FOLD, "bilagrid_fold") X(BILAGRID_RGB_BWD, "bilagrid_rgb_backward") X(BILAGRID_TV, "bilagrid_tv")               \
-    X(BILAGRID_TV_BWD, "bilagrid_tv_backward")
+    X(BILAGRID_TV_BWD, "bilagrid_tv_backward")                                                                                 \
+    X(FILTER3D_COMPUTE, "filter3d_compute") X(FILTER3D_APPLY, "filter3d_apply") X(FILTER3D_APPLY_BWD, "filter3d_apply_backward")
 #define C3DGS_X(id, name) ST_##id,
 enum Stage { C3DGS_STAGE_TABLE(C3DGS_X) ST_COUNT };
 #undef C3DGS_X
@@ -770,6 +771,67 @@ int c3dgs_aa_opacity_backward(const c3dgs_raster_params* p, const int32_t* radii
     if (!radii) return fail(C3DGS_E_INVALID, "aa_opacity_backward: radii is required");
     C3DGS_TIMED_STAGE(ST_AA_OPACITY_BWD, p->debug, (hipStream_t)stream,
                       launch_aa_opacity_backward(*p, radii, *grads, (hipStream_t)stream));
+    return C3DGS_OK;
+}
+
+size_t c3dgs_filter3d_workspace_bytes(int32_t) { return 256; }    // {bits of the largest seen dist, bits of the focal}
+
+int c3dgs_filter3d_compute(int32_t P, int32_t C, const float* xyz, const float* cameras, float* filter_3D, uint8_t* seen,
+                           void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (P < 0) return fail(C3DGS_E_INVALID, "filter3d_compute: P must be >= 0");
+    if (C <= 0) return fail(C3DGS_E_INVALID, "filter3d_compute: C must be positive (a filter needs at least one camera)");
+    if (P == 0) return C3DGS_OK;
+    if (!xyz || !cameras || !filter_3D) return fail(C3DGS_E_INVALID, "filter3d_compute: xyz, cameras and filter_3D are required");
+    if (!workspace || workspace_bytes < c3dgs_filter3d_workspace_bytes(P) || (reinterpret_cast<uintptr_t>(workspace) & 7u))
+        return fail(C3DGS_E_INVALID, "filter3d_compute: workspace must hold c3dgs_filter3d_workspace_bytes(P) bytes, 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    {
+        StageTimer t_(ST_FILTER3D_COMPUTE, s);
+        hipError_t e = hipMemsetAsync(workspace, 0, 8, s);
+        if (e != hipSuccess) return fail(C3DGS_E_HIP, std::string("filter3d_compute: hipMemsetAsync: ") + hipGetErrorString(e));
+        launch_filter3d_dist(P, C, xyz, cameras, filter_3D, (uint32_t*)workspace, s);
+        launch_filter3d_finish(P, (const uint32_t*)workspace, filter_3D, seen, s);
+    }
+    C3DGS_STAGE_CHECK(ST_FILTER3D_COMPUTE, 0, s);
+    return C3DGS_OK;
+}
+
+// what c3dgs_filter3d_apply and c3dgs_filter3d_apply_backward both ask of the rows
+static int filter3d_validate(const char* who, const c3dgs_filter3d_rows* r)
+{
+    const std::string w(who);
+    if (!r) return fail(C3DGS_E_INVALID, w + ": rows is NULL");
+    if (r->n < 0) return fail(C3DGS_E_INVALID, w + ": n must be >= 0");
+    if (r->g_indices && !r->scale_factors) return fail(C3DGS_E_INVALID, w + ": g_indices need scale_factors");
+    if (r->visible && (!r->rank || r->P_model < 0)) return fail(C3DGS_E_INVALID, w + ": visible needs rank and P_model >= 0");
+    if (r->n == 0) return C3DGS_OK;
+    if (!r->opacities || !r->scales || !r->filter_3D || (!r->rotations && !r->cov3D_precomp))
+        return fail(C3DGS_E_INVALID, w + ": opacities, scales, rotations (unless cov3D_precomp is given) and filter_3D are required");
+    if (reinterpret_cast<uintptr_t>(r->rotations) & 15u)
+        return fail(C3DGS_E_INVALID, w + ": rotations must be 16-byte aligned");
+    return C3DGS_OK;
+}
+
+int c3dgs_filter3d_apply(const c3dgs_filter3d_rows* r, float* cov3D_out, float* opacity_out, void* stream)
+{
+    if (int rc = filter3d_validate("filter3d_apply", r)) return rc;
+    if (r->n == 0) return C3DGS_OK;
+    if (!cov3D_out || !opacity_out) return fail(C3DGS_E_INVALID, "filter3d_apply: cov3D_out and opacity_out are required");
+    C3DGS_TIMED_STAGE(ST_FILTER3D_APPLY, 0, (hipStream_t)stream, launch_filter3d_apply(*r, cov3D_out, opacity_out, (hipStream_t)stream));
+    return C3DGS_OK;
+}
+
+int c3dgs_filter3d_apply_backward(const c3dgs_filter3d_rows* r, const c3dgs_filter3d_grads* g, void* stream)
+{
+    if (int rc = filter3d_validate("filter3d_apply_backward", r)) return rc;
+    if (!g) return fail(C3DGS_E_INVALID, "filter3d_apply_backward: grads is NULL");
+    if (r->n == 0) return C3DGS_OK;
+    if (!g->dL_dopacity && !g->dL_dscales && !g->dL_drotations && !g->dL_dscale_factors)
+        return fail(C3DGS_E_INVALID, "filter3d_apply_backward: at least one output gradient is required");
+    if (reinterpret_cast<uintptr_t>(g->dL_drotations) & 15u)
+        return fail(C3DGS_E_INVALID, "filter3d_apply_backward: dL_drotations must be 16-byte aligned");
+    C3DGS_TIMED_STAGE(ST_FILTER3D_APPLY_BWD, 0, (hipStream_t)stream, launch_filter3d_apply_backward(*r, *g, (hipStream_t)stream));
     return C3DGS_OK;
 }
 

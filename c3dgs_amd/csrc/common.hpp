@@ -404,6 +404,11 @@ void launch_pose_fold(int P, const float* rows, const float* pose, float* out, h
 // aa_opacity.hip (antialiased rasterization: o' = o rho in front of the forward, the chain through rho behind the backward)
 void launch_aa_opacity(const c3dgs_raster_params& p, float* opacity_out, float* rho, hipStream_t s);
 void launch_aa_opacity_backward(const c3dgs_raster_params& p, const int32_t* radii, const c3dgs_raster_grads& gr, hipStream_t s);
+// filter3d.hip (the 3D smoothing filter: per-Gaussian minimum size over a camera table, applied around the rasterizer)
+void launch_filter3d_dist(int P, int C, const float* xyz, const float* cams, float* filter, uint32_t* ws, hipStream_t s);
+void launch_filter3d_finish(int P, const uint32_t* ws, float* filter, uint8_t* seen, hipStream_t s);
+void launch_filter3d_apply(const c3dgs_filter3d_rows& p, float* cov3D_out, float* opacity_out, hipStream_t s);
+void launch_filter3d_apply_backward(const c3dgs_filter3d_rows& p, const c3dgs_filter3d_grads& g, hipStream_t s);
 // backward_preprocess.hip
 void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,
                                 const c3dgs_raster_grads& gr, hipStream_t s);

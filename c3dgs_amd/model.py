@@ -338,6 +338,9 @@ class GaussianModel:
                 self._modules_qa[k].disable_observer()
             self.xyz_qa = lambda x: x
         self._count_host = None
+        # the 3D smoothing filter (compute_3D_filter): f32 [P] or None; stale: the model had one and rows were created since
+        self.filter_3D = None
+        self._filter_3D_stale = False
         self.spatial_lr_scale = 0.0                             # set by the scene loader in the reference (gaussian_model.py:286)
         self.optimizer = None
         self.xyz_scheduler_args = None
@@ -366,6 +369,7 @@ class GaussianModel:
         self._gaussian_indices = None if gaussian_indices is None else gaussian_indices.to(self.device, torch.int64).contiguous()
         self.color_index_mode = ColorMode.ALL_INDEXED if feature_indices is not None else ColorMode.NOT_INDEXED
         self.active_sh_degree = self.max_sh_degree if active_sh_degree is None else active_sh_degree
+        self.filter_3D, self._filter_3D_stale = None, False
         return self
 
     def parameters(self):
@@ -437,9 +441,73 @@ class GaussianModel:
     def get_normalized_covariance(self, scaling_modifier=1, strip_sym=True):
         return _covariance(self.get_scaling_normalized, scaling_modifier, self.get_rotation, strip_sym)
 
+    # ---- the 3D smoothing filter (Mip-Splatting; csrc/filter3d.hip, c3dgs_amd/filter3d.py; not in the reference)
+    def compute_3D_filter(self, cameras, table=None):
+        """Sets `filter_3D` (f32 [P], no grad) over `cameras`: per Gaussian sqrt(0.2) x its smallest depth among the cameras that
+        see it / the largest focal length (filter3d.compute; the nearest seen distance stands in for a Gaussian no camera sees).
+        From then on render() draws every Gaussian with Sigma + f^2 I and the matching opacity (filter3d.apply), until
+        clear_3D_filter(). -> the `seen` flags (bool [P]). Building the camera table reads every camera's pose on the host (one
+        device -> host copy per camera); a caller that recomputes over the same cameras passes the `table` of
+        filter3d.camera_table(cameras, device) instead and the call is then stream-ordered, without a host read."""
+        from . import filter3d
+        with torch.no_grad():
+            if table is None:
+                table = filter3d.camera_table(cameras, self.device)
+            self.filter_3D, seen = filter3d.compute(self._xyz.detach(), table)
+        self._filter_3D_stale = False
+        return seen
+
+    def clear_3D_filter(self):
+        self.filter_3D, self._filter_3D_stale = None, False
+
+    def _carry_3D_filter(self, rows):
+        """a pure selection or permutation of the rows (a mask or an index tensor) takes the filter along"""
+        if self.filter_3D is not None:
+            rows = rows.to(self.device)
+            rows = rows.bool() if rows.dtype in (torch.bool, torch.uint8) else rows.long()
+            self.filter_3D = self.filter_3D[rows].contiguous()
+
+    def _drop_3D_filter(self):
+        """rows were created: their filter values do not exist, so render() refuses until compute_3D_filter has run again"""
+        if self.filter_3D is not None:
+            self.filter_3D, self._filter_3D_stale = None, True
+
+    def _checked_3D_filter(self, pipe, cov3d, viewpoint_camera):
+        """render()'s filter, or None without one; raises for what the filtered path does not cover"""
+        if self._filter_3D_stale:
+            raise RuntimeError("render(): rows were added since the 3D filter was computed; call compute_3D_filter(cameras) again "
+                               "(or clear_3D_filter())")
+        if self.filter_3D is None:
+            return None
+        if pipe.compute_cov3D_python:
+            raise NotImplementedError("render() with a 3D filter: compute_cov3D_python is not covered")
+        if viewpoint_camera.extrinsic_vector.requires_grad:
+            raise ValueError("render() with a 3D filter: the gradient to a camera pose that requires grad is not covered")
+        if self.filter_3D.shape[0] != self._xyz.shape[0]:
+            raise RuntimeError(f"render(): filter_3D has {self.filter_3D.shape[0]} rows for {self._xyz.shape[0]} Gaussians; call "
+                               "compute_3D_filter(cameras) again")
+        return self.filter_3D
+
+    @property
+    def get_scaling_with_3D_filter(self):
+        """sqrt(s^2 + f^2) of the activated scales, for inspection (torch ops; render() uses filter3d.apply)"""
+        s = self.get_scaling
+        return s if self.filter_3D is None else torch.sqrt(s * s + (self.filter_3D * self.filter_3D)[:, None])
+
+    @property
+    def get_opacity_with_3D_filter(self):
+        """o x sqrt(prod_k s_k^2 / (s_k^2 + f^2)), for inspection (torch ops; render() uses filter3d.apply)"""
+        o = self.get_opacity
+        if self.filter_3D is None:
+            return o
+        s2, f2 = self.get_scaling ** 2, (self.filter_3D * self.filter_3D)[:, None]
+        r = torch.where(f2 == 0, torch.ones_like(s2), s2 / (s2 + f2))
+        return o * torch.sqrt(r[:, 0] * r[:, 1] * r[:, 2])[:, None]
+
     # ---- what compress_gaussians needs (gaussian_model.py:1027-1059)
     def mask_splats(self, mask):
         with torch.no_grad():
+            self._carry_3D_filter(mask)
             keep = lambda t: None if t is None else t.detach()[mask].contiguous().requires_grad_(t.requires_grad)
             self._xyz, self._opacity, self._scaling_factor = keep(self._xyz), keep(self._opacity), keep(self._scaling_factor)
             if self.is_color_indexed:
@@ -471,6 +539,7 @@ class GaussianModel:
         from . import encode
         with torch.no_grad():
             order = encode.morton_order(self._xyz.detach())
+            self._carry_3D_filter(order)
             take = lambda t: None if t is None else t.detach()[order].contiguous().requires_grad_(t.requires_grad)
             self._xyz, self._opacity, self._scaling_factor = take(self._xyz), take(self._opacity), take(self._scaling_factor)
             if self.is_color_indexed:
@@ -540,6 +609,9 @@ class GaussianModel:
                      "feature_indices", "gaussian_indices", "scaling", "scaling_scale", "scaling_zero_point",
                      "scaling_factor", "scaling_factor_scale", "scaling_factor_zero_point", "rotation", "rotation_scale",
                      "rotation_zero_point"]
+            if self.filter_3D is not None:                      # behind the reference's keys: its loader never asks for it
+                d["filter_3D"] = host(self.filter_3D.to(dtype))
+                order.append("filter_3D")
             (np.savez_compressed if compress else np.savez)(path, **{k: d[k] for k in order if k in d})
 
     def load_npz(self, path, override_quantization=False):
@@ -584,6 +656,8 @@ class GaussianModel:
         self._gaussian_indices = torch.from_numpy(sd["gaussian_indices"]).long().to(dev) if "gaussian_indices" in sd else None
         self.color_index_mode = ColorMode.ALL_INDEXED if self._feature_indices is not None else ColorMode.NOT_INDEXED
         self.active_sh_degree = self.max_sh_degree
+        self.filter_3D = torch.from_numpy(sd["filter_3D"]).to(dev, torch.float32).contiguous() if "filter_3D" in sd else None
+        self._filter_3D_stale = False
         return self
 
     # ---- PLY files (gaussian_model.py:324-387 save_ply, :389-396 load, :398-503 load_ply)
@@ -596,9 +670,12 @@ class GaussianModel:
         names += [f"rot_{i}" for i in range(self._rotation.shape[1])]
         return names
 
-    def save_ply(self, path):
+    def save_ply(self, path, fuse_filter=False):
         """The standard 3DGS PLY every viewer reads: dense per-Gaussian attributes (an indexed model is expanded),
-        raw opacity, log of the activated scale (scale factor folded in), activated rotation, zero normals."""
+        raw opacity, log of the activated scale (scale factor folded in), activated rotation, zero normals.
+        A model with a 3D filter appends it as the property `filter_3D`, which load_ply restores; with fuse_filter=True the
+        filter is baked in instead (scale sqrt(s^2 + f^2), opacity logit(o coef)): a standard PLY for viewers that know nothing of
+        the filter, which renders like the filtered model when the rotations are unit quaternions."""
         import os
         import numpy as np
         from . import ply
@@ -613,8 +690,16 @@ class GaussianModel:
             opacities = self._opacity.detach().cpu().numpy()
             scale = torch.log(self.get_scaling.detach()).cpu().numpy()   # scaling_factor_inverse / scaling_inverse = log
             rotation = self.get_rotation.detach().cpu().numpy()
-        attributes = np.concatenate((xyz, np.zeros_like(xyz), f_dc, f_rest, opacities, scale, rotation), axis=1)
-        ply.write_ply(path, {name: attributes[:, k] for k, name in enumerate(self._ply_attributes())})
+            names = self._ply_attributes()
+            extra = ()
+            if self.filter_3D is not None and fuse_filter:
+                o = self.get_opacity_with_3D_filter.detach().double()
+                opacities = torch.log(o / (1 - o)).float().cpu().numpy()
+                scale = torch.log(self.get_scaling_with_3D_filter.detach()).cpu().numpy()
+            elif self.filter_3D is not None:
+                names, extra = names + ["filter_3D"], (self.filter_3D[:, None].cpu().numpy(),)
+        attributes = np.concatenate((xyz, np.zeros_like(xyz), f_dc, f_rest, opacities, scale, rotation) + extra, axis=1)
+        ply.write_ply(path, {name: attributes[:, k] for k, name in enumerate(names)})
 
     def load(self, path, override_quantization=False):
         import os
@@ -697,6 +782,8 @@ class GaussianModel:
         self._feature_indices = self._gaussian_indices = None
         self.color_index_mode = ColorMode.NOT_INDEXED
         self.max_radii2D = torch.zeros(n, device=dev)
+        self.filter_3D = torch.tensor(v["filter_3D"], dtype=torch.float, device=dev).contiguous() if "filter_3D" in keys else None
+        self._filter_3D_stale = False
         return self
 
     # ---- optimizer plumbing of the fine-tuning loop (gaussian_model.py:292-322)
@@ -885,6 +972,11 @@ class GaussianModel:
         if new_xyz is not None:
             new_xyz(tab.new["_xyz"])
         self._install(tab.new, tab.moments)
+        # carry_stats is prune_points: every new row is an original (the 3D filter follows); anything else creates rows
+        if carry_stats:
+            self._carry_3D_filter(src)
+        else:
+            self._drop_3D_filter()
         if stats_new is not None:
             self.xyz_gradient_accum, self.denom, self.max_radii2D = stats_new
         else:                                                 # densification_postfix, :1209-1211
@@ -1014,6 +1106,7 @@ class GaussianModel:
                 draws = torch.rand(n, dtype=torch.float64, device=self.device)
             sources = mcmc.draw(w, draws, n)
             mcmc.apply(P, n, rows, 0, sources, w.counts, self._mcmc_table(), True, min_opacity, w.ws, self.device)
+            self._drop_3D_filter()                                  # the relocated rows are new Gaussians
             return n
 
     def add_new_gs(self, cap_max, draws=None, min_opacity=0.005):
@@ -1256,6 +1349,7 @@ class GaussianModel:
                     new.update(n)
                     moments.update(m)
             self._install(new, moments)
+            self._carry_3D_filter(src)
             self.xyz_gradient_accum, self.denom, self.max_radii2D = stats
             if fi is not None:
                 self._feature_indices = new0
@@ -1338,7 +1432,13 @@ class GaussianModel:
         antialiasing: None (the default) reads `pipe.antialiasing`; True multiplies every opacity by the compensation factor of the
         rasterizer's 0.3 px^2 low-pass (GaussianRasterizationSettings(antialiasing=True), csrc/aa_opacity.hip), on the fused indexed
         and the composed path alike, with gradients to the model's parameters. As with depth_grad, the pose receives no gradient
-        and a camera pose that requires grad raises ValueError."""
+        and a camera pose that requires grad raises ValueError.
+        With a 3D filter (compute_3D_filter) both paths draw every Gaussian with Sigma + (scaling_modifier f)^2 I and the opacity
+        o sqrt(prod_k s_k^2 / (s_k^2 + f^2)) (filter3d.apply in front of the rasterizer, which takes them as cov3D_precomp and
+        opacities), with gradients to the model's parameters; every option above sees those. A caller's `cov3d=` becomes
+        cov3d + (scaling_modifier f)^2 I and keeps its gradient, the opacity factor then takes the model's scales as constants.
+        pipe.compute_cov3D_python then raises NotImplementedError, a pose that requires grad ValueError, and a filter that rows
+        were added behind RuntimeError until compute_3D_filter has run again."""
         if antialiasing is None:
             antialiasing = getattr(pipe, "antialiasing", False)
         if depth_grad and viewpoint_camera.extrinsic_vector.requires_grad:
@@ -1349,6 +1449,7 @@ class GaussianModel:
             raise NotImplementedError("convert_SHs_python: SH evaluation in Python is outside the mirrored render path")
         if pose_grad not in ("reference", "exact"):
             raise ValueError(f'pose_grad must be "reference" or "exact", not {pose_grad!r}')
+        filter_3D = self._checked_3D_filter(pipe, cov3d, viewpoint_camera)
         dev = self.device
         settings = GaussianRasterizationSettings(
             intrinsic=viewpoint_camera.intrinsic.to(dev), extrinsic_vector=viewpoint_camera.extrinsic_vector.to(dev),
@@ -1360,9 +1461,9 @@ class GaussianModel:
             not pipe.compute_cov3D_python
         screenspace_points = torch.zeros(self._xyz.shape, dtype=torch.float32, device=dev, requires_grad=True)
         if fused:
-            return self._render_indexed_fused(settings, screenspace_points, pose_grad)
+            return self._render_indexed_fused(settings, screenspace_points, pose_grad, filter_3D)
         return self._render_composed(settings, screenspace_points, indexed, pipe, scaling_modifier, override_color, cov3d,
-                                     gather_visible, pose_grad)
+                                     gather_visible, pose_grad, filter_3D)
 
     def _visible(self, settings):
         """visible flags, their exclusive scan and a deferred host read of the count."""
@@ -1393,11 +1494,22 @@ class GaussianModel:
             return int(self._count_host[0])
         return visible, rank, read
 
-    def _render_indexed_fused(self, settings, screenspace_points, pose_grad="reference"):
+    def _render_indexed_fused(self, settings, screenspace_points, pose_grad="reference", filter_3D=None):
         visible, rank, read = self._visible(settings)
         (means3D, means2D, opac, sfac, scales_n, rotations, shs, sh_idx, g_idx) = _QatGetters.apply(
             self, (visible, rank, read), self._feature_indices, self._gaussian_indices, self._xyz, screenspace_points,
             self._opacity, self._scaling_factor, self._scaling, self._rotation, self._features_dc, self._features_rest)
+        if filter_3D is not None:
+            # the getters hand out the visible subset; the kernel reads the filter's rows through the same visible / rank tables.
+            # The rasterizer then runs on (cov3D_precomp, opacities) = (Sigma', o'), without a pose gradient (render() has refused one)
+            from . import filter3d
+            cov3D, opac = filter3d.apply(opac, scales_n, rotations, filter_3D, settings.scale_modifier, scale_factors=sfac,
+                                         g_indices=g_idx, visible=visible, rank=rank)
+            image, radii, *extras = _rz.rasterize_gaussians_indexed(means3D, means2D, shs, sh_idx, g_idx, _rz._empty(), opac,
+                                                                    _rz._empty(), _rz._empty(), _rz._empty(), cov3D, settings,
+                                                                    settings.extrinsic_vector)
+            return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
+                    "visible": visible.bool(), **self._extra_keys(settings, extras, rank)}
         # what GaussianRasterizerIndexed(settings, optimize_camera=True)(...) calls, without building an nn.Module per view
         # (the host has ~0.2 ms of Python between the visible count's arrival and the rasterizer's first launch, and the GPU
         # idles for the part of it the getter kernels do not cover)
@@ -1522,7 +1634,7 @@ class GaussianModel:
         return n
 
     def _render_composed(self, settings, screenspace_points, indexed, pipe, scaling_modifier, override_color, cov3d,
-                         gather_visible=True, pose_grad="reference"):
+                         gather_visible=True, pose_grad="reference", filter_3D=None):
         """Every other configuration of render(): the same getters, composed with torch gathers like the reference.
         gather_visible=False (the sensitivity pass) hands all rows to the rasterizer instead of the reference's `t[visible]`
         copies: the rasterizer culls the same Gaussians itself (mark_visible is its own frustum test), so image and gradients
@@ -1530,7 +1642,7 @@ class GaussianModel:
         means3D = self.get_xyz
         opacity = self.get_opacity
         exact = pose_grad == "exact"
-        if settings.depth_grad or settings.antialiasing:   # no pose gradient in these modes (render() has refused a pose that wants one)
+        if settings.depth_grad or settings.antialiasing or filter_3D is not None:   # no pose gradient in these modes (render() has refused a pose that wants one)
             rasterizer = (GaussianRasterizerIndexed if indexed else GaussianRasterizer)(raster_settings=settings, optimize_camera=False)
         else:
             rasterizer = GaussianRasterizerIndexed(raster_settings=settings, optimize_camera="exact" if exact else True) if indexed \
@@ -1544,6 +1656,21 @@ class GaussianModel:
                 scales = self.get_scaling_normalized if indexed else self.get_scaling
                 rotations = self._rotation_post_activation if indexed else self.get_rotation
         scale_factors = self.get_scaling_factor if indexed else None
+        if filter_3D is not None:
+            # all P rows in one launch, in front of the gathers: the rasterizer takes (cov3D_precomp, opacities) = (Sigma', o')
+            from . import filter3d
+            if indexed and not torch.is_tensor(scale_factors):
+                scale_factors = torch.ones_like(opacity)
+            given = cov3D_precomp
+            if given is not None:
+                # a caller's covariance (train()'s frozen one, the sensitivity pass's leaf): Sigma' = cov3d + f^2 I with the
+                # gradient to cov3d untouched; the opacity factor takes the model's own scales, as constants like the covariance
+                scales = (self.get_scaling_normalized if indexed else self.get_scaling).detach()
+                scale_factors = scale_factors.detach() if indexed else None
+            cov3D_precomp, opacity = filter3d.apply(opacity, scales, rotations, filter_3D, scaling_modifier,
+                                                    scale_factors=scale_factors if indexed else None,
+                                                    g_indices=self._gaussian_indices if indexed else None, cov3d=given)
+            scales = rotations = scale_factors = None
         shs = colors_precomp = None
         if override_color is None:
             shs = self._get_features_raw if indexed else self.get_features

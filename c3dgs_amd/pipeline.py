@@ -203,6 +203,8 @@ def _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, 
                 if prune_min_views > 0:
                     stats = gaussians.contribution_stats(_train_cameras(scene), pipe, background)
                     gaussians.prune_by_contribution(stats, min_views=prune_min_views)
+                if gaussians.filter_3D is not None:                  # the survivors carry their values; a pruned scene is re-measured
+                    gaussians.compute_3D_filter(_train_cameras(scene))
                 if log is not None:
                     log(iteration, ema_loss_for_log)
     return ema_loss_for_log
@@ -211,7 +213,7 @@ def _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, 
 def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, degree_up_iter=1000, *, densify_by="grad",
           error_threshold=None, optimizer_type=None, optimizer_visibility="radii", lambda_depth=0.0, lambda_alpha=0.0,
           strategy="default", cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01, min_opacity=0.005,
-          bilagrid=None, bilagrid_lr=2e-3, bilagrid_tv=10.0):
+          bilagrid=None, bilagrid_lr=2e-3, bilagrid_tv=10.0, filter_3d=False, filter_3d_interval=100):
     """train.py:15-173 without its disabled compression-statistics branch: optimise a non-indexed model (usually
     GaussianModel.load_ply of a point cloud) with adaptive density control.
 
@@ -274,7 +276,17 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     they stay out of the model's optimizer, so densification and MCMC never see their moments. The defaults (2e-3, 10.0) are
     gsplat's, quoted from memory; nobody has tuned them here. densify_by="error" with a grid raises ValueError: the error map
     inside render() would compare the uncorrected image. Every epoch's `info` also carries "epoch_loss", the mean of the epoch's
-    losses (the values the moving average is fed)."""
+    losses (the values the moving average is fed).
+
+    `filter_3d` (not in the reference: the 3D smoothing filter of Mip-Splatting; csrc/filter3d.hip) = False is the loop above,
+    launch for launch. True trains with GaussianModel.compute_3D_filter over ALL training cameras (whatever `camera_stride`
+    visits): computed before the first iteration, again in front of every iteration that is a positive multiple of
+    `filter_3d_interval`, and after every step that changed rows (densify_and_prune by gradient or by error, MCMC relocation or
+    growth). The camera table is built once per call (the one place that reads the poses on the host); the recomputes are
+    stream-ordered. The loop itself is unchanged: the default strategy still hands render() its frozen covariance, which the
+    filtered render takes as cov3d + f^2 I. The model keeps the filter when train() returns."""
+    if filter_3d and int(filter_3d_interval) < 1:
+        raise ValueError("train: filter_3d_interval must be a positive number of iterations")
     if bilagrid is not None and densify_by == "error":
         raise ValueError("train: densify_by='error' compares the uncorrected render inside render(); it cannot be combined with bilagrid")
     if strategy not in ("default", "mcmc"):
@@ -322,10 +334,16 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     degree_up = calc_epoch(degree_up_iter)
 
     iteration = 0
+    if filter_3d:
+        from . import filter3d as _filter3d
+        camera_table = _filter3d.camera_table(cameras, gaussians.device)
+        gaussians.compute_3D_filter(cameras, camera_table)
     for epoch in range(epoch_count):
         pending = []
         for viewpoint_cam in cameras[::camera_stride]:
             gaussians.update_learning_rate(iteration)
+            if filter_3d and iteration > 0 and iteration % int(filter_3d_interval) == 0:
+                gaussians.compute_3D_filter(cameras, camera_table)
             if not mcmc:
                 cov3d_scaled = gaussians.get_covariance().detach()
                 scaling_factor = gaussians.get_scaling_factor
@@ -406,6 +424,8 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
                 if epoch > 0 and epoch % opacity_reset_interval == 0:
                     gaussians.reset_opacity()
                     info["reset_opacity"] = True
+        if filter_3d and gaussians._filter_3D_stale:                 # rows were created: their filter values are measured now
+            gaussians.compute_3D_filter(cameras, camera_table)
         if epoch % degree_up == 0:
             gaussians.oneupSHdegree()
         info["N"] = gaussians._xyz.shape[0]
@@ -434,6 +454,8 @@ def refine_poses(scene_or_cameras, gaussians, pipe, background, iterations, lr=1
         cams = [cams[i] for i in cameras]
     if not cams:
         return []
+    if gaussians.filter_3D is not None or gaussians._filter_3D_stale:
+        raise ValueError("refine_poses: the render with a 3D filter has no pose gradient; clear_3D_filter() first")
     dev = gaussians.device
     params = gaussians.parameters()
     was = [t.requires_grad for t in params]

@@ -305,6 +305,55 @@ int c3dgs_aa_opacity(const c3dgs_raster_params* p, float* opacity_out /*[P]*/, f
 int c3dgs_aa_opacity_backward(const c3dgs_raster_params* p, const int32_t* radii /*[P]*/, const c3dgs_raster_grads* grads,
                               void* stream);
 
+/* ---- the 3D smoothing filter of Mip-Splatting (csrc/filter3d.hip; no reference counterpart) ----
+ * c3dgs_filter3d_compute: filter_3D [P] and, when not NULL, seen [P] over the camera table `cameras` [C, 16] (device memory; per
+ * camera the rows 0..2 of the world -> camera matrix, row-major, then fx, fy, W, H). In fp32, each operation rounded on its own
+ * in this order:  x = ((m0 px + m1 py) + m2 pz) + m3 (y, z likewise), u = (x / z) fx + W 0.5, v = (y / z) fy + H 0.5,
+ * valid = z > 0.2 and -0.15 W <= u <= 1.15 W and -0.15 H <= v <= 1.15 H; dist = min over the valid cameras of z, for a Gaussian
+ * no camera sees the maximum of dist over the seen ones (0 when none is seen); filter_3D = (dist / max over all cameras of fx)
+ * float(sqrt(0.2)). Three stream operations (an 8-byte clear of the workspace and two kernels), no host read, no float atomics:
+ * bitwise reproducible. `workspace`: c3dgs_filter3d_workspace_bytes(P) bytes, 8-byte aligned.
+ * c3dgs_filter3d_apply: for the n rows of `r` (opacities [n], and either scales [n,3] + rotations [n,4] or, with g_indices [n],
+ * codebooks addressed by it and scale_factors [n]), with f the row's filter value, sf its scale factor (1 without g_indices):
+ *   cov3D_out = cov3D(scales, sf x scale_modifier, rotation) + (scale_modifier f)^2 on elements 0, 3, 5,
+ *   s_k = sf scale_k, r_k = s_k^2 / (s_k^2 + f^2), opacity_out = opacity sqrt((r_0 r_1) r_2);
+ * a row with f == 0 gets the plain covariance and its opacity bit for bit. Without `visible`, f = filter_3D[row] (filter_3D has n
+ * rows). With `visible` [P_model] (bytes) and `rank` [P_model] (int32), the rows are the visible subset of a model: the kernel runs
+ * one lane per model row i, and row rank[i] takes f = filter_3D[i] (filter_3D has P_model rows) where visible[i]; a rank outside
+ * [0, n) is skipped. With cov3D_precomp [n,6], cov3D_out = cov3D_precomp + (scale_modifier f)^2 on elements 0, 3, 5: the scales
+ * serve the opacity factor alone, rotations may be NULL, and the gradient of cov3D_precomp is dL_dcov3D itself (the backward
+ * ignores g->dL_dcov3D and chains dL_dopacity_out only).
+ * rotations and g->dL_drotations are read and written four floats at a time: both must be 16-byte aligned.
+ * c3dgs_filter3d_apply_backward: from g->dL_dcov3D [n,6] (the gradient of cov3D_out) and g->dL_dopacity_out [n] (either may be
+ * NULL = zeros), for the rows where one of them is non-zero -- the other rows of the outputs are NOT written, the caller hands in
+ * zeros --: dL_dopacity = coef x dL_dopacity_out; the covariance gradient chained to scales, rotations and scale factors as the
+ * rasterizer's backward chains it (exact in scale_modifier), plus the terms through coef,
+ * dL/ds_k += opacity dL_dopacity_out coef f^2 / (s_k (s_k^2 + f^2)) unless s_k == 0 or f == 0. fp32 throughout. Row-sized outputs
+ * are plain stores; with g_indices, dL_dscales [GS,3] and dL_drotations [GS,4] are ADDED with fp32 atomics (not reproducible run
+ * to run) and dL_dscale_factors [n] is stored. NULL outputs are skipped.
+ * C3DGS_E_INVALID before any device work: P or n < 0; C <= 0; for P > 0 a NULL xyz, cameras, filter_3D or workspace, or a workspace
+ * that is too small or misaligned; r or g NULL; for n > 0 a NULL opacities, scales, filter_3D or (without cov3D_precomp)
+ * rotations, a rotations or dL_drotations pointer that is not 16-byte aligned, g_indices without scale_factors, visible without rank or with P_model < 0, a NULL cov3D_out or opacity_out, or every output of the backward NULL.
+ * P == 0 / n == 0 launch nothing. Stage names: "filter3d_compute", "filter3d_apply", "filter3d_apply_backward". */
+typedef struct c3dgs_filter3d_rows {
+    int32_t n, P_model;
+    const float* opacities; const float* scales; const float* rotations; const float* scale_factors;
+    const int64_t* g_indices;
+    const float* cov3D_precomp;   /* [n,6] | NULL: the caller's covariance in place of the one scales and rotations build */
+    const float* filter_3D; const uint8_t* visible; const int32_t* rank;
+    float scale_modifier;
+} c3dgs_filter3d_rows;
+typedef struct c3dgs_filter3d_grads {
+    const float* dL_dcov3D; const float* dL_dopacity_out;
+    float* dL_dopacity; float* dL_dscales; float* dL_drotations; float* dL_dscale_factors;
+} c3dgs_filter3d_grads;
+size_t c3dgs_filter3d_workspace_bytes(int32_t P);
+int c3dgs_filter3d_compute(int32_t P, int32_t C, const float* xyz /*[P,3]*/, const float* cameras /*[C,16]*/,
+                           float* filter_3D /*[P]*/, uint8_t* seen /*[P] | NULL*/, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int c3dgs_filter3d_apply(const c3dgs_filter3d_rows* r, float* cov3D_out /*[n,6]*/, float* opacity_out /*[n]*/, void* stream);
+int c3dgs_filter3d_apply_backward(const c3dgs_filter3d_rows* r, const c3dgs_filter3d_grads* g, void* stream);
+
 /* ---- weighted_distance._C.weightedDistance (weighted_distance.cu:46-93) ----
  * coefs [N,K], codebook [C,K] row-major fp32 -> min squared distance [N] and argmin [N] (int64).
  * Exact reference semantics: fp32 k-ordered FMA chain, strict '<' (lowest index wins ties).

@@ -5,7 +5,7 @@ before / after, and seconds per phase.
 
     python tools/run_train.py [--iterations 400] [--out profiles/r06_train_synth.json]
                               [--densify-by grad|error] [--error-threshold T] [--optimizer default|sparse_adam]
-                              [--lambda-depth X] [--lambda-alpha Y] [--antialiasing]
+                              [--lambda-depth X] [--lambda-alpha Y] [--antialiasing] [--filter-3d [--filter-3d-interval N]]
                               [--strategy default|mcmc] [--cap-max N] [--noise-lr X]
                               [--bilagrid L HG WG | --exposure] [--bilagrid-lr X] [--bilagrid-tv Y] [--exposure-jitter S]
 
@@ -32,7 +32,11 @@ only, replaces every training image by a_k * image + b_k with per-camera, per-ch
 density control, in place of the two default runs; the JSON carries "bilagrid" (the shape or null), "exposure_jitter" and under
 "run" the run: "final_loss" (the mean loss over the last epoch, which every run reports), "psnr_after" as always (the RAW render against the
 training images as they were trained on, jittered or not) and, here only, "psnr_vs_clean_images" (the raw render against the
-teacher's own images; it carries a global gain ambiguity that only a colour-corrected metric would remove)."""
+teacher's own images; it carries a global gain ambiguity that only a colour-corrected metric would remove).
+--filter-3d [--filter-3d-interval N] makes the run without density control four times -- plain, PipelineParams(antialiasing=True),
+pipeline.train(filter_3d=True, filter_3d_interval=N) (the 3D smoothing filter, csrc/filter3d.hip) and both -- and scores each
+trained student at 0.5x, 1x and 2x as --antialiasing does (the student keeps its filter for the evaluation). One run each,
+nothing tuned; the JSON carries "filter_3d" in place of the two default runs."""
 import argparse
 import json
 import os
@@ -95,7 +99,7 @@ def resolution_eval(student, cams, pipe):
 
 
 def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer="default", lambda_depth=0.0, lambda_alpha=0.0,
-        with_maps=False, antialiasing=None, mcmc=None, bilagrid=None, jitter=0.0):
+        with_maps=False, antialiasing=None, mcmc=None, bilagrid=None, jitter=0.0, filter_3d=None):
     from c3dgs_amd import pipeline
     from c3dgs_amd.model import PipelineParams
     with tempfile.TemporaryDirectory() as tmp:
@@ -103,7 +107,7 @@ def run(iterations, densify, densify_by="grad", error_threshold=None, optimizer=
         student, cams, extent = train_scene.make(tmp)
         torch.cuda.synchronize()
         t_setup = time.perf_counter() - t0
-    extra = dict(bilagrid or {})
+    extra = dict(bilagrid or {}, **(filter_3d or {}))
     clean = [cam.original_image.clone() for cam in cams]
     if jitter:
         from tests import bilagrid_ref
@@ -173,6 +177,8 @@ def main():
     ap.add_argument("--bilagrid-lr", type=float, default=2e-3)
     ap.add_argument("--bilagrid-tv", type=float, default=10.0)
     ap.add_argument("--exposure-jitter", type=float, default=0.0)
+    ap.add_argument("--filter-3d", action="store_true")
+    ap.add_argument("--filter-3d-interval", type=int, default=100)
     args = ap.parse_args()
     if args.exposure and args.bilagrid is not None:
         ap.error("--exposure is --bilagrid 1 1 1; give one of the two")
@@ -183,9 +189,20 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("run_train.py needs the GPU; there is no CPU path")
     out = {"scene": "tests/train_scene.py: 4000-Gaussian synth-v1 teacher, 8 views 160x112, student = every 8th position as a point cloud"}
-    if args.antialiasing:
+    if args.antialiasing and not args.filter_3d:
         out["antialiasing"] = {"off": run(args.iterations, False, optimizer=args.optimizer, antialiasing=False),
                                "on": run(args.iterations, False, optimizer=args.optimizer, antialiasing=True)}
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
+    if args.filter_3d:
+        f3 = dict(filter_3d=True, filter_3d_interval=args.filter_3d_interval)
+        out["filter_3d_interval"] = args.filter_3d_interval
+        out["filter_3d"] = {name: run(args.iterations, False, optimizer=args.optimizer, antialiasing=aa, filter_3d=f)
+                            for name, aa, f in (("plain", False, None), ("antialiasing", True, None), ("filter_3d", False, f3),
+                                                ("antialiasing_and_filter_3d", True, f3))}
         print(json.dumps(out))
         if args.out:
             with open(args.out, "w") as f:
