@@ -39,12 +39,15 @@ SOURCES = {
     "render_error.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # MFMA accumulators in VGPRs (no v_accvgpr_read per value in the top-2 update of the search kernel)
     "vq.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"] + os.environ.get("C3DGS_VQ_FLAGS", "").split(),
-    # the exact pose gradient rebuilds Sigma and the SH direction term with preprocess's / backward_preprocess's expressions (csrc/gsmath.hpp)
+    # the exact pose gradient rebuilds Sigma as preprocess does (csrc/gsmath.hpp) and the SH direction term with the function
+    # backward_preprocess calls (csrc/gsgrad.hpp)
     "pose_grad.hip": ["-ffp-contract=off"],
-    # the opacity compensation of the antialiased mode forms the 2D covariance with preprocess's expressions (csrc/gsmath.hpp)
+    # the opacity compensation of the antialiased mode forms the 2D covariance with preprocess's expressions (csrc/gsmath.hpp) and
+    # chains its gradient with the functions of csrc/gsgrad.hpp
     "aa_opacity.hip": ["-ffp-contract=off"],
     # the 3D smoothing filter: its projections are single fp32 operations a NumPy restatement repeats bit for bit, and its
-    # covariance is preprocess's (csrc/gsmath.hpp)
+    # covariance is preprocess's (csrc/gsmath.hpp); its backward is the covariance chain of csrc/gsgrad.hpp, which must round as
+    # backward_preprocess's does (tests/test_gsgrad_gpu.py)
     "filter3d.hip": ["-ffp-contract=off"],
     "draws.hip": [],
     "loss.hip": [],
@@ -63,7 +66,8 @@ SOURCES = {
     "ray_fill.hip": ["-ffp-contract=off"],  # x * (1 - a) + a * y of the new positions is four separately rounded operations
     "image_io.hip": ["-ffp-contract=off"],  # t0 * (1 - f) + t1 * f of the bilinear taps is separately rounded (csrc/image_io.hip)
 }
-HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), os.path.join(CSRC, "render_diag.hpp"),
+HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), os.path.join(CSRC, "gsgrad.hpp"),
+           os.path.join(CSRC, "render_diag.hpp"),
            os.path.join(CSRC, "render_common.hpp"), os.path.join(CSRC, "replay.hpp"), os.path.join(CSRC, "scan_blocks.hpp"), os.path.join(CSRC, "adam_common.hpp"), os.path.join(CSRC, "mcmc.hpp"), os.path.join(CSRC, "jobs.hpp"),
            os.path.join(CSRC, "bilagrid.hpp"),
            os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h")]

@@ -8,8 +8,9 @@
 //   aa_opacity_kernel           (one lane per Gaussian, all P, no LDS): o'[P] and, when asked, rho[P];
 //   aa_opacity_backward_kernel  (one lane per Gaussian, working where radii > 0 and g' != 0, behind the whole backward on its stream): rewrites
 //       dL_dopacity = rho g' in place and ADDS the terms through rho (dL/drho = o g') to dL_dmeans3D, dL_dcov3D, dL_dscales,
-//       dL_drotations, dL_dscale_factors with backward_preprocess.hip's chain from (dL/da, dL/db, dL/dc) on (T, J, the clamped
-//       t.x, t.y held constant). It recomputes the covariance; nothing but the opacity gradient comes from the forward.
+//       dL_drotations, dL_dscale_factors with gsgrad.hpp's chain from (dL/da, dL/db, dL/dc): conic_grad_to_cov3d,
+//       conic_grad_to_mean, cov3d_grad_to_scale_rot, in double (backward_preprocess.hip restates the three in fp32).
+//       It recomputes the covariance; nothing but the opacity gradient comes from the forward.
 // rho is finite for every row: a row preprocess.hip's near-plane test culls, one with D1 == 0 and one with a non-finite D0, D1
 // or r get rho = 1 and no gradient through rho; r <= 0.000025 gets the floor and no gradient through rho either.
 // rho itself and every decision are fp32, the forward's own operations in the forward's order (this file is compiled with
@@ -18,10 +19,9 @@
 // fp32 the scale gradient of a needle scene came out 3e-3 from the float64 derivative, in double at fp32 rounding of the sum.
 // The kernel stays bound by its scattered rows: ~300 double operations per visible Gaussian.
 // Everything P-sized is a plain read-modify-write (one lane owns one row). The codebook-sized outputs of the indexed form are
-// scatter-ADDED the way backward_preprocess.hip does it: factors parked in LDS, then the wave walks its 64 Gaussians so that
-// adjacent lanes of one atomic instruction cover whole codebook rows (MI355X_MICROARCH.md, Global float atomics).
+// scatter-ADDED by gsgrad.hpp's scatter_add_scale_rot(), as backward_preprocess.hip's are.
 #include "common.hpp"
-#include "gsmath.hpp"
+#include "gsgrad.hpp"
 
 namespace c3dgs {
 
@@ -43,8 +43,7 @@ struct AaRow {
     bool live;                 // rho = sqrt(r) with r above the floor: the only rows with a gradient through rho
     bool clamp_x, clamp_y;     // t.x / t.y was clamped at 1.3 tan_fov: no gradient through that coordinate
     f3 m;
-    float sc[3]; float4 rot; float sf; size_t gi;      // scale / rotation form: the row, its codebook index, its scale factor (or 1)
-    float cov3D[6];
+    ScaleRotRow g;             // scales, rotation, codebook row, scale factor (or their neutral values) and Sigma
 };
 
 // rho of Gaussian i, and the inputs the backward chains through
@@ -53,21 +52,10 @@ __device__ __forceinline__ void aa_row(const AaArgs& a, const int i, const float
     const size_t si = (size_t)i;
     w.rho = 1.f; w.live = false; w.clamp_x = w.clamp_y = false;
     w.m = { a.means3D[3 * si], a.means3D[3 * si + 1], a.means3D[3 * si + 2] };
-    w.gi = si; w.sf = 1.f;
-    w.sc[0] = w.sc[1] = w.sc[2] = 0.f; w.rot = make_float4(1, 0, 0, 0);
-    if (a.cov3D_precomp) {
-#pragma unroll
-        for (int q = 0; q < 6; q++) w.cov3D[q] = a.cov3D_precomp[6 * si + q];
-    } else {
-        float mod = a.scale_modifier;
-        if (a.g_indices) { w.gi = (size_t)a.g_indices[i]; w.sf = a.scale_factors[i]; mod = w.sf * a.scale_modifier; }
-        w.sc[0] = a.scales[3 * w.gi]; w.sc[1] = a.scales[3 * w.gi + 1]; w.sc[2] = a.scales[3 * w.gi + 2];
-        w.rot = *reinterpret_cast<const float4*>(a.rotations + 4 * w.gi);
-        cov3d_from_scale_rot(w.sc[0], w.sc[1], w.sc[2], mod, w.rot, w.cov3D);
-    }
+    load_scale_rot_row(a.cov3D_precomp, a.scales, a.rotations, a.scale_factors, a.g_indices, si, a.scale_modifier, w.g);
     const f3 p_view = xform4x3(w.m, view);
     if (!a.prefiltered && p_view.z <= 0.01f) return;               // preprocess.hip's near-plane test
-    const Cov2D cv = cov2d_raw(w.m, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, w.cov3D, view);
+    const Cov2D cv = cov2d_raw(w.m, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, w.g.cov3D, view);
     const float limx = 1.3f * a.tan_fovx, limy = 1.3f * a.tan_fovy;
     w.clamp_x = cv.txtz < -limx || cv.txtz > limx;
     w.clamp_y = cv.tytz < -limy || cv.tytz > limy;
@@ -99,36 +87,35 @@ __device__ __forceinline__ bool aa_chain(const AaArgs& a, const AaRow& w, const 
                                          const bool scale_rot, AaChain& c)
 {
     const double h = (double)AA_H;
-    double v[12];                                                  // view[4 k + j], k = 0..2: rotation rows of world -> camera
+    double v[3][3];                                                // view[4 k + j]: the rotation of world -> camera, column major
 #pragma unroll
     for (int k = 0; k < 3; k++)
 #pragma unroll
-        for (int j = 0; j < 3; j++) v[3 * k + j] = (double)view[4 * k + j];
+        for (int j = 0; j < 3; j++) v[k][j] = (double)view[4 * k + j];
     const double mx = w.m.x, my = w.m.y, mz = w.m.z;
-    const double t0 = v[0] * mx + v[3] * my + v[6] * mz + (double)view[12];
-    const double t1 = v[1] * mx + v[4] * my + v[7] * mz + (double)view[13];
-    const double tz = v[2] * mx + v[5] * my + v[8] * mz + (double)view[14];
+    const double t0 = v[0][0] * mx + v[1][0] * my + v[2][0] * mz + (double)view[12];
+    const double t1 = v[0][1] * mx + v[1][1] * my + v[2][1] * mz + (double)view[13];
+    const double tz = v[0][2] * mx + v[1][2] * my + v[2][2] * mz + (double)view[14];
     const double fx = (double)a.W / (2.0 * (double)a.tan_fovx), fy = (double)a.H / (2.0 * (double)a.tan_fovy);
     const double limx = (double)1.3f * (double)a.tan_fovx, limy = (double)1.3f * (double)a.tan_fovy;
     const double tx = w.clamp_x ? (t0 < 0 ? -limx : limx) * tz : t0;
     const double ty = w.clamp_y ? (t1 < 0 ? -limy : limy) * tz : t1;
-    const double iz = 1.0 / tz, iz2 = iz * iz, iz3 = iz2 * iz;
+    const double iz = 1.0 / tz, iz2 = iz * iz;
     const double J[2][3] = { { fx * iz, 0.0, -fx * tx * iz2 }, { 0.0, fy * iz, -fy * ty * iz2 } };
     double A[2][3];                                                // upper 2x3 of J * R_w2c
 #pragma unroll
     for (int q = 0; q < 2; q++)
 #pragma unroll
-        for (int k = 0; k < 3; k++) A[q][k] = J[q][0] * v[3 * k] + J[q][1] * v[3 * k + 1] + J[q][2] * v[3 * k + 2];
+        for (int k = 0; k < 3; k++) A[q][k] = J[q][0] * v[k][0] + J[q][1] * v[k][1] + J[q][2] * v[k][2];
 
     // Sigma, and for the scale / rotation form L = Rm diag(s) with Sigma = L L^T
-    double Sg[3][3], Rm[3][3] = { { 1, 0, 0 }, { 0, 1, 0 }, { 0, 0, 1 } }, s[3] = { 0, 0, 0 };
-    const double qr = w.rot.x, qx = w.rot.y, qy = w.rot.z, qz = w.rot.w;
+    double Sg[3][3], s[3] = { 0, 0, 0 };
+    const double qr = w.g.rot.x, qx = w.g.rot.y, qy = w.g.rot.z, qz = w.g.rot.w;
     if (scale_rot) {
-        const double mod = (double)w.sf * (double)a.scale_modifier;
-        s[0] = mod * w.sc[0]; s[1] = mod * w.sc[1]; s[2] = mod * w.sc[2];
-        Rm[0][0] = 1.0 - 2.0 * (qy * qy + qz * qz); Rm[0][1] = 2.0 * (qx * qy - qr * qz); Rm[0][2] = 2.0 * (qx * qz + qr * qy);
-        Rm[1][0] = 2.0 * (qx * qy + qr * qz); Rm[1][1] = 1.0 - 2.0 * (qx * qx + qz * qz); Rm[1][2] = 2.0 * (qy * qz - qr * qx);
-        Rm[2][0] = 2.0 * (qx * qz - qr * qy); Rm[2][1] = 2.0 * (qy * qz + qr * qx); Rm[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
+        const double mod = (double)w.g.sf * (double)a.scale_modifier;
+        s[0] = mod * w.g.sc[0]; s[1] = mod * w.g.sc[1]; s[2] = mod * w.g.sc[2];
+        double Rm[3][3];
+        quat_to_rot(qr, qx, qy, qz, Rm);
 #pragma unroll
         for (int u = 0; u < 3; u++)
 #pragma unroll
@@ -139,8 +126,8 @@ __device__ __forceinline__ bool aa_chain(const AaArgs& a, const AaRow& w, const 
                 Sg[u][k] = acc;
             }
     } else {
-        Sg[0][0] = w.cov3D[0]; Sg[0][1] = Sg[1][0] = w.cov3D[1]; Sg[0][2] = Sg[2][0] = w.cov3D[2];
-        Sg[1][1] = w.cov3D[3]; Sg[1][2] = Sg[2][1] = w.cov3D[4]; Sg[2][2] = w.cov3D[5];
+        Sg[0][0] = w.g.cov3D[0]; Sg[0][1] = Sg[1][0] = w.g.cov3D[1]; Sg[0][2] = Sg[2][0] = w.g.cov3D[2];
+        Sg[1][1] = w.g.cov3D[3]; Sg[1][2] = Sg[2][1] = w.g.cov3D[4]; Sg[2][2] = w.g.cov3D[5];
     }
     double AS[2][3];
 #pragma unroll
@@ -161,65 +148,10 @@ __device__ __forceinline__ bool aa_chain(const AaArgs& a, const AaRow& w, const 
     const double dL_dc = dL_dr * (a0 * D1 - D0 * (a0 + h)) * iD1sq;
     const double dL_db = dL_dr * (-2.0 * b * (D1 - D0)) * iD1sq;
 
-    // (a0, b, c0) -> cov3D / mean: backward_preprocess.hip (b)
-    const double Gm[2][2] = { { dL_da, 0.5 * dL_db }, { 0.5 * dL_db, dL_dc } };
-    double S3[3][3];
-#pragma unroll
-    for (int u = 0; u < 3; u++)
-#pragma unroll
-        for (int k = u; k < 3; k++) {
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < 2; q++)
-#pragma unroll
-                for (int p = 0; p < 2; p++) acc += A[q][u] * Gm[q][p] * A[p][k];
-            S3[u][k] = acc;
-        }
-    c.dcov[0] = S3[0][0]; c.dcov[3] = S3[1][1]; c.dcov[5] = S3[2][2];
-    c.dcov[1] = 2.0 * S3[0][1]; c.dcov[2] = 2.0 * S3[0][2]; c.dcov[4] = 2.0 * S3[1][2];
-
-    double dA[2][3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        dA[0][k] = 2.0 * AS[0][k] * dL_da + AS[1][k] * dL_db;
-        dA[1][k] = 2.0 * AS[1][k] * dL_dc + AS[0][k] * dL_db;
-    }
-    const double dJ00 = v[0] * dA[0][0] + v[3] * dA[0][1] + v[6] * dA[0][2];
-    const double dJ02 = v[2] * dA[0][0] + v[5] * dA[0][1] + v[8] * dA[0][2];
-    const double dJ11 = v[1] * dA[1][0] + v[4] * dA[1][1] + v[7] * dA[1][2];
-    const double dJ12 = v[2] * dA[1][0] + v[5] * dA[1][1] + v[8] * dA[1][2];
-    const double dtx = w.clamp_x ? 0.0 : -fx * iz2 * dJ02;
-    const double dty = w.clamp_y ? 0.0 : -fy * iz2 * dJ12;
-    const double dtz = -fx * iz2 * dJ00 - fy * iz2 * dJ11 + 2.0 * fx * tx * iz3 * dJ02 + 2.0 * fy * ty * iz3 * dJ12;
-    c.dmean[0] = v[0] * dtx + v[1] * dty + v[2] * dtz;
-    c.dmean[1] = v[3] * dtx + v[4] * dty + v[5] * dtz;
-    c.dmean[2] = v[6] * dtx + v[7] * dty + v[8] * dtz;
-
-    // cov3D -> scale / rotation: backward_preprocess.hip, dL/dL = 2 G L; d_s is with respect to the SCALED scale s
-    if (scale_rot) {
-        const double G3[3][3] = { { c.dcov[0], 0.5 * c.dcov[1], 0.5 * c.dcov[2] },
-                                  { 0.5 * c.dcov[1], c.dcov[3], 0.5 * c.dcov[4] },
-                                  { 0.5 * c.dcov[2], 0.5 * c.dcov[4], c.dcov[5] } };
-        double Q[3][3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double col[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                double acc = 0.0;
-#pragma unroll
-                for (int q = 0; q < 3; q++) acc += G3[k][q] * (Rm[q][j] * s[j]);
-                col[k] = 2.0 * acc;
-            }
-            c.d_s[j] = Rm[0][j] * col[0] + Rm[1][j] * col[1] + Rm[2][j] * col[2];
-#pragma unroll
-            for (int k = 0; k < 3; k++) Q[k][j] = col[k] * s[j];
-        }
-        c.dq[0] = 2 * qz * (Q[1][0] - Q[0][1]) + 2 * qy * (Q[0][2] - Q[2][0]) + 2 * qx * (Q[2][1] - Q[1][2]);
-        c.dq[1] = 2 * qy * (Q[0][1] + Q[1][0]) + 2 * qz * (Q[0][2] + Q[2][0]) + 2 * qr * (Q[2][1] - Q[1][2]) - 4 * qx * (Q[2][2] + Q[1][1]);
-        c.dq[2] = 2 * qx * (Q[0][1] + Q[1][0]) + 2 * qr * (Q[0][2] - Q[2][0]) + 2 * qz * (Q[2][1] + Q[1][2]) - 4 * qy * (Q[2][2] + Q[0][0]);
-        c.dq[3] = 2 * qr * (Q[1][0] - Q[0][1]) + 2 * qx * (Q[0][2] + Q[2][0]) + 2 * qy * (Q[2][1] + Q[1][2]) - 4 * qz * (Q[1][1] + Q[0][0]);
-    }
+    // (a0, b, c0) -> cov3D / mean -> scale / rotation: gsgrad.hpp; d_s is with respect to the SCALED scale s
+    conic_grad_to_cov3d(A, dL_da, dL_db, dL_dc, c.dcov);
+    conic_grad_to_mean(A, Sg, v, fx, fy, tx, ty, tz, w.clamp_x, w.clamp_y, dL_da, dL_db, dL_dc, c.dmean);
+    if (scale_rot) cov3d_grad_to_scale_rot(c.dcov, s, qr, qx, qy, qz, c.d_s, c.dq);
     return true;
 }
 
@@ -254,15 +186,15 @@ __global__ void __launch_bounds__(256) aa_opacity_backward_kernel(const AaArgs a
                 for (int q = 0; q < 3; q++) o.dL_dmeans3D[3 * si + q] += (float)c.dmean[q];
             if (scale_rot) {
                 // exact derivatives: scale = sf x scale_modifier x the row (sf = 1 without g_indices)
-                const double mod = (double)w.sf * (double)a.scale_modifier;
+                const double mod = (double)w.g.sf * (double)a.scale_modifier;
                 if (INDEXED) {
 #pragma unroll
                     for (int q = 0; q < 3; q++) s_ds[threadIdx.x][q] = (float)(c.d_s[q] * mod);
 #pragma unroll
                     for (int q = 0; q < 4; q++) s_dq[threadIdx.x][q] = (float)c.dq[q];
-                    s_gi[threadIdx.x] = (int32_t)w.gi;
+                    s_gi[threadIdx.x] = (int32_t)w.g.gi;
                     if (o.dL_dscale_factors)
-                        o.dL_dscale_factors[si] += (float)((double)a.scale_modifier * (c.d_s[0] * w.sc[0] + c.d_s[1] * w.sc[1] + c.d_s[2] * w.sc[2]));
+                        o.dL_dscale_factors[si] += (float)((double)a.scale_modifier * (c.d_s[0] * w.g.sc[0] + c.d_s[1] * w.g.sc[1] + c.d_s[2] * w.g.sc[2]));
                 } else {
                     if (o.dL_dscales)
 #pragma unroll
@@ -279,24 +211,8 @@ __global__ void __launch_bounds__(256) aa_opacity_backward_kernel(const AaArgs a
 
     if (INDEXED) {
         // each wave scatter-adds what its own 64 lanes parked: wave-level ordering of the LDS traffic is all that is needed
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63;
-        if (o.dL_dscales)
-#pragma unroll
-            for (int it = 0; it < 3; it++) {
-                const int q = it * 64 + lane, j = q / 3, c = q - 3 * j;
-                const int32_t gi = s_gi[wbase + j];
-                if (gi >= 0) atomicAdd(o.dL_dscales + 3 * (size_t)gi + c, s_ds[wbase + j][c]);
-            }
-        if (o.dL_drotations)
-#pragma unroll
-            for (int it = 0; it < 4; it++) {
-                const int q = it * 64 + lane, j = q >> 2, c = q & 3;
-                const int32_t gi = s_gi[wbase + j];
-                if (gi >= 0) atomicAdd(o.dL_drotations + 4 * (size_t)gi + c, s_dq[wbase + j][c]);
-            }
+        wave_lds_fence();
+        scatter_add_scale_rot(s_gi, s_ds, s_dq, o.dL_dscales, o.dL_drotations);
     }
 }
 

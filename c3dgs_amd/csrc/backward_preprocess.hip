@@ -15,7 +15,7 @@
 // (pre-zeroed by the C-ABI entry point); atomicAdd(float*) is a single global_atomic_add_f32 on gfx950.
 // 3D covariances are recomputed from scale/rotation instead of being stored by the forward.
 #include "common.hpp"
-#include "gsmath.hpp"
+#include "gsgrad.hpp"        // the chains shared with aa_opacity.hip, filter3d.hip and pose_grad.hip; includes gsmath.hpp
 #include "render_common.hpp" // slot_run
 
 #ifndef C3DGS_BWD_CH
@@ -29,8 +29,11 @@
 #define C3DGS_BWD_FG 8
 #endif
 #ifndef C3DGS_BWD_WAVES
-#define C3DGS_BWD_WAVES 3   // waves per SIMD of backward_preprocess_kernel (168 VGPRs, nothing spilled); measured on one box,
-#endif                      // interleaved: 3 -> 0.153 ms, 4 (128 VGPRs, 32 spilled) -> 0.166, 5 -> 0.20
+#define C3DGS_BWD_WAVES 3   // waves per SIMD of backward_preprocess_kernel; measured on one box, interleaved: 3 -> 0.153 ms,
+#endif                      // 4 (128 VGPRs, 32 spilled) -> 0.166, 5 -> 0.20. At 3 the degree-3 instantiations use all 168 VGPRs and
+                            // spill once, outside any loop: one store at the head of the SH section, one reload behind it.
+                            // <3, true> 7 dwords (the record's conic a, b, c and opacity as loaded, 5 dwords, and the 64-bit codebook
+                            // row), <3, false> 3 dwords (conic a, b and the ninth partial sum); degrees 0-2 use 82-116 VGPRs, no scratch
 
 namespace c3dgs {
 
@@ -52,70 +55,29 @@ struct BwdArgs {
 };
 
 // SH backward. c = this Gaussian's coefficients; the gradient row is basis_out[k] * g[ch], which the caller writes (or
-// scatter-adds) cooperatively, a wave per row.
+// scatter-adds) cooperatively, a wave per row. The share of dL/dmean through the view direction is gsgrad.hpp's.
 template <int DEG>
 __device__ __forceinline__ void sh_backward(const float* c, const f3 d0, const float g[3], float dmean_add[3], float* basis_out)
 {
     const float len = sqrtf(d0.x * d0.x + d0.y * d0.y + d0.z * d0.z);
     const float x = d0.x / len, y = d0.y / len, z = d0.z / len;
-    float dx[3] = { 0, 0, 0 }, dy[3] = { 0, 0, 0 }, dz[3] = { 0, 0, 0 };
-    constexpr int NB = (DEG + 1) * (DEG + 1);
-    float basis[NB];
-    basis[0] = SH_C0;
-    if (DEG > 0) {
-        basis[1] = -SH_C1 * y; basis[2] = SH_C1 * z; basis[3] = -SH_C1 * x;
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            dx[ch] = -SH_C1 * c[3 * 3 + ch];
-            dy[ch] = -SH_C1 * c[1 * 3 + ch];
-            dz[ch] = SH_C1 * c[2 * 3 + ch];
-        }
-    }
+    basis_out[0] = SH_C0;
+    if (DEG > 0) { basis_out[1] = -SH_C1 * y; basis_out[2] = SH_C1 * z; basis_out[3] = -SH_C1 * x; }
     if (DEG > 1) {
         const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-        basis[4] = SH_C2_0 * xy; basis[5] = SH_C2_1 * yz; basis[6] = SH_C2_2 * (2.f * zz - xx - yy);
-        basis[7] = SH_C2_3 * xz; basis[8] = SH_C2_4 * (xx - yy);
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            const float s4 = c[4 * 3 + ch], s5 = c[5 * 3 + ch], s6 = c[6 * 3 + ch], s7 = c[7 * 3 + ch], s8 = c[8 * 3 + ch];
-            dx[ch] += SH_C2_0 * y * s4 + SH_C2_2 * 2.f * -x * s6 + SH_C2_3 * z * s7 + SH_C2_4 * 2.f * x * s8;
-            dy[ch] += SH_C2_0 * x * s4 + SH_C2_1 * z * s5 + SH_C2_2 * 2.f * -y * s6 + SH_C2_4 * 2.f * -y * s8;
-            dz[ch] += SH_C2_1 * y * s5 + SH_C2_2 * 2.f * 2.f * z * s6 + SH_C2_3 * x * s7;
-        }
+        basis_out[4] = SH_C2_0 * xy; basis_out[5] = SH_C2_1 * yz; basis_out[6] = SH_C2_2 * (2.f * zz - xx - yy);
+        basis_out[7] = SH_C2_3 * xz; basis_out[8] = SH_C2_4 * (xx - yy);
         if (DEG > 2) {
-            basis[9] = SH_C3_0 * y * (3.f * xx - yy);
-            basis[10] = SH_C3_1 * xy * z;
-            basis[11] = SH_C3_2 * y * (4.f * zz - xx - yy);
-            basis[12] = SH_C3_3 * z * (2.f * zz - 3.f * xx - 3.f * yy);
-            basis[13] = SH_C3_4 * x * (4.f * zz - xx - yy);
-            basis[14] = SH_C3_5 * z * (xx - yy);
-            basis[15] = SH_C3_6 * x * (xx - 3.f * yy);
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                const float s9 = c[9 * 3 + ch], s10 = c[10 * 3 + ch], s11 = c[11 * 3 + ch], s12 = c[12 * 3 + ch],
-                            s13 = c[13 * 3 + ch], s14 = c[14 * 3 + ch], s15 = c[15 * 3 + ch];
-                dx[ch] += SH_C3_0 * s9 * 3.f * 2.f * xy + SH_C3_1 * s10 * yz + SH_C3_2 * s11 * -2.f * xy +
-                          SH_C3_3 * s12 * -3.f * 2.f * xz + SH_C3_4 * s13 * (-3.f * xx + 4.f * zz - yy) +
-                          SH_C3_5 * s14 * 2.f * xz + SH_C3_6 * s15 * 3.f * (xx - yy);
-                dy[ch] += SH_C3_0 * s9 * 3.f * (xx - yy) + SH_C3_1 * s10 * xz + SH_C3_2 * s11 * (-3.f * yy + 4.f * zz - xx) +
-                          SH_C3_3 * s12 * -3.f * 2.f * yz + SH_C3_4 * s13 * -2.f * xy + SH_C3_5 * s14 * -2.f * yz +
-                          SH_C3_6 * s15 * -3.f * 2.f * xy;
-                dz[ch] += SH_C3_1 * s10 * xy + SH_C3_2 * s11 * 4.f * 2.f * yz + SH_C3_3 * s12 * 3.f * (2.f * zz - xx - yy) +
-                          SH_C3_4 * s13 * 4.f * 2.f * xz + SH_C3_5 * s14 * (xx - yy);
-            }
+            basis_out[9] = SH_C3_0 * y * (3.f * xx - yy);
+            basis_out[10] = SH_C3_1 * xy * z;
+            basis_out[11] = SH_C3_2 * y * (4.f * zz - xx - yy);
+            basis_out[12] = SH_C3_3 * z * (2.f * zz - 3.f * xx - 3.f * yy);
+            basis_out[13] = SH_C3_4 * x * (4.f * zz - xx - yy);
+            basis_out[14] = SH_C3_5 * z * (xx - yy);
+            basis_out[15] = SH_C3_6 * x * (xx - 3.f * yy);
         }
     }
-#pragma unroll
-    for (int k = 0; k < NB; k++) basis_out[k] = basis[k];
-    const float ddx = dx[0] * g[0] + dx[1] * g[1] + dx[2] * g[2];
-    const float ddy = dy[0] * g[0] + dy[1] * g[1] + dy[2] * g[2];
-    const float ddz = dz[0] * g[0] + dz[1] * g[1] + dz[2] * g[2];
-    // dnormvdv, auxiliary.h:107-117
-    const float sum2 = d0.x * d0.x + d0.y * d0.y + d0.z * d0.z;
-    const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-    dmean_add[0] = ((+sum2 - d0.x * d0.x) * ddx - d0.y * d0.x * ddy - d0.z * d0.x * ddz) * invsum32;
-    dmean_add[1] = (-d0.x * d0.y * ddx + (sum2 - d0.y * d0.y) * ddy - d0.z * d0.y * ddz) * invsum32;
-    dmean_add[2] = (-d0.x * d0.z * ddx - d0.y * d0.z * ddy + (sum2 - d0.z * d0.z) * ddz) * invsum32;
+    sh_view_dir_grad<DEG>(c, d0, g, dmean_add);
 }
 
 // position of the r-th (0-based) set bit of m; r < popcount(m)
@@ -404,7 +366,7 @@ backward_preprocess_kernel(const BwdArgs a, const float* __restrict__ cam_view, 
     }
     constexpr int NC = (DEG + 1) * (DEG + 1) * 3;
     float c[NC];
-    if (a.sh) {
+    if (a.sh) {     // restates gsgrad.hpp's load_sh_row(): through the call <3, true> spills 48 bytes, not 32 (profiles/gsgrad/README.md)
         const float* shp = a.sh + row * (size_t)a.M * 3;
         if ((a.M * 3) % 4 == 0 && NC % 4 == 0) {
 #pragma unroll
@@ -465,6 +427,7 @@ backward_preprocess_kernel(const BwdArgs a, const float* __restrict__ cam_view, 
         dL_da = denom2inv * (-cc * cc * dcon_x + 2 * cb * cc * dcon_y + (denom - ca * cc) * dcon_w);
         dL_dc = denom2inv * (-ca * ca * dcon_w + 2 * ca * cb * dcon_y + (denom - ca * cc) * dcon_x);
         dL_db = denom2inv * 2 * (cb * cc * dcon_x - (denom + 2 * cb * cb) * dcon_y + ca * cb * dcon_w);
+        // restates gsgrad.hpp's conic_grad_to_cov3d(): called, the kernel measured slower (profiles/gsgrad/README.md)
         const float Gm[2][2] = { { dL_da, 0.5f * dL_db }, { 0.5f * dL_db, dL_dc } };
         float S3[3][3];
 #pragma unroll
@@ -485,6 +448,7 @@ backward_preprocess_kernel(const BwdArgs a, const float* __restrict__ cam_view, 
 #pragma unroll
         for (int q = 0; q < 6; q++) o.dL_dcov3D[6 * si + q] = dcov[q];
 
+    // restates gsgrad.hpp's conic_grad_to_mean() (Rv[k][j] = view[4 k + j]), for the same reason
     float AS[2][3], dA[2][3];
 #pragma unroll
     for (int q = 0; q < 2; q++)
@@ -528,6 +492,7 @@ backward_preprocess_kernel(const BwdArgs a, const float* __restrict__ cam_view, 
         const float s[3] = { (INDEXED ? sf * a.scale_modifier : a.scale_modifier) * sc[0],
                              (INDEXED ? sf * a.scale_modifier : a.scale_modifier) * sc[1],
                              (INDEXED ? sf * a.scale_modifier : a.scale_modifier) * sc[2] };
+        // restates gsgrad.hpp's cov3d_grad_to_scale_rot(), for the same reason; tests/test_gsgrad_gpu.py holds the two together
         const float r = rot.x, x = rot.y, y = rot.z, z = rot.w;
         const float Rm[3][3] = { { 1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y) },
                                  { 2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x) },
@@ -572,9 +537,7 @@ backward_preprocess_kernel(const BwdArgs a, const float* __restrict__ cam_view, 
     {
         // each wave scatter-adds (indexed) or stores (non-indexed) its own 64 rows: wave-level ordering of the LDS traffic is
         // all that is needed
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_fence();
         const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63;
         if (o.dL_dsh && a.sh) {
             const int k = min(lane / 3, NB - 1), ch = lane - 3 * (lane / 3);
@@ -588,25 +551,7 @@ backward_preprocess_kernel(const BwdArgs a, const float* __restrict__ cam_view, 
             }
         }
     }
-    if (INDEXED) {
-        const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63;
-        if (a.scales) {
-            if (o.dL_dscales)
-#pragma unroll
-                for (int it = 0; it < 3; it++) {
-                    const int q = it * 64 + lane, j = q / 3, c = q - 3 * j;
-                    const int32_t gi = s_gi[wbase + j];
-                    if (gi >= 0) atomicAdd(o.dL_dscales + 3 * (size_t)gi + c, s_ds[wbase + j][c]);
-                }
-            if (o.dL_drotations)
-#pragma unroll
-                for (int it = 0; it < 4; it++) {
-                    const int q = it * 64 + lane, j = q >> 2, c = q & 3;
-                    const int32_t gi = s_gi[wbase + j];
-                    if (gi >= 0) atomicAdd(o.dL_drotations + 4 * (size_t)gi + c, s_dq[wbase + j][c]);
-                }
-        }
-    }
+    if (INDEXED && a.scales) scatter_add_scale_rot(s_gi, s_ds, s_dq, o.dL_dscales, o.dL_drotations);
 }
 
 void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,

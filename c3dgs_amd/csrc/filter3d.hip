@@ -28,14 +28,14 @@
 // visible subset, row rank[i] for model row i with visible[i]) the kernel runs one lane per MODEL row and reads filter_3D[i].
 //
 // BACKWARD (filter3d_apply_backward_kernel), for rows where dL_dcov3D' or g' = dL/do' is non-zero (others are not touched: the
-// caller hands in zeros): dL/dSigma = dL/dSigma' element for element, chained to scales, rotations and scale factors with
-// backward_preprocess.hip's covariance chain (its factor 1/2 on the off-diagonal elements; exact derivatives with respect to the
-// scale_modifier, as aa_opacity.hip has them); dL/do = coef g'; dL/ds_k += o g' coef f^2 / (s_k (s_k^2 + f^2)) unless s_k == 0 or
-// f == 0, distributed to sc_k (x sf) and sf (x sc_k). All in fp32. P-sized outputs are plain stores (one lane owns one row);
-// the codebook-sized outputs of the indexed form are scatter-ADDED as aa_opacity.hip does it (factors parked in LDS, adjacent
-// lanes of one atomic instruction covering whole rows), so those rows are NOT bitwise reproducible.
+// caller hands in zeros): dL/dSigma = dL/dSigma' element for element, chained to scales, rotations and scale factors by
+// gsgrad.hpp's cov3d_grad_to_scale_rot(), which backward_preprocess.hip restates and tests/test_gsgrad_gpu.py holds it to (its
+// factor 1/2 on the off-diagonal elements; exact derivatives with respect to the scale_modifier, as aa_opacity.hip has them);
+// dL/do = coef g'; dL/ds_k += o g' coef f^2 / (s_k (s_k^2 + f^2)) unless s_k == 0 or f == 0, distributed to sc_k (x sf) and
+// sf (x sc_k). All in fp32. P-sized outputs are plain stores (one lane owns one row); the codebook-sized outputs of the indexed form are scatter-ADDED by gsgrad.hpp's scatter_add_scale_rot(), so those rows are
+// NOT bitwise reproducible.
 #include "common.hpp"
-#include "gsmath.hpp"
+#include "gsgrad.hpp"
 
 namespace c3dgs {
 
@@ -94,8 +94,9 @@ struct F3Args {
 };
 
 struct F3Row {
-    size_t j, gi;                    // output row, row of scales / rotations
-    float f, sf, sc[3]; float4 rot;
+    size_t j;                        // output row
+    float f;
+    ScaleRotRow g;                   // scales, rotation, codebook row, scale factor; Sigma before the filter
     float s[3], r[3], coef;          // s_k = sf sc_k
 };
 
@@ -111,14 +112,11 @@ __device__ __forceinline__ bool f3_row(const F3Args& a, const int t, F3Row& w)
         w.j = (size_t)t;
     }
     w.f = a.filter[t];
-    w.gi = w.j; w.sf = 1.f;
-    if (a.g_indices) { w.gi = (size_t)a.g_indices[w.j]; w.sf = a.scale_factors[w.j]; }
-    w.sc[0] = a.scales[3 * w.gi]; w.sc[1] = a.scales[3 * w.gi + 1]; w.sc[2] = a.scales[3 * w.gi + 2];
-    w.rot = a.cov3D_in ? make_float4(1, 0, 0, 0) : *reinterpret_cast<const float4*>(a.rotations + 4 * w.gi);
+    load_scale_rot_row(a.cov3D_in, a.scales, a.rotations, a.scale_factors, a.g_indices, w.j, a.scale_modifier, w.g);
     const float f2 = w.f * w.f;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        w.s[k] = w.sf * w.sc[k];
+        w.s[k] = w.g.sf * w.g.sc[k];
         const float s2 = w.s[k] * w.s[k];
         w.r[k] = w.f == 0.f ? 1.f : s2 / (s2 + f2);
     }
@@ -131,13 +129,7 @@ __global__ void __launch_bounds__(256) filter3d_apply_kernel(const F3Args a, flo
 {
     F3Row w;
     if (!f3_row(a, blockIdx.x * 256 + threadIdx.x, w)) return;
-    float cov[6];
-    if (a.cov3D_in) {
-#pragma unroll
-        for (int q = 0; q < 6; q++) cov[q] = a.cov3D_in[6 * w.j + q];
-    } else {
-        cov3d_from_scale_rot(w.sc[0], w.sc[1], w.sc[2], w.sf * a.scale_modifier, w.rot, cov);
-    }
+    float* cov = w.g.cov3D;
     float o = a.opacities[w.j];
     if (w.f != 0.f) {
         const float mf = a.scale_modifier * w.f, add = mf * mf;
@@ -172,37 +164,11 @@ __global__ void __launch_bounds__(256) filter3d_apply_backward_kernel(const F3Ar
         const float gp = o.dL_dopacity_out ? o.dL_dopacity_out[w.j] : 0.f;
         if (any || gp != 0.f) {
             if (o.dL_dopacity) o.dL_dopacity[w.j] = w.coef * gp;
-            // Sigma -> scale / rotation: backward_preprocess.hip, L = Rm diag(s), Sigma = L L^T, dL/dL = 2 G L; d_s is with respect
-            // to the SCALED scale mod sc_k
-            const float mod = w.sf * a.scale_modifier;
-            const float s[3] = { mod * w.sc[0], mod * w.sc[1], mod * w.sc[2] };
-            const float r = w.rot.x, x = w.rot.y, y = w.rot.z, z = w.rot.w;
-            const float Rm[3][3] = { { 1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y) },
-                                     { 2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x) },
-                                     { 2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y) } };
-            const float G3[3][3] = { { dcov[0], 0.5f * dcov[1], 0.5f * dcov[2] },
-                                     { 0.5f * dcov[1], dcov[3], 0.5f * dcov[4] },
-                                     { 0.5f * dcov[2], 0.5f * dcov[4], dcov[5] } };
-            float Q[3][3], d_s[3];
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                float col[3];
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    float accv = 0.f;
-#pragma unroll
-                    for (int q = 0; q < 3; q++) accv += G3[k][q] * (Rm[q][j] * s[j]);
-                    col[k] = 2.0f * accv;
-                }
-                d_s[j] = Rm[0][j] * col[0] + Rm[1][j] * col[1] + Rm[2][j] * col[2];
-#pragma unroll
-                for (int k = 0; k < 3; k++) Q[k][j] = col[k] * s[j];
-            }
-            float dq[4];
-            dq[0] = 2 * z * (Q[1][0] - Q[0][1]) + 2 * y * (Q[0][2] - Q[2][0]) + 2 * x * (Q[2][1] - Q[1][2]);
-            dq[1] = 2 * y * (Q[0][1] + Q[1][0]) + 2 * z * (Q[0][2] + Q[2][0]) + 2 * r * (Q[2][1] - Q[1][2]) - 4 * x * (Q[2][2] + Q[1][1]);
-            dq[2] = 2 * x * (Q[0][1] + Q[1][0]) + 2 * r * (Q[0][2] - Q[2][0]) + 2 * z * (Q[2][1] + Q[1][2]) - 4 * y * (Q[2][2] + Q[0][0]);
-            dq[3] = 2 * r * (Q[1][0] - Q[0][1]) + 2 * x * (Q[0][2] + Q[2][0]) + 2 * y * (Q[2][1] + Q[1][2]) - 4 * z * (Q[1][1] + Q[0][0]);
+            // Sigma -> scale / rotation; d_s is with respect to the SCALED scale mod sc_k
+            const float mod = w.g.sf * a.scale_modifier;
+            const float s[3] = { mod * w.g.sc[0], mod * w.g.sc[1], mod * w.g.sc[2] };
+            float d_s[3], dq[4];
+            cov3d_grad_to_scale_rot(dcov, s, w.g.rot.x, w.g.rot.y, w.g.rot.z, w.g.rot.w, d_s, dq);
             // through coef, with respect to s_k = sf sc_k: d coef / d s_k = coef f^2 / (s_k (s_k^2 + f^2))
             float d_c[3] = { 0.f, 0.f, 0.f };
             if (w.f != 0.f && gp != 0.f) {
@@ -214,15 +180,15 @@ __global__ void __launch_bounds__(256) filter3d_apply_backward_kernel(const F3Ar
             // to the row sc_k: d_s mod + d_c sf; to the factor sf: scale_modifier sum d_s sc_k + sum d_c sc_k
             float drow[3];
 #pragma unroll
-            for (int k = 0; k < 3; k++) drow[k] = d_s[k] * mod + d_c[k] * w.sf;
+            for (int k = 0; k < 3; k++) drow[k] = d_s[k] * mod + d_c[k] * w.g.sf;
             if (INDEXED) {
 #pragma unroll
                 for (int q = 0; q < 3; q++) s_ds[threadIdx.x][q] = drow[q];
                 s_dq[threadIdx.x][0] = dq[0]; s_dq[threadIdx.x][1] = dq[1]; s_dq[threadIdx.x][2] = dq[2]; s_dq[threadIdx.x][3] = dq[3];
-                s_gi[threadIdx.x] = (int32_t)w.gi;
+                s_gi[threadIdx.x] = (int32_t)w.g.gi;
                 if (o.dL_dscale_factors)
-                    o.dL_dscale_factors[w.j] = a.scale_modifier * (d_s[0] * w.sc[0] + d_s[1] * w.sc[1] + d_s[2] * w.sc[2]) +
-                                               (d_c[0] * w.sc[0] + d_c[1] * w.sc[1] + d_c[2] * w.sc[2]);
+                    o.dL_dscale_factors[w.j] = a.scale_modifier * (d_s[0] * w.g.sc[0] + d_s[1] * w.g.sc[1] + d_s[2] * w.g.sc[2]) +
+                                               (d_c[0] * w.g.sc[0] + d_c[1] * w.g.sc[1] + d_c[2] * w.g.sc[2]);
             } else {
                 if (o.dL_dscales) { o.dL_dscales[3 * w.j] = drow[0]; o.dL_dscales[3 * w.j + 1] = drow[1]; o.dL_dscales[3 * w.j + 2] = drow[2]; }
                 if (o.dL_drotations) *reinterpret_cast<float4*>(o.dL_drotations + 4 * w.j) = make_float4(dq[0], dq[1], dq[2], dq[3]);
@@ -232,24 +198,8 @@ __global__ void __launch_bounds__(256) filter3d_apply_backward_kernel(const F3Ar
 
     if (INDEXED) {
         // each wave scatter-adds what its own 64 lanes parked: wave-level ordering of the LDS traffic is all that is needed
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63;
-        if (o.dL_dscales)
-#pragma unroll
-            for (int it = 0; it < 3; it++) {
-                const int q = it * 64 + lane, j = q / 3, c = q - 3 * j;
-                const int32_t gi = s_gi[wbase + j];
-                if (gi >= 0) atomicAdd(o.dL_dscales + 3 * (size_t)gi + c, s_ds[wbase + j][c]);
-            }
-        if (o.dL_drotations)
-#pragma unroll
-            for (int it = 0; it < 4; it++) {
-                const int q = it * 64 + lane, j = q >> 2, c = q & 3;
-                const int32_t gi = s_gi[wbase + j];
-                if (gi >= 0) atomicAdd(o.dL_drotations + 4 * (size_t)gi + c, s_dq[wbase + j][c]);
-            }
+        wave_lds_fence();
+        scatter_add_scale_rot(s_gi, s_ds, s_dq, o.dL_dscales, o.dL_drotations);
     }
 }
 

@@ -17,7 +17,7 @@
 //       lane then applies R^-T, the c^T term and the quaternion chain and stores seven floats.
 // No atomics: the result is bitwise reproducible from run to run.
 #include "common.hpp"
-#include "gsmath.hpp"
+#include "gsgrad.hpp"    // sh_view_dir_grad, load_scale_rot_row; includes gsmath.hpp
 
 namespace c3dgs {
 
@@ -59,56 +59,6 @@ __device__ __forceinline__ PoseCamera pose_camera(const float* __restrict__ pose
     return o;
 }
 
-// The share of dL/dmean that arrives through the SH view direction: backward_preprocess.hip's sh_backward without the basis
-// row (reference backward.cu:20-139 and dnormvdv, auxiliary.h:107-117), the same expressions in the same order. c = this
-// Gaussian's coefficients, d0 = mean - campos, g = dL/dcolour with the clamped channels zeroed. DEG >= 1.
-template <int DEG>
-__device__ __forceinline__ void sh_direction_grad(const float* c, const f3 d0, const float g[3], float out[3])
-{
-    const float len = sqrtf(d0.x * d0.x + d0.y * d0.y + d0.z * d0.z);
-    const float x = d0.x / len, y = d0.y / len, z = d0.z / len;
-    float dx[3], dy[3], dz[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        dx[ch] = -SH_C1 * c[3 * 3 + ch];
-        dy[ch] = -SH_C1 * c[1 * 3 + ch];
-        dz[ch] = SH_C1 * c[2 * 3 + ch];
-    }
-    if (DEG > 1) {
-        const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            const float s4 = c[4 * 3 + ch], s5 = c[5 * 3 + ch], s6 = c[6 * 3 + ch], s7 = c[7 * 3 + ch], s8 = c[8 * 3 + ch];
-            dx[ch] += SH_C2_0 * y * s4 + SH_C2_2 * 2.f * -x * s6 + SH_C2_3 * z * s7 + SH_C2_4 * 2.f * x * s8;
-            dy[ch] += SH_C2_0 * x * s4 + SH_C2_1 * z * s5 + SH_C2_2 * 2.f * -y * s6 + SH_C2_4 * 2.f * -y * s8;
-            dz[ch] += SH_C2_1 * y * s5 + SH_C2_2 * 2.f * 2.f * z * s6 + SH_C2_3 * x * s7;
-        }
-        if (DEG > 2) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                const float s9 = c[9 * 3 + ch], s10 = c[10 * 3 + ch], s11 = c[11 * 3 + ch], s12 = c[12 * 3 + ch],
-                            s13 = c[13 * 3 + ch], s14 = c[14 * 3 + ch], s15 = c[15 * 3 + ch];
-                dx[ch] += SH_C3_0 * s9 * 3.f * 2.f * xy + SH_C3_1 * s10 * yz + SH_C3_2 * s11 * -2.f * xy +
-                          SH_C3_3 * s12 * -3.f * 2.f * xz + SH_C3_4 * s13 * (-3.f * xx + 4.f * zz - yy) +
-                          SH_C3_5 * s14 * 2.f * xz + SH_C3_6 * s15 * 3.f * (xx - yy);
-                dy[ch] += SH_C3_0 * s9 * 3.f * (xx - yy) + SH_C3_1 * s10 * xz + SH_C3_2 * s11 * (-3.f * yy + 4.f * zz - xx) +
-                          SH_C3_3 * s12 * -3.f * 2.f * yz + SH_C3_4 * s13 * -2.f * xy + SH_C3_5 * s14 * -2.f * yz +
-                          SH_C3_6 * s15 * -3.f * 2.f * xy;
-                dz[ch] += SH_C3_1 * s10 * xy + SH_C3_2 * s11 * 4.f * 2.f * yz + SH_C3_3 * s12 * 3.f * (2.f * zz - xx - yy) +
-                          SH_C3_4 * s13 * 4.f * 2.f * xz + SH_C3_5 * s14 * (xx - yy);
-            }
-        }
-    }
-    const float ddx = dx[0] * g[0] + dx[1] * g[1] + dx[2] * g[2];
-    const float ddy = dy[0] * g[0] + dy[1] * g[1] + dy[2] * g[2];
-    const float ddz = dz[0] * g[0] + dz[1] * g[1] + dz[2] * g[2];
-    const float sum2 = d0.x * d0.x + d0.y * d0.y + d0.z * d0.z;
-    const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-    out[0] = ((+sum2 - d0.x * d0.x) * ddx - d0.y * d0.x * ddy - d0.z * d0.x * ddz) * invsum32;
-    out[1] = (-d0.x * d0.y * ddx + (sum2 - d0.y * d0.y) * ddy - d0.z * d0.y * ddz) * invsum32;
-    out[2] = (-d0.x * d0.z * ddx - d0.y * d0.z * ddy + (sum2 - d0.z * d0.z) * ddz) * invsum32;
-}
-
 // ---- stage A. DEG = the active SH degree, 0 when the colours were precomputed or the degree is 0 (gdir is zero then and
 // neither dL_dcolors, the clamped byte nor the SH row is read).
 // Of a dense view's Gaussians about a tenth is ever blended; every other row of the three gradients is exact zeros. Such a
@@ -136,24 +86,15 @@ __global__ void __launch_bounds__(256) pose_sums_kernel(const PoseArgs a, const 
         const bool any_col = dcol[0] != 0.f || dcol[1] != 0.f || dcol[2] != 0.f;
         if (any_geom || any_col) {
             const f3 m = { a.means3D[3 * si], a.means3D[3 * si + 1], a.means3D[3 * si + 2] };
-            // Sigma exactly as preprocess_kernel builds it
-            float cov3D[6];
-            if (a.cov3D_precomp) {
-#pragma unroll
-                for (int q = 0; q < 6; q++) cov3D[q] = a.cov3D_precomp[6 * si + q];
-            } else if (a.g_indices) {
-                const size_t gi = (size_t)a.g_indices[i];
-                const float4 rot = *reinterpret_cast<const float4*>(a.rotations + 4 * gi);
-                cov3d_from_scale_rot(a.scales[3 * gi], a.scales[3 * gi + 1], a.scales[3 * gi + 2],
-                                     a.scale_factors[i] * a.scale_modifier, rot, cov3D);
-            } else {
-                const float4 rot = *reinterpret_cast<const float4*>(a.rotations + 4 * si);
-                cov3d_from_scale_rot(a.scales[3 * si], a.scales[3 * si + 1], a.scales[3 * si + 2], a.scale_modifier, rot, cov3D);
-            }
+            ScaleRotRow w;                                         // Sigma exactly as preprocess_kernel builds it
+            load_scale_rot_row(a.cov3D_precomp, a.scales, a.rotations, a.scale_factors, a.g_indices, si, a.scale_modifier, w);
+            const float* cov3D = w.cov3D;
             float gdir[3] = { 0.f, 0.f, 0.f };
             if (DEG > 0 && any_col) {
                 constexpr int NC = (DEG + 1) * (DEG + 1) * 3;
                 const size_t row = a.sh_indices ? (size_t)a.sh_indices[i] : si;
+                // scalar loads, not gsgrad.hpp's load_sh_row(): with its 16-byte loads the degree-3 kernel needs 136 VGPRs and
+                // three waves per SIMD fit instead of four (0.118 -> 0.141 ms at P = 3M, profiles/gsgrad/README.md)
                 const float* shp = a.sh + row * (size_t)a.M * 3;
                 float c[NC];
 #pragma unroll
@@ -162,7 +103,7 @@ __global__ void __launch_bounds__(256) pose_sums_kernel(const PoseArgs a, const 
                 const float gc[3] = { (cl & 1) ? 0.f : dcol[0], (cl & 2) ? 0.f : dcol[1], (cl & 4) ? 0.f : dcol[2] };
                 const PoseCamera cam = pose_camera(pose);
                 const f3 d0 = { m.x - cam.campos[0], m.y - cam.campos[1], m.z - cam.campos[2] };
-                sh_direction_grad<DEG>(c, d0, gc, gdir);
+                sh_view_dir_grad<DEG>(c, d0, gc, gdir);
             }
             const float mu[3] = { m.x, m.y, m.z };
             const float Sg[3][3] = { { cov3D[0], cov3D[1], cov3D[2] }, { cov3D[1], cov3D[3], cov3D[4] }, { cov3D[2], cov3D[4], cov3D[5] } };

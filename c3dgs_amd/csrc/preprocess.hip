@@ -15,7 +15,7 @@
 // The last three words let the backward find the instance slot of (Gaussian, tile) without any
 // extra gather (see render.hip).
 #include "common.hpp"
-#include "gsmath.hpp"
+#include "gsgrad.hpp"       // load_sh_row; includes gsmath.hpp
 #include "scan_blocks.hpp"
 
 namespace c3dgs {
@@ -254,16 +254,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(const PreArgs a)
             const float* shp = a.sh + row * (size_t)a.M * 3;
             constexpr int NC = (DEG + 1) * (DEG + 1) * 3;
             float c[NC];
-            if ((a.M * 3) % 4 == 0 && NC % 4 == 0) {               // 16-byte aligned rows: M = 4, 16
-#pragma unroll
-                for (int q = 0; q < NC / 4; q++) {
-                    const float4 v = reinterpret_cast<const float4*>(shp)[q];
-                    c[4 * q] = v.x; c[4 * q + 1] = v.y; c[4 * q + 2] = v.z; c[4 * q + 3] = v.w;
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < NC; q++) c[q] = shp[q];
-            }
+            load_sh_row<NC>(shp, a.M, c);
             f3 dir = { p.x - a.campos[0], p.y - a.campos[1], p.z - a.campos[2] };
             const float len = sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
             dir.x = dir.x / len; dir.y = dir.y / len; dir.z = dir.z / len;
