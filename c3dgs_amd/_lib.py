@@ -218,6 +218,9 @@ PROTOTYPES = {
     "c3dgs_debug_sort_pairs": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "c3dgs_debug_tile_sort_temp_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "c3dgs_debug_tile_sort_pairs": (C.c_int, [C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "c3dgs_debug_depth_plan": (C.c_int, [C.c_int32, C.c_uint32, C.c_int64, _vp, _vp, _vp]),
+    "c3dgs_debug_depth_sort_temp_bytes": (C.c_size_t, [C.c_int64]),
+    "c3dgs_debug_depth_sort": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "c3dgs_get_geom_layout": (C.c_int, [C.c_int32, C.POINTER(GeomLayout)]),
     "c3dgs_get_binning_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(BinningLayout)]),
     "c3dgs_get_image_layout": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(ImageLayout)]),

@@ -22,7 +22,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno
           "-fno-gpu-rdc", "-DNDEBUG"]
 SOURCES = {
     "c_abi.hip": [],
-    "c_abi_debug.hip": [],      # test hooks (include/c3dgs_hip_debug.h)
+    "c_abi_debug.hip": [],      # test hooks (include/c3dgs_hip_debug.h, c3dgs_hip_depth_sort_debug.h)
     "preprocess.hip": ["-ffp-contract=off"],
     "backward_preprocess.hip": ["-ffp-contract=off"] + os.environ.get("C3DGS_BWDPRE_FLAGS", "").split(),
     "binning.hip": [],
@@ -70,7 +70,8 @@ HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), o
            os.path.join(CSRC, "render_diag.hpp"),
            os.path.join(CSRC, "render_common.hpp"), os.path.join(CSRC, "replay.hpp"), os.path.join(CSRC, "scan_blocks.hpp"), os.path.join(CSRC, "adam_common.hpp"), os.path.join(CSRC, "mcmc.hpp"), os.path.join(CSRC, "jobs.hpp"),
            os.path.join(CSRC, "bilagrid.hpp"),
-           os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h")]
+           os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h"),
+           os.path.join(HERE, "..", "include", "c3dgs_hip_depth_sort_debug.h")]
 
 
 def _stale(target, deps):

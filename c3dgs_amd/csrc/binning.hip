@@ -14,6 +14,7 @@
 // emission (= id) order that the reference's single stable sort yields, so the sorted point list is bit-identical
 // (asserted against the oracle). (The umbrella <rocprim/rocprim.hpp> does not compile on this ROCm install.)
 #include "common.hpp"
+#include <cstdlib>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
@@ -87,6 +88,13 @@ hipError_t run_depth_sort(void* temp, size_t temp_bytes, const uint32_t* kin, ui
     if (e != hipSuccess) return e;
     gather_u64_kernel<<<(P + 255) / 256, 256, 0, s>>>(P, vout, rects, rects_sorted);
     return hipGetLastError();
+}
+
+// the biased three-pass plan is the hand-written sort's, with the rectangles as its packed second payload
+bool depth_sort3_available(int P, size_t temp_bytes, bool rects_fit_bytes)
+{
+    static const bool no_pay2 = []() { const char* e = std::getenv("C3DGS_DEPTH_SORT_GATHER"); return e && e[0] == '1'; }();
+    return rects_fit_bytes && !no_pay2 && P > 0 && depth_sort_clear_bytes(P) != 0 && onesweep_depth_temp_bytes(P) <= temp_bytes;
 }
 
 hipError_t run_tile_sort(void* temp, size_t temp_bytes, const void* kin, void* kout, int key_bytes, const uint32_t* vin,

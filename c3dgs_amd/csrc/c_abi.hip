@@ -92,6 +92,8 @@ struct StageTimer {
 // sequence number -- no copy command on the stream (a ~4 us launch + a ~6 us bubble per forward). Otherwise (`dev` null):
 // a hipMemcpyAsync into it behind an event, as before.
 // One read is begin() -> [the producing kernel is launched with `dev` and the sequence number] -> queue_copy() -> wait().
+// Words 3 and 4 of the mapped pad are a second read of the same kind, {largest visible depth key, sequence number}, which the
+// biased depth sort's histogram stores when its last workgroup finishes: wait_max().
 struct HostRead {
     uint32_t* pinned = nullptr;
     uint32_t* dev = nullptr;      // device-side address of `pinned`, or null
@@ -163,6 +165,23 @@ struct HostRead {
         }
         words[0] = pinned[0]; words[1] = pinned[1];
         return C3DGS_OK;
+    }
+    // mapped pad only: the largest visible depth key of this read (device copy of the word at `src`), polled like wait()
+    int wait_max(const uint32_t* src, hipStream_t s, uint32_t* max_key)
+    {
+        volatile uint32_t* pad = pinned;
+        for (long spins = 0;; spins++) {
+            if (__atomic_load_n(&pad[4], __ATOMIC_ACQUIRE) == seq) { *max_key = pinned[3]; return C3DGS_OK; }
+            if ((spins & 0xffff) != 0xffff) continue;
+            const hipError_t q = hipStreamQuery(s);
+            if (q == hipErrorNotReady) continue;
+            if (q != hipSuccess) return fail(C3DGS_E_HIP, std::string("depth key range read: ") + hipGetErrorString(q));
+            if (__atomic_load_n(&pad[4], __ATOMIC_ACQUIRE) == seq) { *max_key = pinned[3]; return C3DGS_OK; }
+            C3DGS_HIP_TRY(hipMemcpyAsync(pinned + 3, src, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            C3DGS_HIP_TRY(hipStreamSynchronize(s));
+            *max_key = pinned[3];
+            return C3DGS_OK;
+        }
     }
 };
 static HostRead& host_read()
@@ -248,11 +267,18 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
     // the id-order scan behind preprocess shares its launch with the depth sort's histograms where that sort is the hand-written
     // one and preprocess has cleared its control words; otherwise it runs alone and the sort does everything itself
     const bool hist_with_scan = dclear != 0;
+    // the depth sort on biased keys in three passes (radix_sort.hip): every visible key has passed the near-plane test, and the
+    // host can read the largest one from the mapped pad. Otherwise the four 8-bit passes on the raw keys.
+    const bool rects_fit_bytes = gx <= 255 && gy <= 255;
+    const bool sort3 = hist_with_scan && hr.dev && !p.prefiltered && depth_sort3_available(P, g.scan_temp_bytes, rects_fit_bytes);
     const int nb = (P + 255) / 256;
     { StageTimer t_(ST_PREPROCESS, s);
       if (geom_gtab_bytes(p)) launch_pack_codebook(p, g.gtab, s);
       launch_preprocess(p, g, radii, img.ranges, g.scan_temp, dclear / 16, s);
-      if (hist_with_scan)
+      if (sort3)
+          C3DGS_HIP_TRY(onesweep_depth3_hist_scan(g.scan_temp, g.scan_temp_bytes, g.depth_keys, P, nb, g.block_base, sort_err, hr.dev, host_seq,
+                                                  hr.dev + 3, s));
+      else if (hist_with_scan)
           C3DGS_HIP_TRY(run_depth_hist_scan(g.scan_temp, g.scan_temp_bytes, g.depth_keys, P, nb, g.block_base, sort_err, hr.dev, host_seq, s));
       else
           launch_scan_blocks(nb, g.block_base, sort_err, hr.dev, host_seq, s); }
@@ -264,14 +290,25 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
     // second word: the device's sticky sort time-out flag as of the start of this call (radix_sort.hip)
     const uint32_t* r_words = g.block_base + nb;
     if (int rc = hr.queue_copy(r_words, s)) return rc;
-    { StageTimer t_(ST_DEPTH_SORT, s);                                               // binning stage 1: P Gaussians by depth
-      C3DGS_HIP_TRY(run_depth_sort(g.scan_temp, g.scan_temp_bytes, g.depth_keys, g.depth_keys_sorted, nullptr, g.depth_order, P,
-                                   reinterpret_cast<const uint2*>(g.rects), g.sorted_offsets, s, dclear != 0,
-                                   /*rects_fit_bytes=*/gx <= 255 && gy <= 255, hist_with_scan)); }
+    uint32_t words[2];
+    if (sort3) {
+        // The host read moves in front of the last pass: passes 1 and 2 are the same whatever the key range, so they are queued
+        // first and run while the host wakes up; the largest visible key then decides between one more pass and two.
+        // One timed stage around both halves: a bubble in front of the last pass would show in it.
+        StageTimer t_(ST_DEPTH_SORT, s);                                             // binning stage 1: P Gaussians by depth
+        C3DGS_HIP_TRY(onesweep_depth3_head(g.scan_temp, g.scan_temp_bytes, g.depth_keys, P, reinterpret_cast<const uint2*>(g.rects), s));
+        uint32_t max_key = 0;
+        if (int rc = hr.wait_max(onesweep_depth3_max_word(g.scan_temp, P), s, &max_key)) return rc;
+        C3DGS_HIP_TRY(onesweep_depth3_tail(g.scan_temp, g.scan_temp_bytes, g.depth_keys, g.depth_keys_sorted, g.depth_order, P,
+                                           reinterpret_cast<const uint2*>(g.rects), g.sorted_offsets, max_key, s));
+    } else {
+        StageTimer t_(ST_DEPTH_SORT, s);
+        C3DGS_HIP_TRY(run_depth_sort(g.scan_temp, g.scan_temp_bytes, g.depth_keys, g.depth_keys_sorted, nullptr, g.depth_order, P,
+                                     reinterpret_cast<const uint2*>(g.rects), g.sorted_offsets, s, dclear != 0, rects_fit_bytes, hist_with_scan));
+    }
     C3DGS_STAGE_CHECK(ST_DEPTH_SORT, p.debug, s);
     if (p.debug && onesweep_timed_out(s)) return fail(C3DGS_E_HIP, "depth sort: look-back timed out");
     C3DGS_TIMED_STAGE(ST_SCAN, p.debug, s, launch_depth_order_scan(P, g, s));        // K3, in depth order (two-level)
-    uint32_t words[2];
     if (int rc = hr.wait(r_words, s, words)) return rc;
     const uint32_t R_u = words[0];
     if (words[1] != 0) {

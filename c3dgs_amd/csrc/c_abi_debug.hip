@@ -2,6 +2,7 @@
 // and codeword search directly. Part of the product library; not part of its public ABI.
 #include "common.hpp"
 #include "../../include/c3dgs_hip_debug.h"
+#include "../../include/c3dgs_hip_depth_sort_debug.h"
 
 using namespace c3dgs;
 
@@ -60,6 +61,59 @@ int c3dgs_debug_tile_sort_pairs(int32_t tiles, int64_t n, const void* keys_in, v
     C3DGS_HIP_TRY(run_tile_sort(temp, temp_bytes, keys_in, keys_out, kb, values_in, values_out, (int)n, end_bit, s, false));
     C3DGS_STAGE("debug_tile_sort_pairs", 1, s);
     if (onesweep_timed_out(s)) return fail(C3DGS_E_HIP, "debug_tile_sort_pairs: look-back timed out");
+    return C3DGS_OK;
+}
+
+int c3dgs_debug_depth_plan(int32_t biased, uint32_t max_visible_key, int64_t n, const uint32_t* keys, uint32_t* plan, uint32_t* digits)
+{
+    if (!plan || n < 0 || (n > 0 && digits && !keys)) return fail(C3DGS_E_INVALID, "debug_depth_plan: bad arguments");
+    const DepthSortPlan dp = depth_sort_plan(biased != 0, max_visible_key);
+    plan[0] = (uint32_t)dp.passes;
+    for (int q = 0; q < 4; q++) plan[1 + q] = q < dp.passes ? (uint32_t)dp.bits[q] : 0u;
+    plan[5] = dp.bias;
+    if (digits)
+        for (int64_t i = 0; i < n; i++)
+            for (int q = 0; q < 4; q++) digits[4 * i + q] = q < dp.passes ? depth_sort_digit(dp, keys[i], q) : 0u;
+    return C3DGS_OK;
+}
+
+static bool debug_depth_sort_args_ok(int64_t n) { return n >= 1 && n <= 0x3fffffff && onesweep_enabled(); }
+
+size_t c3dgs_debug_depth_sort_temp_bytes(int64_t n)
+{
+    if (!debug_depth_sort_args_ok(n)) return 256;
+    return onesweep_depth_temp_bytes((int)n) + 256;                 // + the one word the histogram launch's scan half leaves
+}
+
+int c3dgs_debug_depth_sort(int64_t n, int32_t prefiltered, const uint32_t* keys, const void* rects, uint32_t* order,
+                           uint32_t* keys_sorted, void* rects_sorted, void* temp, size_t temp_bytes, int32_t* passes_run, void* stream)
+{
+    if (!debug_depth_sort_args_ok(n)) return fail(C3DGS_E_INVALID, "debug_depth_sort: bad arguments (or the rocPRIM path is selected)");
+    if (!keys || !rects || !order || !keys_sorted || !rects_sorted || !temp || !passes_run)
+        return fail(C3DGS_E_INVALID, "debug_depth_sort: NULL buffer");
+    if (temp_bytes < c3dgs_debug_depth_sort_temp_bytes(n))
+        return fail(C3DGS_E_INVALID, "debug_depth_sort: temp smaller than c3dgs_debug_depth_sort_temp_bytes()");
+    hipStream_t s = (hipStream_t)stream;
+    const int P = (int)n;
+    const size_t sort_bytes = onesweep_depth_temp_bytes(P);
+    const uint2* r_in = (const uint2*)rects;
+    uint2* r_out = (uint2*)rects_sorted;
+    if (prefiltered || !depth_sort3_available(P, sort_bytes, true)) {
+        C3DGS_HIP_TRY(run_depth_sort(temp, sort_bytes, keys, keys_sorted, nullptr, order, P, r_in, r_out, s, false, true, false));
+        *passes_run = 4;
+    } else {
+        uint32_t* scan_word = (uint32_t*)((char*)temp + sort_bytes);
+        uint32_t max_key = 0;
+        C3DGS_HIP_TRY(hipMemsetAsync(temp, 0, depth_sort_clear_bytes(P), s));
+        C3DGS_HIP_TRY(onesweep_depth3_hist_scan(temp, sort_bytes, keys, P, 0, scan_word, nullptr, nullptr, 0u, nullptr, s));
+        C3DGS_HIP_TRY(onesweep_depth3_head(temp, sort_bytes, keys, P, r_in, s));
+        C3DGS_HIP_TRY(hipMemcpyAsync(&max_key, onesweep_depth3_max_word(temp, P), sizeof(max_key), hipMemcpyDeviceToHost, s));
+        C3DGS_HIP_TRY(hipStreamSynchronize(s));
+        C3DGS_HIP_TRY(onesweep_depth3_tail(temp, sort_bytes, keys, keys_sorted, order, P, r_in, r_out, max_key, s));
+        *passes_run = depth_sort_plan(true, max_key).passes;
+    }
+    C3DGS_STAGE("debug_depth_sort", 1, s);
+    if (onesweep_timed_out(s)) return fail(C3DGS_E_HIP, "debug_depth_sort: look-back timed out");
     return C3DGS_OK;
 }
 

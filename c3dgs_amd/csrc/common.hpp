@@ -53,6 +53,33 @@ __device__ __host__ __forceinline__ float ord2f(uint32_t o)
     return f;
 }
 
+// ---------------------------------------------------------------- depth-sort digit plan
+// A depth key is the bit pattern of view-space z; preprocess culls z <= 0.01 unless `prefiltered`, and marks culled Gaussians with
+// DEPTH_KEY_CULLED. Every visible key of a forward that is not prefiltered is therefore at least DEPTH_KEY_BIAS (the bits of
+// 2^-7), and key - bias keeps the order of the keys. The sentinel keeps its value. Digits of the sort are taken from that biased
+// key, least significant first: three 9-bit digits order every key below DEPTH_KEY_LIMIT3 (depths below 512; the largest 27-bit
+// value is left to the sentinel's low digits, so no visible key ties with it), a fourth digit of 5 bits orders the rest.
+// Not biased (prefiltered input: keys below the bias can occur): the raw key in four 8-bit digits.
+constexpr uint32_t DEPTH_KEY_CULLED = 0xFFFFFFFFu, DEPTH_KEY_BIAS = 0x3C000000u;
+constexpr int DEPTH_SORT3_BITS = 9;
+constexpr uint32_t DEPTH_KEY_LIMIT3 = DEPTH_KEY_BIAS + (1u << (3 * DEPTH_SORT3_BITS)) - 1u;
+__host__ __device__ __forceinline__ uint32_t depth_key_biased(uint32_t key) { return key == DEPTH_KEY_CULLED ? key : key - DEPTH_KEY_BIAS; }
+struct DepthSortPlan { int passes; int bits[4]; uint32_t bias; };
+// max_visible_key: the largest key that is not the sentinel (0 = none visible)
+inline DepthSortPlan depth_sort_plan(bool biased, uint32_t max_visible_key)
+{
+    if (!biased) return { 4, { 8, 8, 8, 8 }, 0u };
+    if (max_visible_key < DEPTH_KEY_LIMIT3) return { 3, { DEPTH_SORT3_BITS, DEPTH_SORT3_BITS, DEPTH_SORT3_BITS, 0 }, DEPTH_KEY_BIAS };
+    return { 4, { DEPTH_SORT3_BITS, DEPTH_SORT3_BITS, DEPTH_SORT3_BITS, 32 - 3 * DEPTH_SORT3_BITS }, DEPTH_KEY_BIAS };
+}
+inline uint32_t depth_sort_digit(const DepthSortPlan& plan, uint32_t key, int pass)
+{
+    const uint32_t t = plan.bias ? depth_key_biased(key) : key;
+    int shift = 0;
+    for (int p = 0; p < pass; p++) shift += plan.bits[p];
+    return (t >> shift) & ((1u << plan.bits[pass]) - 1u);
+}
+
 // ---------------------------------------------------------------- scratch layouts
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
@@ -333,6 +360,9 @@ hipError_t run_depth_hist_scan(void* temp, size_t temp_bytes, const uint32_t* ke
 hipError_t run_tile_sort(void* temp, size_t temp_bytes, const void* kin, void* kout, int key_bytes, const uint32_t* vin,
                          uint32_t* vout, int R, int end_bit, hipStream_t s, bool ctrl_cleared = false);
 size_t depth_sort_clear_bytes(int P);
+// may this forward's depth sort take the biased three-pass plan (onesweep_depth3_* below)? The caller adds what only it knows:
+// not prefiltered, control words cleared, a mapped host pad to read the largest visible key from
+bool depth_sort3_available(int P, size_t temp_bytes, bool rects_fit_bytes);
 size_t tile_sort_clear_bytes(int R, int end_bit, int key_bytes);
 // radix_sort.hip (hand-written onesweep; C3DGS_SORT_ROCPRIM=1 selects the rocPRIM path of binning.hip instead)
 bool onesweep_enabled();
@@ -347,6 +377,16 @@ hipError_t onesweep_depth_sort(void* temp, size_t temp_bytes, const uint32_t* ki
                                bool rects_fit_bytes = false, bool hist_done = false);
 hipError_t onesweep_depth_hist_scan(void* temp, size_t temp_bytes, const uint32_t* keys, int P, int nb, uint32_t* base,
                                     const uint32_t* sort_err, uint32_t* host_out, uint32_t host_seq, hipStream_t s);
+// the depth sort on biased keys (depth_sort_plan above), in two halves around the forward's host read: histogram (+ id-order scan,
+// + the largest visible key to the two mapped host words at `host_max`: {key, host_seq}), passes 1-2, then -- once the host knows
+// the largest visible key -- the last pass or two. Needs the packed-rectangle payload (grids up to 255 x 255 tiles) and the first
+// onesweep_depth_clear_bytes(P) bytes of `temp` cleared by an earlier kernel on the stream.
+hipError_t onesweep_depth3_hist_scan(void* temp, size_t temp_bytes, const uint32_t* keys, int P, int nb, uint32_t* base,
+                                     const uint32_t* sort_err, uint32_t* host_out, uint32_t host_seq, uint32_t* host_max, hipStream_t s);
+const uint32_t* onesweep_depth3_max_word(void* temp, int P);   // device word that holds the largest visible key behind that launch
+hipError_t onesweep_depth3_head(void* temp, size_t temp_bytes, const uint32_t* kin, int P, const uint2* rects, hipStream_t s);
+hipError_t onesweep_depth3_tail(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout, uint32_t* vout, int P,
+                                const uint2* rects, uint2* rects_sorted, uint32_t max_visible_key, hipStream_t s);
 hipError_t onesweep_tile_sort32(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout, const uint32_t* vin, uint32_t* vout,
                                 int R, int end_bit, hipStream_t s, bool ctrl_cleared = false);   // 32-bit tile keys (more than 65,536 tiles)
 hipError_t onesweep_tile_sort(void* temp, size_t temp_bytes, const uint16_t* kin, uint16_t* kout, const uint32_t* vin, uint32_t* vout,

@@ -13,6 +13,8 @@
 //           os_pass_kernel<.., PRE = false> finds the offsets by a chained look-back over the earlier tiles' status words. ONE
 //           clear per sort (digit histograms + look-back words + tickets are one contiguous block, normally cleared by the kernel
 //           in front of the sort) instead of the two 5-microsecond fill launches rocPRIM issues in front of every digit pass.
+//       The forward's depth sort takes its digits from a biased key and runs three 9-bit passes of this kind instead of four 8-bit
+//           ones (os_hist3_scan_kernel, onesweep_depth3_head / _tail; the plan is common.hpp's depth_sort_plan).
 // Structure of one digit pass (os_pass_kernel), per tile:
 //   ticket      (look-back passes only) blocks take their tile index from an atomic counter, so every predecessor of a block is
 //               already running (forward progress of the look-back does not depend on the dispatch order); table-driven passes
@@ -29,6 +31,7 @@
 #include "scan_blocks.hpp"
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace c3dgs {
 
@@ -83,6 +86,16 @@ __device__ unsigned long long g_os_times[64 * 8];   // stays zero in a diag vari
 #endif
 
 struct OsPlan { int passes; int bits[OS_MAX_PASSES]; };
+
+// The depth sort on biased keys (common.hpp: depth_sort_plan / depth_key_biased). A depth key that passed preprocess's near-plane
+// test is at least DEPTH_KEY_BIAS, so key - bias has 27 live bits for every depth below 512: three 9-bit digit passes order what
+// four 8-bit passes order on the raw pattern. The culled sentinel 0xFFFFFFFF keeps its value, so its three low digits are the top
+// of the digit range and it sorts last. A visible key at or above DEPTH_KEY_LIMIT3 needs a fourth pass on the 5 bits above the 27:
+// the histogram launch reduces the largest visible key, the host reads it with num_rendered and queues the last pass or two.
+constexpr int OS_RADIX3 = 512, OS_BITS3 = 9, OS_BITS3_TOP = 32 - 3 * OS_BITS3;
+static_assert(OS_RADIX3 == C3DGS_OS_BLOCK32, "one thread per digit in the biased depth sort's passes");
+static_assert(OS_RADIX3 == (1 << DEPTH_SORT3_BITS) && 3 * OS_BITS3 == 27 && DEPTH_KEY_LIMIT3 == DEPTH_KEY_BIAS + (1u << 27) - 1u, "common.hpp's plan");
+template <bool XF> __device__ __forceinline__ uint32_t os_digit_src(uint32_t k) { return XF ? depth_key_biased(k) : k; }
 
 // Measured for the two table-driven passes of the 13-bit tile sort (16.4 M pairs, whole sort): 7 + 6 153.6 us, 6 + 7 154.4 us,
 // 8 + 5 158.9 us -- an 8-bit pass costs 8 us more than a 7-bit one (scatter runs half as long), a 5-bit pass saves 5 us on a 6-bit one
@@ -181,6 +194,93 @@ os_hist_scan_kernel(const uint32_t* __restrict__ keys, size_t n, OsPlan plan, ui
     else os_hist_body<uint32_t>(keys, n, plan, hist, blockIdx.x - 1, gridDim.x - 1);
 }
 
+// The biased depth sort's histogram: three 9-bit digits of the transformed key and the largest visible key, one read of the keys.
+// Control words behind the look-back words (os3_layout): `maxw` takes every workgroup's largest visible key, `done` counts the
+// workgroups that have added theirs; the one that counts last stores the result to the mapped host words {max key, host_seq}
+// (`host_max`, optional). Nobody waits for anybody: the last arrival is whoever it is.
+__device__ __forceinline__ void os_hist3_body(const uint32_t* __restrict__ keys, size_t n, uint32_t* __restrict__ hist, uint32_t* __restrict__ maxw,
+                                              uint32_t* __restrict__ done, uint32_t* __restrict__ host_max, uint32_t host_seq,
+                                              unsigned block, unsigned nblocks)
+{
+    __shared__ uint32_t s_h[3][OS_RADIX3];
+    __shared__ uint32_t s_max;
+    for (int q = threadIdx.x; q < 3 * OS_RADIX3; q += OS_HIST_BLOCK) (&s_h[0][0])[q] = 0;
+    if (threadIdx.x == 0) s_max = 0;
+    __syncthreads();
+    uint32_t mx = 0;
+    auto add = [&](uint32_t k) {
+        const uint32_t t = depth_key_biased(k);
+        atomicAdd(&s_h[0][t & (OS_RADIX3 - 1)], 1u);
+        atomicAdd(&s_h[1][(t >> OS_BITS3) & (OS_RADIX3 - 1)], 1u);
+        atomicAdd(&s_h[2][(t >> (2 * OS_BITS3)) & (OS_RADIX3 - 1)], 1u);
+        if (k != DEPTH_KEY_CULLED) mx = max(mx, k);
+    };
+    auto add4 = [&](const uint4 v) { add(v.x); add(v.y); add(v.z); add(v.w); };
+    const size_t nvec = n / 4;
+    const uint4* k4 = reinterpret_cast<const uint4*>(keys);
+    const size_t stride = (size_t)nblocks * OS_HIST_BLOCK;
+    size_t i = (size_t)block * OS_HIST_BLOCK + threadIdx.x;
+    for (; i + 3 * stride < nvec; i += 4 * stride) {
+        const uint4 v0 = k4[i], v1 = k4[i + stride], v2 = k4[i + 2 * stride], v3 = k4[i + 3 * stride];
+        add4(v0); add4(v1); add4(v2); add4(v3);
+    }
+    for (; i < nvec; i += stride) add4(k4[i]);
+    for (size_t j = nvec * 4 + (size_t)block * OS_HIST_BLOCK + threadIdx.x; j < n; j += stride) add(keys[j]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+    if ((threadIdx.x & 63) == 0 && mx) atomicMax(&s_max, mx);
+    __syncthreads();
+    for (int q = threadIdx.x; q < 3 * OS_RADIX3; q += OS_HIST_BLOCK) {
+        const uint32_t v = (&s_h[0][0])[q];
+        if (v) atomicAdd(&hist[q], v);
+    }
+    if (threadIdx.x == 0) {
+        if (s_max) __hip_atomic_fetch_max(maxw, s_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t before = __hip_atomic_fetch_add(done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (before == nblocks - 1 && host_max) {
+            const uint32_t m = __hip_atomic_load(maxw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(host_max, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(host_max + 1, host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);   // publishes the word above
+        }
+    }
+}
+
+// as os_hist_scan_kernel, for the biased depth sort: workgroup 0 the id-order scan and its num_rendered store, the others the histogram
+__global__ void __launch_bounds__(OS_HIST_BLOCK)
+os_hist3_scan_kernel(const uint32_t* __restrict__ keys, size_t n, uint32_t* __restrict__ hist, uint32_t* __restrict__ maxw, uint32_t* __restrict__ done,
+                     uint32_t* __restrict__ host_max, int nb, uint32_t* __restrict__ base, const uint32_t* __restrict__ sort_err,
+                     uint32_t* __restrict__ host_out, uint32_t host_seq)
+{
+    if (blockIdx.x == 0) scan_blocks_body(nb, base, sort_err, host_out, host_seq);
+    else os_hist3_body(keys, n, hist, maxw, done, host_max, host_seq, blockIdx.x - 1, gridDim.x - 1);
+}
+
+// the fourth pass's histogram (the 5 bits above the 27), launched only where the largest visible key asks for that pass: most keys
+// share a digit, so a wave counts its lanes per distinct digit with a ballot and adds once
+__global__ void __launch_bounds__(OS_HIST_BLOCK) os_hist3_top_kernel(const uint32_t* __restrict__ keys, size_t n, uint32_t* __restrict__ hist)
+{
+    __shared__ uint32_t s_h[1 << OS_BITS3_TOP];
+    if (threadIdx.x < (1 << OS_BITS3_TOP)) s_h[threadIdx.x] = 0;
+    __syncthreads();
+    const size_t stride = (size_t)gridDim.x * OS_HIST_BLOCK;
+    const size_t rounds = (n + stride - 1) / stride;                 // uniform trip count: every lane takes part in the ballots
+    for (size_t r = 0; r < rounds; r++) {
+        const size_t i = r * stride + (size_t)blockIdx.x * OS_HIST_BLOCK + threadIdx.x;
+        const bool ok = i < n;
+        const uint32_t d = ok ? depth_key_biased(keys[i]) >> (3 * OS_BITS3) : 0u;
+        unsigned long long left = __ballot(ok);
+        while (left) {
+            const int leader = __ffsll((long long)left) - 1;
+            const uint32_t dl = (uint32_t)__shfl((int)d, leader);
+            const unsigned long long same = __ballot(ok && d == dl) & left;
+            if ((int)(threadIdx.x & 63) == leader) atomicAdd(&s_h[dl], (uint32_t)__popcll(same));
+            left &= ~same;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < (1 << OS_BITS3_TOP) && s_h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], s_h[threadIdx.x]);
+}
+
 // tile-by-tile histogram of ONE digit of the u16 sort: workgroup b counts the digit (bits [shift, shift + bits)) over tile b of
 // `keys` (the tile b of the pass kernel that reads the same keys) and stores the counts as row b of the table -- plain stores, no
 // global atomics (the closing atomics of os_hist_kernel are what makes it slower with more workgroups)
@@ -261,7 +361,10 @@ __device__ __forceinline__ uint2 os_unpack_rect(uint32_t w)
     return make_uint2((w & 0xffu) | (((w >> 8) & 0xffu) << 16), ((w >> 16) & 0xffu) | ((w >> 24) << 16));
 }
 
-template <class K, int BITS, bool PRE, bool PAY2 = false>
+// RADIX / XF (depth sort on biased keys, see os_depth_xf): RADIX = 512 gives every one of the 512 threads a digit; its per-wave
+// counters are 16 bits wide (a wave owns TILE / waves = 1536 items, a tile 12288: both below 65,536), which is what keeps the PAY2
+// instantiation inside the LDS. XF: the digit is taken from the transformed key; the keys that travel and are stored stay as they are.
+template <class K, int BITS, bool PRE, bool PAY2 = false, int RADIX = OS_RADIX, bool XF = false>
 __global__ void __launch_bounds__(OsShape<K>::BLOCK)
 os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* __restrict__ vin, uint32_t* __restrict__ vout,
                uint32_t n, int shift, const uint32_t* __restrict__ hist, uint32_t* __restrict__ status, uint32_t* __restrict__ ticket,
@@ -271,19 +374,25 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
     constexpr uint32_t ERR_BIT = sizeof(K) == 2 ? 1u : 2u;
     constexpr uint32_t MASK = (1u << BITS) - 1;
     constexpr int OS_BLOCK = OsShape<K>::BLOCK, OS_IPT = OsShape<K>::IPT, OS_WAVES = OS_BLOCK / 64;
-    __shared__ uint32_t s_cnt[OS_WAVES][OS_RADIX];   // per-wave digit counters, later exclusive prefixes across the waves
-    __shared__ uint32_t s_start[OS_RADIX];           // start of every digit in the tile-sorted order
-    __shared__ int32_t s_gbase[OS_RADIX];            // global position = s_gbase[digit] + tile-sorted position
-    __shared__ uint32_t s_wtot[4];
-    __shared__ uint32_t s_bid;
     constexpr int OS_TILE = OsShape<K>::TILE;
+    using CNT = typename std::conditional<(RADIX > 256), uint16_t, uint32_t>::type;
+    static_assert(RADIX % 64 == 0 && RADIX <= OS_BLOCK && BITS <= 9 && (1 << BITS) <= RADIX, "one thread per digit");
+    static_assert(!XF || sizeof(K) == 4, "the transform is the depth keys'");
+    static_assert(sizeof(CNT) == 4 || OS_TILE < 65536, "a 16-bit counter holds up to a tile's items");
+    static_assert(sizeof(CNT) * OS_WAVES * RADIX + 8 * RADIX + 4 * (RADIX / 64) + 4 + sizeof(K) * OS_TILE + 4 * OS_TILE * (PAY2 ? 2 : 1) + (PAY2 ? 0 : 4)
+                      <= 160 * 1024, "LDS of one workgroup (160 KB per CU)");
+    __shared__ CNT s_cnt[OS_WAVES][RADIX];        // per-wave digit counters, later exclusive prefixes across the waves
+    __shared__ uint32_t s_start[RADIX];           // start of every digit in the tile-sorted order
+    __shared__ int32_t s_gbase[RADIX];            // global position = s_gbase[digit] + tile-sorted position
+    __shared__ uint32_t s_wtot[RADIX / 64];
+    __shared__ uint32_t s_bid;
     __shared__ K s_keys[OS_TILE];
     __shared__ uint32_t s_vals[OS_TILE];
     __shared__ uint32_t s_vals2[PAY2 ? OS_TILE : 1];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) s_bid = PRE ? blockIdx.x : atomicAdd(ticket, 1u);
-    for (int q = tid; q < OS_WAVES * OS_RADIX; q += OS_BLOCK) (&s_cnt[0][0])[q] = 0;
+    for (int q = tid; q < OS_WAVES * RADIX; q += OS_BLOCK) (&s_cnt[0][0])[q] = 0;
     __syncthreads();
     const uint32_t bid = s_bid;
     OS_T(0)
@@ -311,12 +420,12 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
     const uint32_t lt_lo = lane < 32 ? (1u << lane) - 1u : 0xffffffffu, lt_hi = lane < 32 ? 0u : (1u << (lane - 32)) - 1u;
     OS_T_LOADS_DONE()
     OS_T(1)
-    uint32_t* wc = s_cnt[wave];                       // other lanes of the wave update these between iterations
+    CNT* wc = s_cnt[wave];                       // other lanes of the wave update these between iterations
 #pragma unroll
     for (int k = 0; k < OS_IPT; k++) {
         const uint32_t idx = wbase + (uint32_t)k * 64u + lane;
         const bool ok = idx < n;
-        const uint32_t d = ((uint32_t)key[k] >> shift) & MASK;
+        const uint32_t d = (os_digit_src<XF>((uint32_t)key[k]) >> shift) & MASK;
         const unsigned long long okb = __ballot(ok);  // padding lanes of the last tile take no part
         uint32_t plo = (uint32_t)okb, phi = (uint32_t)(okb >> 32);
 #pragma unroll
@@ -331,7 +440,7 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
             const uint32_t before = __hip_atomic_load(&wc[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
             const uint32_t below = (uint32_t)__popc(plo & lt_lo) + (uint32_t)__popc(phi & lt_hi);
             rank[k] = before + below;
-            if (below == 0) __hip_atomic_store(&wc[d], before + (uint32_t)__popc(plo) + (uint32_t)__popc(phi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            if (below == 0) __hip_atomic_store(&wc[d], (CNT)(before + (uint32_t)__popc(plo) + (uint32_t)__popc(phi)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -340,32 +449,32 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
     OS_T(2)
     __syncthreads();
     OS_T(3)
-    // thread d (< 256): the tile's count of digit d, exclusive prefixes across the waves, then across the digits
+    // thread d (< RADIX): the tile's count of digit d, exclusive prefixes across the waves, then across the digits
     uint32_t tot = 0;
-    if (tid < OS_RADIX) {
+    if (tid < RADIX) {
 #pragma unroll
-        for (int w = 0; w < OS_WAVES; w++) { const uint32_t c = s_cnt[w][tid]; s_cnt[w][tid] = tot; tot += c; }
+        for (int w = 0; w < OS_WAVES; w++) { const uint32_t c = s_cnt[w][tid]; s_cnt[w][tid] = (CNT)tot; tot += c; }
     }
     uint32_t incl = tot;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-    if (tid < OS_RADIX && lane == 63) s_wtot[wave] = incl;
+    if (tid < RADIX && lane == 63) s_wtot[wave] = incl;
     __syncthreads();
     uint32_t start = 0, pre = 0;
-    if (tid < OS_RADIX) {
+    if (tid < RADIX) {
         uint32_t off = 0;
         for (int w = 0; w < wave; w++) off += s_wtot[w];
         start = off + incl - tot;
         s_start[tid] = start;
         // decoupled look-back over the earlier tiles for digit `tid`
-        uint32_t* my = status + (size_t)bid * OS_RADIX + tid;
+        uint32_t* my = status + (size_t)bid * RADIX + tid;
         if (PRE) pre = tid < (1 << BITS) ? status[(size_t)tid * gridDim.x + bid] : 0u;   // column-major table of this pass's digit
         else if (bid == 0) os_store(my, OS_FLAG_PRE | tot);
         else {
             os_store(my, OS_FLAG_AGG | tot);
             for (int64_t b = (int64_t)bid - 1;; b--) {
                 uint32_t s, spins = 0;
-                do { s = os_load(status + (size_t)b * OS_RADIX + tid); } while ((s >> 30) == 0 && ++spins < OS_SPIN_LIMIT);
+                do { s = os_load(status + (size_t)b * RADIX + tid); } while ((s >> 30) == 0 && ++spins < OS_SPIN_LIMIT);
                 if ((s >> 30) == 0) { atomicOr(&g_os_error, ERR_BIT); break; }   // never hang the device: give up, flag it
                 pre += s & OS_CNT_MASK;
                 if (s & OS_FLAG_PRE) break;
@@ -374,15 +483,15 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
         }
     }
     OS_T(4)
-    // exclusive scan of the global digit histogram by the same 256 threads
-    const uint32_t h = tid < OS_RADIX ? hist[tid] : 0u;
+    // exclusive scan of the global digit histogram by the same RADIX threads
+    const uint32_t h = tid < RADIX ? hist[tid] : 0u;
     uint32_t hincl = h;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(hincl, o); if (lane >= o) hincl += t; }
     __syncthreads();
-    if (tid < OS_RADIX && lane == 63) s_wtot[wave] = hincl;
+    if (tid < RADIX && lane == 63) s_wtot[wave] = hincl;
     __syncthreads();
-    if (tid < OS_RADIX) {
+    if (tid < RADIX) {
         uint32_t off = 0;
         for (int w = 0; w < wave; w++) off += s_wtot[w];
         s_gbase[tid] = (int32_t)(off + hincl - h + pre) - (int32_t)start;
@@ -393,7 +502,7 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
     for (int k = 0; k < OS_IPT; k++) {
         const uint32_t idx = wbase + (uint32_t)k * 64u + lane;
         if (idx < n) {
-            const uint32_t d = ((uint32_t)key[k] >> shift) & MASK;
+            const uint32_t d = (os_digit_src<XF>((uint32_t)key[k]) >> shift) & MASK;
             const uint32_t p = s_start[d] + s_cnt[wave][d] + rank[k];
             s_keys[p] = key[k];
             s_vals[p] = val[k];
@@ -407,7 +516,7 @@ os_pass_kernel(const K* __restrict__ kin, K* __restrict__ kout, const uint32_t* 
         const uint32_t p = (uint32_t)tid + (uint32_t)m * OS_BLOCK;
         if (p < valid) {
             const K kk = s_keys[p];
-            const uint32_t d = ((uint32_t)kk >> shift) & MASK;
+            const uint32_t d = (os_digit_src<XF>((uint32_t)kk) >> shift) & MASK;
             const uint32_t g = (uint32_t)(s_gbase[d] + (int32_t)p);
             kout[g] = kk;
             const uint32_t vv = s_vals[p];
@@ -539,6 +648,84 @@ static hipError_t os_sort(void* temp, size_t temp_bytes, const K* kin, K* kout, 
     }
 }
 
+// ---- the depth sort on biased keys: scratch layout and the two halves of the sort around the forward's host read
+// control block (all cleared by the caller's earlier kernel, onesweep_depth_clear_bytes):
+//   [histograms: 3 x 512 | 256 | look-back words: 3 x tiles x 512 | tiles x 256 | 64 words: tickets 0..3, 8 = max visible key, 9 = done]
+// then the two (key, id) buffers and the two second-payload buffers, as os_sort lays them out.
+struct Os3Layout {
+    size_t blocks, ctrl_bytes, total_bytes;
+    uint32_t *hist[4], *status[4], *ticket, *maxw, *done;
+    uint32_t *tk[2], *tv[2], *t2[2];
+};
+static Os3Layout os3_layout(void* temp, size_t n)
+{
+    Os3Layout L;
+    L.blocks = os_blocks<uint32_t>(n);
+    const size_t hist_words = 3 * OS_RADIX3 + OS_RADIX, status_words = L.blocks * hist_words;
+    L.ctrl_bytes = align_up((hist_words + status_words + 64) * sizeof(uint32_t));
+    uint32_t* w = (uint32_t*)temp;
+    for (int p = 0; p < 4; p++) {
+        L.hist[p] = w + (size_t)p * OS_RADIX3;
+        L.status[p] = w + hist_words + (size_t)p * L.blocks * OS_RADIX3;
+    }
+    L.ticket = w + hist_words + status_words;
+    L.maxw = L.ticket + 8;
+    L.done = L.ticket + 9;
+    char* q = (char*)temp + L.ctrl_bytes;
+    const size_t a = align_up(n * sizeof(uint32_t));
+    for (int i = 0; i < 2; i++) { L.tk[i] = (uint32_t*)q; q += a; L.tv[i] = (uint32_t*)q; q += a; }
+    for (int i = 0; i < 2; i++) { L.t2[i] = (uint32_t*)q; q += a; }
+    L.total_bytes = (size_t)(q - (char*)temp);
+    return L;
+}
+static bool os3_args_ok(size_t temp_bytes, int P)
+{
+    return P > 0 && (size_t)P < ((size_t)1 << 30) && os3_layout(nullptr, (size_t)P).total_bytes <= temp_bytes;
+}
+
+hipError_t onesweep_depth3_hist_scan(void* temp, size_t temp_bytes, const uint32_t* keys, int P, int nb, uint32_t* base,
+                                     const uint32_t* sort_err, uint32_t* host_out, uint32_t host_seq, uint32_t* host_max, hipStream_t s)
+{
+    if (!os3_args_ok(temp_bytes, P)) return hipErrorInvalidValue;
+    const Os3Layout L = os3_layout(temp, (size_t)P);
+    os_hist3_scan_kernel<<<1u + os_hist_blocks<uint32_t>((size_t)P), OS_HIST_BLOCK, 0, s>>>(keys, (size_t)P, L.hist[0], L.maxw, L.done, host_max, nb,
+                                                                                            base, sort_err, host_out, host_seq);
+    return hipGetLastError();
+}
+const uint32_t* onesweep_depth3_max_word(void* temp, int P) { return os3_layout(temp, (size_t)(P > 0 ? P : 1)).maxw; }
+
+// passes 1 and 2 (of the low 18 bits): they do not depend on how many passes follow
+hipError_t onesweep_depth3_head(void* temp, size_t temp_bytes, const uint32_t* kin, int P, const uint2* rects, hipStream_t s)
+{
+    if (!os3_args_ok(temp_bytes, P) || !rects) return hipErrorInvalidValue;
+    const Os3Layout L = os3_layout(temp, (size_t)P);
+    const unsigned blocks = (unsigned)L.blocks;
+    os_pass_kernel<uint32_t, OS_BITS3, false, true, OS_RADIX3, true><<<blocks, C3DGS_OS_BLOCK32, 0, s>>>(
+        kin, L.tk[0], nullptr, L.tv[0], (uint32_t)P, 0, L.hist[0], L.status[0], L.ticket + 0, rects, nullptr, nullptr, L.t2[0]);
+    os_pass_kernel<uint32_t, OS_BITS3, false, true, OS_RADIX3, true><<<blocks, C3DGS_OS_BLOCK32, 0, s>>>(
+        L.tk[0], L.tk[1], L.tv[0], L.tv[1], (uint32_t)P, OS_BITS3, L.hist[1], L.status[1], L.ticket + 1, rects, nullptr, L.t2[0], L.t2[1]);
+    return hipGetLastError();
+}
+// pass 3, the last one where every visible key is below DEPTH_KEY_LIMIT3; otherwise pass 3 into the free buffer, the histogram of
+// the 5 bits above and pass 4 on them. Either way the results land in kout / vout / rects_sorted as the four 8-bit passes leave them.
+hipError_t onesweep_depth3_tail(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout, uint32_t* vout, int P,
+                                const uint2* rects, uint2* rects_sorted, uint32_t max_visible_key, hipStream_t s)
+{
+    if (!os3_args_ok(temp_bytes, P) || !rects || !rects_sorted) return hipErrorInvalidValue;
+    const Os3Layout L = os3_layout(temp, (size_t)P);
+    const unsigned blocks = (unsigned)L.blocks;
+    const bool four = depth_sort_plan(true, max_visible_key).passes == 4;
+    os_pass_kernel<uint32_t, OS_BITS3, false, true, OS_RADIX3, true><<<blocks, C3DGS_OS_BLOCK32, 0, s>>>(
+        L.tk[1], four ? L.tk[0] : kout, L.tv[1], four ? L.tv[0] : vout, (uint32_t)P, 2 * OS_BITS3, L.hist[2], L.status[2], L.ticket + 2, rects,
+        rects_sorted, L.t2[1], four ? L.t2[0] : nullptr);
+    if (four) {
+        os_hist3_top_kernel<<<os_hist_blocks<uint32_t>((size_t)P), OS_HIST_BLOCK, 0, s>>>(kin, (size_t)P, L.hist[3]);
+        os_pass_kernel<uint32_t, OS_BITS3_TOP, false, true, OS_RADIX, true><<<blocks, C3DGS_OS_BLOCK32, 0, s>>>(
+            L.tk[0], kout, L.tv[0], vout, (uint32_t)P, 3 * OS_BITS3, L.hist[3], L.status[3], L.ticket + 3, rects, rects_sorted, L.t2[0], nullptr);
+    }
+    return hipGetLastError();
+}
+
 #ifdef C3DGS_DIAG
 int os_read_times(unsigned long long* out512)
 {
@@ -577,12 +764,21 @@ bool onesweep_enabled()
     static const bool on = []() { const char* e = std::getenv("C3DGS_SORT_ROCPRIM"); return !(e && e[0] == '1'); }();
     return on;
 }
-size_t onesweep_depth_temp_bytes(int P) { return os_temp_bytes<uint32_t>((size_t)(P > 0 ? P : 1), 32, true); }   // room for the second payload
+// room for the second payload, in the four-pass and in the biased layout
+size_t onesweep_depth_temp_bytes(int P)
+{
+    const size_t n = (size_t)(P > 0 ? P : 1);
+    return std::max(os_temp_bytes<uint32_t>(n, 32, true), os3_layout(nullptr, n).total_bytes);
+}
 size_t onesweep_tile_temp_bytes(int R, int end_bit, int key_bytes)
 {
     return key_bytes == 4 ? os_temp_bytes<uint32_t>((size_t)(R > 0 ? R : 1), end_bit) : os_temp_bytes<uint16_t>((size_t)(R > 0 ? R : 1), end_bit);
 }
-size_t onesweep_depth_clear_bytes(int P) { return os_clear_bytes<uint32_t>((size_t)(P > 0 ? P : 1), 32); }
+size_t onesweep_depth_clear_bytes(int P)      // covers the control words of both layouts (both start at the front of the scratch)
+{
+    const size_t n = (size_t)(P > 0 ? P : 1);
+    return std::max(os_clear_bytes<uint32_t>(n, 32), os3_layout(nullptr, n).ctrl_bytes);
+}
 size_t onesweep_tile_clear_bytes(int R, int end_bit, int key_bytes)
 {
     return key_bytes == 4 ? os_clear_bytes<uint32_t>((size_t)(R > 0 ? R : 1), end_bit) : os_clear_bytes<uint16_t>((size_t)(R > 0 ? R : 1), end_bit);
