@@ -184,8 +184,9 @@ def _draws_for_counts(q, wanted):
     return np.array(u, dtype=np.float64)
 
 
-@pytest.mark.parametrize("factor", [True, False])
-def test_relocation_values_against_float64(hip, factor):
+def _relocation_case(factor):
+    """-> (model, snapshot before, dead mask on the device, draws, wanted counts, counts, number of dead rows): the case of
+    test_relocation_values_against_float64, shared with tests/test_scratch_poison_gpu.py"""
     from c3dgs_amd import mcmc
     os_, ks = (0.006, 0.3, 0.9, 0.99, 1 - 1e-6), (1, 2, 4, 19, 50)         # N = count + 1 in {2, 3, 5, 20, 51}
     live = [(o, k) for o in os_ for k in ks]
@@ -204,6 +205,12 @@ def test_relocation_values_against_float64(hip, factor):
     assert draws.shape[0] == n_dead
     _, counts, _ = ref.sample(q, draws)
     assert np.array_equal(counts, wanted)
+    return m, before, dead_d, draws, wanted, counts, n_dead
+
+
+@pytest.mark.parametrize("factor", [True, False])
+def test_relocation_values_against_float64(hip, factor):
+    m, before, dead_d, draws, wanted, counts, n_dead = _relocation_case(factor)
     assert m.relocate_gs(dead_d, MIN_OPACITY, torch.from_numpy(draws).to(DEV)) == n_dead
     worst = _check_values(m, before, np.nonzero(wanted)[0], counts, f"factor={factor}")
     print(f"relocation values, factor={factor}: worst relative distance from float64: raw opacity {worst[0]:.3g}, raw scale {worst[1]:.3g}")

@@ -71,6 +71,12 @@ def test_kernels_alone_against_float64_on_the_same_arrays(hip, name, case, kw):
     against float64 add a few 2^-24 of their own terms)."""
     inp, cam, indexed, pose, fw, bw = _kernel_inputs(case, kw)
     got = _pose_grad(hip, inp, fw, bw, pose).cpu().numpy().astype(np.float64)
+    check_kernels_alone(name, inp, cam, pose, fw, bw, got)
+
+
+def check_kernels_alone(name, inp, cam, pose, fw, bw, got):
+    """the seven components `got` (float64) of the kernels on forward `fw` and backward `bw` against float64 on the same arrays, at
+    the bar of test_kernels_alone_against_float64_on_the_same_arrays; shared with tests/test_scratch_poison_gpu.py"""
     u = gpu_util.unpack(fw)
     radii = u["radii"]
     assert int((radii > 0).sum()) >= 1 and np.abs(bw["dL_dmeans3D"]).max() > 0          # something was blended

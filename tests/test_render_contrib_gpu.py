@@ -83,6 +83,21 @@ def _reference(name):
     return contrib_ref.walk(st, st.W, st.H)
 
 
+def check_against_walk(name, u, wsum, wmax, hits, ref=None):
+    """the three rows of scene `name` (its forward unpacked: `u`) against the float64 walk (`ref`: contrib_ref.walk of another
+    scene's oracle state): point 1 of the module's list, shared with tests/test_scratch_poison_gpu.py and
+    tests/test_call_sequence_gpu.py"""
+    P = int(u["radii"].size)
+    ref = _reference(name) if ref is None else ref
+    exempt, rel_sum, rel_max = contrib_ref.compare(wsum, wmax, hits, ref, name + " GPU vs float64 walk:")
+    assert exempt <= contrib_ref.exemption_cap(P)
+    assert rel_sum <= 1e-4 and rel_max <= 1e-4
+    dead = u["radii"] == 0
+    assert (_bits(wsum)[dead] == 0).all() and (_bits(wmax)[dead] == 0).all() and (hits[dead] == 0).all()
+    never = hits == 0
+    assert (_bits(wsum)[never] == 0).all() and (_bits(wmax)[never] == 0).all()
+
+
 @pytest.mark.parametrize("name", list(depth_ref.SCENES) + ["long_run"])
 def test_statistics_replay_the_forward(hip, orc, name):
     """Measured on an MI355X, over the seven scenes of tests/depth_ref.py: 0 Gaussians exempt; largest relative difference against
@@ -106,14 +121,7 @@ def test_statistics_replay_the_forward(hip, orc, name):
         assert ((u["tiles_touched"] > 256) & (hits > 0)).any(), "no blended Gaussian whose run takes two trips of the whole-wave fold"
 
     # 1. against the float64 walk
-    ref = _reference(name)
-    exempt, rel_sum, rel_max = contrib_ref.compare(wsum, wmax, hits, ref, name + " GPU vs float64 walk:")
-    assert exempt <= contrib_ref.exemption_cap(P)
-    assert rel_sum <= 1e-4 and rel_max <= 1e-4
-    dead = u["radii"] == 0
-    assert (_bits(wsum)[dead] == 0).all() and (_bits(wmax)[dead] == 0).all() and (hits[dead] == 0).all()
-    never = hits == 0
-    assert (_bits(wsum)[never] == 0).all() and (_bits(wmax)[never] == 0).all()
+    check_against_walk(name, u, wsum, wmax, hits)
 
     # 2. against the product backward: dL_dcolors of an all-ones image gradient
     g = torch.Generator().manual_seed(5)

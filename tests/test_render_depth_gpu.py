@@ -72,26 +72,11 @@ def _median_reference(name):
     return depth_ref.walk(st, st.W, st.H)
 
 
-@pytest.mark.parametrize("name", depth_ref.SCENES)
-def test_maps_replay_the_forward(hip, orc, name):
-    inp, cam, indexed = depth_ref.scene(name)
+def check_maps(name, inp, cam, indexed, st, u, depth, alpha, median, walk=None):
+    """points 1 to 3 of the module's list for the three maps of scene `name` (its forward unpacked: `u`, its oracle state: `st`;
+    `walk`: depth_ref.walk of `st` where the scene is not one of depth_ref.SCENES); shared with tests/test_scratch_poison_gpu.py
+    and tests/test_call_sequence_gpu.py"""
     W, H = cam["W"], cam["H"]
-    st = depth_ref.oracle_state(name)
-    fw = gpu_util.hip_forward(inp, cam, indexed)
-    u = gpu_util.unpack(fw)
-    assert fw["num_rendered"] > 0
-    depth, alpha, median = _maps(fw)
-    assert np.isfinite(depth).all() and np.isfinite(alpha).all() and np.isfinite(median).all()
-
-    if name == "deep":                                      # more than two staged batches of compact entries, per tile and per pixel
-        from tests.test_compact_lists_gpu import _compact
-        c = _compact(fw, u)
-        assert c["tile_used_c"].max() > 2 * 256 + 1 and c["n_contrib_c"].max() > 512, (c["tile_used_c"].max(), c["n_contrib_c"].max())
-    if name == "huge_faint":                                # compact index != list position: whole batches of dead entries
-        from tests.test_compact_lists_gpu import _compact
-        c = _compact(fw, u)
-        assert (u["n_contrib"].astype(np.int64) - c["n_contrib_c"]).max() >= 512
-
     # 1. depth == the product forward's image of the depth-coloured scene, bit for bit
     z = u["depths"].copy()
     z[~np.isfinite(z)] = 0.0                                # culled rows hold 0xFFFFFFFF
@@ -114,7 +99,7 @@ def test_maps_replay_the_forward(hip, orc, name):
     np.testing.assert_array_equal(_bits(alpha).reshape(-1), _bits(np.float32(1.0) - u["final_T"]))
 
     # 3. median against the float64 walk
-    ref = _median_reference(name)
+    ref = _median_reference(name) if walk is None else walk
     n_hip = u["n_contrib"].astype(np.int64)
     skip = n_hip != st.n_contrib.astype(np.int64)
     print(name, "pixels skipped (HIP forward and oracle disagree on n_contrib):", int(skip.sum()))
@@ -133,6 +118,29 @@ def test_maps_replay_the_forward(hip, orc, name):
     print(name, "median: pixels with a crossing", nonzero, "of", int((~skip).sum()), "; with more than one admissible answer", banded)
     assert not wrong, (len(wrong), wrong[:5])
     assert nonzero > 0                                      # T crosses 0.5 somewhere
+
+
+@pytest.mark.parametrize("name", depth_ref.SCENES)
+def test_maps_replay_the_forward(hip, orc, name):
+    inp, cam, indexed = depth_ref.scene(name)
+    W, H = cam["W"], cam["H"]
+    st = depth_ref.oracle_state(name)
+    fw = gpu_util.hip_forward(inp, cam, indexed)
+    u = gpu_util.unpack(fw)
+    assert fw["num_rendered"] > 0
+    depth, alpha, median = _maps(fw)
+    assert np.isfinite(depth).all() and np.isfinite(alpha).all() and np.isfinite(median).all()
+
+    if name == "deep":                                      # more than two staged batches of compact entries, per tile and per pixel
+        from tests.test_compact_lists_gpu import _compact
+        c = _compact(fw, u)
+        assert c["tile_used_c"].max() > 2 * 256 + 1 and c["n_contrib_c"].max() > 512, (c["tile_used_c"].max(), c["n_contrib_c"].max())
+    if name == "huge_faint":                                # compact index != list position: whole batches of dead entries
+        from tests.test_compact_lists_gpu import _compact
+        c = _compact(fw, u)
+        assert (u["n_contrib"].astype(np.int64) - c["n_contrib_c"]).max() >= 512
+
+    check_maps(name, inp, cam, indexed, st, u, depth, alpha, median)
 
     # 4. reproducible, and independent of the backward
     again = _maps(fw)

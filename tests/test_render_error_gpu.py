@@ -120,7 +120,15 @@ def test_scores_against_the_float64_walk(hip, orc, name):
         assert ((u["tiles_touched"] > 256) & (hits > 0)).any(), "no blended Gaussian whose run takes two trips of the whole-wave fold"
         assert hits[0] == W * H                                  # the screen-filling one is blended at every pixel
 
-    ref = _reference(name)
+    check_scores(name, u, err, hits)
+
+
+def check_scores(name, u, err, hits, ref=None):
+    """err_sum under the standard map and the hits of the same forward (unpacked: `u`) against the float64 walk (`ref`: error_ref.walk
+    of another scene's oracle state under the map in use): the bar of test_scores_against_the_float64_walk, shared with
+    tests/test_scratch_poison_gpu.py and tests/test_call_sequence_gpu.py"""
+    P = int(u["radii"].size)
+    ref = _reference(name) if ref is None else ref
     same = hits.astype(np.int64) == ref.hits
     exempt = int((~same).sum())
     d = np.abs(err.astype(np.float64)[same] - ref.err_sum[same]) / np.where(ref.err_sum[same] > 0, ref.err_sum[same], 1.0)
