@@ -125,6 +125,15 @@ PROTOTYPES = {
                                                                    RESIZE_FN, C.c_void_p, C.POINTER(RasterGrads), C.c_void_p]),
     "c3dgs_depth_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "c3dgs_render_depth": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "c3dgs_render_distortion": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp,
+                                          _vp]),
+    "c3dgs_rasterize_gaussians_backward_distortion": (C.c_int, [C.POINTER(RasterParams), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp, _vp,
+                                                                _vp, _vp, C.c_float, C.c_float, RESIZE_FN, _vp,
+                                                                C.POINTER(RasterGrads), _vp]),
+    "c3dgs_rasterize_gaussians_backward_distortion_indexed": (C.c_int, [C.POINTER(RasterParams), _vp, _vp, _vp, _vp, C.c_int32, _vp,
+                                                                        _vp, _vp, _vp, _vp, C.c_float, C.c_float, RESIZE_FN, _vp,
+                                                                        C.POINTER(RasterGrads), _vp]),
+    "c3dgs_distortion_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "c3dgs_contrib_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "c3dgs_render_contrib": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8),
     "c3dgs_contrib_accumulate": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 10),

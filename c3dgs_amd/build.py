@@ -33,6 +33,9 @@ SOURCES = {
     "render_depth.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the gradients through the depth / alpha maps: the same replay, walked back to front with render.hip's backward recurrences
     "render_depth_backward.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
+    # the distortion map and the three-map backward replay: siblings of the two above, render.hip's flags for the same reason
+    "render_distortion.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
+    "render_distortion_backward.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the per-Gaussian blend statistics: the same replay, the same flags
     "render_contrib.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the per-Gaussian error scores: the same replay and the same reduction network, the same flags

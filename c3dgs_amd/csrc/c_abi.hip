@@ -24,13 +24,14 @@ void set_error(const std::string& msg) { g_last_error = msg; }
 #define C3DGS_STAGE_TABLE(X)                                                                                                   \
     X(MARK_VISIBLE, "mark_visible") X(PREPROCESS, "preprocess") X(DEPTH_SORT, "depth_sort") X(SCAN, "scan")                    \
     X(DUPLICATE, "duplicate_with_keys") X(SORT, "sort") X(RANGES, "identify_ranges") X(RENDER_FWD, "render_forward")           \
-    X(RENDER_DEPTH, "render_depth")                                                                                            \
+    X(RENDER_DEPTH, "render_depth") X(RENDER_DISTORTION, "render_distortion")                                                  \
     X(RENDER_CONTRIB, "render_contrib") X(RENDER_CONTRIB_BLEND, "render_contrib_blend") X(RENDER_CONTRIB_SUM, "render_contrib_sum") \
     X(RENDER_ERROR, "render_error") X(RENDER_ERROR_BLEND, "render_error_blend") X(RENDER_ERROR_SUM, "render_error_sum")           \
     X(ERROR_MAP_L1, "error_map_l1")                                                                                            \
     X(POSE_GRAD, "pose_grad") X(POSE_GRAD_SUMS, "pose_grad_sums") X(POSE_GRAD_FOLD, "pose_grad_fold")                          \
     X(ZERO_PARTIALS, "zero_partials") X(RENDER_BWD, "render_backward") X(BWD_PREPROCESS, "backward_preprocess")                \
     X(RENDER_DEPTH_BWD, "render_depth_backward") X(DEPTH_BWD_FOLD, "depth_backward_fold")                                      \
+    X(RENDER_DISTORTION_BWD, "render_distortion_backward")                                                                     \
     X(WDIST, "weighted_distance") X(VQ_ACC, "vq_accumulate") X(VQ_APPLY, "vq_apply") X(LOSS_FWD, "l1_ssim_forward")            \
     X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
     X(QAT_VISIBLE, "qat_visible") X(QAT_POINTS, "qat_points") X(QAT_POINTS_BWD, "qat_points_backward")                         \
@@ -351,10 +352,18 @@ static int forward_impl(const c3dgs_raster_params* pp, bool indexed, c3dgs_resiz
 static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int32_t* radii, const void* geom_buffer,
                          const void* binning_buffer, const void* image_buffer, int32_t R, const float* dL_dout_color,
                          c3dgs_resize_fn ws_resize, void* ws_user, const c3dgs_raster_grads* grads, void* stream_,
-                         const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr)
+                         const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr,
+                         const float* dL_ddistortion = nullptr, const float* moment = nullptr, float near_ = 0.f, float far_ = 0.f)
 {
-    // gradients through the depth / alpha maps (render_depth_backward.hip): without a map, exactly the plain backward below
-    const bool maps = dL_ddepth != nullptr || dL_dalpha != nullptr;
+    // gradients through the depth / alpha maps (render_depth_backward.hip): without a map, exactly the plain backward below.
+    // With the distortion map's gradient, render_distortion_backward.hip's replay serves all three maps in that one's place;
+    // without it the other four distortion arguments are not looked at
+    if (dL_ddistortion) {
+        if (!moment) return fail(C3DGS_E_INVALID, "backward_distortion: moment is required with dL_ddistortion");
+        if (!(far_ <= 0.f) && !(near_ > 0.f && near_ < far_))       // a NaN fails here as well
+            return fail(C3DGS_E_INVALID, "backward_distortion: 0 < near < far is required (far <= 0 selects the raw mode)");
+    }
+    const bool maps = dL_ddepth != nullptr || dL_dalpha != nullptr || dL_ddistortion != nullptr;
     if (int rc = validate(pp, indexed, true)) return rc;
     if (!grads) return fail(C3DGS_E_INVALID, "grads is NULL");
     c3dgs_raster_params p = *pp;
@@ -417,7 +426,11 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
             C3DGS_TIMED_STAGE(ST_RENDER_BWD, p.debug, s,
                               launch_render_backward(W, H, img, g.splat, g.block_base, p.background, dL_dout_color, w.partials, w.touched,
                                                      cl, cb_zero, cb_zero16, s)); // K10
-        if (maps)
+        if (dL_ddistortion)
+            C3DGS_TIMED_STAGE(ST_RENDER_DISTORTION_BWD, p.debug, s,
+                              launch_render_distortion_backward(W, H, img, cl, g, w, dz_plane, dL_ddepth, dL_dalpha, dL_ddistortion,
+                                                                moment, distortion_map(near_, far_), sort_err, s));
+        else if (maps)
             C3DGS_TIMED_STAGE(ST_RENDER_DEPTH_BWD, p.debug, s,
                               launch_render_depth_backward(W, H, img, cl, g, w, dz_plane, dL_ddepth, dL_dalpha, sort_err, s));
     }
@@ -611,6 +624,59 @@ int c3dgs_rasterize_gaussians_backward_depth_indexed(const c3dgs_raster_params* 
 }
 
 size_t c3dgs_depth_backward_workspace_bytes(int32_t P, int32_t R) { return depth_backward_layout(P, R).total_bytes; }
+
+int c3dgs_rasterize_gaussians_backward_distortion(const c3dgs_raster_params* p, const int32_t* radii, const void* geom_buffer,
+                                                  const void* binning_buffer, const void* image_buffer, int32_t R,
+                                                  const float* dL_dout_color, const float* dL_ddepth, const float* dL_dalpha,
+                                                  const float* dL_ddistortion, const float* moment, float near_, float far_,
+                                                  c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                                  const c3dgs_raster_grads* grads, void* stream)
+{
+    return backward_impl(p, false, radii, geom_buffer, binning_buffer, image_buffer, R, dL_dout_color, workspace_resize,
+                         workspace_user, grads, stream, dL_ddepth, dL_dalpha, dL_ddistortion, moment, near_, far_);
+}
+
+int c3dgs_rasterize_gaussians_backward_distortion_indexed(const c3dgs_raster_params* p, const int32_t* radii, const void* geom_buffer,
+                                                          const void* binning_buffer, const void* image_buffer, int32_t R,
+                                                          const float* dL_dout_color, const float* dL_ddepth, const float* dL_dalpha,
+                                                          const float* dL_ddistortion, const float* moment, float near_, float far_,
+                                                          c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                                          const c3dgs_raster_grads* grads, void* stream)
+{
+    return backward_impl(p, true, radii, geom_buffer, binning_buffer, image_buffer, R, dL_dout_color, workspace_resize,
+                         workspace_user, grads, stream, dL_ddepth, dL_dalpha, dL_ddistortion, moment, near_, far_);
+}
+
+size_t c3dgs_distortion_backward_workspace_bytes(int32_t P, int32_t R) { return depth_backward_layout(P, R).total_bytes; }
+
+int c3dgs_render_distortion(int32_t P, int32_t W, int32_t H, int32_t R, const void* geom_buffer, const void* binning_buffer,
+                            const void* image_buffer, float near_, float far_, float* out_distortion, float* out_moment, void* stream)
+{
+    if (W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, "render_distortion: W and H must be positive");
+    if (P < 0 || R < 0) return fail(C3DGS_E_INVALID, "render_distortion: P and R must be >= 0");
+    if (!out_distortion) return fail(C3DGS_E_INVALID, "render_distortion: out_distortion is required");
+    if (!(far_ <= 0.f) && !(near_ > 0.f && near_ < far_))
+        return fail(C3DGS_E_INVALID, "render_distortion: 0 < near < far is required (far <= 0 selects the raw mode)");
+    if (R > 0 && P == 0) return fail(C3DGS_E_INVALID, "render_distortion: R > 0 instances cannot come from P = 0");
+    if (R > 0 && (!geom_buffer || !binning_buffer || !image_buffer))
+        return fail(C3DGS_E_INVALID, "render_distortion: the forward's geometry, binning and image buffers are required");
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0 || R == 0) {            // nothing was blended anywhere
+        const size_t bytes = (size_t)W * H * sizeof(float);
+        for (float* o : { out_distortion, out_moment })
+            if (o) C3DGS_HIP_TRY(hipMemsetAsync(o, 0, bytes, s));
+        return C3DGS_OK;
+    }
+    uint32_t* sort_err = onesweep_error_word();
+    if (!sort_err) return fail(C3DGS_E_HIP, "cannot resolve the sort error word");
+    const GeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
+    const ImgPtrs img = img_ptrs(const_cast<void*>(image_buffer), W, H);
+    const BinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), R, W, H);
+    C3DGS_TIMED_STAGE(ST_RENDER_DISTORTION, 0, s,
+                      launch_render_distortion(W, H, img, compact_ptrs(b, R), g.splat, g.depth_keys, distortion_map(near_, far_),
+                                               out_distortion, out_moment, sort_err, s));
+    return C3DGS_OK;
+}
 
 int c3dgs_render_depth(int32_t P, int32_t W, int32_t H, int32_t R, const void* geom_buffer, const void* binning_buffer,
                        const void* image_buffer, float* out_depth, float* out_alpha, float* out_median, void* stream)

@@ -212,6 +212,30 @@ inline DepthBackwardLayout depth_backward_layout(int P, int R)
     return L;
 }
 
+// s = f(z) of the distortion passes (render_distortion.hip, render_distortion_backward.hip). ndc == 0: raw, f(z) = z. Otherwise
+// f(z) = far / (far - near) * (1 - near / z) = c0 - c1 / z, c0 and c1 rounded from double (raw: c0 = 0), on the correctly rounded
+// rz = 1 / z. The map and its gradient only see differences of s, and a sum of w s of the size of s cannot carry them in fp32
+// where a ray's spread is small (ndc: s near 1, spreads of 0.01). So no pass forms s itself per entry: rel() is s - c0, which the
+// forward sums about the pixel's first entry, and about() is s - p for a pivot p, given q = c0 - p, in ONE rounding at the size
+// of the difference. f'(z) = c1 rz^2. The backward's workspace is depth_backward_layout's.
+struct DistortionMap {
+    float c0, c1;
+    int ndc;
+    __device__ __forceinline__ float rz(float z) const { return (ndc && z > 0.f) ? 1.0f / z : 0.f; }
+    __device__ __forceinline__ float rel(float z, float rz_) const { return ndc ? -c1 * rz_ : z; }
+    __device__ __forceinline__ float about(float z, float rz_, float q) const { return ndc ? fmaf(-c1, rz_, q) : z + q; }
+    __device__ __forceinline__ float ds(float rz_) const { return ndc ? (c1 * rz_) * rz_ : 1.0f; }
+};
+inline DistortionMap distortion_map(float near_, float far_)          // far <= 0: raw
+{
+    DistortionMap f = { 0.f, 0.f, 0 };
+    if (far_ > 0.f) {
+        const double c0 = (double)far_ / ((double)far_ - (double)near_);
+        f.c0 = (float)c0; f.c1 = (float)(c0 * (double)near_); f.ndc = 1;
+    }
+    return f;
+}
+
 // Blend-statistics workspace (render_contrib.hip): one {sum, max, hits} record per backward slot, f32 f32 u32 [R] | their
 // 1-byte "written" flags. Same slot numbering as the backward's partials; only the flags are cleared per call.
 struct ContribSlot { float sum, max; uint32_t hits; };
@@ -410,6 +434,15 @@ void launch_render_depth_backward(int W, int H, const ImgPtrs& img, const Compac
                                   hipStream_t s);
 void launch_depth_backward_fold(int P, const GeomPtrs& g, const BwdPtrs& w, const float* dz_plane, const float* view,
                                 float* dL_dmeans3D, const uint32_t* sort_err, hipStream_t s);
+// render_distortion.hip (forward-only replay of the blend: the distortion map and the first moment sum w s; out_moment may be null)
+void launch_render_distortion(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const float4* splat, const uint32_t* depth_keys,
+                              const DistortionMap& f, float* out_distortion, float* out_moment, const uint32_t* sort_err, hipStream_t s);
+// render_distortion_backward.hip (gradients through the depth, alpha AND distortion maps in one blend replay: it stands where
+// launch_render_depth_backward stands, with the same slots, flags and dL/dz plane, and launch_depth_backward_fold follows it as it
+// follows that; dL_ddepth / dL_dalpha may be null = zeros, dL_ddistortion and moment are required)
+void launch_render_distortion_backward(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const BwdPtrs& w,
+                                       float* dz_plane, const float* dL_ddepth, const float* dL_dalpha, const float* dL_ddistortion,
+                                       const float* moment, const DistortionMap& f, const uint32_t* sort_err, hipStream_t s);
 // render_contrib.hip (forward-only replay of the blend: per-Gaussian sum / max of alpha T and blended-pair count; null outputs are
 // skipped): the blend replay into the slots (the caller has cleared w.touched on the stream), the per-Gaussian fold of the slots,
 // and the fold of one view's rows into model-sized accumulators.

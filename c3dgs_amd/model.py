@@ -1413,7 +1413,7 @@ class GaussianModel:
     # ---- render (gaussian_model.py:766-886)
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, clamp_color=True,
                cov3d=None, gather_visible=True, return_depth=False, return_contrib=False, error_target=None,
-               pose_grad="reference", depth_grad=False, antialiasing=None):
+               pose_grad="reference", depth_grad=False, antialiasing=None, distortion=False):
         """pose_grad: what a camera pose that requires grad receives. "reference" (the default): the reference's formula on the
         indexed rasterizer (rasterizer.camera_pose_jacobian_sum), nothing on the other. "exact": the gradient of the render itself
         on both (rasterizer._C.pose_grad, one pass behind the backward). A pose that does not require grad costs nothing either way.
@@ -1429,6 +1429,12 @@ class GaussianModel:
         indexed and the composed path alike (GaussianRasterizationSettings(depth_grad=True), csrc/render_depth_backward.hip);
         "median_depth" stays non-differentiable. The pose receives no gradient on this path, whatever `pose_grad` says: a camera
         pose that requires grad raises ValueError (not covered yet).
+        distortion=True | (near, far): the keys and gradients of depth_grad plus "distortion", [H, W]: per pixel
+        sum_i sum_j w_i w_j |s_i - s_j| over the blended entries (w = alpha T; s = the view-space depth z, or with a pair
+        far / (far - near) (1 - near / z), 2DGS's mapping), Mip-NeRF 360's distortion regulariser, with gradient to the model's
+        parameters on the fused indexed and the composed path alike (GaussianRasterizationSettings(distortion=),
+        csrc/render_distortion.hip, csrc/render_distortion_backward.hip). It composes with `antialiasing` and the 3D filter as
+        depth_grad does, and like it refuses a camera pose that requires grad (ValueError).
         antialiasing: None (the default) reads `pipe.antialiasing`; True multiplies every opacity by the compensation factor of the
         rasterizer's 0.3 px^2 low-pass (GaussianRasterizationSettings(antialiasing=True), csrc/aa_opacity.hip), on the fused indexed
         and the composed path alike, with gradients to the model's parameters. As with depth_grad, the pose receives no gradient
@@ -1443,6 +1449,10 @@ class GaussianModel:
             antialiasing = getattr(pipe, "antialiasing", False)
         if depth_grad and viewpoint_camera.extrinsic_vector.requires_grad:
             raise ValueError("render(depth_grad=True): the gradient to a camera pose that requires grad is not covered yet")
+        if distortion is None:
+            distortion = False
+        if distortion is not False and viewpoint_camera.extrinsic_vector.requires_grad:
+            raise ValueError("render(distortion=...): the gradient to a camera pose that requires grad is not covered yet")
         if antialiasing and viewpoint_camera.extrinsic_vector.requires_grad:
             raise ValueError("render(antialiasing=True): the gradient to a camera pose that requires grad is not covered")
         if pipe.convert_SHs_python and override_color is None:
@@ -1455,7 +1465,8 @@ class GaussianModel:
             intrinsic=viewpoint_camera.intrinsic.to(dev), extrinsic_vector=viewpoint_camera.extrinsic_vector.to(dev),
             bg=bg_color.to(dev), scale_modifier=scaling_modifier, sh_degree=self.active_sh_degree, prefiltered=False,
             debug=pipe.debug, clamp_color=clamp_color, depth=bool(return_depth), contrib=bool(return_contrib),
-            error_target=error_target, depth_grad=bool(depth_grad), antialiasing=bool(antialiasing))
+            error_target=error_target, depth_grad=bool(depth_grad) or distortion is not False, antialiasing=bool(antialiasing),
+            distortion=distortion)
         indexed = self.color_index_mode == ColorMode.ALL_INDEXED and self.is_gaussian_indexed
         fused = indexed and self.use_factor_scaling and cov3d is None and override_color is None and \
             not pipe.compute_cov3D_python
@@ -1525,10 +1536,12 @@ class GaussianModel:
     def _extra_keys(settings, extras, rank):
         """the rasterizer's extra outputs -> the keys render() adds: the three maps under settings.depth, then under
         settings.contrib the three per-Gaussian rows and "contrib_rank" (int32 [P]: the row of a visible Gaussian in them, or
-        None when they are indexed by Gaussian), then under settings.error_target "error_sum" and "error_rank" (the same rank)"""
+        None when they are indexed by Gaussian), then under settings.error_target "error_sum" and "error_rank" (the same rank),
+        then under settings.distortion the "distortion" map, the rasterizer's last output"""
         scored = settings.error_target is not None
         names = (("depth", "alpha", "median_depth") if (settings.depth or settings.depth_grad) else ()) + \
-            (("contrib_sum", "contrib_max", "contrib_hits") if settings.contrib else ()) + (("error_sum",) if scored else ())
+            (("contrib_sum", "contrib_max", "contrib_hits") if settings.contrib else ()) + (("error_sum",) if scored else ()) + \
+            (("distortion",) if settings.distortion is not False else ())
         assert len(names) == len(extras)
         out = dict(zip(names, extras))
         if settings.contrib:

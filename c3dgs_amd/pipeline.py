@@ -113,7 +113,7 @@ def _train_cameras(scene):
 
 
 def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_interval=0, prune_min_opacity=0.005,
-             prune_min_views=0, bilagrid=None):
+             prune_min_views=0, bilagrid=None, lambda_dist=0.0, dist_near_far=None, dist_from_iter=0):
     """finetune.py:10-66. One camera per iteration, drawn without replacement from a stack that is refilled when empty
     (`pop(randint(0, len - 1))` on Python's `random`, like the reference); render -> (1 - l) L1 + l (1 - SSIM) ->
     backward -> learning-rate update -> Adam step (not after the last iteration).
@@ -133,19 +133,32 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
     pass renders every training camera once but leaves the QAT observers as it found them (contribution_stats restores them).
     `bilagrid` (not in the reference; None changes nothing): a trained bilagrid.BilateralGrid whose row k belongs to camera k of
     the training list. The loss then sees bilagrid.slice(render, k), so the fine-tuning does not fight the exposure differences
-    the grids had absorbed. The grids are frozen: no optimizer, requires_grad is switched off for the call and restored."""
+    the grids had absorbed. The grids are frozen: no optimizer, requires_grad is switched off for the call and restored.
+    `lambda_dist`, `dist_near_far`, `dist_from_iter`: train()'s depth-distortion term (see there; 0, the default, changes
+    nothing), from the `dist_from_iter`-th iteration of this call on."""
     gaussians = scene.gaussians if hasattr(scene, "gaussians") else dataset.gaussians
+    dist = (_distortion_option("finetune", lambda_dist, dist_near_far), float(lambda_dist), int(dist_from_iter))
     if bilagrid is not None:
         camera_index = _camera_indices(_train_cameras(scene), bilagrid)
         grids_required_grad = bilagrid.grids.requires_grad
         bilagrid.grids.requires_grad_(False)
         try:
             return _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, prune_min_opacity, prune_min_views,
-                             gaussians, bilagrid, camera_index)
+                             gaussians, bilagrid, camera_index, dist)
         finally:
             bilagrid.grids.requires_grad_(grids_required_grad)
     return _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, prune_min_opacity, prune_min_views, gaussians,
-                     None, None)
+                     None, None, dist)
+
+
+def _distortion_option(who, lambda_dist, dist_near_far):
+    """-> what render(distortion=) takes for the depth-distortion term of train() / finetune(): False when the weight is 0"""
+    if lambda_dist < 0:
+        raise ValueError(f"{who}: lambda_dist must be >= 0")
+    if lambda_dist == 0:
+        return False
+    from .rasterizer import _distortion_setting
+    return _distortion_setting(True if dist_near_far is None else dist_near_far)
 
 
 def _camera_indices(cameras, bilagrid):
@@ -156,7 +169,8 @@ def _camera_indices(cameras, bilagrid):
 
 
 def _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, prune_min_opacity, prune_min_views, gaussians,
-              bilagrid, camera_index):
+              bilagrid, camera_index, dist=(False, 0.0, 0)):
+    distortion, lambda_dist, dist_from_iter = dist
     first_iter = int(getattr(scene, "loaded_iter", 0) or 0)
     max_iter = first_iter + comp.finetune_iterations
     bg_color = [1, 1, 1] if getattr(dataset, "white_background", False) else [0, 0, 0]
@@ -175,12 +189,15 @@ def _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, 
         viewpoint_cam = viewpoint_stack.pop(randint(0, len(viewpoint_stack) - 1))
         if (iteration - 1) == debug_from:
             pipe.debug = True
-        render_pkg = gaussians.render(viewpoint_cam, pipe, background)
+        with_dist = distortion is not False and iteration - first_iter >= dist_from_iter
+        render_pkg = gaussians.render(viewpoint_cam, pipe, background, **({"distortion": distortion} if with_dist else {}))
         image = render_pkg["render"]
         if bilagrid is not None:
             image = bilagrid.slice(image, camera_index[id(viewpoint_cam)])
         gt_image = viewpoint_cam.original_image.to(image.device)
         loss = _loss.l1_ssim_loss(image, gt_image, opt.lambda_dssim)
+        if with_dist:
+            loss = loss + lambda_dist * render_pkg["distortion"].mean()
         loss.backward()
         gaussians.update_learning_rate(iteration)
         pending.append(loss.detach())
@@ -213,7 +230,8 @@ def _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, 
 def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, degree_up_iter=1000, *, densify_by="grad",
           error_threshold=None, optimizer_type=None, optimizer_visibility="radii", lambda_depth=0.0, lambda_alpha=0.0,
           strategy="default", cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01, min_opacity=0.005,
-          bilagrid=None, bilagrid_lr=2e-3, bilagrid_tv=10.0, filter_3d=False, filter_3d_interval=100):
+          bilagrid=None, bilagrid_lr=2e-3, bilagrid_tv=10.0, filter_3d=False, filter_3d_interval=100, lambda_dist=0.0,
+          dist_near_far=None, dist_from_iter=0):
     """train.py:15-173 without its disabled compression-statistics branch: optimise a non-indexed model (usually
     GaussianModel.load_ply of a point cloud) with adaptive density control.
 
@@ -251,6 +269,15 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     adds lambda_depth x the mean over the measured pixels of |depth - alpha x depth_target|, a residual in weight space (depth is
     sum alpha T z, not normalised), so nothing is divided. Both at 0 (the default), and views without the attributes, run the
     loop above with its launches.
+
+    `lambda_dist` (not in the reference: the depth-distortion loss of Mip-NeRF 360 as 2DGS and gsplat use it;
+    csrc/render_distortion.hip, csrc/render_distortion_backward.hip) = 0 is the loop above, launch for launch. A positive value
+    adds lambda_dist x render(distortion=...)["distortion"].mean() from iteration `dist_from_iter` on (counted like `iteration`
+    of `info`, from 0): per pixel sum_i sum_j w_i w_j |s_i - s_j| over the blended entries, which pulls the mass along a ray
+    together and needs no measured depth. `dist_near_far` = None takes s = the view-space depth; a pair (near, far) takes 2DGS's
+    mapping far / (far - near) (1 - near / z). There is no default weight because nobody has tuned one here: 2DGS's own values
+    (100 to 1000, from iteration 3000) are for ITS mapping and its normalised depth, which is the reason `dist_near_far` is
+    offered; in raw mode the loss scales with the square of the scene's depth unit. A negative value raises ValueError.
 
     `strategy` = "default" is the loop above, launch for launch. "mcmc" (not in the reference: "3D Gaussian Splatting as Markov
     Chain Monte Carlo", gsplat's MCMCStrategy; csrc/mcmc.hip) trains towards a hard budget of `cap_max` Gaussians (required):
@@ -298,6 +325,7 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
         raise ValueError("train: strategy='mcmc' needs cap_max, the budget of Gaussians (there is no default)")
     if lambda_depth < 0 or lambda_alpha < 0:
         raise ValueError("train: lambda_depth and lambda_alpha must be >= 0")
+    distortion = _distortion_option("train", lambda_dist, dist_near_far)
     if optimizer_visibility not in ("radii", "blended", None):
         raise ValueError(f"train: optimizer_visibility must be 'radii', 'blended' or None, not {optimizer_visibility!r}")
     if densify_by not in ("grad", "error"):
@@ -354,6 +382,9 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             alpha_target = getattr(viewpoint_cam, "alpha_target", None) if lambda_alpha > 0 else None
             depth_target = getattr(viewpoint_cam, "depth_target", None) if lambda_depth > 0 else None
             extra = dict(extra_base, depth_grad=True) if (alpha_target is not None or depth_target is not None) else extra_base
+            with_dist = distortion is not False and iteration >= dist_from_iter
+            if with_dist:
+                extra = dict(extra, distortion=distortion)
             if mcmc:
                 render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, gather_visible=False, **extra)
             elif by_error:
@@ -378,6 +409,8 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
                 measured = target > 0
                 residual = ((render_pkg["depth"] - render_pkg["alpha"] * target).abs() * measured).sum()
                 loss = loss + lambda_depth * residual / measured.sum().clamp(min=1)
+            if with_dist:
+                loss = loss + lambda_dist * render_pkg["distortion"].mean()
             if mcmc:
                 loss = loss + opacity_reg * torch.sigmoid(gaussians._opacity).mean() + scale_reg * gaussians.get_scaling.mean()
             loss.backward()

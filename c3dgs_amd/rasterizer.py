@@ -5,7 +5,7 @@ on top of the MI355X C-ABI library.  Same names, argument order and error behavi
     GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,
     rasterize_gaussians, rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,
     getProjectionMatrix, quat_to_mat, mat_to_quat, and `_C` with the five pybind entry points
-    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`, `render_contrib`, `render_error`, `error_map_l1`,
+    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`, `render_distortion`, `render_contrib`, `render_error`, `error_map_l1`,
     `pose_grad`, `aa_opacity` and `aa_opacity_backward`.
 
 Beyond the reference: `GaussianRasterizationSettings(depth=True)` / `_C.render_depth` add depth, accumulated-opacity and
@@ -18,7 +18,10 @@ csrc/render_error.hip); `GaussianRasterizer(rs, optimize_camera="exact")` / `Gau
 the backward), where `optimize_camera=True` keeps the reference's formula; `GaussianRasterizationSettings(depth_grad=True)` makes
 the depth and alpha maps differentiable outputs (csrc/render_depth_backward.hip, one blend replay and one fold in the backward);
 `GaussianRasterizationSettings(antialiasing=True)` / `_C.aa_opacity` / `_C.aa_opacity_backward` compensate every opacity for the
-0.3 px^2 low-pass (csrc/aa_opacity.hip, one per-Gaussian launch in front of the forward and one behind the backward).
+0.3 px^2 low-pass (csrc/aa_opacity.hip, one per-Gaussian launch in front of the forward and one behind the backward);
+`GaussianRasterizationSettings(distortion=True | (near, far))` / `_C.render_distortion` append the depth-distortion map of
+Mip-NeRF 360 as a differentiable last output (csrc/render_distortion.hip; in the backward ONE blend replay for the depth, alpha
+and distortion maps, csrc/render_distortion_backward.hip).
 
 PyTorch is plumbing only here (device memory, streams, autograd bookkeeping); every numeric stage
 runs in libc3dgs_hip.so.  There is no CPU path: tensors must live on the GPU.
@@ -319,23 +322,32 @@ def _forward(indexed, background, means3D, colors, opacity, scales, scale_factor
 
 def _backward(indexed, background, means3D, radii, colors, scales, scale_factors, rotations, scale_modifier, cov3D_precomp,
               viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-              imageBuffer, debug, sh_indices, g_indices, skip=(), dL_ddepth=None, dL_dalpha=None):
+              imageBuffer, debug, sh_indices, g_indices, skip=(), dL_ddepth=None, dL_dalpha=None, dL_ddistortion=None, moment=None,
+              near_far=None):
     """`dL_ddepth` / `dL_dalpha`: [H, W] fp32 gradients of the depth / alpha maps of _C.render_depth, or None. With either, the call
     goes to the library's *_backward_depth entry (csrc/render_depth_backward.hip: one blend replay in front of the per-Gaussian
     kernels, one small fold behind them) and `dL_dout_color` may be None (the loss does not use the image: no colour blend
     launch). With neither it is the plain backward, launch for launch.
+    `dL_ddistortion`: [H, W] fp32 gradient of the distortion map of _C.render_distortion, or None; with it `moment` is that call's
+    second output and `near_far` its mode (None: raw), and the call goes to the *_backward_distortion entry
+    (csrc/render_distortion_backward.hip: one blend replay for the three maps in the place of the depth one). Without it the three
+    arguments are ignored.
     `skip`: names among ("dL_dcolors", "dL_dcov3D") that are neither allocated nor written and come back as None. The
     autograd wrappers name the gradients of ABSENT optional inputs: dL_dcolors (12 B x P) and dL_dcov3D (24 B x P) are
     108 MB of stores per 3M-Gaussian backward. The pybind-order entry points (_C.*) skip nothing, like the reference."""
     L = _lib.lib()
-    maps = dL_ddepth is not None or dL_dalpha is not None
+    dist = dL_ddistortion is not None
+    maps = dL_ddepth is not None or dL_dalpha is not None or dist
     if dL_dout_color is not None:
         H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))           # rasterize_points.cu:143-145
     elif maps:
-        H, W = (int(v) for v in (dL_ddepth if dL_ddepth is not None else dL_dalpha).shape)
+        H, W = (int(v) for v in next(m for m in (dL_ddepth, dL_dalpha, dL_ddistortion) if m is not None).shape)
     else:
         raise RuntimeError("dL_dout_color is required")
-    for name, m in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha)):
+    if dist and moment is None:
+        raise RuntimeError("c3dgs_amd: dL_ddistortion needs the moment map of _C.render_distortion")
+    for name, m in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha), ("dL_ddistortion", dL_ddistortion),
+                    ("moment", moment if dist else None)):
         if m is not None:
             _check_map(m, (H, W), means3D.device, name)
     # opacities are not an input of the reference's backward either (they live in the geometry buffer)
@@ -380,7 +392,12 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
         radii_c = radii.contiguous()
         dpix = _optional(dL_dout_color, "dL_dout_color")
         scratch = _Scratch(dev)
-        if maps:
+        if dist:
+            fn = (L.c3dgs_rasterize_gaussians_backward_distortion_indexed if indexed else
+                  L.c3dgs_rasterize_gaussians_backward_distortion)
+            near, far = _near_far(near_far)
+            extra = (_ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(dL_ddistortion), _ptr(moment), near, far)
+        elif maps:
             fn = L.c3dgs_rasterize_gaussians_backward_depth_indexed if indexed else L.c3dgs_rasterize_gaussians_backward_depth
             extra = (_ptr(dL_ddepth), _ptr(dL_dalpha))
         else:
@@ -420,19 +437,20 @@ def _c_rasterize_gaussians_indexed(background, means3D, colors, opacity, scales,
 
 def _c_rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                                    geomBuffer, R, binningBuffer, imageBuffer, debug, skip=(), dL_ddepth=None, dL_dalpha=None):
+                                    geomBuffer, R, binningBuffer, imageBuffer, debug, skip=(), dL_ddepth=None, dL_dalpha=None,
+                                    **distortion):
     return _backward(False, background, means3D, radii, colors, scales, None, rotations, scale_modifier, cov3D_precomp,
                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R,
-                     binningBuffer, imageBuffer, debug, None, None, skip, dL_ddepth, dL_dalpha)
+                     binningBuffer, imageBuffer, debug, None, None, skip, dL_ddepth, dL_dalpha, **distortion)
 
 
 def _c_rasterize_gaussians_backward_indexed(background, means3D, radii, colors, scales, scale_factors, rotations,
                                             scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                                             dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-                                            debug, sh_indices, g_indices, skip=(), dL_ddepth=None, dL_dalpha=None):
+                                            debug, sh_indices, g_indices, skip=(), dL_ddepth=None, dL_dalpha=None, **distortion):
     return _backward(True, background, means3D, radii, colors, scales, scale_factors, rotations, scale_modifier,
                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer,
-                     R, binningBuffer, imageBuffer, debug, sh_indices, g_indices, skip, dL_ddepth, dL_dalpha)
+                     R, binningBuffer, imageBuffer, debug, sh_indices, g_indices, skip, dL_ddepth, dL_dalpha, **distortion)
 
 
 def _c_mark_visible(means3D, viewmatrix, projmatrix):
@@ -486,6 +504,42 @@ def _c_render_depth(P, W, H, R, geomBuffer, binningBuffer, imgBuffer):
                                            ptr(out[2]), _stream(dev))
     _lib.check(rc)
     return out[0], out[1], out[2]
+
+
+def _near_far(near_far):
+    """None / False / True -> (0.0, 0.0), the library's raw mode; (near, far) with 0 < near < far -> the two floats, as the fp32
+    values the library receives: a pair that is in order as doubles but not as floats (a near that underflows, a pair that
+    rounds to one value) is refused here, with ValueError, and not by the library"""
+    if near_far is None or near_far is True or near_far is False:
+        return 0.0, 0.0
+    try:
+        with np.errstate(over="ignore"):                        # a far beyond fp32 becomes inf, which is refused below
+            near, far = (float(np.float32(float(v))) for v in near_far)
+    except (TypeError, ValueError):
+        raise ValueError(f"distortion must be False, True or (near, far), not {near_far!r}") from None
+    if not 0.0 < near < far or math.isinf(far):
+        raise ValueError(f"distortion=(near, far) needs 0 < near < far, finite; got {near_far!r}")
+    return near, far
+
+
+def _c_render_distortion(P, W, H, R, geomBuffer, binningBuffer, imgBuffer, near_far=None):
+    """The depth-distortion map of the forward that filled the three buffers (c3dgs_render_distortion): -> (distortion, moment),
+    each [H, W] fp32, on the current stream. distortion = sum_i sum_j w_i w_j |s_i - s_j| over the pixel's blended entries, with
+    w = alpha T and s = the view-space depth z (`near_far` None) or 2DGS's far / (far - near) (1 - near / z) (`near_far` a pair with
+    0 < near < far); moment = sum_k w_k s_k, which the backward needs next to the gradient of `distortion`. Valid before or after
+    the matching backward."""
+    if not imgBuffer.is_cuda:
+        raise RuntimeError("c3dgs_amd: render_distortion needs the forward's GPU buffers (there is no CPU path)")
+    dev = imgBuffer.device
+    P, W, H, R = int(P), int(W), int(H), int(R)
+    near, far = _near_far(near_far)
+    with torch.cuda.device(dev):
+        out = torch.empty((2, max(H, 0), max(W, 0)), dtype=torch.float32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        rc = _lib.lib().c3dgs_render_distortion(P, W, H, R, ptr(geomBuffer), ptr(binningBuffer), ptr(imgBuffer), near, far,
+                                                ptr(out[0]), ptr(out[1]), _stream(dev))
+    _lib.check(rc)
+    return out[0], out[1]
 
 
 class _GrowOnly:
@@ -698,6 +752,7 @@ def _c_error_map_l1(img, gt):
 
 _C = SimpleNamespace(
     render_depth=_c_render_depth,
+    render_distortion=_c_render_distortion,
     render_contrib=_c_render_contrib,
     render_error=_c_render_error,
     error_map_l1=_c_error_map_l1,
@@ -756,7 +811,9 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     # with `raster_settings.depth`: the (depth, alpha, median) maps, queued right behind the forward on the same stream;
     # otherwise no launch
     extras = ()
-    depth_grad = bool(getattr(rs, "depth_grad", False))
+    # `raster_settings.distortion` implies depth_grad's outputs, in their positions
+    distortion = getattr(rs, "distortion", False)
+    depth_grad = bool(getattr(rs, "depth_grad", False)) or distortion is not False
     if getattr(rs, "depth", False) or depth_grad:
         extras = _C.render_depth(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer)
     # with `raster_settings.contrib`: (weight_sum, weight_max, hits) per Gaussian, behind whatever `depth` added
@@ -768,6 +825,14 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
         _check_map(target, color.shape, color.device, "error_target")
         emap = _C.error_map_l1(color.detach(), target)
         extras = tuple(extras) + (_C.render_error(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer, emap),)
+    # with `raster_settings.distortion`: the distortion map, the LAST output and a differentiable one; its moment map stays here
+    # for the backward
+    n_fixed = len(extras)
+    moment = None
+    if distortion is not False:
+        dist_map, moment = _C.render_distortion(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer,
+                                                distortion)
+        extras = tuple(extras) + (dist_map,)
     ctx.raster_settings = rs
     ctx.indexed = indexed
     ctx.num_rendered = num_rendered
@@ -776,14 +841,16 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     ctx.antialiasing = antialiasing
     ctx.image_size = (H, W)
     ctx.save_for_backward(extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii, sh,
-                          geomBuffer, binningBuffer, imgBuffer, sh_indices, g_indices, *((raw_opacities,) if antialiasing else ()))
+                          geomBuffer, binningBuffer, imgBuffer, sh_indices, g_indices, *((raw_opacities,) if antialiasing else ()),
+                          *((moment,) if moment is not None else ()))
+    ctx.distortion = distortion
     ctx.image_shape = tuple(color.shape)
     # without this, autograd hands backward a zero-filled int32[P] "gradient" for radii on every call (a 12 MB fill at P = 3M)
     ctx.set_materialize_grads(False)
     # the extras are forward-only: non-differentiable like radii, no gradient flows through them -- except, with
     # `raster_settings.depth_grad`, the depth and alpha maps (outputs 2 and 3), whose gradients the backward takes
     ctx.depth_grad = depth_grad
-    ctx.mark_non_differentiable(radii, *(extras[2:] if depth_grad else extras))
+    ctx.mark_non_differentiable(radii, *(extras[2:n_fixed] if depth_grad else extras))
     return (color, radii) + tuple(extras)
 
 
@@ -800,7 +867,10 @@ def _map_grads(ctx, params):
     loss sent through the two maps of a `depth_grad` forward, as contiguous fp32, or (None, None)."""
     if not getattr(ctx, "depth_grad", False):
         return None, None
-    return tuple(None if g is None else g.to(torch.float32).contiguous() for g in params[1:3])
+    fit = lambda g: None if g is None else g.to(torch.float32).contiguous()            # noqa: E731
+    # behind them, of a `distortion` forward: dL_ddistortion, the gradient of the last output
+    last = (fit(params[-1]),) if getattr(ctx, "distortion", False) is not False else ()
+    return tuple(fit(g) for g in params[1:3]) + last
 
 
 def _autograd_backward(ctx, grad_out_color, exact_pose=False, map_grads=(None, None)):
@@ -812,8 +882,13 @@ def _autograd_backward(ctx, grad_out_color, exact_pose=False, map_grads=(None, N
     rs = ctx.raster_settings
     (extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
      binningBuffer, imgBuffer, sh_indices, g_indices) = ctx.saved_tensors[:14]
-    grad_depth, grad_alpha = map_grads
+    grad_depth, grad_alpha = map_grads[:2]
+    grad_dist = map_grads[2] if len(map_grads) > 2 else None
     maps = dict(dL_ddepth=grad_depth, dL_dalpha=grad_alpha) if (grad_depth is not None or grad_alpha is not None) else {}
+    if grad_dist is not None:
+        # the moment map is the last saved tensor; without a gradient for the distortion map the backward is today's
+        maps = dict(dL_ddepth=grad_depth, dL_dalpha=grad_alpha, dL_ddistortion=grad_dist, moment=ctx.saved_tensors[-1],
+                    near_far=ctx.distortion)
     if grad_out_color is None and not maps:
         # set_materialize_grads(False): an image nobody differentiated through arrives as None (backward still runs when only
         # `radii` was used downstream of a graph that needs grad); the library wants a dense dL/dC
@@ -1042,6 +1117,18 @@ def _check_depth_grad_camera(raster_settings, optimize_camera):
     if optimize_camera is not False and getattr(raster_settings, "depth_grad", False):
         raise ValueError("depth_grad=True cannot be combined with optimize_camera: the gradient to the camera pose through the "
                          "depth and alpha maps is not implemented")
+    if optimize_camera is not False and getattr(raster_settings, "distortion", False) is not False:
+        raise ValueError("distortion cannot be combined with optimize_camera: the gradient to the camera pose through the "
+                         "depth, alpha and distortion maps is not implemented")
+
+
+def _distortion_setting(value):
+    """False | True | (near, far) of GaussianRasterizationSettings(distortion=), checked and normalised"""
+    if value is None or value is False:
+        return False
+    if value is True:
+        return True
+    return _near_far(value)
 
 
 def _check_antialiasing_camera(raster_settings, optimize_camera):
@@ -1099,13 +1186,22 @@ class GaussianRasterizationSettings(_SettingsFields):
     the covariance, scales, rotations and scale factors), so that a splat smaller than a pixel is not drawn with the energy of
     the low-passed one. Radii, tile keys and conics are the plain render's; every output, the extra ones included, sees the
     compensated opacity. False: the plain rasterizer's launches and bits. The gradient to the camera pose through rho is not
-    covered: with `antialiasing`, `optimize_camera` other than False raises ValueError."""
+    covered: with `antialiasing`, `optimize_camera` other than False raises ValueError.
+    `distortion` (keyword only, default False) is a fifth such attribute: False, True (raw mode: s = the view-space depth z) or
+    a pair (near, far) with 0 < near < far (s = far / (far - near) (1 - near / z), 2DGS's mapping; anything else raises
+    ValueError). Not False: the rasterizers return depth_grad's outputs in their positions, differentiable as there, and append
+    the depth-distortion map sum_i sum_j w_i w_j |s_i - s_j| of every pixel's blended entries, [H, W], as the LAST element of the
+    tuple (csrc/render_distortion.hip, one more forward replay), a differentiable output as well: a loss on it reaches every input
+    the depth map reaches, through ONE blend replay in the backward for the three maps (csrc/render_distortion_backward.hip, in
+    the place of the depth maps' replay). When it receives no gradient the backward is depth_grad's. With `distortion`,
+    `optimize_camera` other than False raises ValueError, as with `depth_grad`."""
     contrib = False
     error_target = None
     depth_grad = False
     antialiasing = False
+    distortion = False
 
-    def __new__(cls, *args, contrib=False, error_target=None, depth_grad=False, antialiasing=False, **kwargs):
+    def __new__(cls, *args, contrib=False, error_target=None, depth_grad=False, antialiasing=False, distortion=False, **kwargs):
         n = len(cls._fields)
         if len(args) == n + 1:
             args, contrib = args[:n], args[n]
@@ -1114,6 +1210,7 @@ class GaussianRasterizationSettings(_SettingsFields):
         self.error_target = error_target
         self.depth_grad = bool(depth_grad)
         self.antialiasing = bool(antialiasing)
+        self.distortion = _distortion_setting(distortion)
         return self
 
     def _replace(self, **kwargs):
@@ -1121,11 +1218,13 @@ class GaussianRasterizationSettings(_SettingsFields):
         error_target = kwargs.pop("error_target", self.error_target)
         depth_grad = kwargs.pop("depth_grad", self.depth_grad)
         antialiasing = kwargs.pop("antialiasing", self.antialiasing)
+        distortion = kwargs.pop("distortion", self.distortion)
         new = super()._replace(**kwargs)
         new.contrib = bool(contrib)
         new.error_target = error_target
         new.depth_grad = bool(depth_grad)
         new.antialiasing = bool(antialiasing)
+        new.distortion = _distortion_setting(distortion)
         return new
 
 

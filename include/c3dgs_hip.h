@@ -164,6 +164,53 @@ int c3dgs_rasterize_gaussians_backward_depth_indexed(const c3dgs_raster_params* 
                                                      const c3dgs_raster_grads* grads, void* stream);
 size_t c3dgs_depth_backward_workspace_bytes(int32_t P, int32_t R);
 
+/* ---- the depth-distortion map of a finished forward (csrc/render_distortion.hip; no reference counterpart) ----
+ * Mip-NeRF 360's distortion regulariser as 2DGS and gsplat use it. Per pixel, over the entries k = 1..m the forward blended
+ * (w_k, T_k, z_k as for c3dgs_render_depth), with s_k = f(z_k):
+ *   far <= 0:       raw mode, f(z) = z (near is not looked at)
+ *   0 < near < far: ndc mode, f(z) = far / (far - near) * (1 - near / z), 2DGS's mapping (anything else: C3DGS_E_INVALID)
+ *   out_distortion = sum_i sum_j w_i w_j |s_i - s_j| = 2 sum_k w_k (s_k A_<k - S_<k),  A_<k = 1 - T_k, S_<k = sum_{j<k} w_j s_j
+ *   out_moment     = sum_k w_k s_k        (what the backward entries below take as `moment`)
+ * The second form is the one evaluated: a tile's list is in ascending fp32 depth and f is increasing. There is no
+ * 1/3 sum w^2 delta term. The call replays the forward's decisions, reads what c3dgs_render_depth reads and, like it, is valid
+ * before or after the matching backward; no atomics, no scratch, bitwise reproducible. out_distortion is required, out_moment may
+ * be NULL. P == 0 or R == 0: zeros, no blend launch. The sort's time-out word set: every output is NaN.
+ * Stage name: "render_distortion". */
+int c3dgs_render_distortion(int32_t P, int32_t W, int32_t H, int32_t R,
+                            const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                            float near, float far, float* out_distortion /*[H,W]*/, float* out_moment /*[H,W] | NULL*/,
+                            void* stream);
+
+/* ---- the two backward entries with gradients through the depth, alpha AND distortion maps
+ * (csrc/render_distortion_backward.hip) ----
+ * The arguments of the *_backward_depth entries plus dL_ddistortion = dL/d(out_distortion) and moment = out_moment of
+ * c3dgs_render_distortion on the same forward, both [H,W] fp32, and that call's near / far.
+ * With dL_ddistortion NULL the call IS the *_backward_depth entry: the same validation, workspace request, launches and bits
+ * (moment, near and far are not looked at). With it, moment is required and near / far are checked as above; errors return
+ * C3DGS_E_INVALID before any device work. Per pixel, with gL = dL_ddistortion, A_>k = T_{k+1} - T_{m+1} and
+ * S_>k = moment - S_<k - w_k s_k:
+ *   u_k         = 2 gL (s_k (A_<k - A_>k) - S_<k + S_>k)                  c_k = dL_ddepth z_k + dL_dalpha + u_k
+ *   dL/dalpha_k = T_k c_k - (sum_{j>k} w_j c_j) / (1 - alpha_k)           dL/dz_k = w_k (dL_ddepth + 2 gL (A_<k - A_>k) f'(z_k))
+ * ONE blend replay (stage "render_distortion_backward") serves the three maps and stands in the place of
+ * "render_depth_backward", which is not launched; "depth_backward_fold" follows as there. The workspace callback is asked for
+ * c3dgs_distortion_backward_workspace_bytes(P, R) == c3dgs_depth_backward_workspace_bytes(P, R). */
+int c3dgs_rasterize_gaussians_backward_distortion(const c3dgs_raster_params* p, const int32_t* radii,
+                                                  const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                                                  int32_t R, const float* dL_dout_color /*[3,H,W] | NULL with a map*/,
+                                                  const float* dL_ddepth /*[H,W] | NULL*/, const float* dL_dalpha /*[H,W] | NULL*/,
+                                                  const float* dL_ddistortion /*[H,W] | NULL*/, const float* moment /*[H,W]*/,
+                                                  float near, float far,
+                                                  c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                                  const c3dgs_raster_grads* grads, void* stream);
+int c3dgs_rasterize_gaussians_backward_distortion_indexed(const c3dgs_raster_params* p, const int32_t* radii,
+                                                          const void* geom_buffer, const void* binning_buffer,
+                                                          const void* image_buffer, int32_t R, const float* dL_dout_color,
+                                                          const float* dL_ddepth, const float* dL_dalpha,
+                                                          const float* dL_ddistortion, const float* moment, float near, float far,
+                                                          c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                                          const c3dgs_raster_grads* grads, void* stream);
+size_t c3dgs_distortion_backward_workspace_bytes(int32_t P, int32_t R);
+
 /* ---- depth, accumulated opacity and median depth of a finished forward (csrc/render_depth.hip; no reference counterpart) ----
  * geom/binning/image buffers are the ones a forward of the same P, W, H filled; R is its num_rendered. Per pixel, over the
  * entries k = 1..m the forward blended (w_k = alpha_k T_k, T_{k+1} = T_k (1 - alpha_k), T_1 = 1, z_k = the fp32 view-space
