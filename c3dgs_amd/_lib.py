@@ -134,6 +134,16 @@ PROTOTYPES = {
                                                                         _vp, _vp, _vp, _vp, C.c_float, C.c_float, RESIZE_FN, _vp,
                                                                         C.POINTER(RasterGrads), _vp]),
     "c3dgs_distortion_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "c3dgs_gaussian_normals": (C.c_int, [C.c_int32] + [_vp] * 7),
+    "c3dgs_render_normal": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_vp] * 6),
+    "c3dgs_rasterize_gaussians_backward_normal": (C.c_int, [C.POINTER(RasterParams), _vp, _vp, _vp, _vp, C.c_int32] + [_vp] * 10 +
+                                                  [C.c_float, C.c_float, RESIZE_FN, _vp, C.POINTER(RasterGrads), _vp]),
+    "c3dgs_rasterize_gaussians_backward_normal_indexed": (C.c_int, [C.POINTER(RasterParams), _vp, _vp, _vp, _vp, C.c_int32] +
+                                                          [_vp] * 10 + [C.c_float, C.c_float, RESIZE_FN, _vp,
+                                                                       C.POINTER(RasterGrads), _vp]),
+    "c3dgs_normal_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "c3dgs_depth_to_normal": (C.c_int, [C.c_int32, C.c_int32, _vp, C.c_float, C.c_float, _vp, _vp]),
+    "c3dgs_depth_to_normal_backward": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, C.c_float, C.c_float, _vp, _vp]),
     "c3dgs_contrib_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "c3dgs_render_contrib": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_vp] * 8),
     "c3dgs_contrib_accumulate": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 10),

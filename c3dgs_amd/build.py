@@ -36,6 +36,12 @@ SOURCES = {
     # the distortion map and the three-map backward replay: siblings of the two above, render.hip's flags for the same reason
     "render_distortion.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     "render_distortion_backward.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
+    # the normal map and the replay that serves every map of a backward: siblings again, the same flags
+    "render_normal.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
+    "render_normal_backward.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
+    # the per-Gaussian normals, their fold and the depth -> normal stencil: single fp32 operations that tests/normal_ref.py
+    # restates, and the chains of csrc/gsgrad.hpp
+    "normals.hip": ["-ffp-contract=off"],
     # the per-Gaussian blend statistics: the same replay, the same flags
     "render_contrib.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the per-Gaussian error scores: the same replay and the same reduction network, the same flags

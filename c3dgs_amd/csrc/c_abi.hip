@@ -32,6 +32,9 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(ZERO_PARTIALS, "zero_partials") X(RENDER_BWD, "render_backward") X(BWD_PREPROCESS, "backward_preprocess")                \
     X(RENDER_DEPTH_BWD, "render_depth_backward") X(DEPTH_BWD_FOLD, "depth_backward_fold")                                      \
     X(RENDER_DISTORTION_BWD, "render_distortion_backward")                                                                     \
+    X(GAUSSIAN_NORMALS, "gaussian_normals") X(RENDER_NORMAL, "render_normal") X(RENDER_NORMAL_BWD, "render_normal_backward")   \
+    X(NORMAL_BWD_FOLD, "normal_backward_fold") X(DEPTH_TO_NORMAL, "depth_to_normal")                                           \
+    X(DEPTH_TO_NORMAL_BWD, "depth_to_normal_backward")                                                                         \
     X(WDIST, "weighted_distance") X(VQ_ACC, "vq_accumulate") X(VQ_APPLY, "vq_apply") X(LOSS_FWD, "l1_ssim_forward")            \
     X(LOSS_BWD, "l1_ssim_backward") X(QAT_OBSERVE, "qat_observe") X(QAT_CODEBOOKS, "qat_codebooks")                            \
     X(QAT_VISIBLE, "qat_visible") X(QAT_POINTS, "qat_points") X(QAT_POINTS_BWD, "qat_points_backward")                         \
@@ -353,7 +356,9 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
                          const void* binning_buffer, const void* image_buffer, int32_t R, const float* dL_dout_color,
                          c3dgs_resize_fn ws_resize, void* ws_user, const c3dgs_raster_grads* grads, void* stream_,
                          const float* dL_ddepth = nullptr, const float* dL_dalpha = nullptr,
-                         const float* dL_ddistortion = nullptr, const float* moment = nullptr, float near_ = 0.f, float far_ = 0.f)
+                         const float* dL_ddistortion = nullptr, const float* moment = nullptr, float near_ = 0.f, float far_ = 0.f,
+                         const float* dL_dnormal = nullptr, const float* normals = nullptr, const float* axes_rotations = nullptr,
+                         const int64_t* axes_g_indices = nullptr, float* dL_daxes_rotations = nullptr)
 {
     // gradients through the depth / alpha maps (render_depth_backward.hip): without a map, exactly the plain backward below.
     // With the distortion map's gradient, render_distortion_backward.hip's replay serves all three maps in that one's place;
@@ -363,7 +368,18 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
         if (!(far_ <= 0.f) && !(near_ > 0.f && near_ < far_))       // a NaN fails here as well
             return fail(C3DGS_E_INVALID, "backward_distortion: 0 < near < far is required (far <= 0 selects the raw mode)");
     }
-    const bool maps = dL_ddepth != nullptr || dL_dalpha != nullptr || dL_ddistortion != nullptr;
+    // With the normal map's gradient, render_normal_backward.hip's replay serves every map of the call in the place of both, and
+    // normal_backward_fold follows backward_preprocess; without it `normals` and the axes are not looked at. The fold chains to the
+    // rotations the normals were made from: the call's own (and its dL_drotations), or, where the call blends a precomputed
+    // covariance, which has no axes, the rotations given beside it, into a gradient tensor of their own that the caller has zeroed
+    if (dL_dnormal) {
+        if (!normals) return fail(C3DGS_E_INVALID, "backward_normal: normals is required with dL_dnormal");
+        if (axes_rotations && !dL_daxes_rotations)
+            return fail(C3DGS_E_INVALID, "backward_normal: dL_daxes_rotations is required with axes_rotations");
+        if (pp && pp->cov3D_precomp && !axes_rotations)
+            return fail(C3DGS_E_INVALID, "backward_normal: a precomputed covariance has no axes; axes_rotations is required beside it");
+    }
+    const bool maps = dL_ddepth != nullptr || dL_dalpha != nullptr || dL_ddistortion != nullptr || dL_dnormal != nullptr;
     if (int rc = validate(pp, indexed, true)) return rc;
     if (!grads) return fail(C3DGS_E_INVALID, "grads is NULL");
     c3dgs_raster_params p = *pp;
@@ -405,10 +421,14 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
     uint32_t* sort_err = maps ? onesweep_error_word() : nullptr;
     if (maps && !sort_err) return fail(C3DGS_E_HIP, "cannot resolve the sort error word");
     // with maps: the same layout and, behind it, the dL/dz plane
-    void* ws_base = ws_resize(ws_user, maps ? depth_backward_layout(P, R).total_bytes : c3dgs_backward_workspace_bytes(P, R));
+    // with the normal map's gradient: behind that, the dn plane
+    void* ws_base = ws_resize(ws_user, dL_dnormal ? normal_backward_layout(P, R).total_bytes
+                                       : maps     ? depth_backward_layout(P, R).total_bytes
+                                                  : c3dgs_backward_workspace_bytes(P, R));
     if (!ws_base) return fail(C3DGS_E_ALLOC, "backward workspace allocation failed");
     const BwdPtrs w = bwd_ptrs(ws_base, P, R);
     float* dz_plane = maps ? (float*)((char*)ws_base + depth_backward_layout(P, R).dz) : nullptr;
+    NormalSlot* dn_plane = dL_dnormal ? (NormalSlot*)((char*)ws_base + normal_backward_layout(P, R).dn) : nullptr;
     // the colour blend launch: always without maps; with maps only where the loss uses the image
     const bool blend = R > 0 && dL_dout_color != nullptr;
 
@@ -426,7 +446,12 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
             C3DGS_TIMED_STAGE(ST_RENDER_BWD, p.debug, s,
                               launch_render_backward(W, H, img, g.splat, g.block_base, p.background, dL_dout_color, w.partials, w.touched,
                                                      cl, cb_zero, cb_zero16, s)); // K10
-        if (dL_ddistortion)
+        if (dL_dnormal)
+            C3DGS_TIMED_STAGE(ST_RENDER_NORMAL_BWD, p.debug, s,
+                              launch_render_normal_backward(W, H, img, cl, g, w, dz_plane, dn_plane, normals, dL_ddepth, dL_dalpha,
+                                                            dL_dnormal, dL_ddistortion, moment, distortion_map(near_, far_), sort_err,
+                                                            s));
+        else if (dL_ddistortion)
             C3DGS_TIMED_STAGE(ST_RENDER_DISTORTION_BWD, p.debug, s,
                               launch_render_distortion_backward(W, H, img, cl, g, w, dz_plane, dL_ddepth, dL_dalpha, dL_ddistortion,
                                                                 moment, distortion_map(near_, far_), sort_err, s));
@@ -438,6 +463,14 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
     if (maps && R > 0 && grads->dL_dmeans3D)
         C3DGS_TIMED_STAGE(ST_DEPTH_BWD_FOLD, p.debug, s,
                           launch_depth_backward_fold(P, g, w, dz_plane, p.viewmatrix, grads->dL_dmeans3D, sort_err, s));
+    if (dL_dnormal && R > 0 && axes_rotations)
+        C3DGS_TIMED_STAGE(ST_NORMAL_BWD_FOLD, p.debug, s,
+                          launch_normal_backward_fold(P, g, w, dn_plane, normals, axes_rotations, axes_g_indices, p.viewmatrix,
+                                                      dL_daxes_rotations, sort_err, s));
+    else if (dL_dnormal && R > 0 && grads->dL_drotations)
+        C3DGS_TIMED_STAGE(ST_NORMAL_BWD_FOLD, p.debug, s,
+                          launch_normal_backward_fold(P, g, w, dn_plane, normals, p.rotations, p.g_indices, p.viewmatrix,
+                                                      grads->dL_drotations, sort_err, s));
     return C3DGS_OK;
 }
 
@@ -648,6 +681,99 @@ int c3dgs_rasterize_gaussians_backward_distortion_indexed(const c3dgs_raster_par
 }
 
 size_t c3dgs_distortion_backward_workspace_bytes(int32_t P, int32_t R) { return depth_backward_layout(P, R).total_bytes; }
+
+int c3dgs_rasterize_gaussians_backward_normal(const c3dgs_raster_params* p, const int32_t* radii, const void* geom_buffer,
+                                              const void* binning_buffer, const void* image_buffer, int32_t R,
+                                              const float* dL_dout_color, const float* dL_ddepth, const float* dL_dalpha,
+                                              const float* dL_dnormal, const float* normals, const float* axes_rotations,
+                                              const int64_t* axes_g_indices, float* dL_daxes_rotations, const float* dL_ddistortion,
+                                              const float* moment, float near_, float far_, c3dgs_resize_fn workspace_resize,
+                                              void* workspace_user, const c3dgs_raster_grads* grads, void* stream)
+{
+    return backward_impl(p, false, radii, geom_buffer, binning_buffer, image_buffer, R, dL_dout_color, workspace_resize,
+                         workspace_user, grads, stream, dL_ddepth, dL_dalpha, dL_ddistortion, moment, near_, far_, dL_dnormal, normals,
+                         axes_rotations, axes_g_indices, dL_daxes_rotations);
+}
+
+int c3dgs_rasterize_gaussians_backward_normal_indexed(const c3dgs_raster_params* p, const int32_t* radii, const void* geom_buffer,
+                                                      const void* binning_buffer, const void* image_buffer, int32_t R,
+                                                      const float* dL_dout_color, const float* dL_ddepth, const float* dL_dalpha,
+                                                      const float* dL_dnormal, const float* normals, const float* axes_rotations,
+                                                      const int64_t* axes_g_indices, float* dL_daxes_rotations,
+                                                      const float* dL_ddistortion, const float* moment, float near_, float far_,
+                                                      c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                                      const c3dgs_raster_grads* grads, void* stream)
+{
+    return backward_impl(p, true, radii, geom_buffer, binning_buffer, image_buffer, R, dL_dout_color, workspace_resize,
+                         workspace_user, grads, stream, dL_ddepth, dL_dalpha, dL_ddistortion, moment, near_, far_, dL_dnormal, normals,
+                         axes_rotations, axes_g_indices, dL_daxes_rotations);
+}
+
+size_t c3dgs_normal_backward_workspace_bytes(int32_t P, int32_t R) { return normal_backward_layout(P, R).total_bytes; }
+
+int c3dgs_gaussian_normals(int32_t P, const float* means3D, const float* scales, const float* rotations, const int64_t* g_indices,
+                           const float* viewmatrix, float* out_normals, void* stream)
+{
+    if (P < 0) return fail(C3DGS_E_INVALID, "gaussian_normals: P must be >= 0");
+    if (P == 0) return C3DGS_OK;
+    if (!means3D || !scales || !rotations || !viewmatrix || !out_normals)
+        return fail(C3DGS_E_INVALID, "gaussian_normals: means3D, scales, rotations, viewmatrix and out_normals are required");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_GAUSSIAN_NORMALS, 0, s,
+                      launch_gaussian_normals(P, means3D, scales, rotations, g_indices, viewmatrix, out_normals, s));
+    return C3DGS_OK;
+}
+
+int c3dgs_render_normal(int32_t P, int32_t W, int32_t H, int32_t R, const void* geom_buffer, const void* binning_buffer,
+                        const void* image_buffer, const float* normals, float* out_normal, void* stream)
+{
+    if (W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, "render_normal: W and H must be positive");
+    if (P < 0 || R < 0) return fail(C3DGS_E_INVALID, "render_normal: P and R must be >= 0");
+    if (!out_normal) return fail(C3DGS_E_INVALID, "render_normal: out_normal is required");
+    if (R > 0 && P == 0) return fail(C3DGS_E_INVALID, "render_normal: R > 0 instances cannot come from P = 0");
+    if (R > 0 && (!geom_buffer || !binning_buffer || !image_buffer || !normals))
+        return fail(C3DGS_E_INVALID, "render_normal: the forward's geometry, binning and image buffers and the normals are required");
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0 || R == 0) {            // nothing was blended anywhere
+        C3DGS_HIP_TRY(hipMemsetAsync(out_normal, 0, (size_t)3 * W * H * sizeof(float), s));
+        return C3DGS_OK;
+    }
+    uint32_t* sort_err = onesweep_error_word();
+    if (!sort_err) return fail(C3DGS_E_HIP, "cannot resolve the sort error word");
+    const GeomPtrs g = geom_ptrs(const_cast<void*>(geom_buffer), P);
+    const ImgPtrs img = img_ptrs(const_cast<void*>(image_buffer), W, H);
+    const BinPtrs b = bin_ptrs(const_cast<void*>(binning_buffer), R, W, H);
+    C3DGS_TIMED_STAGE(ST_RENDER_NORMAL, 0, s,
+                      launch_render_normal(W, H, img, compact_ptrs(b, R), g.splat, normals, out_normal, sort_err, s));
+    return C3DGS_OK;
+}
+
+static int stencil_args(const char* who, int32_t W, int32_t H, float tan_fovx, float tan_fovy)
+{
+    if (W <= 0 || H <= 0) return fail(C3DGS_E_INVALID, std::string(who) + ": W and H must be positive");
+    if (!(tan_fovx > 0.f) || !(tan_fovy > 0.f)) return fail(C3DGS_E_INVALID, std::string(who) + ": tan_fovx and tan_fovy must be positive");
+    return C3DGS_OK;
+}
+
+int c3dgs_depth_to_normal(int32_t W, int32_t H, const float* z, float tan_fovx, float tan_fovy, float* out_normal, void* stream)
+{
+    if (int rc = stencil_args("depth_to_normal", W, H, tan_fovx, tan_fovy)) return rc;
+    if (!z || !out_normal) return fail(C3DGS_E_INVALID, "depth_to_normal: z and out_normal are required");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_DEPTH_TO_NORMAL, 0, s, launch_depth_to_normal(W, H, z, tan_fovx, tan_fovy, out_normal, s));
+    return C3DGS_OK;
+}
+
+int c3dgs_depth_to_normal_backward(int32_t W, int32_t H, const float* z, const float* dL_dnormal, float tan_fovx, float tan_fovy,
+                                   float* dL_dz, void* stream)
+{
+    if (int rc = stencil_args("depth_to_normal_backward", W, H, tan_fovx, tan_fovy)) return rc;
+    if (!z || !dL_dnormal || !dL_dz) return fail(C3DGS_E_INVALID, "depth_to_normal_backward: z, dL_dnormal and dL_dz are required");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_DEPTH_TO_NORMAL_BWD, 0, s,
+                      launch_depth_to_normal_backward(W, H, z, dL_dnormal, tan_fovx, tan_fovy, dL_dz, s));
+    return C3DGS_OK;
+}
 
 int c3dgs_render_distortion(int32_t P, int32_t W, int32_t H, int32_t R, const void* geom_buffer, const void* binning_buffer,
                             const void* image_buffer, float near_, float far_, float* out_distortion, float* out_moment, void* stream)

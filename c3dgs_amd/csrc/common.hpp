@@ -212,6 +212,21 @@ inline DepthBackwardLayout depth_backward_layout(int P, int R)
     return L;
 }
 
+// Workspace of a backward with a gradient through the normal map (render_normal_backward.hip): depth_backward_layout's, unchanged and
+// at the same offsets, and behind it the dn plane, three floats per slot in the same numbering: sum over the tile's pixels of
+// w gN for the slot's (Gaussian, tile). Never cleared either: valid where the slot's flag is set behind the replay.
+struct NormalSlot { float x, y, z; };
+struct NormalBackwardLayout { size_t dz, dn, total_bytes; };
+inline NormalBackwardLayout normal_backward_layout(int P, int R)
+{
+    const DepthBackwardLayout D = depth_backward_layout(P, R);
+    const size_t r = (size_t)(R > 0 ? R : 1);
+    NormalBackwardLayout L;
+    L.dz = D.dz; L.dn = D.total_bytes;
+    L.total_bytes = align_up(L.dn + r * sizeof(NormalSlot));
+    return L;
+}
+
 // s = f(z) of the distortion passes (render_distortion.hip, render_distortion_backward.hip). ndc == 0: raw, f(z) = z. Otherwise
 // f(z) = far / (far - near) * (1 - near / z) = c0 - c1 / z, c0 and c1 rounded from double (raw: c0 = 0), on the correctly rounded
 // rz = 1 / z. The map and its gradient only see differences of s, and a sum of w s of the size of s cannot carry them in fp32
@@ -443,6 +458,26 @@ void launch_render_distortion(int W, int H, const ImgPtrs& img, const CompactPtr
 void launch_render_distortion_backward(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const BwdPtrs& w,
                                        float* dz_plane, const float* dL_ddepth, const float* dL_dalpha, const float* dL_ddistortion,
                                        const float* moment, const DistortionMap& f, const uint32_t* sort_err, hipStream_t s);
+// normals.hip: the per-Gaussian normals [P, 4] = {n_x, n_y, n_z, sigma (m + 1)} (g_indices null: the rows are the Gaussians' own),
+// the fold of the dn plane into dL_drotations behind launch_backward_preprocess (beside launch_depth_backward_fold), and the
+// depth -> normal stencil with its gather backward
+void launch_gaussian_normals(int P, const float* means3D, const float* scales, const float* rotations, const int64_t* g_indices,
+                             const float* view, float* out, hipStream_t s);
+void launch_normal_backward_fold(int P, const GeomPtrs& g, const BwdPtrs& w, const NormalSlot* dn_plane, const float* normals,
+                                 const float* rotations, const int64_t* g_indices, const float* view, float* dL_drotations,
+                                 const uint32_t* sort_err, hipStream_t s);
+void launch_depth_to_normal(int W, int H, const float* z, float tan_fovx, float tan_fovy, float* out, hipStream_t s);
+void launch_depth_to_normal_backward(int W, int H, const float* z, const float* dL_dnormal, float tan_fovx, float tan_fovy,
+                                     float* dL_dz, hipStream_t s);
+// render_normal.hip (forward-only replay of the blend: the normal map [3, H, W] = sum w n)
+void launch_render_normal(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const float4* splat, const float* normals,
+                          float* out_normal, const uint32_t* sort_err, hipStream_t s);
+// render_normal_backward.hip (gradients through the depth, alpha, normal and -- dL_ddistortion not null -- distortion maps in one
+// blend replay: it stands where launch_render_depth_backward / launch_render_distortion_backward stand, and both folds follow it)
+void launch_render_normal_backward(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const BwdPtrs& w,
+                                   float* dz_plane, NormalSlot* dn_plane, const float* normals, const float* dL_ddepth,
+                                   const float* dL_dalpha, const float* dL_dnormal, const float* dL_ddistortion, const float* moment,
+                                   const DistortionMap& f, const uint32_t* sort_err, hipStream_t s);
 // render_contrib.hip (forward-only replay of the blend: per-Gaussian sum / max of alpha T and blended-pair count; null outputs are
 // skipped): the blend replay into the slots (the caller has cleared w.touched on the stream), the per-Gaussian fold of the slots,
 // and the fold of one view's rows into model-sized accumulators.

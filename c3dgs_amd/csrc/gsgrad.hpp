@@ -215,6 +215,78 @@ __device__ __forceinline__ void cov3d_grad_to_scale_rot(const T dcov[6], const T
     dq[3] = 2 * r * (Q[1][0] - Q[0][1]) + 2 * x * (Q[0][2] + Q[2][0]) + 2 * y * (Q[2][1] + Q[1][2]) - 4 * z * (Q[1][1] + Q[0][0]);
 }
 
+// ---- the per-Gaussian normal (normals.hip): the shortest axis of the Gaussian, in view space, facing the camera.
+// m = the index of the smallest entry of the RAW scale row (no modifier, no scale factor: multiplying first can round two scales
+// into a tie and pick another axis than an exact comparison does), the lowest index on a tie; c = column m of quat_to_rot(q),
+// q as stored; v = R_view c / |c| (the zero vector where |c| == 0), R_view[i][k] = view[4 k + i]; n = sigma v with sigma = -1 where
+// v . p > 0 for the view-space mean p, else +1. m and sigma are piecewise constant: the only gradient is the one to q.
+__device__ __forceinline__ int smallest_axis(const float s0, const float s1, const float s2)
+{
+    int m = 0;
+    float v = s0;
+    if (s1 < v) { m = 1; v = s1; }
+    if (s2 < v) m = 2;
+    return m;
+}
+
+// column m of quat_to_rot(q) and its length
+template <class T>
+__device__ __forceinline__ T rot_column(const T r, const T x, const T y, const T z, const int m, T c[3])
+{
+    T Rm[3][3];
+    quat_to_rot(r, x, y, z, Rm);
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = m == 0 ? Rm[k][0] : (m == 1 ? Rm[k][1] : Rm[k][2]);
+    return sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+}
+
+// v = R_view c / |c|: the normal up to its sign
+template <class T>
+__device__ __forceinline__ void normal_from_quat(const T r, const T x, const T y, const T z, const int m, const float* view, T v[3])
+{
+    T c[3];
+    const T len = rot_column(r, x, y, z, m, c);
+    const T inv = len > T(0) ? T(1) / len : T(0);
+#pragma unroll
+    for (int k = 0; k < 3; k++) c[k] = c[k] * inv;
+#pragma unroll
+    for (int i = 0; i < 3; i++) v[i] = T(view[i]) * c[0] + T(view[4 + i]) * c[1] + T(view[8 + i]) * c[2];
+}
+
+// g = dL/dn -> dq = dL/dq as stored, through n = sigma R_view c / |c|, the 1 / |c| included; zero where |c| == 0
+template <class T>
+__device__ __forceinline__ void normal_grad_to_quat(const T r, const T x, const T y, const T z, const int m, const T sigma,
+                                                    const float* view, const T g[3], T dq[4])
+{
+    T c[3], gh[3], gc[3];
+    const T len = rot_column(r, x, y, z, m, c);
+    const T inv = len > T(0) ? T(1) / len : T(0);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        c[k] = c[k] * inv;
+        gh[k] = sigma * (T(view[4 * k]) * g[0] + T(view[4 * k + 1]) * g[1] + T(view[4 * k + 2]) * g[2]);
+    }
+    const T d = c[0] * gh[0] + c[1] * gh[1] + c[2] * gh[2];
+#pragma unroll
+    for (int k = 0; k < 3; k++) gc[k] = (gh[k] - c[k] * d) * inv;
+    if (m == 0) {           // c = (1 - 2 (y y + z z), 2 (x y + r z), 2 (x z - r y))
+        dq[0] = 2 * z * gc[1] - 2 * y * gc[2];
+        dq[1] = 2 * y * gc[1] + 2 * z * gc[2];
+        dq[2] = -4 * y * gc[0] + 2 * x * gc[1] - 2 * r * gc[2];
+        dq[3] = -4 * z * gc[0] + 2 * r * gc[1] + 2 * x * gc[2];
+    } else if (m == 1) {    // c = (2 (x y - r z), 1 - 2 (x x + z z), 2 (y z + r x))
+        dq[0] = -2 * z * gc[0] + 2 * x * gc[2];
+        dq[1] = 2 * y * gc[0] - 4 * x * gc[1] + 2 * r * gc[2];
+        dq[2] = 2 * x * gc[0] + 2 * z * gc[2];
+        dq[3] = -2 * r * gc[0] - 4 * z * gc[1] + 2 * y * gc[2];
+    } else {                // c = (2 (x z + r y), 2 (y z - r x), 1 - 2 (x x + y y))
+        dq[0] = 2 * y * gc[0] - 2 * x * gc[1];
+        dq[1] = 2 * z * gc[0] - 2 * r * gc[1] - 4 * x * gc[2];
+        dq[2] = 2 * r * gc[0] + 2 * z * gc[1] - 4 * y * gc[2];
+        dq[3] = 2 * x * gc[0] + 2 * y * gc[1];
+    }
+}
+
 // ---- codebook-sized gradients of the indexed model are scatter-ADDED. One lane per Gaussian would issue each atomic with 64
 // lanes in 64 different rows, the slowest shape for the chip's memory-side float atomics (MI355X_MICROARCH.md, Global float
 // atomics). So every lane parks its row (s_gi: codebook row, -1 = nothing to add), its three scale and four rotation terms in the

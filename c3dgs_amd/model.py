@@ -1413,7 +1413,7 @@ class GaussianModel:
     # ---- render (gaussian_model.py:766-886)
     def render(self, viewpoint_camera, pipe, bg_color, scaling_modifier=1.0, override_color=None, clamp_color=True,
                cov3d=None, gather_visible=True, return_depth=False, return_contrib=False, error_target=None,
-               pose_grad="reference", depth_grad=False, antialiasing=None, distortion=False):
+               pose_grad="reference", depth_grad=False, antialiasing=None, distortion=False, normal=False):
         """pose_grad: what a camera pose that requires grad receives. "reference" (the default): the reference's formula on the
         indexed rasterizer (rasterizer.camera_pose_jacobian_sum), nothing on the other. "exact": the gradient of the render itself
         on both (rasterizer._C.pose_grad, one pass behind the backward). A pose that does not require grad costs nothing either way.
@@ -1435,6 +1435,15 @@ class GaussianModel:
         parameters on the fused indexed and the composed path alike (GaussianRasterizationSettings(distortion=),
         csrc/render_distortion.hip, csrc/render_distortion_backward.hip). It composes with `antialiasing` and the 3D filter as
         depth_grad does, and like it refuses a camera pose that requires grad (ValueError).
+        normal=True: the keys and gradients of depth_grad plus "normal", [3, H, W]: per pixel sum_k w_k n_k over the blended
+        entries, n the Gaussian's shortest axis in VIEW space (x right, y down, z forward), unit length and facing the camera; not
+        normalised, no background term (GaussianRasterizationSettings(normal=True), csrc/normals.hip, csrc/render_normal.hip,
+        csrc/render_normal_backward.hip), with gradient to the model's parameters -- the rotations included -- on the fused indexed
+        and the composed path alike. normals.normal_consistency(out["depth"], out["alpha"], out["normal"], camera.intrinsic) is
+        2DGS's term on it. It composes with `antialiasing` and `distortion` (one blend replay in the backward for all maps) and
+        refuses a camera pose that requires grad (ValueError). A covariance has no axes: `cov3d=` and pipe.compute_cov3D_python
+        raise ValueError. With a 3D filter the rasterizer blends the filtered covariance as ever and the normals are made from the
+        model's own scales and rotations: the filter adds the same amount to every squared scale, so the shortest axis is the same.
         antialiasing: None (the default) reads `pipe.antialiasing`; True multiplies every opacity by the compensation factor of the
         rasterizer's 0.3 px^2 low-pass (GaussianRasterizationSettings(antialiasing=True), csrc/aa_opacity.hip), on the fused indexed
         and the composed path alike, with gradients to the model's parameters. As with depth_grad, the pose receives no gradient
@@ -1455,6 +1464,10 @@ class GaussianModel:
             raise ValueError("render(distortion=...): the gradient to a camera pose that requires grad is not covered yet")
         if antialiasing and viewpoint_camera.extrinsic_vector.requires_grad:
             raise ValueError("render(antialiasing=True): the gradient to a camera pose that requires grad is not covered")
+        if normal and viewpoint_camera.extrinsic_vector.requires_grad:
+            raise ValueError("render(normal=True): the gradient to a camera pose that requires grad is not covered yet")
+        if normal and (cov3d is not None or pipe.compute_cov3D_python):
+            raise ValueError("render(normal=True): a precomputed covariance has no axes, so no normal")
         if pipe.convert_SHs_python and override_color is None:
             raise NotImplementedError("convert_SHs_python: SH evaluation in Python is outside the mirrored render path")
         if pose_grad not in ("reference", "exact"):
@@ -1465,8 +1478,8 @@ class GaussianModel:
             intrinsic=viewpoint_camera.intrinsic.to(dev), extrinsic_vector=viewpoint_camera.extrinsic_vector.to(dev),
             bg=bg_color.to(dev), scale_modifier=scaling_modifier, sh_degree=self.active_sh_degree, prefiltered=False,
             debug=pipe.debug, clamp_color=clamp_color, depth=bool(return_depth), contrib=bool(return_contrib),
-            error_target=error_target, depth_grad=bool(depth_grad) or distortion is not False, antialiasing=bool(antialiasing),
-            distortion=distortion)
+            error_target=error_target, depth_grad=bool(depth_grad) or distortion is not False or bool(normal),
+            antialiasing=bool(antialiasing), distortion=distortion, normal=bool(normal))
         indexed = self.color_index_mode == ColorMode.ALL_INDEXED and self.is_gaussian_indexed
         fused = indexed and self.use_factor_scaling and cov3d is None and override_color is None and \
             not pipe.compute_cov3D_python
@@ -1516,8 +1529,11 @@ class GaussianModel:
             from . import filter3d
             cov3D, opac = filter3d.apply(opac, scales_n, rotations, filter_3D, settings.scale_modifier, scale_factors=sfac,
                                          g_indices=g_idx, visible=visible, rank=rank)
+            # with `normal`: the scales and rotations ride beside the covariance as the normals' axes (unfiltered: the filter moves
+            # no axis and leaves the shortest one the shortest)
+            axes = (scales_n, rotations) if settings.normal else (_rz._empty(), _rz._empty())
             image, radii, *extras = _rz.rasterize_gaussians_indexed(means3D, means2D, shs, sh_idx, g_idx, _rz._empty(), opac,
-                                                                    _rz._empty(), _rz._empty(), _rz._empty(), cov3D, settings,
+                                                                    axes[0], _rz._empty(), axes[1], cov3D, settings,
                                                                     settings.extrinsic_vector)
             return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
                     "visible": visible.bool(), **self._extra_keys(settings, extras, rank)}
@@ -1537,11 +1553,12 @@ class GaussianModel:
         """the rasterizer's extra outputs -> the keys render() adds: the three maps under settings.depth, then under
         settings.contrib the three per-Gaussian rows and "contrib_rank" (int32 [P]: the row of a visible Gaussian in them, or
         None when they are indexed by Gaussian), then under settings.error_target "error_sum" and "error_rank" (the same rank),
-        then under settings.distortion the "distortion" map, the rasterizer's last output"""
+        then under settings.distortion the "distortion" map, then under settings.normal the "normal" map, the rasterizer's last
+        output"""
         scored = settings.error_target is not None
         names = (("depth", "alpha", "median_depth") if (settings.depth or settings.depth_grad) else ()) + \
             (("contrib_sum", "contrib_max", "contrib_hits") if settings.contrib else ()) + (("error_sum",) if scored else ()) + \
-            (("distortion",) if settings.distortion is not False else ())
+            (("distortion",) if settings.distortion is not False else ()) + (("normal",) if settings.normal else ())
         assert len(names) == len(extras)
         out = dict(zip(names, extras))
         if settings.contrib:
@@ -1683,7 +1700,9 @@ class GaussianModel:
             cov3D_precomp, opacity = filter3d.apply(opacity, scales, rotations, filter_3D, scaling_modifier,
                                                     scale_factors=scale_factors if indexed else None,
                                                     g_indices=self._gaussian_indices if indexed else None, cov3d=given)
-            scales = rotations = scale_factors = None
+            if not (settings.normal and given is None):         # with `normal` the pair stays, as the normals' axes
+                scales = rotations = None
+            scale_factors = None
         shs = colors_precomp = None
         if override_color is None:
             shs = self._get_features_raw if indexed else self.get_features

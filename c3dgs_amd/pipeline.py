@@ -22,6 +22,7 @@ import torch
 from . import bilagrid as _bilagrid
 from . import loss as _loss
 from . import metrics as _metrics
+from . import normals as _normals
 from . import optim as _optim
 from . import sensitivity as _sensitivity
 from .vq import CompressionSettings, compress_gaussians
@@ -113,7 +114,8 @@ def _train_cameras(scene):
 
 
 def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_interval=0, prune_min_opacity=0.005,
-             prune_min_views=0, bilagrid=None, lambda_dist=0.0, dist_near_far=None, dist_from_iter=0):
+             prune_min_views=0, bilagrid=None, lambda_dist=0.0, dist_near_far=None, dist_from_iter=0, lambda_normal=0.0,
+             normal_from_iter=0):
     """finetune.py:10-66. One camera per iteration, drawn without replacement from a stack that is refilled when empty
     (`pop(randint(0, len - 1))` on Python's `random`, like the reference); render -> (1 - l) L1 + l (1 - SSIM) ->
     backward -> learning-rate update -> Adam step (not after the last iteration).
@@ -135,9 +137,14 @@ def finetune(scene, dataset, opt, comp, pipe, debug_from=-1, log=None, *, prune_
     the training list. The loss then sees bilagrid.slice(render, k), so the fine-tuning does not fight the exposure differences
     the grids had absorbed. The grids are frozen: no optimizer, requires_grad is switched off for the call and restored.
     `lambda_dist`, `dist_near_far`, `dist_from_iter`: train()'s depth-distortion term (see there; 0, the default, changes
-    nothing), from the `dist_from_iter`-th iteration of this call on."""
+    nothing), from the `dist_from_iter`-th iteration of this call on.
+    `lambda_normal`, `normal_from_iter`: train()'s normal-consistency term (see there; 0, the default, changes nothing), from the
+    `normal_from_iter`-th iteration of this call on. Both terms together still cost one blend replay per backward."""
     gaussians = scene.gaussians if hasattr(scene, "gaussians") else dataset.gaussians
-    dist = (_distortion_option("finetune", lambda_dist, dist_near_far), float(lambda_dist), int(dist_from_iter))
+    if lambda_normal < 0:
+        raise ValueError("finetune: lambda_normal must be >= 0")
+    dist = (_distortion_option("finetune", lambda_dist, dist_near_far), float(lambda_dist), int(dist_from_iter),
+            float(lambda_normal), int(normal_from_iter))
     if bilagrid is not None:
         camera_index = _camera_indices(_train_cameras(scene), bilagrid)
         grids_required_grad = bilagrid.grids.requires_grad
@@ -169,8 +176,8 @@ def _camera_indices(cameras, bilagrid):
 
 
 def _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, prune_min_opacity, prune_min_views, gaussians,
-              bilagrid, camera_index, dist=(False, 0.0, 0)):
-    distortion, lambda_dist, dist_from_iter = dist
+              bilagrid, camera_index, dist=(False, 0.0, 0, 0.0, 0)):
+    distortion, lambda_dist, dist_from_iter, lambda_normal, normal_from_iter = dist
     first_iter = int(getattr(scene, "loaded_iter", 0) or 0)
     max_iter = first_iter + comp.finetune_iterations
     bg_color = [1, 1, 1] if getattr(dataset, "white_background", False) else [0, 0, 0]
@@ -190,7 +197,9 @@ def _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, 
         if (iteration - 1) == debug_from:
             pipe.debug = True
         with_dist = distortion is not False and iteration - first_iter >= dist_from_iter
-        render_pkg = gaussians.render(viewpoint_cam, pipe, background, **({"distortion": distortion} if with_dist else {}))
+        with_normal = lambda_normal > 0 and iteration - first_iter >= normal_from_iter
+        render_pkg = gaussians.render(viewpoint_cam, pipe, background, **({"distortion": distortion} if with_dist else {}),
+                                      **({"normal": True} if with_normal else {}))
         image = render_pkg["render"]
         if bilagrid is not None:
             image = bilagrid.slice(image, camera_index[id(viewpoint_cam)])
@@ -198,6 +207,9 @@ def _finetune(scene, dataset, opt, comp, pipe, debug_from, log, prune_interval, 
         loss = _loss.l1_ssim_loss(image, gt_image, opt.lambda_dssim)
         if with_dist:
             loss = loss + lambda_dist * render_pkg["distortion"].mean()
+        if with_normal:
+            loss = loss + lambda_normal * _normals.normal_consistency(render_pkg["depth"], render_pkg["alpha"], render_pkg["normal"],
+                                                                      viewpoint_cam.intrinsic)
         loss.backward()
         gaussians.update_learning_rate(iteration)
         pending.append(loss.detach())
@@ -231,7 +243,7 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
           error_threshold=None, optimizer_type=None, optimizer_visibility="radii", lambda_depth=0.0, lambda_alpha=0.0,
           strategy="default", cap_max=None, noise_lr=5e5, opacity_reg=0.01, scale_reg=0.01, min_opacity=0.005,
           bilagrid=None, bilagrid_lr=2e-3, bilagrid_tv=10.0, filter_3d=False, filter_3d_interval=100, lambda_dist=0.0,
-          dist_near_far=None, dist_from_iter=0):
+          dist_near_far=None, dist_from_iter=0, lambda_normal=0.0, normal_from_iter=0):
     """train.py:15-173 without its disabled compression-statistics branch: optimise a non-indexed model (usually
     GaussianModel.load_ply of a point cloud) with adaptive density control.
 
@@ -278,6 +290,16 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     mapping far / (far - near) (1 - near / z). There is no default weight because nobody has tuned one here: 2DGS's own values
     (100 to 1000, from iteration 3000) are for ITS mapping and its normalised depth, which is the reason `dist_near_far` is
     offered; in raw mode the loss scales with the square of the scene's depth unit. A negative value raises ValueError.
+
+    `lambda_normal` (not in the reference: 2DGS's normal-consistency loss; csrc/normals.hip, csrc/render_normal.hip,
+    csrc/render_normal_backward.hip) = 0 is the loop above, launch for launch. A positive value adds
+    lambda_normal x normals.normal_consistency(depth, alpha, normal, intrinsic) of render(normal=True) from iteration
+    `normal_from_iter` on: the mean over the pixels of 1 - N . Ns, with N the blended map of the Gaussians' shortest axes and Ns the
+    normal of the rendered depth map, weighted by alpha. A normal needs axes, so from that iteration on the render takes the
+    model's scales and rotations and not the loop's frozen covariance: they receive gradients (from the image as well), which is
+    what the term is for. With `lambda_dist` the two terms share one blend replay in the backward. 2DGS uses 0.05 from iteration
+    7000; nobody has tuned a value here. With `filter_3d` the filtered covariance is blended and the normals come from the
+    unfiltered axes. A negative value raises ValueError.
 
     `strategy` = "default" is the loop above, launch for launch. "mcmc" (not in the reference: "3D Gaussian Splatting as Markov
     Chain Monte Carlo", gsplat's MCMCStrategy; csrc/mcmc.hip) trains towards a hard budget of `cap_max` Gaussians (required):
@@ -326,6 +348,8 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     if lambda_depth < 0 or lambda_alpha < 0:
         raise ValueError("train: lambda_depth and lambda_alpha must be >= 0")
     distortion = _distortion_option("train", lambda_dist, dist_near_far)
+    if lambda_normal < 0:
+        raise ValueError("train: lambda_normal must be >= 0")
     if optimizer_visibility not in ("radii", "blended", None):
         raise ValueError(f"train: optimizer_visibility must be 'radii', 'blended' or None, not {optimizer_visibility!r}")
     if densify_by not in ("grad", "error"):
@@ -385,15 +409,17 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
             with_dist = distortion is not False and iteration >= dist_from_iter
             if with_dist:
                 extra = dict(extra, distortion=distortion)
-            if mcmc:
-                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, gather_visible=False, **extra)
-            elif by_error:
+            with_normal = lambda_normal > 0 and iteration >= normal_from_iter
+            if with_normal:
+                extra = dict(extra, normal=True)
+            # a normal needs axes: with the term the rasterizer builds the covariance from the scales and rotations itself
+            frozen = {} if (mcmc or with_normal) else {"cov3d": cov3d * coeff}
+            if by_error:
                 gt_image = viewpoint_cam.original_image.to(dev)
-                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False,
-                                              error_target=gt_image, **extra)
+                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, gather_visible=False,
+                                              error_target=gt_image, **frozen, **extra)
             else:
-                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, cov3d=cov3d * coeff, gather_visible=False,
-                                              **extra)
+                render_pkg = gaussians.render(viewpoint_cam, pipe, bg, clamp_color=False, gather_visible=False, **frozen, **extra)
             image, viewspace_point_tensor, radii = render_pkg["render"], render_pkg["viewspace_points"], render_pkg["radii"]
             if not by_error:
                 gt_image = viewpoint_cam.original_image.to(image.device)
@@ -411,6 +437,9 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
                 loss = loss + lambda_depth * residual / measured.sum().clamp(min=1)
             if with_dist:
                 loss = loss + lambda_dist * render_pkg["distortion"].mean()
+            if with_normal:
+                loss = loss + lambda_normal * _normals.normal_consistency(render_pkg["depth"], render_pkg["alpha"],
+                                                                          render_pkg["normal"], viewpoint_cam.intrinsic)
             if mcmc:
                 loss = loss + opacity_reg * torch.sigmoid(gaussians._opacity).mean() + scale_reg * gaussians.get_scaling.mean()
             loss.backward()

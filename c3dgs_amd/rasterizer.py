@@ -5,8 +5,8 @@ on top of the MI355X C-ABI library.  Same names, argument order and error behavi
     GaussianRasterizationSettings, GaussianRasterizer, GaussianRasterizerIndexed,
     rasterize_gaussians, rasterize_gaussians_indexed, rasterize_gaussians_indexed_camera,
     getProjectionMatrix, quat_to_mat, mat_to_quat, and `_C` with the five pybind entry points
-    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`, `render_distortion`, `render_contrib`, `render_error`, `error_map_l1`,
-    `pose_grad`, `aa_opacity` and `aa_opacity_backward`.
+    (submodules/diff-gaussian-rasterization/ext.cpp:15-21) plus `render_depth`, `render_distortion`, `gaussian_normals`, `render_normal`,
+    `render_contrib`, `render_error`, `error_map_l1`, `pose_grad`, `aa_opacity` and `aa_opacity_backward`.
 
 Beyond the reference: `GaussianRasterizationSettings(depth=True)` / `_C.render_depth` add depth, accumulated-opacity and
 median-depth maps of a forward (forward-only, csrc/render_depth.hip); `GaussianRasterizationSettings(contrib=True)` /
@@ -21,7 +21,11 @@ the depth and alpha maps differentiable outputs (csrc/render_depth_backward.hip,
 0.3 px^2 low-pass (csrc/aa_opacity.hip, one per-Gaussian launch in front of the forward and one behind the backward);
 `GaussianRasterizationSettings(distortion=True | (near, far))` / `_C.render_distortion` append the depth-distortion map of
 Mip-NeRF 360 as a differentiable last output (csrc/render_distortion.hip; in the backward ONE blend replay for the depth, alpha
-and distortion maps, csrc/render_distortion_backward.hip).
+and distortion maps, csrc/render_distortion_backward.hip); `GaussianRasterizationSettings(normal=True)` / `_C.gaussian_normals` /
+`_C.render_normal` append the blended map of the Gaussians' view-space normals as a differentiable last output (csrc/normals.hip,
+csrc/render_normal.hip; in the backward ONE blend replay for every map of the call, csrc/render_normal_backward.hip, and the
+gradient to the rotations through the normals); c3dgs_amd/normals.py has the depth -> normal stencil and the normal-consistency
+term on top of it.
 
 PyTorch is plumbing only here (device memory, streams, autograd bookkeeping); every numeric stage
 runs in libc3dgs_hip.so.  There is no CPU path: tensors must live on the GPU.
@@ -323,7 +327,7 @@ def _forward(indexed, background, means3D, colors, opacity, scales, scale_factor
 def _backward(indexed, background, means3D, radii, colors, scales, scale_factors, rotations, scale_modifier, cov3D_precomp,
               viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
               imageBuffer, debug, sh_indices, g_indices, skip=(), dL_ddepth=None, dL_dalpha=None, dL_ddistortion=None, moment=None,
-              near_far=None):
+              near_far=None, dL_dnormal=None, normals=None, normal_axes=None):
     """`dL_ddepth` / `dL_dalpha`: [H, W] fp32 gradients of the depth / alpha maps of _C.render_depth, or None. With either, the call
     goes to the library's *_backward_depth entry (csrc/render_depth_backward.hip: one blend replay in front of the per-Gaussian
     kernels, one small fold behind them) and `dL_dout_color` may be None (the loss does not use the image: no colour blend
@@ -332,16 +336,23 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
     second output and `near_far` its mode (None: raw), and the call goes to the *_backward_distortion entry
     (csrc/render_distortion_backward.hip: one blend replay for the three maps in the place of the depth one). Without it the three
     arguments are ignored.
+    `dL_dnormal`: [3, H, W] fp32 gradient of the normal map of _C.render_normal, or None; with it `normals` is the [P, 4] buffer
+    of _C.gaussian_normals for the same forward, and the call goes to the *_backward_normal entry
+    (csrc/render_normal_backward.hip: one blend replay for EVERY map of the call in the place of the other two, and one more
+    fold, which adds into dL_drotations). `normal_axes` = (rotations, g_indices | None): the rows the normals were made from where
+    the call blends a `cov3D_precomp` (a filtered covariance, say), which has no axes; the fold's gradient then comes back as one
+    more element at the END of the returned tuple, of the shape of those rotations. Without `dL_dnormal` both are ignored.
     `skip`: names among ("dL_dcolors", "dL_dcov3D") that are neither allocated nor written and come back as None. The
     autograd wrappers name the gradients of ABSENT optional inputs: dL_dcolors (12 B x P) and dL_dcov3D (24 B x P) are
     108 MB of stores per 3M-Gaussian backward. The pybind-order entry points (_C.*) skip nothing, like the reference."""
     L = _lib.lib()
     dist = dL_ddistortion is not None
-    maps = dL_ddepth is not None or dL_dalpha is not None or dist
+    nrm = dL_dnormal is not None
+    maps = dL_ddepth is not None or dL_dalpha is not None or dist or nrm
     if dL_dout_color is not None:
         H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))           # rasterize_points.cu:143-145
     elif maps:
-        H, W = (int(v) for v in next(m for m in (dL_ddepth, dL_dalpha, dL_ddistortion) if m is not None).shape)
+        H, W = (int(v) for v in next(m for m in (dL_ddepth, dL_dalpha, dL_ddistortion, dL_dnormal) if m is not None).shape[-2:])
     else:
         raise RuntimeError("dL_dout_color is required")
     if dist and moment is None:
@@ -350,6 +361,13 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
                     ("moment", moment if dist else None)):
         if m is not None:
             _check_map(m, (H, W), means3D.device, name)
+    if nrm:
+        if normals is None:
+            raise RuntimeError("c3dgs_amd: dL_dnormal needs the normals buffer of _C.gaussian_normals")
+        if cov3D_precomp is not None and cov3D_precomp.numel() and normal_axes is None:
+            raise ValueError("normal: a precomputed covariance has no axes, so no normal (pass normal_axes beside it)")
+        _check_map(dL_dnormal, (3, H, W), means3D.device, "dL_dnormal")
+        _check_map(normals, (int(means3D.size(0)), 4), means3D.device, "normals")
     # opacities are not an input of the reference's backward either (they live in the geometry buffer)
     p, t = _params(background=background, means3D=means3D, colors=colors, opacity=None, scales=scales,
                    scale_factors=scale_factors, rotations=rotations, scale_modifier=scale_modifier,
@@ -391,8 +409,18 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
         g.dL_dscale_factors = dL_dscale_factors.data_ptr() if (dL_dscale_factors is not None and P > 0) else None
         radii_c = radii.contiguous()
         dpix = _optional(dL_dout_color, "dL_dout_color")
+        axes_rot = axes_gi = dL_daxes = None
+        if nrm and normal_axes is not None:
+            axes_rot = _lib.gpu_tensor(normal_axes[0], "normal_axes rotations", torch.float32)
+            axes_gi = _optional(normal_axes[1], "normal_axes g_indices", torch.int64)
+            dL_daxes = torch.zeros_like(axes_rot)               # the fold adds into it
         scratch = _Scratch(dev)
-        if dist:
+        if nrm:
+            fn = L.c3dgs_rasterize_gaussians_backward_normal_indexed if indexed else L.c3dgs_rasterize_gaussians_backward_normal
+            near, far = _near_far(near_far)
+            extra = (_ptr(dL_ddepth), _ptr(dL_dalpha), _ptr(dL_dnormal), _ptr(normals), _ptr(axes_rot), _ptr(axes_gi), _ptr(dL_daxes),
+                     _ptr(dL_ddistortion), _ptr(moment if dist else None), near, far)
+        elif dist:
             fn = (L.c3dgs_rasterize_gaussians_backward_distortion_indexed if indexed else
                   L.c3dgs_rasterize_gaussians_backward_distortion)
             near, far = _near_far(near_far)
@@ -410,12 +438,13 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
                 scratch.callback("ws"), None, C.byref(g), _stream(dev))
     scratch.release()       # the workspace goes back to the (stream-ordered) caching allocator right away
     _lib.check(rc)
+    tail = (dL_daxes,) if dL_daxes is not None else ()
     if indexed:
         if t["scales"] is None:
             dL_dscale_factors.zero_()
         return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_dscale_factors,
-                dL_drotations)
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+                dL_drotations) + tail
+    return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations) + tail
 
 
 # ---- the five entry points with the pybind argument order (ext.cpp:15-21, rasterize_points.h:18-122), and render_depth
@@ -540,6 +569,46 @@ def _c_render_distortion(P, W, H, R, geomBuffer, binningBuffer, imgBuffer, near_
                                                 ptr(out[0]), ptr(out[1]), _stream(dev))
     _lib.check(rc)
     return out[0], out[1]
+
+
+def _c_gaussian_normals(means3D, scales, rotations, g_indices, viewmatrix):
+    """The per-Gaussian normals of a view (c3dgs_gaussian_normals): -> [P, 4] fp32 {n_x, n_y, n_z, sigma (m + 1)} on the current
+    stream. n is the Gaussian's shortest axis in VIEW space (x right, y down, z forward), unit length, facing the camera: with
+    q, s the Gaussian's rows of `rotations` / `scales` (`g_indices` None) or the codebook rows g_indices selects,
+    m = argmin_j s[j] on the raw row (lowest j on a tie), c = column m of the rotation matrix of q (q not normalised),
+    v = R_view c / |c| (0 where |c| == 0), sigma = -1 where v . p > 0 for the view-space mean p, else +1, n = sigma v. Every row
+    is written, culled or not."""
+    if not means3D.is_cuda:
+        raise RuntimeError("c3dgs_amd: gaussian_normals needs GPU tensors (there is no CPU path)")
+    dev = means3D.device
+    P = int(means3D.size(0))
+    t = [_lib.gpu_tensor(means3D, "means3D", torch.float32) if P else None, _optional(scales, "scales"),
+         _optional(rotations, "rotations"), _optional(g_indices, "g_indices", torch.int64), _optional(viewmatrix, "viewmatrix")]
+    if P and (t[1] is None or t[2] is None):
+        raise ValueError("normal: scales and rotations are required (a precomputed covariance has no axes, so no normal)")
+    with torch.cuda.device(dev):
+        out = torch.empty((P, 4), dtype=torch.float32, device=dev)
+        rc = _lib.lib().c3dgs_gaussian_normals(P, *(_ptr(v) for v in t), _ptr(out) if P else None, _stream(dev))
+    _lib.check(rc)
+    return out
+
+
+def _c_render_normal(P, W, H, R, geomBuffer, binningBuffer, imgBuffer, normals):
+    """The normal map of the forward that filled the three buffers (c3dgs_render_normal): -> [3, H, W] fp32 on the current stream,
+    sum_k w_k n_k over the pixel's blended entries with w = alpha T and n = the rows of `normals` (_C.gaussian_normals);
+    accumulated like a colour channel, not normalised, no background term. Valid before or after the matching backward."""
+    if not imgBuffer.is_cuda:
+        raise RuntimeError("c3dgs_amd: render_normal needs the forward's GPU buffers (there is no CPU path)")
+    dev = imgBuffer.device
+    P, W, H, R = int(P), int(W), int(H), int(R)
+    _check_map(normals, (P, 4), dev, "normals")
+    with torch.cuda.device(dev):
+        out = torch.empty((3, max(H, 0), max(W, 0)), dtype=torch.float32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        rc = _lib.lib().c3dgs_render_normal(P, W, H, R, ptr(geomBuffer), ptr(binningBuffer), ptr(imgBuffer), ptr(normals),
+                                            ptr(out), _stream(dev))
+    _lib.check(rc)
+    return out
 
 
 class _GrowOnly:
@@ -753,6 +822,8 @@ def _c_error_map_l1(img, gt):
 _C = SimpleNamespace(
     render_depth=_c_render_depth,
     render_distortion=_c_render_distortion,
+    gaussian_normals=_c_gaussian_normals,
+    render_normal=_c_render_normal,
     render_contrib=_c_render_contrib,
     render_error=_c_render_error,
     error_map_l1=_c_error_map_l1,
@@ -788,6 +859,16 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     rs = raster_settings
     dev = means3D.device
     antialiasing = bool(getattr(rs, "antialiasing", False))
+    normal = bool(getattr(rs, "normal", False))
+    axes = None
+    if normal and cov3Ds_precomp is not None and cov3Ds_precomp.numel():
+        # a covariance has no axes. Where the caller blends one it has built itself (a filtered one: Sigma + f^2 I has the axes of
+        # Sigma, and adding the same amount to every squared scale leaves the shortest axis where it was), the scales and rotations
+        # given BESIDE it are the rows the normals are made from; the rasterizer itself sees the covariance alone
+        if scales is None or rotations is None or not scales.numel() or not rotations.numel():
+            raise ValueError("normal=True: a precomputed covariance has no axes, so no normal (pass scales and rotations beside it)")
+        axes = (scales, rotations)
+        scales = rotations = _empty()
     raw_opacities = opacities
     for _attempt in range(2):          # a second pass only if the cached intrinsic scalars turn out stale (_IntrinsicGuard)
         guard = []
@@ -813,7 +894,7 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     extras = ()
     # `raster_settings.distortion` implies depth_grad's outputs, in their positions
     distortion = getattr(rs, "distortion", False)
-    depth_grad = bool(getattr(rs, "depth_grad", False)) or distortion is not False
+    depth_grad = bool(getattr(rs, "depth_grad", False)) or distortion is not False or normal
     if getattr(rs, "depth", False) or depth_grad:
         extras = _C.render_depth(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer)
     # with `raster_settings.contrib`: (weight_sum, weight_max, hits) per Gaussian, behind whatever `depth` added
@@ -833,6 +914,13 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
         dist_map, moment = _C.render_distortion(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer,
                                                 distortion)
         extras = tuple(extras) + (dist_map,)
+    # with `raster_settings.normal`: one per-Gaussian launch and one more replay; the normal map goes behind everything else and
+    # is differentiable, the per-Gaussian normals stay here for the backward
+    normals = None
+    if normal:
+        normals = _C.gaussian_normals(means3D, *(axes or (scales, rotations)), g_indices if indexed else None, view)
+        extras = tuple(extras) + (_C.render_normal(int(means3D.size(0)), W, H, num_rendered, geomBuffer, binningBuffer, imgBuffer,
+                                                   normals),)
     ctx.raster_settings = rs
     ctx.indexed = indexed
     ctx.num_rendered = num_rendered
@@ -842,8 +930,11 @@ def _autograd_forward(ctx, indexed, means3D, sh, sh_indices, g_indices, colors_p
     ctx.image_size = (H, W)
     ctx.save_for_backward(extrinsic_vector, colors_precomp, means3D, scales, scale_factors, rotations, cov3Ds_precomp, radii, sh,
                           geomBuffer, binningBuffer, imgBuffer, sh_indices, g_indices, *((raw_opacities,) if antialiasing else ()),
+                          *((normals,) if normals is not None else ()), *((axes[1],) if axes is not None else ()),
                           *((moment,) if moment is not None else ()))
     ctx.distortion = distortion
+    ctx.normal = normal
+    ctx.normal_axes = axes is not None
     ctx.image_shape = tuple(color.shape)
     # without this, autograd hands backward a zero-filled int32[P] "gradient" for radii on every call (a 12 MB fill at P = 3M)
     ctx.set_materialize_grads(False)
@@ -868,7 +959,11 @@ def _map_grads(ctx, params):
     if not getattr(ctx, "depth_grad", False):
         return None, None
     fit = lambda g: None if g is None else g.to(torch.float32).contiguous()            # noqa: E731
-    # behind them, of a `distortion` forward: dL_ddistortion, the gradient of the last output
+    # behind them, of a `distortion` forward: dL_ddistortion, the gradient of the last output; of a `normal` forward the normal
+    # map is the last output and the distortion map, if any, the one in front of it: then (.., dL_ddistortion | None, dL_dnormal)
+    if getattr(ctx, "normal", False):
+        dist = fit(params[-2]) if getattr(ctx, "distortion", False) is not False else None
+        return tuple(fit(g) for g in params[1:3]) + (dist, fit(params[-1]))
     last = (fit(params[-1]),) if getattr(ctx, "distortion", False) is not False else ()
     return tuple(fit(g) for g in params[1:3]) + last
 
@@ -889,6 +984,15 @@ def _autograd_backward(ctx, grad_out_color, exact_pose=False, map_grads=(None, N
         # the moment map is the last saved tensor; without a gradient for the distortion map the backward is today's
         maps = dict(dL_ddepth=grad_depth, dL_dalpha=grad_alpha, dL_ddistortion=grad_dist, moment=ctx.saved_tensors[-1],
                     near_far=ctx.distortion)
+    grad_normal = map_grads[3] if len(map_grads) > 3 else None
+    if grad_normal is not None:
+        # the per-Gaussian normals sit behind the 14 fixed tensors and the raw opacities; without a gradient for the normal map
+        # the backward is what the other settings give
+        at = 14 + int(bool(getattr(ctx, "antialiasing", False)))
+        maps = dict(maps or dict(dL_ddepth=grad_depth, dL_dalpha=grad_alpha), dL_dnormal=grad_normal, normals=ctx.saved_tensors[at])
+        if getattr(ctx, "normal_axes", False):
+            # the rotations the normals were made from, beside a precomputed covariance: the fold's gradient is theirs
+            maps["normal_axes"] = (ctx.saved_tensors[at + 1], g_indices if ctx.indexed else None)
     if grad_out_color is None and not maps:
         # set_materialize_grads(False): an image nobody differentiated through arrives as None (backward still runs when only
         # `radii` was used downstream of a graph that needs grad); the library wants a dense dL/dC
@@ -904,14 +1008,15 @@ def _autograd_backward(ctx, grad_out_color, exact_pose=False, map_grads=(None, N
                 proj, tanfovx, tanfovy, grad_out_color, sh, rs.sh_degree, campos, geomBuffer, ctx.num_rendered, binningBuffer,
                 imgBuffer, rs.debug, sh_indices, g_indices)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_scale_factors, grad_rotations) = _call_debug(_C.rasterize_gaussians_backward_indexed, args, rs.debug,
-                                                           "snapshot_bw.dump", skip=skip, **maps)
+         grad_scale_factors, grad_rotations, *grad_axes) = _call_debug(_C.rasterize_gaussians_backward_indexed, args, rs.debug,
+                                                                       "snapshot_bw.dump", skip=skip, **maps)
     else:
         args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, view, proj,
                 tanfovx, tanfovy, grad_out_color, sh, rs.sh_degree, campos, geomBuffer, ctx.num_rendered, binningBuffer,
                 imgBuffer, rs.debug)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _call_debug(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump", skip=skip, **maps)
+         grad_rotations, *grad_axes) = _call_debug(_C.rasterize_gaussians_backward, args, rs.debug, "snapshot_bw.dump", skip=skip,
+                                                   **maps)
     if getattr(ctx, "antialiasing", False):
         # behind the whole backward (the depth maps' part included) on the same stream: dL/do' becomes dL/do and the terms through
         # rho are added to the gradients the backward has just written (csrc/aa_opacity.hip)
@@ -935,7 +1040,7 @@ def _autograd_backward(ctx, grad_out_color, exact_pose=False, map_grads=(None, N
     return SimpleNamespace(pose=grad_pose, means3D=grad_means3D, means2D=grad_means2D, sh=_fit(grad_sh, sh),
                            colors_precomp=_fit(grad_colors_precomp, colors_precomp), opacities=grad_opacities,
                            scales=_fit(grad_scales, scales), scale_factors=_fit(grad_scale_factors, scale_factors),
-                           rotations=_fit(grad_rotations, rotations), cov3Ds_precomp=_fit(grad_cov3Ds_precomp, cov3Ds_precomp))
+                           rotations=grad_axes[0] if grad_axes else _fit(grad_rotations, rotations), cov3Ds_precomp=_fit(grad_cov3Ds_precomp, cov3Ds_precomp))
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -1120,6 +1225,9 @@ def _check_depth_grad_camera(raster_settings, optimize_camera):
     if optimize_camera is not False and getattr(raster_settings, "distortion", False) is not False:
         raise ValueError("distortion cannot be combined with optimize_camera: the gradient to the camera pose through the "
                          "depth, alpha and distortion maps is not implemented")
+    if optimize_camera is not False and getattr(raster_settings, "normal", False):
+        raise ValueError("normal=True cannot be combined with optimize_camera: the gradient to the camera pose through the "
+                         "depth, alpha and normal maps is not implemented")
 
 
 def _distortion_setting(value):
@@ -1194,14 +1302,28 @@ class GaussianRasterizationSettings(_SettingsFields):
     tuple (csrc/render_distortion.hip, one more forward replay), a differentiable output as well: a loss on it reaches every input
     the depth map reaches, through ONE blend replay in the backward for the three maps (csrc/render_distortion_backward.hip, in
     the place of the depth maps' replay). When it receives no gradient the backward is depth_grad's. With `distortion`,
-    `optimize_camera` other than False raises ValueError, as with `depth_grad`."""
+    `optimize_camera` other than False raises ValueError, as with `depth_grad`.
+    `normal` (keyword only, default False) is a sixth such attribute. True: the rasterizers return depth_grad's outputs in their
+    positions, differentiable as there, and append the normal map N[3, H, W] = sum_k w_k n_k of every pixel's blended entries as
+    the LAST element of the tuple, behind `distortion` when both are set (csrc/normals.hip, csrc/render_normal.hip: one
+    per-Gaussian launch and one more forward replay). n is the Gaussian's shortest axis in VIEW space (x right, y down, z
+    forward), unit length and facing the camera (_C.gaussian_normals says how it is chosen); N is not normalised and has no
+    background term, like `depth`. It is a differentiable output: a loss on it reaches the opacities, means and covariances
+    through w, and the rotations through n as well, through ONE blend replay in the backward for every map of the call
+    (csrc/render_normal_backward.hip, in the place of the other two) and one more fold. When it receives no gradient the backward
+    is what the other settings give. A precomputed covariance has no axes: with `normal`, `cov3D_precomp` alone raises ValueError.
+    A caller that blends a covariance it has built from scales and rotations (a filtered one) passes the pair BESIDE it: the
+    rasterizer sees the covariance, the normals are made from the pair, and the rotations receive the normals' gradient.
+    `optimize_camera` other than False raises ValueError."""
     contrib = False
     error_target = None
     depth_grad = False
     antialiasing = False
     distortion = False
+    normal = False
 
-    def __new__(cls, *args, contrib=False, error_target=None, depth_grad=False, antialiasing=False, distortion=False, **kwargs):
+    def __new__(cls, *args, contrib=False, error_target=None, depth_grad=False, antialiasing=False, distortion=False, normal=False,
+                **kwargs):
         n = len(cls._fields)
         if len(args) == n + 1:
             args, contrib = args[:n], args[n]
@@ -1211,6 +1333,7 @@ class GaussianRasterizationSettings(_SettingsFields):
         self.depth_grad = bool(depth_grad)
         self.antialiasing = bool(antialiasing)
         self.distortion = _distortion_setting(distortion)
+        self.normal = bool(normal)
         return self
 
     def _replace(self, **kwargs):
@@ -1219,18 +1342,24 @@ class GaussianRasterizationSettings(_SettingsFields):
         depth_grad = kwargs.pop("depth_grad", self.depth_grad)
         antialiasing = kwargs.pop("antialiasing", self.antialiasing)
         distortion = kwargs.pop("distortion", self.distortion)
+        normal = kwargs.pop("normal", self.normal)
         new = super()._replace(**kwargs)
         new.contrib = bool(contrib)
         new.error_target = error_target
         new.depth_grad = bool(depth_grad)
         new.antialiasing = bool(antialiasing)
         new.distortion = _distortion_setting(distortion)
+        new.normal = bool(normal)
         return new
 
 
-def _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp):
+def _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp, axes_beside_covariance=False):
+    """`axes_beside_covariance` (settings.normal): a scale / rotation pair NEXT TO a precomputed covariance is accepted; the
+    rasterizer blends the covariance and the normals are made from the pair"""
     if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
         raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+    if axes_beside_covariance and cov3D_precomp is not None and scales is not None and rotations is not None:
+        return
     if ((scales is None or rotations is None) and cov3D_precomp is None) or (
             (scales is not None or rotations is not None) and cov3D_precomp is not None):
         raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
@@ -1282,7 +1411,7 @@ class GaussianRasterizer(_Rasterizer):
                 cov3D_precomp=None, extrinsic_vector=None, extrinsic=None):
         _check_depth_grad_camera(self.raster_settings, self.optimize_camera)
         _check_antialiasing_camera(self.raster_settings, self.optimize_camera)
-        _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp, bool(getattr(self.raster_settings, "normal", False)))
         if extrinsic_vector is None:
             extrinsic_vector = extrinsic if extrinsic is not None else self.raster_settings.extrinsic_vector
         shs, colors_precomp, scales, rotations, cov3D_precomp = _absent_to_empty(shs, colors_precomp, scales, rotations,
@@ -1306,7 +1435,7 @@ class GaussianRasterizerIndexed(_Rasterizer):
                 scale_factors=None, rotations=None, cov3D_precomp=None, extrinsic_vector=None):
         _check_depth_grad_camera(self.raster_settings, bool(self.optimize_camera))
         _check_antialiasing_camera(self.raster_settings, bool(self.optimize_camera))
-        _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        _check_exclusive(shs, colors_precomp, scales, rotations, cov3D_precomp, bool(getattr(self.raster_settings, "normal", False)))
         if extrinsic_vector is None:
             extrinsic_vector = self.raster_settings.extrinsic_vector
         shs, colors_precomp, scales, scale_factors, rotations, cov3D_precomp = _absent_to_empty(

@@ -211,6 +211,80 @@ int c3dgs_rasterize_gaussians_backward_distortion_indexed(const c3dgs_raster_par
                                                           const c3dgs_raster_grads* grads, void* stream);
 size_t c3dgs_distortion_backward_workspace_bytes(int32_t P, int32_t R);
 
+/* ---- normal maps (csrc/normals.hip, csrc/render_normal.hip, csrc/render_normal_backward.hip; no reference counterpart) ----
+ * All normals are in VIEW space: x right, y down, z forward, the frame of `viewmatrix`.
+ *
+ * c3dgs_gaussian_normals: one lane per Gaussian. With q = rotations[g], s = scales[g] (g_indices NULL) or the codebook rows
+ * rotations[g_indices[g]], scales[g_indices[g]]:
+ *   m = argmin_j s[j] on the RAW row (no scale modifier, no scale factor), the lowest j on a tie
+ *   c = column m of the rotation matrix of q as preprocess builds it (q is not normalised); v = R_view c / |c|, 0 where |c| == 0
+ *   n = sigma v, sigma = -1 where v . p > 0 for the view-space mean p, else +1: the normal faces the camera
+ *   out_normals[g] = {n_x, n_y, n_z, sigma (m + 1)}
+ * Every row is written, whether preprocess culled the Gaussian or not. Run it on the forward's stream. Stage "gaussian_normals".
+ *
+ * c3dgs_render_normal: out_normal[c] = sum_k w_k n_k,c over the entries the forward blended (w_k, T_k as for c3dgs_render_depth),
+ * accumulated like a colour channel of the forward; not normalised, no background term. A replay of the forward's decisions,
+ * valid before or after the matching backward; no atomics, bitwise reproducible. P == 0 or R == 0: zeros, no blend launch. The
+ * sort's time-out word set: NaN. Stage "render_normal". */
+int c3dgs_gaussian_normals(int32_t P, const float* means3D /*[P,3]*/, const float* scales, const float* rotations,
+                           const int64_t* g_indices /*[P] | NULL*/, const float* viewmatrix /*[16]*/,
+                           float* out_normals /*[P,4]*/, void* stream);
+int c3dgs_render_normal(int32_t P, int32_t W, int32_t H, int32_t R,
+                        const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                        const float* normals /*[P,4]*/, float* out_normal /*[3,H,W]*/, void* stream);
+
+/* ---- the two backward entries with a gradient through the normal map (csrc/render_normal_backward.hip) ----
+ * The arguments of the *_backward_distortion entries plus dL_dnormal = dL/d(out_normal), [3,H,W] fp32, and normals = the buffer
+ * c3dgs_gaussian_normals filled for the same forward.
+ * With dL_dnormal NULL the call IS the *_backward_distortion entry (normals and the three axes arguments are not looked at). With
+ * it, normals is required. The fold chains to the rotations the normals were made from. axes_rotations NULL: those are
+ * p->rotations under p->g_indices, the gradient goes into grads->dL_drotations, and p->cov3D_precomp must be NULL (a covariance
+ * has no axes). axes_rotations not NULL: the call may blend a precomputed covariance (a filtered one, say) while the normals come
+ * from these rows, [P,4] or a codebook under axes_g_indices ([P] | NULL); the gradient is ADDED into dL_daxes_rotations (required
+ * then, of the shape of axes_rotations, zeroed by the caller) and grads->dL_drotations is left to the rest of the backward.
+ * Violations: C3DGS_E_INVALID before any device work. Then
+ *   c_k += dL_dnormal . n_k     in the recurrences of the depth / distortion entries (the pivoted ones where dL_ddistortion is set)
+ * and ONE blend replay (stage "render_normal_backward") serves every map of the call: it stands in the place of
+ * "render_depth_backward" / "render_distortion_backward", neither of which is launched. Behind "backward_preprocess" and
+ * "depth_backward_fold", "normal_backward_fold" chains dL/dn_g = sum w_k dL_dnormal to the quaternion (the 1 / |c| included; m and
+ * sigma carry no gradient, and none flows to the mean, the scales or the pose) and ADDS it into dL_drotations: the Gaussian's
+ * own row, or the codebook row of the indexed entry. The workspace callback is asked for
+ * c3dgs_normal_backward_workspace_bytes(P, R): the depth entries' layout and behind it three floats per slot. */
+int c3dgs_rasterize_gaussians_backward_normal(const c3dgs_raster_params* p, const int32_t* radii,
+                                              const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
+                                              int32_t R, const float* dL_dout_color /*[3,H,W] | NULL with a map*/,
+                                              const float* dL_ddepth /*[H,W] | NULL*/, const float* dL_dalpha /*[H,W] | NULL*/,
+                                              const float* dL_dnormal /*[3,H,W] | NULL*/, const float* normals /*[P,4]*/,
+                                              const float* axes_rotations /*NULL | rows x 4*/,
+                                              const int64_t* axes_g_indices /*NULL | [P]*/,
+                                              float* dL_daxes_rotations /*NULL | rows x 4, zeroed*/,
+                                              const float* dL_ddistortion /*[H,W] | NULL*/, const float* moment /*[H,W]*/,
+                                              float near, float far,
+                                              c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                              const c3dgs_raster_grads* grads, void* stream);
+int c3dgs_rasterize_gaussians_backward_normal_indexed(const c3dgs_raster_params* p, const int32_t* radii,
+                                                      const void* geom_buffer, const void* binning_buffer,
+                                                      const void* image_buffer, int32_t R, const float* dL_dout_color,
+                                                      const float* dL_ddepth, const float* dL_dalpha,
+                                                      const float* dL_dnormal, const float* normals,
+                                                      const float* axes_rotations, const int64_t* axes_g_indices,
+                                                      float* dL_daxes_rotations,
+                                                      const float* dL_ddistortion, const float* moment, float near, float far,
+                                                      c3dgs_resize_fn workspace_resize, void* workspace_user,
+                                                      const c3dgs_raster_grads* grads, void* stream);
+size_t c3dgs_normal_backward_workspace_bytes(int32_t P, int32_t R);
+
+/* ---- the normal of a depth map (csrc/normals.hip) ----
+ * z[H,W] = view-space depths. P(x, y) = z(x, y) ((x + 0.5 - W / 2) / fx, (y + 0.5 - H / 2) / fy, 1) with fx = W / (2 tan_fovx),
+ * fy = H / (2 tan_fovy). Interior pixels: normalize(cross(P(x, y + 1) - P(x, y - 1), P(x + 1, y) - P(x - 1, y))) with
+ * normalize(c) = c / max(|c|, 1e-12): a fronto-parallel plane gives (0, 0, -1). The one-pixel border is 0 (W < 3 or H < 3: all).
+ * The backward gathers, per pixel, the at most four stencils that read it: dL_dz[H,W] is written everywhere, no atomics.
+ * One launch each: stages "depth_to_normal", "depth_to_normal_backward". */
+int c3dgs_depth_to_normal(int32_t W, int32_t H, const float* z /*[H,W]*/, float tan_fovx, float tan_fovy,
+                          float* out_normal /*[3,H,W]*/, void* stream);
+int c3dgs_depth_to_normal_backward(int32_t W, int32_t H, const float* z /*[H,W]*/, const float* dL_dnormal /*[3,H,W]*/,
+                                   float tan_fovx, float tan_fovy, float* dL_dz /*[H,W]*/, void* stream);
+
 /* ---- depth, accumulated opacity and median depth of a finished forward (csrc/render_depth.hip; no reference counterpart) ----
  * geom/binning/image buffers are the ones a forward of the same P, W, H filled; R is its num_rendered. Per pixel, over the
  * entries k = 1..m the forward blended (w_k = alpha_k T_k, T_{k+1} = T_k (1 - alpha_k), T_1 = 1, z_k = the fp32 view-space
