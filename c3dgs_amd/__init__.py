@@ -19,7 +19,7 @@ Drop-in for the reference's two native extensions and the Python directly around
 
 Beyond the reference, the rasterizer also returns depth / accumulated-opacity / median-depth maps, per-Gaussian blend statistics and
 error scores and the exact pose gradient; with GaussianRasterizationSettings(depth_grad=True) the depth and alpha maps carry
-gradient (csrc/render_depth_backward.hip), which GaussianModel.render(depth_grad=True) and pipeline.train(lambda_depth=,
+gradient (csrc/render_maps_backward.hip), which GaussianModel.render(depth_grad=True) and pipeline.train(lambda_depth=,
 lambda_alpha=) use for depth and silhouette losses; GaussianRasterizationSettings(antialiasing=True) / PipelineParams(antialiasing=True)
 compensate every opacity for the rasterizer's 0.3 px^2 low-pass (csrc/aa_opacity.hip), upstream 3DGS's `antialiasing`.
 pipeline.train(strategy="mcmc", cap_max=N) trains towards a hard budget of Gaussians ("3DGS as Markov Chain Monte Carlo":

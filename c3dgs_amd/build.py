@@ -31,14 +31,11 @@ SOURCES = {
     "render.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the depth / alpha / median replay of the forward's blend: render.hip's flags, so that the shared alpha expression compiles alike
     "render_depth.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
-    # the gradients through the depth / alpha maps: the same replay, walked back to front with render.hip's backward recurrences
-    "render_depth_backward.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
-    # the distortion map and the three-map backward replay: siblings of the two above, render.hip's flags for the same reason
+    # the gradients through every map: the same replay, walked back to front with render.hip's backward recurrences
+    "render_maps_backward.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
+    # the distortion and normal maps: siblings of render_depth.hip, render.hip's flags for the same reason
     "render_distortion.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
-    "render_distortion_backward.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
-    # the normal map and the replay that serves every map of a backward: siblings again, the same flags
     "render_normal.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
-    "render_normal_backward.hip": os.environ.get("C3DGS_RENDER_FLAGS", "-fno-slp-vectorize").split(),
     # the per-Gaussian normals, their fold and the depth -> normal stencil: single fp32 operations that tests/normal_ref.py
     # restates, and the chains of csrc/gsgrad.hpp
     "normals.hip": ["-ffp-contract=off"],

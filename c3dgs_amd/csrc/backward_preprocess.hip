@@ -17,6 +17,7 @@
 #include "common.hpp"
 #include "gsgrad.hpp"        // the chains shared with aa_opacity.hip, filter3d.hip and pose_grad.hip; includes gsmath.hpp
 #include "render_common.hpp" // slot_run
+#include "replay.hpp"        // listed_gaussian
 
 #ifndef C3DGS_BWD_CH
 #define C3DGS_BWD_CH 128
@@ -299,18 +300,11 @@ backward_preprocess_kernel(const BwdArgs a, const float* __restrict__ cam_view, 
 {
     // the workgroup's list fills whole waves from the front: a wave past its end has nothing to do (waves are independent:
     // no workgroup barrier below)
-    // Workgroup -> (list, quarter of the list): all FIRST quarters come first in the grid, then all second ones, ...
-    // Lists fill from the front, so the populated quarters are spread evenly over the XCDs (consecutive workgroups go to
-    // consecutive XCDs; quarter = blockIdx % 4 would send every full quarter to the same two of the eight) and the
-    // mostly empty ones come last.
-    const uint32_t n_lists = gridDim.x / (BWD_LIST / 256);
-    const uint32_t list = blockIdx.x % n_lists, quarter = blockIdx.x / n_lists;
-    const uint32_t n_live = a.live_count[list];
-    const uint32_t off = quarter * 256u + threadIdx.x;
-    if ((off & ~63u) >= n_live) return;
-    const size_t pos = (size_t)list * BWD_LIST + off;
-    const bool live = off < n_live;
-    const int i = live ? (int)a.live_ids[pos] : 0;
+    const ListedGaussian lg = listed_gaussian(a.live_count, a.live_ids);
+    if (!lg.wave_has_work) return;
+    const size_t pos = lg.pos;
+    const bool live = lg.live;
+    const int i = lg.i;
     const size_t si = (size_t)i;
     const c3dgs_raster_grads& o = a.g;
     constexpr int NB = (DEG + 1) * (DEG + 1);

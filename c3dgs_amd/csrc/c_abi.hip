@@ -360,16 +360,14 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
                          const float* dL_dnormal = nullptr, const float* normals = nullptr, const float* axes_rotations = nullptr,
                          const int64_t* axes_g_indices = nullptr, float* dL_daxes_rotations = nullptr)
 {
-    // gradients through the depth / alpha maps (render_depth_backward.hip): without a map, exactly the plain backward below.
-    // With the distortion map's gradient, render_distortion_backward.hip's replay serves all three maps in that one's place;
-    // without it the other four distortion arguments are not looked at
+    // gradients through the maps (render_maps_backward.hip: one blend replay for every map of the call): without a map, exactly
+    // the plain backward below. Without the distortion map's gradient the other four distortion arguments are not looked at
     if (dL_ddistortion) {
         if (!moment) return fail(C3DGS_E_INVALID, "backward_distortion: moment is required with dL_ddistortion");
         if (!(far_ <= 0.f) && !(near_ > 0.f && near_ < far_))       // a NaN fails here as well
             return fail(C3DGS_E_INVALID, "backward_distortion: 0 < near < far is required (far <= 0 selects the raw mode)");
     }
-    // With the normal map's gradient, render_normal_backward.hip's replay serves every map of the call in the place of both, and
-    // normal_backward_fold follows backward_preprocess; without it `normals` and the axes are not looked at. The fold chains to the
+    // With the normal map's gradient normal_backward_fold follows backward_preprocess; without it `normals` and the axes are not looked at. The fold chains to the
     // rotations the normals were made from: the call's own (and its dL_drotations), or, where the call blends a precomputed
     // covariance, which has no axes, the rotations given beside it, into a gradient tensor of their own that the caller has zeroed
     if (dL_dnormal) {
@@ -446,18 +444,13 @@ static int backward_impl(const c3dgs_raster_params* pp, bool indexed, const int3
             C3DGS_TIMED_STAGE(ST_RENDER_BWD, p.debug, s,
                               launch_render_backward(W, H, img, g.splat, g.block_base, p.background, dL_dout_color, w.partials, w.touched,
                                                      cl, cb_zero, cb_zero16, s)); // K10
-        if (dL_dnormal)
-            C3DGS_TIMED_STAGE(ST_RENDER_NORMAL_BWD, p.debug, s,
-                              launch_render_normal_backward(W, H, img, cl, g, w, dz_plane, dn_plane, normals, dL_ddepth, dL_dalpha,
-                                                            dL_dnormal, dL_ddistortion, moment, distortion_map(near_, far_), sort_err,
-                                                            s));
-        else if (dL_ddistortion)
-            C3DGS_TIMED_STAGE(ST_RENDER_DISTORTION_BWD, p.debug, s,
-                              launch_render_distortion_backward(W, H, img, cl, g, w, dz_plane, dL_ddepth, dL_dalpha, dL_ddistortion,
-                                                                moment, distortion_map(near_, far_), sort_err, s));
-        else if (maps)
-            C3DGS_TIMED_STAGE(ST_RENDER_DEPTH_BWD, p.debug, s,
-                              launch_render_depth_backward(W, H, img, cl, g, w, dz_plane, dL_ddepth, dL_dalpha, sort_err, s));
+        if (maps) {
+            // one replay for every map of the call; the stage is named after the widest map it serves
+            const int stage = dL_dnormal ? ST_RENDER_NORMAL_BWD : dL_ddistortion ? ST_RENDER_DISTORTION_BWD : ST_RENDER_DEPTH_BWD;
+            C3DGS_TIMED_STAGE(stage, p.debug, s,
+                              launch_render_maps_backward(W, H, img, cl, g, w, dz_plane, dn_plane, normals, dL_ddepth, dL_dalpha,
+                                                          dL_dnormal, dL_ddistortion, moment, distortion_map(near_, far_), sort_err, s));
+        }
     }
     C3DGS_TIMED_STAGE(ST_BWD_PREPROCESS, p.debug, s, launch_backward_preprocess(p, radii, g, w, *grads, s)); // K11 + K12(i)
     if (maps && R > 0 && grads->dL_dmeans3D)

@@ -198,9 +198,9 @@ inline void backward_layout(int P, int R, c3dgs_backward_layout* L)
     L->total_bytes = o;
 }
 
-// Workspace of a backward with depth / alpha map gradients (render_depth_backward.hip): the backward's layout above, unchanged and
+// Workspace of a backward with depth / alpha map gradients (render_maps_backward.hip): the backward's layout above, unchanged and
 // at the same offsets, and behind it the dL/dz plane, f32 [R], in the slot numbering of the partials. The plane is never cleared:
-// an element means something only where the slot's "written" flag is set behind render_depth_backward_kernel.
+// an element means something only where the slot's "written" flag is set behind render_maps_backward_kernel.
 struct DepthBackwardLayout { size_t dz, total_bytes; };
 inline DepthBackwardLayout depth_backward_layout(int P, int R)
 {
@@ -212,7 +212,7 @@ inline DepthBackwardLayout depth_backward_layout(int P, int R)
     return L;
 }
 
-// Workspace of a backward with a gradient through the normal map (render_normal_backward.hip): depth_backward_layout's, unchanged and
+// Workspace of a backward with a gradient through the normal map (render_maps_backward.hip): depth_backward_layout's, unchanged and
 // at the same offsets, and behind it the dn plane, three floats per slot in the same numbering: sum over the tile's pixels of
 // w gN for the slot's (Gaussian, tile). Never cleared either: valid where the slot's flag is set behind the replay.
 struct NormalSlot { float x, y, z; };
@@ -227,7 +227,7 @@ inline NormalBackwardLayout normal_backward_layout(int P, int R)
     return L;
 }
 
-// s = f(z) of the distortion passes (render_distortion.hip, render_distortion_backward.hip). ndc == 0: raw, f(z) = z. Otherwise
+// s = f(z) of the distortion passes (render_distortion.hip, render_maps_backward.hip). ndc == 0: raw, f(z) = z. Otherwise
 // f(z) = far / (far - near) * (1 - near / z) = c0 - c1 / z, c0 and c1 rounded from double (raw: c0 = 0), on the correctly rounded
 // rz = 1 / z. The map and its gradient only see differences of s, and a sum of w s of the size of s cannot carry them in fp32
 // where a ray's spread is small (ndc: s near 1, spreads of 0.01). So no pass forms s itself per entry: rel() is s - c0, which the
@@ -440,24 +440,21 @@ void launch_render_backward(int W, int H, const ImgPtrs& img, const float4* spla
 // render_depth.hip (forward-only replay of the blend: depth / accumulated opacity / median depth; null outputs are skipped)
 void launch_render_depth(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const float4* splat, const uint32_t* depth_keys,
                          float* out_depth, float* out_alpha, float* out_median, const uint32_t* sort_err, hipStream_t s);
-// render_depth_backward.hip (gradients through the depth / alpha maps; either map may be null = zeros): the blend replay that adds
-// its six moments into the backward's partial-sum slots (behind render_backward or the flag clear, in front of
-// launch_backward_preprocess) and writes the dL/dz plane, and the fold of that plane into dL_dmeans3D behind
-// launch_backward_preprocess (it walks that launch's lists of blended Gaussians).
-void launch_render_depth_backward(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const BwdPtrs& w,
-                                  float* dz_plane, const float* dL_ddepth, const float* dL_dalpha, const uint32_t* sort_err,
-                                  hipStream_t s);
+// render_maps_backward.hip (gradients through the depth, alpha, distortion and normal maps in ONE blend replay; dL_ddepth /
+// dL_dalpha may be null = zeros; dL_ddistortion not null: with the distortion map, moment is required; dL_dnormal not null: with
+// the normal map, normals and dn_plane are required): the blend replay that adds its six moments into the backward's partial-sum
+// slots (behind render_backward or the flag clear, in front of launch_backward_preprocess) and writes the dL/dz plane and, with
+// the normal map, the dn plane; and the fold of the dL/dz plane into dL_dmeans3D behind launch_backward_preprocess (it walks
+// that launch's lists of blended Gaussians).
+void launch_render_maps_backward(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const BwdPtrs& w,
+                                 float* dz_plane, NormalSlot* dn_plane, const float* normals, const float* dL_ddepth,
+                                 const float* dL_dalpha, const float* dL_dnormal, const float* dL_ddistortion, const float* moment,
+                                 const DistortionMap& f, const uint32_t* sort_err, hipStream_t s);
 void launch_depth_backward_fold(int P, const GeomPtrs& g, const BwdPtrs& w, const float* dz_plane, const float* view,
                                 float* dL_dmeans3D, const uint32_t* sort_err, hipStream_t s);
 // render_distortion.hip (forward-only replay of the blend: the distortion map and the first moment sum w s; out_moment may be null)
 void launch_render_distortion(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const float4* splat, const uint32_t* depth_keys,
                               const DistortionMap& f, float* out_distortion, float* out_moment, const uint32_t* sort_err, hipStream_t s);
-// render_distortion_backward.hip (gradients through the depth, alpha AND distortion maps in one blend replay: it stands where
-// launch_render_depth_backward stands, with the same slots, flags and dL/dz plane, and launch_depth_backward_fold follows it as it
-// follows that; dL_ddepth / dL_dalpha may be null = zeros, dL_ddistortion and moment are required)
-void launch_render_distortion_backward(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const BwdPtrs& w,
-                                       float* dz_plane, const float* dL_ddepth, const float* dL_dalpha, const float* dL_ddistortion,
-                                       const float* moment, const DistortionMap& f, const uint32_t* sort_err, hipStream_t s);
 // normals.hip: the per-Gaussian normals [P, 4] = {n_x, n_y, n_z, sigma (m + 1)} (g_indices null: the rows are the Gaussians' own),
 // the fold of the dn plane into dL_drotations behind launch_backward_preprocess (beside launch_depth_backward_fold), and the
 // depth -> normal stencil with its gather backward
@@ -472,12 +469,6 @@ void launch_depth_to_normal_backward(int W, int H, const float* z, const float* 
 // render_normal.hip (forward-only replay of the blend: the normal map [3, H, W] = sum w n)
 void launch_render_normal(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const float4* splat, const float* normals,
                           float* out_normal, const uint32_t* sort_err, hipStream_t s);
-// render_normal_backward.hip (gradients through the depth, alpha, normal and -- dL_ddistortion not null -- distortion maps in one
-// blend replay: it stands where launch_render_depth_backward / launch_render_distortion_backward stand, and both folds follow it)
-void launch_render_normal_backward(int W, int H, const ImgPtrs& img, const CompactPtrs& cl, const GeomPtrs& g, const BwdPtrs& w,
-                                   float* dz_plane, NormalSlot* dn_plane, const float* normals, const float* dL_ddepth,
-                                   const float* dL_dalpha, const float* dL_dnormal, const float* dL_ddistortion, const float* moment,
-                                   const DistortionMap& f, const uint32_t* sort_err, hipStream_t s);
 // render_contrib.hip (forward-only replay of the blend: per-Gaussian sum / max of alpha T and blended-pair count; null outputs are
 // skipped): the blend replay into the slots (the caller has cleared w.touched on the stream), the per-Gaussian fold of the slots,
 // and the fold of one view's rows into model-sized accumulators.

@@ -1,11 +1,11 @@
 // normals.hip -- the per-Gaussian passes and the image stencil of the normal maps, for gfx950. The reference's rasterizer has no
-// counterpart. (The two blend replays are render_normal.hip and render_normal_backward.hip.)
+// counterpart. (The two blend replays are render_normal.hip and render_maps_backward.hip.)
 //
 //   gaussian_normals_kernel        one lane per Gaussian, behind preprocess on the forward's stream: n_g (gsgrad.hpp: the
 //                                  shortest axis in view space, facing the camera) -> out[g] = {n_x, n_y, n_z, sigma (m + 1)},
 //                                  so that the backward re-derives neither the axis nor the sign. EVERY row is written, the rows
 //                                  preprocess culled included: they hold the definition's value for the Gaussian as well.
-//   normal_backward_fold_kernel    behind backward_preprocess, beside depth_backward_fold_kernel (render_depth_backward.hip, whose
+//   normal_backward_fold_kernel    behind backward_preprocess, beside depth_backward_fold_kernel (render_maps_backward.hip, whose
 //                                  lists, grid and time-out rule it has): one lane per LISTED Gaussian folds the flagged slots of
 //                                  its run of the dn plane, dL/dn_g = sum over tiles of sum_pix w gN, chains it to the quaternion
 //                                  (gsgrad.hpp: normal_grad_to_quat) and ADDS into dL_drotations: the Gaussian's own row, or
@@ -59,15 +59,10 @@ normal_backward_fold_kernel(int P, const uint32_t* __restrict__ live_count, cons
 {
     __shared__ float s_dq[256][4];
     __shared__ int32_t s_gi[256];
-    const uint32_t n_lists = gridDim.x / (BWD_LIST / 256);
-    const uint32_t list = blockIdx.x % n_lists, quarter = blockIdx.x / n_lists;
-    const uint32_t n_live = live_count[list];
-    const uint32_t off = quarter * 256u + threadIdx.x;
-    if ((off & ~63u) >= n_live) return;                          // whole waves only: the shuffles below need every lane
-    const int lane = threadIdx.x & 63;
-    const bool live = off < n_live;
-    const int i = live ? (int)live_ids[(size_t)list * BWD_LIST + off] : 0;
-    const bool mine = live && i < P;
+    const ListedGaussian lg = listed_gaussian(live_count, live_ids);
+    if (!lg.wave_has_work) return;
+    const int i = lg.i, lane = threadIdx.x & 63;
+    const bool mine = lg.live && i < P;
     const bool poisoned = *sort_err != 0u;
     NormalSlot sum = { 0.f, 0.f, 0.f };
     if (!poisoned) {

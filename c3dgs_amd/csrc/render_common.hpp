@@ -146,7 +146,7 @@ __device__ __forceinline__ void transpose_step(float* v, bool hi, Op op)
 //   then three plain levels over the 8 pixel rows: row_ror:8, v_permlane16_swap, v_permlane32_swap
 // Both operands of every combination are the same in the two lanes of a pair and op is commutative: all lanes that hold a
 // candidate hold the same bits, and the order of the float sum is the network's, not the timing's.
-// The network's two halves are also used apart (render_depth_backward.hip forms the y-moments of a pixel row between them, as
+// The network's two halves are also used apart (render_maps_backward.hip forms the y-moments of a pixel row between them, as
 // render_backward_kernel does between its column and row levels: the same pairings, so the same sums).
 __device__ __forceinline__ int candidate_of_lane(int lane)      // beta(lane): where this lane's reduced values belong
 {

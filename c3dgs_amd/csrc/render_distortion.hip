@@ -15,7 +15,7 @@
 // s - p. The map does not change when every s of a pixel moves by a constant, and its fp32 round-off then scales with the ray's
 // spread and not with s; the moment is put together at the end, M = c0 A + p A + sum w (s - c0 - p) with A = 1 - T, so that it
 // is sum w s to within a rounding of its own size -- which is what the backward's own pivot needs of it
-// (render_distortion_backward.hip). No atomics, no scratch, no list stores: bitwise reproducible.
+// (render_maps_backward.hip). No atomics, no scratch, no list stores: bitwise reproducible.
 #include "common.hpp"
 #include "render_common.hpp"
 #include "replay.hpp"

@@ -1,7 +1,8 @@
 // replay.hpp -- the skeleton of the passes that REPLAY a finished forward (render_depth.hip, render_contrib.hip, render_error.hip,
-// render_depth_backward.hip), and the fold of a Gaussian's slot run behind three of them. One owner per piece, so that the passes
-// walk the same entries, take the same cuts, number the same slots and add in the same order: a map of ones gives weight_sum's
-// bits, render_depth's w is render_contrib's, the depth backward touches the slots the product backward numbers. Device code only.
+// render_maps_backward.hip), the fold of a Gaussian's slot run behind three of them, and the lane -> listed Gaussian map of the
+// kernels that walk sum_partials_kernel's lists. One owner per piece, so that the passes walk the same entries, take the same cuts,
+// number the same slots and add in the same order: a map of ones gives weight_sum's bits, render_depth's w is render_contrib's,
+// the map backward touches the slots the product backward numbers. Device code only.
 //
 // A replay decides nothing again: it walks the tile's compact list (cid / cqm: the entries that can reach the tile, in list order)
 // up to tile_used_c[tile], and a pixel only takes entries whose compact index is <= n_contrib_c[pix] -- the forward's own early
@@ -218,6 +219,30 @@ __device__ __forceinline__ V fold_slot_run(SlotRun run, const V* __restrict__ sl
         if (lane == src) acc = part;
     }
     return acc;
+}
+
+// ---------------------------------------------------------------- one lane per listed Gaussian
+// sum_partials_kernel's lists of blended Gaussians (BWD_LIST entries per list, filled from the front) are walked by grids of
+// n_lists * (BWD_LIST / 256) workgroups of 256: backward_preprocess_kernel and the folds behind it. Workgroup -> (list, quarter of
+// the list): all FIRST quarters come first in the grid, then all second ones, ... Lists fill from the front, so the populated
+// quarters are spread evenly over the XCDs (consecutive workgroups go to consecutive XCDs; quarter = blockIdx % 4 would send every
+// full quarter to the same two of the eight) and the mostly empty ones come last.
+struct ListedGaussian {
+    bool wave_has_work;                               // false: the wave lies past the list's end, return (whole waves only: the
+                                                      // shuffles of a fold need every lane, and no workgroup barrier may follow)
+    bool live;                                        // this lane has an entry
+    size_t pos;                                       // ... at this index of live_ids (and of what else is kept per entry)
+    int i;                                            // ... which is this Gaussian (0 for a lane without)
+};
+__device__ __forceinline__ ListedGaussian listed_gaussian(const uint32_t* __restrict__ live_count, const uint32_t* __restrict__ live_ids)
+{
+    const uint32_t n_lists = gridDim.x / (BWD_LIST / 256);
+    const uint32_t list = blockIdx.x % n_lists, quarter = blockIdx.x / n_lists;
+    const uint32_t n_live = live_count[list];
+    const uint32_t off = quarter * 256u + threadIdx.x;
+    ListedGaussian c = { (off & ~63u) < n_live, off < n_live, (size_t)list * BWD_LIST + off, 0 };
+    if (c.live) c.i = (int)live_ids[c.pos];
+    return c;
 }
 
 // ---------------------------------------------------------------- a view's rows into model-sized accumulators

@@ -1426,19 +1426,19 @@ class GaussianModel:
         sum of alpha T x mean |render - target| over the pairs the forward blended (rasterizer._C.render_error), indexed like
         "radii", and "error_rank" (the same convention as "contrib_rank"); forward-only as well.
         depth_grad=True: the keys of return_depth, but "depth" and "alpha" carry gradient to the model's parameters, on the fused
-        indexed and the composed path alike (GaussianRasterizationSettings(depth_grad=True), csrc/render_depth_backward.hip);
+        indexed and the composed path alike (GaussianRasterizationSettings(depth_grad=True), csrc/render_maps_backward.hip);
         "median_depth" stays non-differentiable. The pose receives no gradient on this path, whatever `pose_grad` says: a camera
         pose that requires grad raises ValueError (not covered yet).
         distortion=True | (near, far): the keys and gradients of depth_grad plus "distortion", [H, W]: per pixel
         sum_i sum_j w_i w_j |s_i - s_j| over the blended entries (w = alpha T; s = the view-space depth z, or with a pair
         far / (far - near) (1 - near / z), 2DGS's mapping), Mip-NeRF 360's distortion regulariser, with gradient to the model's
         parameters on the fused indexed and the composed path alike (GaussianRasterizationSettings(distortion=),
-        csrc/render_distortion.hip, csrc/render_distortion_backward.hip). It composes with `antialiasing` and the 3D filter as
+        csrc/render_distortion.hip, csrc/render_maps_backward.hip). It composes with `antialiasing` and the 3D filter as
         depth_grad does, and like it refuses a camera pose that requires grad (ValueError).
         normal=True: the keys and gradients of depth_grad plus "normal", [3, H, W]: per pixel sum_k w_k n_k over the blended
         entries, n the Gaussian's shortest axis in VIEW space (x right, y down, z forward), unit length and facing the camera; not
         normalised, no background term (GaussianRasterizationSettings(normal=True), csrc/normals.hip, csrc/render_normal.hip,
-        csrc/render_normal_backward.hip), with gradient to the model's parameters -- the rotations included -- on the fused indexed
+        csrc/render_maps_backward.hip), with gradient to the model's parameters -- the rotations included -- on the fused indexed
         and the composed path alike. normals.normal_consistency(out["depth"], out["alpha"], out["normal"], camera.intrinsic) is
         2DGS's term on it. It composes with `antialiasing` and `distortion` (one blend replay in the backward for all maps) and
         refuses a camera pose that requires grad (ValueError). A covariance has no axes: `cov3d=` and pipe.compute_cov3D_python

@@ -276,14 +276,14 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     (csrc/render_contrib.hip) in every view; None steps every row (the dense step through the sparse optimizer).
 
     `lambda_depth`, `lambda_alpha` (not in the reference) add losses on the depth and alpha maps of render(depth_grad=True)
-    (csrc/render_depth_backward.hip) for the views whose camera object carries a target, attached by the caller as [H, W] fp32:
+    (csrc/render_maps_backward.hip) for the views whose camera object carries a target, attached by the caller as [H, W] fp32:
     `alpha_target` (a mask or silhouette) adds lambda_alpha x mean |alpha - alpha_target|; `depth_target` (0 = no measurement)
     adds lambda_depth x the mean over the measured pixels of |depth - alpha x depth_target|, a residual in weight space (depth is
     sum alpha T z, not normalised), so nothing is divided. Both at 0 (the default), and views without the attributes, run the
     loop above with its launches.
 
     `lambda_dist` (not in the reference: the depth-distortion loss of Mip-NeRF 360 as 2DGS and gsplat use it;
-    csrc/render_distortion.hip, csrc/render_distortion_backward.hip) = 0 is the loop above, launch for launch. A positive value
+    csrc/render_distortion.hip, csrc/render_maps_backward.hip) = 0 is the loop above, launch for launch. A positive value
     adds lambda_dist x render(distortion=...)["distortion"].mean() from iteration `dist_from_iter` on (counted like `iteration`
     of `info`, from 0): per pixel sum_i sum_j w_i w_j |s_i - s_j| over the blended entries, which pulls the mass along a ray
     together and needs no measured depth. `dist_near_far` = None takes s = the view-space depth; a pair (near, far) takes 2DGS's
@@ -292,7 +292,7 @@ def train(scene, dataset, opt, pipe, log=None, extent=None, camera_stride=10, de
     offered; in raw mode the loss scales with the square of the scene's depth unit. A negative value raises ValueError.
 
     `lambda_normal` (not in the reference: 2DGS's normal-consistency loss; csrc/normals.hip, csrc/render_normal.hip,
-    csrc/render_normal_backward.hip) = 0 is the loop above, launch for launch. A positive value adds
+    csrc/render_maps_backward.hip) = 0 is the loop above, launch for launch. A positive value adds
     lambda_normal x normals.normal_consistency(depth, alpha, normal, intrinsic) of render(normal=True) from iteration
     `normal_from_iter` on: the mean over the pixels of 1 - N . Ns, with N the blended map of the Gaussians' shortest axes and Ns the
     normal of the rendered depth map, weighted by alpha. A normal needs axes, so from that iteration on the render takes the

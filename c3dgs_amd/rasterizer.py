@@ -16,14 +16,14 @@ forward blended (forward-only, csrc/render_contrib.hip); `GaussianRasterizationS
 csrc/render_error.hip); `GaussianRasterizer(rs, optimize_camera="exact")` / `GaussianRasterizerIndexed(rs, optimize_camera="exact")`
 / `_C.pose_grad` give the exact gradient of the render with respect to the 7-element pose (csrc/pose_grad.hip, one pass behind
 the backward), where `optimize_camera=True` keeps the reference's formula; `GaussianRasterizationSettings(depth_grad=True)` makes
-the depth and alpha maps differentiable outputs (csrc/render_depth_backward.hip, one blend replay and one fold in the backward);
+the depth and alpha maps differentiable outputs (csrc/render_maps_backward.hip, one blend replay and one fold in the backward);
 `GaussianRasterizationSettings(antialiasing=True)` / `_C.aa_opacity` / `_C.aa_opacity_backward` compensate every opacity for the
 0.3 px^2 low-pass (csrc/aa_opacity.hip, one per-Gaussian launch in front of the forward and one behind the backward);
 `GaussianRasterizationSettings(distortion=True | (near, far))` / `_C.render_distortion` append the depth-distortion map of
 Mip-NeRF 360 as a differentiable last output (csrc/render_distortion.hip; in the backward ONE blend replay for the depth, alpha
-and distortion maps, csrc/render_distortion_backward.hip); `GaussianRasterizationSettings(normal=True)` / `_C.gaussian_normals` /
+and distortion maps, csrc/render_maps_backward.hip); `GaussianRasterizationSettings(normal=True)` / `_C.gaussian_normals` /
 `_C.render_normal` append the blended map of the Gaussians' view-space normals as a differentiable last output (csrc/normals.hip,
-csrc/render_normal.hip; in the backward ONE blend replay for every map of the call, csrc/render_normal_backward.hip, and the
+csrc/render_normal.hip; in the backward ONE blend replay for every map of the call, csrc/render_maps_backward.hip, and the
 gradient to the rotations through the normals); c3dgs_amd/normals.py has the depth -> normal stencil and the normal-consistency
 term on top of it.
 
@@ -329,16 +329,16 @@ def _backward(indexed, background, means3D, radii, colors, scales, scale_factors
               imageBuffer, debug, sh_indices, g_indices, skip=(), dL_ddepth=None, dL_dalpha=None, dL_ddistortion=None, moment=None,
               near_far=None, dL_dnormal=None, normals=None, normal_axes=None):
     """`dL_ddepth` / `dL_dalpha`: [H, W] fp32 gradients of the depth / alpha maps of _C.render_depth, or None. With either, the call
-    goes to the library's *_backward_depth entry (csrc/render_depth_backward.hip: one blend replay in front of the per-Gaussian
+    goes to the library's *_backward_depth entry (csrc/render_maps_backward.hip: one blend replay in front of the per-Gaussian
     kernels, one small fold behind them) and `dL_dout_color` may be None (the loss does not use the image: no colour blend
     launch). With neither it is the plain backward, launch for launch.
     `dL_ddistortion`: [H, W] fp32 gradient of the distortion map of _C.render_distortion, or None; with it `moment` is that call's
     second output and `near_far` its mode (None: raw), and the call goes to the *_backward_distortion entry
-    (csrc/render_distortion_backward.hip: one blend replay for the three maps in the place of the depth one). Without it the three
+    (csrc/render_maps_backward.hip: one blend replay for the three maps in the place of the depth one). Without it the three
     arguments are ignored.
     `dL_dnormal`: [3, H, W] fp32 gradient of the normal map of _C.render_normal, or None; with it `normals` is the [P, 4] buffer
     of _C.gaussian_normals for the same forward, and the call goes to the *_backward_normal entry
-    (csrc/render_normal_backward.hip: one blend replay for EVERY map of the call in the place of the other two, and one more
+    (csrc/render_maps_backward.hip: one blend replay for EVERY map of the call in the place of the other two, and one more
     fold, which adds into dL_drotations). `normal_axes` = (rotations, g_indices | None): the rows the normals were made from where
     the call blends a `cov3D_precomp` (a filtered covariance, say), which has no axes; the fold's gradient then comes back as one
     more element at the END of the returned tuple, of the shape of those rotations. Without `dL_dnormal` both are ignored.
@@ -1284,7 +1284,7 @@ class GaussianRasterizationSettings(_SettingsFields):
     unchanged. A wrong shape, dtype or device raises RuntimeError. None: no launch.
     `depth_grad` (keyword only, default False) is a third such attribute. True implies the outputs of `depth=True`, in the same
     position -- (color, radii, depth, alpha, median, ...) with the forward's bits -- and makes `depth` and `alpha` differentiable
-    outputs: a loss on them reaches every input the image reaches (csrc/render_depth_backward.hip: one blend replay and one small
+    outputs: a loss on them reaches every input the image reaches (csrc/render_maps_backward.hip: one blend replay and one small
     fold added to the backward). `median` (piecewise constant) and `radii` stay non-differentiable. When neither map receives a
     gradient the backward issues the plain backward's launches. The gradient to the camera pose through the maps is not covered
     yet: with `depth_grad`, `optimize_camera` other than False raises ValueError.
@@ -1300,7 +1300,7 @@ class GaussianRasterizationSettings(_SettingsFields):
     ValueError). Not False: the rasterizers return depth_grad's outputs in their positions, differentiable as there, and append
     the depth-distortion map sum_i sum_j w_i w_j |s_i - s_j| of every pixel's blended entries, [H, W], as the LAST element of the
     tuple (csrc/render_distortion.hip, one more forward replay), a differentiable output as well: a loss on it reaches every input
-    the depth map reaches, through ONE blend replay in the backward for the three maps (csrc/render_distortion_backward.hip, in
+    the depth map reaches, through ONE blend replay in the backward for the three maps (csrc/render_maps_backward.hip, in
     the place of the depth maps' replay). When it receives no gradient the backward is depth_grad's. With `distortion`,
     `optimize_camera` other than False raises ValueError, as with `depth_grad`.
     `normal` (keyword only, default False) is a sixth such attribute. True: the rasterizers return depth_grad's outputs in their
@@ -1310,7 +1310,7 @@ class GaussianRasterizationSettings(_SettingsFields):
     forward), unit length and facing the camera (_C.gaussian_normals says how it is chosen); N is not normalised and has no
     background term, like `depth`. It is a differentiable output: a loss on it reaches the opacities, means and covariances
     through w, and the rotations through n as well, through ONE blend replay in the backward for every map of the call
-    (csrc/render_normal_backward.hip, in the place of the other two) and one more fold. When it receives no gradient the backward
+    (csrc/render_maps_backward.hip, in the place of the other two) and one more fold. When it receives no gradient the backward
     is what the other settings give. A precomputed covariance has no axes: with `normal`, `cov3D_precomp` alone raises ValueError.
     A caller that blends a covariance it has built from scales and rotations (a filtered one) passes the pair BESIDE it: the
     rasterizer sees the covariance, the normals are made from the pair, and the rotations receive the normals' gradient.

@@ -136,7 +136,7 @@ int c3dgs_rasterize_gaussians_backward_indexed(const c3dgs_raster_params* p, con
                                                const c3dgs_raster_grads* grads, void* stream);
 
 /* ---- the two backward entries with gradients through the depth and alpha maps of c3dgs_render_depth
- * (csrc/render_depth_backward.hip; no reference counterpart) ----
+ * (csrc/render_maps_backward.hip; no reference counterpart) ----
  * The arguments of the entries above plus dL_ddepth and dL_dalpha, [H,W] fp32 device maps: dL/d(out_depth) and dL/d(out_alpha)
  * of the forward that filled the buffers. Either may be NULL (zeros). out_median is piecewise constant: no gradient.
  * With both maps NULL the call IS the entry above: the same validation, workspace request, launches and bits.
@@ -182,7 +182,7 @@ int c3dgs_render_distortion(int32_t P, int32_t W, int32_t H, int32_t R,
                             void* stream);
 
 /* ---- the two backward entries with gradients through the depth, alpha AND distortion maps
- * (csrc/render_distortion_backward.hip) ----
+ * (csrc/render_maps_backward.hip) ----
  * The arguments of the *_backward_depth entries plus dL_ddistortion = dL/d(out_distortion) and moment = out_moment of
  * c3dgs_render_distortion on the same forward, both [H,W] fp32, and that call's near / far.
  * With dL_ddistortion NULL the call IS the *_backward_depth entry: the same validation, workspace request, launches and bits
@@ -211,7 +211,7 @@ int c3dgs_rasterize_gaussians_backward_distortion_indexed(const c3dgs_raster_par
                                                           const c3dgs_raster_grads* grads, void* stream);
 size_t c3dgs_distortion_backward_workspace_bytes(int32_t P, int32_t R);
 
-/* ---- normal maps (csrc/normals.hip, csrc/render_normal.hip, csrc/render_normal_backward.hip; no reference counterpart) ----
+/* ---- normal maps (csrc/normals.hip, csrc/render_normal.hip, csrc/render_maps_backward.hip; no reference counterpart) ----
  * All normals are in VIEW space: x right, y down, z forward, the frame of `viewmatrix`.
  *
  * c3dgs_gaussian_normals: one lane per Gaussian. With q = rotations[g], s = scales[g] (g_indices NULL) or the codebook rows
@@ -233,7 +233,7 @@ int c3dgs_render_normal(int32_t P, int32_t W, int32_t H, int32_t R,
                         const void* geom_buffer, const void* binning_buffer, const void* image_buffer,
                         const float* normals /*[P,4]*/, float* out_normal /*[3,H,W]*/, void* stream);
 
-/* ---- the two backward entries with a gradient through the normal map (csrc/render_normal_backward.hip) ----
+/* ---- the two backward entries with a gradient through the normal map (csrc/render_maps_backward.hip) ----
  * The arguments of the *_backward_distortion entries plus dL_dnormal = dL/d(out_normal), [3,H,W] fp32, and normals = the buffer
  * c3dgs_gaussian_normals filled for the same forward.
  * With dL_dnormal NULL the call IS the *_backward_distortion entry (normals and the three axes arguments are not looked at). With

@@ -1,4 +1,4 @@
-"""Float64 reference for the gradients through the depth and alpha maps (csrc/render_depth_backward.hip); test infrastructure.
+"""Float64 reference for the gradients through the depth and alpha maps (csrc/render_maps_backward.hip); test infrastructure.
 
 Two independent float64 computations of the same gradients, on the discrete structure of one oracle forward (which Gaussians
 are in which tile, in which order), as tests/dense_ref.py borrows it:

@@ -1,4 +1,4 @@
-"""Float64 reference for the depth-distortion map and its gradient (csrc/render_distortion.hip, csrc/render_distortion_backward.hip);
+"""Float64 reference for the depth-distortion map and its gradient (csrc/render_distortion.hip, csrc/render_maps_backward.hip);
 test infrastructure, built on tests/depth_ref.py's walk and tests/depth_grad_ref.py's walk_flipped / projection / chain.
 
 Per pixel, over the entries k = 1..m the walk blends, with w_k = alpha_k T_k, T_{k+1} = T_k (1 - alpha_k), s_k = f(z_k):
@@ -223,7 +223,7 @@ def _per_pair_f32(pr, gD, gA, gL, mode, maps=None, pivot=True):
     M = _fma(np.full(N, c0, f), one - Tfin, _fma(p1, one - Tfin, S))
     if maps is not None:
         maps["distortion"], maps["moment"] = (f(2.0) * dist).reshape(pr.H, pr.W), M.reshape(pr.H, pr.W)
-    # render_distortion_backward_kernel, back to front; M is the forward kernel's moment, Tfin its final T
+    # render_maps_backward_kernel<DIST = true>, back to front; M is the forward kernel's moment, Tfin its final T
     gD, gA = gD.reshape(-1).astype(f), gA.reshape(-1).astype(f)
     gL2 = f(2.0) * gL.reshape(-1).astype(f)
     Sd, Ss = np.zeros(N, f), np.zeros(N, f)

@@ -1,4 +1,4 @@
-"""Float64 references for the normal maps (csrc/normals.hip, csrc/render_normal.hip, csrc/render_normal_backward.hip); test
+"""Float64 references for the normal maps (csrc/normals.hip, csrc/render_normal.hip, csrc/render_maps_backward.hip); test
 infrastructure, numpy / torch, built on tests/depth_ref.py, tests/depth_grad_ref.py and tests/distortion_ref.py.
 
 All normals are in VIEW space (x right, y down, z forward). The definitions, restated:

@@ -1,5 +1,5 @@
 """CPU: the C ABI of the backward through the depth and alpha maps (c3dgs_rasterize_gaussians_backward_depth,
-c3dgs_rasterize_gaussians_backward_depth_indexed, c3dgs_depth_backward_workspace_bytes; csrc/render_depth_backward.hip). The
+c3dgs_rasterize_gaussians_backward_depth_indexed, c3dgs_depth_backward_workspace_bytes; csrc/render_maps_backward.hip). The
 symbols are exported and bound, the ABI version did not move (new entry points only, c3dgs_raster_params unchanged), the
 kernel's file is built with render.hip's flags, the two new launches have stage names, the workspace is the backward's plus
 the dL/dz plane, and every invalid call is refused with its message before any device work -- which is why these run without
@@ -32,8 +32,8 @@ def test_symbols_are_exported_and_bound(L):
 
 
 def test_kernel_file_is_built_with_the_blend_kernels_flags():
-    assert "render_depth_backward.hip" in build.SOURCES
-    assert build.SOURCES["render_depth_backward.hip"] == build.SOURCES["render.hip"] == build.SOURCES["render_depth.hip"]
+    assert "render_maps_backward.hip" in build.SOURCES
+    assert build.SOURCES["render_maps_backward.hip"] == build.SOURCES["render.hip"] == build.SOURCES["render_depth.hip"]
 
 
 def test_stage_names(L):

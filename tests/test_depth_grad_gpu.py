@@ -1,4 +1,4 @@
-"""-m gpu: gradients through the depth and alpha maps (csrc/render_depth_backward.hip; GaussianRasterizationSettings(depth_grad=True),
+"""-m gpu: gradients through the depth and alpha maps (csrc/render_maps_backward.hip; GaussianRasterizationSettings(depth_grad=True),
 GaussianModel.render(depth_grad=True), pipeline.train(lambda_depth=, lambda_alpha=)).
 
   identity   By linearity the map gradients equal the PRODUCT backward's on the same scene with colours (z, 1, 0), a black

@@ -1,6 +1,6 @@
 """CPU: the C ABI of the depth-distortion map and its backward (c3dgs_render_distortion,
 c3dgs_rasterize_gaussians_backward_distortion, c3dgs_rasterize_gaussians_backward_distortion_indexed,
-c3dgs_distortion_backward_workspace_bytes; csrc/render_distortion.hip, csrc/render_distortion_backward.hip). The symbols are
+c3dgs_distortion_backward_workspace_bytes; csrc/render_distortion.hip, csrc/render_maps_backward.hip). The symbols are
 exported and bound, the header names them, the ABI version did not move (new entry points only), the two kernel files are built
 with render.hip's flags, the two new launches have stage names, the workspace is the depth backward's, and every invalid call is
 refused with its message before any device work -- which is why these run without a GPU."""
@@ -48,7 +48,7 @@ def test_header_names_the_entries():
 
 
 def test_kernel_files_are_built_with_the_blend_kernels_flags():
-    for src in ("render_distortion.hip", "render_distortion_backward.hip"):
+    for src in ("render_distortion.hip", "render_maps_backward.hip"):
         assert src in build.SOURCES and os.path.exists(os.path.join(build.CSRC, src)), src
         assert build.SOURCES[src] == build.SOURCES["render.hip"] == build.SOURCES["render_depth.hip"]
 

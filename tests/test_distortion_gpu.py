@@ -1,4 +1,4 @@
-"""-m gpu: the depth-distortion map and its gradient (csrc/render_distortion.hip, csrc/render_distortion_backward.hip;
+"""-m gpu: the depth-distortion map and its gradient (csrc/render_distortion.hip, csrc/render_maps_backward.hip;
 GaussianRasterizationSettings(distortion=), GaussianModel.render(distortion=), pipeline.train(lambda_dist=)).
 
   forward    on tests/depth_ref.py's scenes, raw and ndc(0.2, 100): against the float64 prefix formula of tests/distortion_ref.py on

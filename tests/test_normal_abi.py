@@ -1,6 +1,6 @@
 """CPU: the C ABI of the normal maps (c3dgs_gaussian_normals, c3dgs_render_normal, c3dgs_rasterize_gaussians_backward_normal(_indexed),
 c3dgs_normal_backward_workspace_bytes, c3dgs_depth_to_normal, c3dgs_depth_to_normal_backward; csrc/normals.hip,
-csrc/render_normal.hip, csrc/render_normal_backward.hip). The symbols are exported and bound, the header names them, the ABI
+csrc/render_normal.hip, csrc/render_maps_backward.hip). The symbols are exported and bound, the header names them, the ABI
 version did not move (new entry points only), the kernel files are built with their siblings' flags, the new launches have stage
 names, the workspace is the depth backward's plus three floats per slot, and every invalid call is refused with its message before
 any device work -- which is why these run without a GPU."""
@@ -53,9 +53,9 @@ def test_header_names_the_entries():
 
 
 def test_kernel_files_and_flags():
-    for src in ("render_normal.hip", "render_normal_backward.hip"):
+    for src in ("render_normal.hip", "render_maps_backward.hip"):
         assert src in build.SOURCES and os.path.exists(os.path.join(build.CSRC, src)), src
-        assert build.SOURCES[src] == build.SOURCES["render.hip"] == build.SOURCES["render_depth_backward.hip"]
+        assert build.SOURCES[src] == build.SOURCES["render.hip"] == build.SOURCES["render_depth.hip"]
     # the per-Gaussian chains of gsgrad.hpp are compiled as everywhere else they are called
     assert build.SOURCES["normals.hip"] == ["-ffp-contract=off"] == build.SOURCES["filter3d.hip"]
 

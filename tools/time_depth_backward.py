@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the backward through the depth and alpha maps (csrc/render_depth_backward.hip, c3dgs_rasterize_gaussians_backward_depth_indexed)
+"""Times the backward through the depth and alpha maps (csrc/render_maps_backward.hip, c3dgs_rasterize_gaussians_backward_depth_indexed)
 on the bench scene -- BASELINE.json configs[2]: 3M Gaussians, 1920x1080, indexed -- and on bench.py's heavy-tailed scene (scale
 sigma 1.2), against the same run's plain backward and against the only route to the same gradients without it: a second
 forward with colours (z, 1, 0) and a second full backward. Prints one JSON line and writes profiles/r15_depth_backward_time.json.

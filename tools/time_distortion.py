@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the depth-distortion map and its backward (csrc/render_distortion.hip, csrc/render_distortion_backward.hip) on the bench
+"""Times the depth-distortion map and its backward (csrc/render_distortion.hip, csrc/render_maps_backward.hip) on the bench
 scene -- BASELINE.json configs[2]: 3M Gaussians, 1920x1080, indexed -- and on bench.py's heavy-tailed scene (scale sigma 1.2), each
 next to its sibling in the same run: render_distortion next to render_depth, the three-map backward replay next to the two-map
 one, and the whole backward with the three maps next to the plain one. Prints one JSON line and writes

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the normal maps (csrc/normals.hip, csrc/render_normal.hip, csrc/render_normal_backward.hip) on the bench scene --
+"""Times the normal maps (csrc/normals.hip, csrc/render_normal.hip, csrc/render_maps_backward.hip) on the bench scene --
 BASELINE.json configs[2]: 3M Gaussians, 1920x1080, indexed -- and on bench.py's heavy-tailed scene (scale sigma 1.2), each next to
 its sibling in the same run: gaussian_normals and render_normal next to render_depth, the four-map backward replay next to the
 three-map one, the whole backward with the term next to the plain one, the stencil pair next to the same stencil in torch ops, and
