@@ -97,6 +97,11 @@ class Filter3DGrads(C.Structure):       # c3dgs_filter3d_grads
                                           "dL_dscale_factors")]
 
 
+class Lattice(C.Structure):             # c3dgs_lattice
+    _fields_ = [("Nx", C.c_int32), ("Ny", C.c_int32), ("Nz", C.c_int32), ("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float),
+                ("voxel_size", C.c_float)]
+
+
 ROLE_COPY, ROLE_XYZ, ROLE_SCALING = 0, 1, 2
 MCMC_ROLE_OPACITY, MCMC_ROLE_SCALE = 3, 4             # c3dgs_mcmc_apply
 ROW_KEEP, ROW_CLONE, ROW_SPLIT, ROW_CHILD_KEPT = 1, 2, 4, 8
@@ -157,6 +162,12 @@ PROTOTYPES = {
     "c3dgs_filter3d_compute": (C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "c3dgs_filter3d_apply": (C.c_int, [C.POINTER(Filter3DRows), _vp, _vp, _vp]),
     "c3dgs_filter3d_apply_backward": (C.c_int, [C.POINTER(Filter3DRows), C.POINTER(Filter3DGrads), _vp]),
+    "c3dgs_tsdf_integrate": (C.c_int, [C.POINTER(Lattice), C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_float, C.c_float,
+                                       C.c_float, _vp, _vp, _vp, _vp]),
+    "c3dgs_mesh_extract_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "c3dgs_mesh_extract_count": (C.c_int, [C.POINTER(Lattice), _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_int64), _vp]),
+    "c3dgs_mesh_extract_emit": (C.c_int, [C.POINTER(Lattice), _vp, _vp, _vp, _vp, C.c_size_t, C.c_int64, C.c_int64, _vp, _vp, _vp,
+                                          _vp]),
     "c3dgs_error_map_l1": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_vp] * 4),
     "c3dgs_error_accumulate": (C.c_int, [C.c_int32, C.c_int32] + [_vp] * 6),
     "c3dgs_weighted_distance": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -55,6 +55,9 @@ SOURCES = {
     # covariance is preprocess's (csrc/gsmath.hpp); its backward is the covariance chain of csrc/gsgrad.hpp, which must round as
     # backward_preprocess's does (tests/test_gsgrad_gpu.py)
     "filter3d.hip": ["-ffp-contract=off"],
+    # mesh extraction: the projections of the TSDF fusion and the edge interpolation of the marching tetrahedra are single fp32
+    # operations that tests/mesh_ref.py restates bit for bit
+    "mesh.hip": ["-ffp-contract=off"],
     "draws.hip": [],
     "loss.hip": [],
     "metrics.hip": [],

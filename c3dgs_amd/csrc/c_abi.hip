@@ -46,7 +46,9 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(BILAGRID_SLICE, "bilagrid_slice") X(BILAGRID_SLICE_BWD, "bilagrid_slice_backward") X(BILAGRID_GATHER, "bilagrid_gather") \
     X(BILAGRID_FOLD, "bilagrid_fold") X(BILAGRID_RGB_BWD, "bilagrid_rgb_backward") X(BILAGRID_TV, "bilagrid_tv")               \
     X(BILAGRID_TV_BWD, "bilagrid_tv_backward")                                                                                 \
-    X(FILTER3D_COMPUTE, "filter3d_compute") X(FILTER3D_APPLY, "filter3d_apply") X(FILTER3D_APPLY_BWD, "filter3d_apply_backward")
+    X(FILTER3D_COMPUTE, "filter3d_compute") X(FILTER3D_APPLY, "filter3d_apply") X(FILTER3D_APPLY_BWD, "filter3d_apply_backward") \
+    X(TSDF_INTEGRATE, "tsdf_integrate") X(MESH_CLASSIFY, "mesh_classify") X(MESH_SCAN, "mesh_scan")                            \
+    X(MESH_EMIT_VERTICES, "mesh_emit_vertices") X(MESH_EMIT_FACES, "mesh_emit_faces")
 #define C3DGS_X(id, name) ST_##id,
 enum Stage { C3DGS_STAGE_TABLE(C3DGS_X) ST_COUNT };
 #undef C3DGS_X
@@ -1054,6 +1056,87 @@ int c3dgs_filter3d_apply_backward(const c3dgs_filter3d_rows* r, const c3dgs_filt
     if (reinterpret_cast<uintptr_t>(g->dL_drotations) & 15u)
         return fail(C3DGS_E_INVALID, "filter3d_apply_backward: dL_drotations must be 16-byte aligned");
     C3DGS_TIMED_STAGE(ST_FILTER3D_APPLY_BWD, 0, (hipStream_t)stream, launch_filter3d_apply_backward(*r, *g, (hipStream_t)stream));
+    return C3DGS_OK;
+}
+
+// what every mesh entry asks of the lattice and the two planes
+static int mesh_validate(const char* who, const c3dgs_lattice* l, const float* tsdf, const float* weight)
+{
+    const std::string w(who);
+    if (!l) return fail(C3DGS_E_INVALID, w + ": lattice is NULL");
+    if (l->Nx < 1 || l->Ny < 1 || l->Nz < 1) return fail(C3DGS_E_INVALID, w + ": Nx, Ny and Nz must be positive");
+    if ((uint64_t)l->Nx * (uint64_t)l->Ny > (uint64_t)INT32_MAX || (uint64_t)l->Nx * (uint64_t)l->Ny * (uint64_t)l->Nz > (uint64_t)INT32_MAX)
+        return fail(C3DGS_E_INVALID, w + ": Nx Ny Nz must be at most 2^31 - 1");
+    if (!(l->voxel_size > 0.f)) return fail(C3DGS_E_INVALID, w + ": voxel_size must be positive");
+    if (!tsdf || !weight) return fail(C3DGS_E_INVALID, w + ": the tsdf and weight planes are required");
+    return C3DGS_OK;
+}
+
+static int mesh_workspace(const char* who, const c3dgs_lattice* l, const void* workspace, size_t workspace_bytes)
+{
+    if (!workspace || workspace_bytes < mesh_extract_workspace_bytes(l->Nx, l->Ny, l->Nz) || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(C3DGS_E_INVALID, std::string(who) + ": workspace must hold c3dgs_mesh_extract_workspace_bytes(Nx, Ny, Nz) bytes, "
+                                                        "256-byte aligned");
+    return C3DGS_OK;
+}
+
+int c3dgs_tsdf_integrate(const c3dgs_lattice* l, int32_t K, int32_t W, int32_t H, const float* depth, const float* color,
+                         const float* cameras, float sdf_trunc, float depth_min, float depth_max, float* tsdf, float* weight,
+                         float* vol_color, void* stream)
+{
+    if (int rc = mesh_validate("tsdf_integrate", l, tsdf, weight)) return rc;
+    if (K < 1) return fail(C3DGS_E_INVALID, "tsdf_integrate: K must be at least 1");
+    if (W < 1 || H < 1) return fail(C3DGS_E_INVALID, "tsdf_integrate: W and H must be positive");
+    if (!(sdf_trunc > 0.f)) return fail(C3DGS_E_INVALID, "tsdf_integrate: sdf_trunc must be positive");
+    if (!(depth_min < depth_max)) return fail(C3DGS_E_INVALID, "tsdf_integrate: depth_min < depth_max is required");
+    if (!depth || !cameras) return fail(C3DGS_E_INVALID, "tsdf_integrate: depth and cameras are required");
+    if ((color != nullptr) != (vol_color != nullptr))
+        return fail(C3DGS_E_INVALID, "tsdf_integrate: color and vol_color come as a pair");
+    C3DGS_TIMED_STAGE(ST_TSDF_INTEGRATE, 0, (hipStream_t)stream,
+                      launch_tsdf_integrate(*l, K, W, H, depth, color, cameras, sdf_trunc, depth_min, depth_max, tsdf, weight, vol_color,
+                                            (hipStream_t)stream));
+    return C3DGS_OK;
+}
+
+size_t c3dgs_mesh_extract_workspace_bytes(int32_t Nx, int32_t Ny, int32_t Nz)
+{
+    if (Nx < 1 || Ny < 1 || Nz < 1 || (uint64_t)Nx * (uint64_t)Ny > (uint64_t)INT32_MAX ||
+        (uint64_t)Nx * (uint64_t)Ny * (uint64_t)Nz > (uint64_t)INT32_MAX) return 0;
+    return mesh_extract_workspace_bytes(Nx, Ny, Nz);
+}
+
+int c3dgs_mesh_extract_count(const c3dgs_lattice* l, const float* tsdf, const float* weight, void* workspace, size_t workspace_bytes,
+                             int64_t* counts, void* stream)
+{
+    if (int rc = mesh_validate("mesh_extract_count", l, tsdf, weight)) return rc;
+    if (int rc = mesh_workspace("mesh_extract_count", l, workspace, workspace_bytes)) return rc;
+    if (!counts) return fail(C3DGS_E_INVALID, "mesh_extract_count: counts is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_MESH_CLASSIFY, 0, s, launch_mesh_classify(*l, tsdf, weight, workspace, s));
+    const uint32_t* totals = nullptr;
+    C3DGS_TIMED_STAGE(ST_MESH_SCAN, 0, s, totals = launch_mesh_scan(*l, workspace, s));
+    uint32_t host[2] = { 0u, 0u };
+    C3DGS_HIP_TRY(hipMemcpyAsync(host, totals, sizeof(host), hipMemcpyDeviceToHost, s));
+    C3DGS_HIP_TRY(hipStreamSynchronize(s));
+    if (host[0] > (uint32_t)INT32_MAX || host[1] > (uint32_t)INT32_MAX)
+        return fail(C3DGS_E_INVALID, "mesh_extract_count: more than 2^31 - 1 vertices or faces; extract a coarser or smaller volume");
+    counts[0] = host[0]; counts[1] = host[1];
+    return C3DGS_OK;
+}
+
+int c3dgs_mesh_extract_emit(const c3dgs_lattice* l, const float* tsdf, const float* weight, const float* vol_color, void* workspace,
+                            size_t workspace_bytes, int64_t V, int64_t F, float* vertices, float* colors, int32_t* faces, void* stream)
+{
+    if (int rc = mesh_validate("mesh_extract_emit", l, tsdf, weight)) return rc;
+    if (int rc = mesh_workspace("mesh_extract_emit", l, workspace, workspace_bytes)) return rc;
+    if (V < 0 || F < 0 || V > INT32_MAX || F > INT32_MAX) return fail(C3DGS_E_INVALID, "mesh_extract_emit: V and F must be in [0, 2^31 - 1]");
+    if (V == 0) return C3DGS_OK;                            // no vertex, no face: the outputs are empty, whatever their pointers
+    if ((vol_color != nullptr) != (colors != nullptr))
+        return fail(C3DGS_E_INVALID, "mesh_extract_emit: vol_color and colors come as a pair");
+    if (!vertices || (F > 0 && !faces)) return fail(C3DGS_E_INVALID, "mesh_extract_emit: vertices and faces are required");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_MESH_EMIT_VERTICES, 0, s, launch_mesh_vertices(*l, tsdf, vol_color, workspace, (uint32_t)V, vertices, colors, s));
+    if (F > 0) C3DGS_TIMED_STAGE(ST_MESH_EMIT_FACES, 0, s, launch_mesh_faces(*l, tsdf, workspace, (uint32_t)F, faces, s));
     return C3DGS_OK;
 }
 

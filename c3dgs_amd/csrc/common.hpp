@@ -508,6 +508,16 @@ void launch_filter3d_dist(int P, int C, const float* xyz, const float* cams, flo
 void launch_filter3d_finish(int P, const uint32_t* ws, float* filter, uint8_t* seen, hipStream_t s);
 void launch_filter3d_apply(const c3dgs_filter3d_rows& p, float* cov3D_out, float* opacity_out, hipStream_t s);
 void launch_filter3d_apply_backward(const c3dgs_filter3d_rows& p, const c3dgs_filter3d_grads& g, hipStream_t s);
+// mesh.hip (mesh extraction: TSDF fusion of depth maps into a dense volume, welded marching tetrahedra over it)
+void launch_tsdf_integrate(const c3dgs_lattice& l, int K, int W, int H, const float* depth, const float* color, const float* cams,
+                           float sdf_trunc, float depth_min, float depth_max, float* tsdf, float* weight, float* vol_color,
+                           hipStream_t s);
+size_t mesh_extract_workspace_bytes(int Nx, int Ny, int Nz);
+void launch_mesh_classify(const c3dgs_lattice& l, const float* tsdf, const float* weight, void* ws, hipStream_t s);
+const uint32_t* launch_mesh_scan(const c3dgs_lattice& l, void* ws, hipStream_t s);     // -> the device words {vertices, faces}
+void launch_mesh_vertices(const c3dgs_lattice& l, const float* tsdf, const float* vol_color, void* ws, uint32_t V, float* vertices,
+                          float* colors, hipStream_t s);
+void launch_mesh_faces(const c3dgs_lattice& l, const float* tsdf, void* ws, uint32_t F, int32_t* faces, hipStream_t s);
 // backward_preprocess.hip
 void launch_backward_preprocess(const c3dgs_raster_params& p, const int32_t* radii, const GeomPtrs& g, const BwdPtrs& w,
                                 const c3dgs_raster_grads& gr, hipStream_t s);

@@ -2,6 +2,8 @@
 
     read_ply(path) -> {property name: np.ndarray[N]}      the `vertex` element of an ascii / binary PLY 1.0 file
     write_ply(path, columns)                               float32 binary little-endian `vertex` element
+    write_mesh_ply(path, vertices, colors, faces)          a coloured triangle mesh (c3dgs_amd/mesh.py), binary little-endian
+    read_mesh_ply(path) -> (vertices, colors, faces)       what write_mesh_ply wrote
 
 The reference reads and writes these files with `plyfile` (GaussianModel.load_ply / save_ply,
 scene/gaussian_model.py:324-503). write_ply produces the same bytes plyfile writes for save_ply: the header
@@ -137,6 +139,61 @@ def _read_ascii(f, path, before, vert):
         except ValueError as e:
             raise ValueError(f"{path}: bad value in vertex property {name!r}: {e}") from None
     return out
+
+
+_MESH_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_MESH_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def write_mesh_ply(path, vertices, colors, faces):
+    """A triangle mesh as binary little-endian PLY: `element vertex` with float x y z and uchar red green blue (`colors` [V, 3]
+    in [0, 1], clamped and rounded to 0..255; None writes 255), `element face` with `property list uchar int vertex_indices`."""
+    v = np.asarray(vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"write_mesh_ply: face indices must be in [0, {len(v)})")
+    rec = np.empty(len(v), _MESH_VERTEX)
+    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is None:
+        rgb = np.full((len(v), 3), 255, np.uint8)
+    else:
+        c = np.asarray(colors, np.float64).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError(f"write_mesh_ply: {len(c)} colours for {len(v)} vertices")
+        rgb = np.rint(np.clip(np.nan_to_num(c), 0.0, 1.0) * 255.0).astype(np.uint8)
+    rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    frec = np.empty(len(f), _MESH_FACE)
+    frec["n"] = 3
+    frec["v"] = f
+    header = (f"ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"property uchar red\nproperty uchar green\nproperty uchar blue\nelement face {len(f)}\n"
+              "property list uchar int vertex_indices\nend_header\n")
+    with open(os.fspath(path), "wb") as fh:
+        fh.write(header.encode("ascii"))
+        rec.tofile(fh)
+        frec.tofile(fh)
+
+
+def read_mesh_ply(path):
+    """-> (vertices [V, 3] float32, colors [V, 3] uint8, faces [F, 3] int32) of a file write_mesh_ply wrote (binary little-endian,
+    exactly its two elements and properties, triangles only). Raises ValueError otherwise."""
+    path = os.fspath(path)
+    with open(path, "rb") as f:
+        fmt, elements = _header(f, path)
+        ok = (fmt == "binary_little_endian" and [e.name for e in elements] == ["vertex", "face"]
+              and elements[0].props == [(n, _MESH_VERTEX[n].str[1:]) for n in _MESH_VERTEX.names]
+              and elements[1].props == [("vertex_indices", None)])
+        if not ok:
+            raise ValueError(f"{path}: not a mesh PLY in write_mesh_ply's layout")
+        rec = np.fromfile(f, _MESH_VERTEX, elements[0].count)
+        frec = np.fromfile(f, _MESH_FACE, elements[1].count)
+    if len(rec) != elements[0].count or len(frec) != elements[1].count:
+        raise ValueError(f"{path}: truncated PLY body")
+    if frec.size and (frec["n"] != 3).any():
+        raise ValueError(f"{path}: only triangles are supported")
+    vertices = np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32)
+    colors = np.stack([rec["red"], rec["green"], rec["blue"]], 1)
+    return vertices, colors, frec["v"].astype(np.int32).reshape(-1, 3)
 
 
 def ply_header(names, n):

@@ -475,6 +475,49 @@ int c3dgs_filter3d_compute(int32_t P, int32_t C, const float* xyz /*[P,3]*/, con
 int c3dgs_filter3d_apply(const c3dgs_filter3d_rows* r, float* cov3D_out /*[n,6]*/, float* opacity_out /*[n]*/, void* stream);
 int c3dgs_filter3d_apply_backward(const c3dgs_filter3d_rows* r, const c3dgs_filter3d_grads* g, void* stream);
 
+/* ---- mesh extraction: TSDF fusion of depth maps and marching tetrahedra (csrc/mesh.hip; no reference counterpart) ----
+ * The volume: Nx x Ny x Nz lattice points at origin + (i, j, k) voxel_size, each component formed in fp32 as
+ * origin + float(index) * voxel_size; fp32 planes [Nz, Ny, Nx] (x fastest, linear index (k Ny + j) Nx + i) owned by the caller and
+ * zero before the first integration: tsdf, weight and optionally vol_color [3, Nz, Ny, Nx]. Nx Ny Nz <= 2^31 - 1.
+ * c3dgs_tsdf_integrate: K depth maps [K, H, W] (view-space z; 0 = no measurement), optionally their colours [K, 3, H, W], and the
+ * [K, 16] camera table of c3dgs_filter3d_compute (its W, H entries are the maps'). For every lattice point p and the cameras in
+ * table order, in fp32, each operation rounded on its own:
+ *   x = ((m0 px + m1 py) + m2 pz) + m3 (y, z likewise);  skip if z < depth_min;
+ *   u = (fx x) / z + 0.5 W, v = (fy y) / z + 0.5 H;  skip unless 0 <= u < W and 0 <= v < H;  d = depth[c][int(v)][int(u)];
+ *   skip unless 0 < d <= depth_max;  sdf = d - z;  skip if sdf < -sdf_trunc;  s = min(1, sdf / sdf_trunc);
+ *   tsdf = (tsdf w + s) / (w + 1), each colour plane likewise with the pixel's colour;  w = w + 1.
+ * One launch, no atomics, bitwise reproducible; K maps in one call give the bits of K calls of one map; a point no camera
+ * updated is not stored. color and vol_color come as a pair. Stage name: "tsdf_integrate".
+ * c3dgs_mesh_extract_count / c3dgs_mesh_extract_emit: marching tetrahedra over the cells whose eight corners all have weight > 0.
+ * A cell is cut into the six Kuhn tetrahedra (0,0,0) -> +a -> +a+b -> (1,1,1), (a, b, c) the permutations of the axes in
+ * lexicographic order; a corner is inside iff its value is < 0 (0.0 and -0.0 are outside). The vertex of the lattice edge
+ * between the points a < b (linear index) is pa + t (pb - pa), t = va / (va - vb), colours likewise; it exists iff the endpoints
+ * differ in sign and a valid cell contains the edge. Vertices are welded (one per edge) and ordered by the owner a, then by the
+ * edge's slot +x, +y, +z, +xy, +xz, +yz, +xyz. With the path positions of the inside corners a < b and the outside ones c < d:
+ * one inside corner gives (a o1, a o2, a o3), three the same about the outside corner, two give (ac, ad, bd) and (ac, bd, bc);
+ * every triangle is wound so that its normal points from the negative to the positive side; zero-area triangles are kept.
+ * count: two launches ("mesh_classify", "mesh_scan") and the one host read: counts[0] = vertices, counts[1] = faces (host memory;
+ * the call synchronises the stream). emit: two launches ("mesh_emit_vertices", "mesh_emit_faces") that fill vertices [V, 3],
+ * colors [V, 3] (with vol_color; both or neither) and faces [F, 3] for the V and F the count returned, from the SAME workspace,
+ * untouched in between, and the same planes. workspace: c3dgs_mesh_extract_workspace_bytes(Nx, Ny, Nz) bytes (about five per
+ * point), 256-byte aligned, content on entry irrelevant. V == 0 launches nothing. More than 2^31 - 1 vertices or faces is refused.
+ * C3DGS_E_INVALID before any device work: l NULL; a dimension < 1; Nx Ny Nz > 2^31 - 1; voxel_size <= 0; a NULL tsdf or weight
+ * plane; color without vol_color or the reverse; sdf_trunc <= 0; depth_min >= depth_max; K < 1; W or H < 1; NULL depth or cameras;
+ * a NULL, small or misaligned workspace; NULL counts; V or F < 0; for V > 0 a NULL vertices, for F > 0 a NULL faces. */
+typedef struct c3dgs_lattice {
+    int32_t Nx, Ny, Nz;
+    float ox, oy, oz, voxel_size;
+} c3dgs_lattice;
+int c3dgs_tsdf_integrate(const c3dgs_lattice* l, int32_t K, int32_t W, int32_t H, const float* depth /*[K,H,W]*/,
+                         const float* color /*[K,3,H,W] | NULL*/, const float* cameras /*[K,16]*/, float sdf_trunc, float depth_min,
+                         float depth_max, float* tsdf, float* weight, float* vol_color /*[3,Nz,Ny,Nx] | NULL*/, void* stream);
+size_t c3dgs_mesh_extract_workspace_bytes(int32_t Nx, int32_t Ny, int32_t Nz);
+int c3dgs_mesh_extract_count(const c3dgs_lattice* l, const float* tsdf, const float* weight, void* workspace,
+                             size_t workspace_bytes, int64_t* counts /*host [2]*/, void* stream);
+int c3dgs_mesh_extract_emit(const c3dgs_lattice* l, const float* tsdf, const float* weight, const float* vol_color /*| NULL*/,
+                            void* workspace, size_t workspace_bytes, int64_t V, int64_t F, float* vertices /*[V,3]*/,
+                            float* colors /*[V,3] | NULL*/, int32_t* faces /*[F,3]*/, void* stream);
+
 /* ---- weighted_distance._C.weightedDistance (weighted_distance.cu:46-93) ----
  * coefs [N,K], codebook [C,K] row-major fp32 -> min squared distance [N] and argmin [N] (int64).
  * Exact reference semantics: fp32 k-ordered FMA chain, strict '<' (lowest index wins ties).
