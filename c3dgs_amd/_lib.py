@@ -197,6 +197,16 @@ PROTOTYPES = {
     "c3dgs_knn_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "c3dgs_knn_mean_dist2": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp]),
     "c3dgs_knn_neighbours": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "c3dgs_nn_index_bytes": (C.c_size_t, [C.c_int32]),
+    "c3dgs_nn_build": (C.c_int, [C.c_int32, _vp, _vp, _vp]),
+    "c3dgs_nn_query_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "c3dgs_nn_query": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "c3dgs_mesh_sample_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "c3dgs_mesh_sample_count": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_float, C.c_uint32, _vp, C.c_size_t,
+                                          C.POINTER(C.c_uint64), _vp]),
+    "c3dgs_mesh_sample_emit": (C.c_int, [C.c_int32, _vp, C.c_int32, _vp, C.c_uint32, _vp, C.c_size_t, C.c_int64, _vp, _vp, _vp]),
+    "c3dgs_geometry_reduce_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "c3dgs_geometry_reduce": (C.c_int, [C.c_int64, _vp, _vp, _f32p, C.c_float, C.c_int32, _f32p, _vp, C.c_size_t, _vp, _vp]),
     "c3dgs_ray_fill_plan_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "c3dgs_ray_fill_plan": (C.c_int, [C.c_int32, _vp, C.c_float, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "c3dgs_ray_fill_xyz": (C.c_int, [C.c_int32, _vp, _vp, _vp, C.c_float, C.c_int64, _vp, _vp, _vp, _vp, _vp]),

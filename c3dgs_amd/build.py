@@ -63,6 +63,11 @@ SOURCES = {
     "metrics.hip": [],
     "encode.hip": [],
     "knn.hip": ["-ffp-contract=off"],       # the distances and box bounds are bit-exact fp32 expressions (csrc/knn.hip)
+    # geometry evaluation: the same distances and bounds for external queries (csrc/knn_tree.hpp), the sampler's areas and
+    # positions, and the reduction's sqrt are single fp32 operations that tests/geometry_ref.py restates bit for bit
+    "nn_query.hip": ["-ffp-contract=off"],
+    "mesh_sample.hip": ["-ffp-contract=off"],
+    "geometry_metrics.hip": ["-ffp-contract=off"],
     "adam.hip": ["-ffp-contract=off"],
     "sparse_adam.hip": ["-ffp-contract=off"],   # adam.hip's arithmetic (csrc/adam_common.hpp), rounded as adam.hip rounds it
     "qat.hip": ["-ffp-contract=off"],
@@ -78,7 +83,7 @@ SOURCES = {
 HEADERS = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "gsmath.hpp"), os.path.join(CSRC, "gsgrad.hpp"),
            os.path.join(CSRC, "render_diag.hpp"),
            os.path.join(CSRC, "render_common.hpp"), os.path.join(CSRC, "replay.hpp"), os.path.join(CSRC, "scan_blocks.hpp"), os.path.join(CSRC, "adam_common.hpp"), os.path.join(CSRC, "mcmc.hpp"), os.path.join(CSRC, "jobs.hpp"),
-           os.path.join(CSRC, "bilagrid.hpp"),
+           os.path.join(CSRC, "bilagrid.hpp"), os.path.join(CSRC, "knn_tree.hpp"),
            os.path.join(HERE, "..", "include", "c3dgs_hip.h"), os.path.join(HERE, "..", "include", "c3dgs_hip_debug.h"),
            os.path.join(HERE, "..", "include", "c3dgs_hip_depth_sort_debug.h")]
 

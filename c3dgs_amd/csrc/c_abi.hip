@@ -48,7 +48,9 @@ void set_error(const std::string& msg) { g_last_error = msg; }
     X(BILAGRID_TV_BWD, "bilagrid_tv_backward")                                                                                 \
     X(FILTER3D_COMPUTE, "filter3d_compute") X(FILTER3D_APPLY, "filter3d_apply") X(FILTER3D_APPLY_BWD, "filter3d_apply_backward") \
     X(TSDF_INTEGRATE, "tsdf_integrate") X(MESH_CLASSIFY, "mesh_classify") X(MESH_SCAN, "mesh_scan")                            \
-    X(MESH_EMIT_VERTICES, "mesh_emit_vertices") X(MESH_EMIT_FACES, "mesh_emit_faces")
+    X(MESH_EMIT_VERTICES, "mesh_emit_vertices") X(MESH_EMIT_FACES, "mesh_emit_faces")                                          \
+    X(NN_QUERY_SORT, "nn_query_sort") X(NN_QUERY, "nn_query") X(MESH_SAMPLE_COUNT, "mesh_sample_count")                        \
+    X(MESH_SAMPLE_SCAN, "mesh_sample_scan") X(MESH_SAMPLE_EMIT, "mesh_sample_emit") X(GEOMETRY_REDUCE, "geometry_reduce")
 #define C3DGS_X(id, name) ST_##id,
 enum Stage { C3DGS_STAGE_TABLE(C3DGS_X) ST_COUNT };
 #undef C3DGS_X
@@ -1315,6 +1317,118 @@ int c3dgs_knn_neighbours(int32_t P, const float* xyz, int32_t* idx, float* d2, v
     C3DGS_STAGE_CHECK(ST_KNN_SORT, 0, s);
     C3DGS_TIMED_STAGE(ST_KNN_BOUNDS, 0, s, launch_knn_bounds(P, workspace, s));
     C3DGS_TIMED_STAGE(ST_KNN_QUERY, 0, s, launch_knn_query_neighbours(P, workspace, idx, d2, s));
+    return C3DGS_OK;
+}
+
+// ---- geometry evaluation (nn_query.hip, mesh_sample.hip, geometry_metrics.hip) ----
+static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+size_t c3dgs_nn_index_bytes(int32_t P) { return P < 0 ? 0 : knn_workspace_bytes(P); }
+
+int c3dgs_nn_build(int32_t P, const float* xyz, void* index, void* stream)
+{
+    if (P < 0) return fail(C3DGS_E_INVALID, "nn_build: P must be >= 0");
+    if (P == 0) return C3DGS_OK;
+    if (!xyz || !index) return fail(C3DGS_E_INVALID, "nn_build: xyz and index are required");
+    if (misaligned(index, 256)) return fail(C3DGS_E_INVALID, "nn_build: index must be 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    { StageTimer t_(ST_KNN_SORT, s);
+      if (run_knn_sort(P, xyz, index, s)) return fail(C3DGS_E_HIP, "nn_build: sort failed"); }
+    C3DGS_STAGE_CHECK(ST_KNN_SORT, 0, s);
+    C3DGS_TIMED_STAGE(ST_KNN_BOUNDS, 0, s, launch_knn_bounds(P, index, s));
+    return C3DGS_OK;
+}
+
+size_t c3dgs_nn_query_workspace_bytes(int32_t Q) { return Q < 0 ? 0 : nn_query_workspace_bytes(Q); }
+
+int c3dgs_nn_query(int32_t P, const void* index, int32_t Q, const float* queries, int32_t sort_queries, int32_t* idx, float* d2,
+                   uint32_t* leaves, void* workspace, void* stream)
+{
+    if (P < 0 || Q < 0) return fail(C3DGS_E_INVALID, "nn_query: P and Q must be >= 0");
+    if (Q == 0) return C3DGS_OK;
+    if (P > 0 && !index) return fail(C3DGS_E_INVALID, "nn_query: index is NULL");
+    const bool sorted = sort_queries != 0 && P > 0;          // without a reference set nothing is walked: nothing to order
+    if (!queries || !idx || !d2) return fail(C3DGS_E_INVALID, "nn_query: queries, idx and d2 are required");
+    if (sorted && !workspace) return fail(C3DGS_E_INVALID, "nn_query: sorted queries need the workspace");
+    if (misaligned(index, 256) || (sorted && misaligned(workspace, 256)))
+        return fail(C3DGS_E_INVALID, "nn_query: index and workspace must be 256-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (sorted) {
+        { StageTimer t_(ST_NN_QUERY_SORT, s);
+          if (run_nn_query_sort(P, index, Q, queries, workspace, s)) return fail(C3DGS_E_HIP, "nn_query: sort failed"); }
+        C3DGS_STAGE_CHECK(ST_NN_QUERY_SORT, 0, s);
+    }
+    C3DGS_TIMED_STAGE(ST_NN_QUERY, 0, s, launch_nn_query(P, index, Q, queries, sorted, workspace, idx, d2, leaves, s));
+    return C3DGS_OK;
+}
+
+size_t c3dgs_mesh_sample_workspace_bytes(int32_t F) { return F < 0 ? 0 : mesh_sample_workspace_bytes(F); }
+
+static int mesh_sample_validate(const char* who, int32_t V, const float* vertices, int32_t F, const int32_t* faces, const void* workspace,
+                                size_t workspace_bytes)
+{
+    const std::string w(who);
+    if (V < 0 || F < 0) return fail(C3DGS_E_INVALID, w + ": V and F must be >= 0");
+    if (F == 0) return C3DGS_OK;
+    if (!vertices || !faces) return fail(C3DGS_E_INVALID, w + ": vertices and faces are required");
+    if (!workspace || workspace_bytes < mesh_sample_workspace_bytes(F) || misaligned(workspace, 256))
+        return fail(C3DGS_E_INVALID, w + ": workspace must hold c3dgs_mesh_sample_workspace_bytes(F) bytes, 256-byte aligned");
+    return C3DGS_OK;
+}
+
+int c3dgs_mesh_sample_count(int32_t V, const float* vertices, int32_t F, const int32_t* faces, float density, uint32_t seed,
+                            void* workspace, size_t workspace_bytes, uint64_t* total, void* stream)
+{
+    if (int rc = mesh_sample_validate("mesh_sample_count", V, vertices, F, faces, workspace, workspace_bytes)) return rc;
+    if (!(density > 0.f) || !(density <= FLT_MAX)) return fail(C3DGS_E_INVALID, "mesh_sample_count: density must be finite and positive");
+    if (!total) return fail(C3DGS_E_INVALID, "mesh_sample_count: total is NULL");
+    *total = 0;
+    if (F == 0) return C3DGS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_HIP_TRY(mesh_sample_clear(F, workspace, s));
+    C3DGS_TIMED_STAGE(ST_MESH_SAMPLE_COUNT, 0, s, launch_mesh_sample_count(V, vertices, F, faces, density, seed, workspace, s));
+    const uint32_t* words = nullptr;
+    C3DGS_TIMED_STAGE(ST_MESH_SAMPLE_SCAN, 0, s, words = launch_mesh_sample_scan(F, workspace, s));
+    uint32_t host[3] = { 0u, 0u, 0u };
+    C3DGS_HIP_TRY(hipMemcpyAsync(host, words, sizeof(host), hipMemcpyDeviceToHost, s));
+    C3DGS_HIP_TRY(hipStreamSynchronize(s));
+    if (host[2] & 1u) return fail(C3DGS_E_INVALID, "mesh_sample_count: a face has a vertex index outside [0, V)");
+    if (host[2] & 2u)
+        return fail(C3DGS_E_INVALID, "mesh_sample_count: a face would get 2^24 or more samples (area * density); lower the density");
+    const uint64_t n = (uint64_t)host[0] | ((uint64_t)host[1] << 32);
+    if ((host[2] & 4u) || n > (uint64_t)INT32_MAX)
+        return fail(C3DGS_E_INVALID, "mesh_sample_count: more than 2^31 - 1 samples; lower the density");
+    *total = n;
+    return C3DGS_OK;
+}
+
+int c3dgs_mesh_sample_emit(int32_t V, const float* vertices, int32_t F, const int32_t* faces, uint32_t seed, const void* workspace,
+                           size_t workspace_bytes, int64_t S, float* points, int32_t* face, void* stream)
+{
+    if (int rc = mesh_sample_validate("mesh_sample_emit", V, vertices, F, faces, workspace, workspace_bytes)) return rc;
+    if (S < 0 || S > INT32_MAX) return fail(C3DGS_E_INVALID, "mesh_sample_emit: S must be in [0, 2^31 - 1]");
+    if (S == 0) return C3DGS_OK;
+    if (F == 0) return fail(C3DGS_E_INVALID, "mesh_sample_emit: a mesh without faces has no samples");
+    if (!points || !face) return fail(C3DGS_E_INVALID, "mesh_sample_emit: points and face are required");
+    hipStream_t s = (hipStream_t)stream;
+    C3DGS_TIMED_STAGE(ST_MESH_SAMPLE_EMIT, 0, s, launch_mesh_sample_emit(V, vertices, F, faces, seed, workspace, (uint32_t)S, points, face, s));
+    return C3DGS_OK;
+}
+
+size_t c3dgs_geometry_reduce_workspace_bytes(int64_t N) { return N < 0 ? 0 : geometry_reduce_workspace_bytes(N); }
+
+int c3dgs_geometry_reduce(int64_t N, const float* d2, const float* points, const float* bounds, float max_dist, int32_t T,
+                          const float* thresholds, void* workspace, size_t workspace_bytes, double* out, void* stream)
+{
+    if (N < 0) return fail(C3DGS_E_INVALID, "geometry_reduce: N must be >= 0");
+    if (T < 0 || T > C3DGS_GEOMETRY_MAX_THRESHOLDS) return fail(C3DGS_E_INVALID, "geometry_reduce: T must be in [0, 8]");
+    if (T > 0 && !thresholds) return fail(C3DGS_E_INVALID, "geometry_reduce: thresholds is NULL");
+    if (N > 0 && (points != nullptr) != (bounds != nullptr)) return fail(C3DGS_E_INVALID, "geometry_reduce: points and bounds come as a pair");
+    if (!out || (N > 0 && !d2)) return fail(C3DGS_E_INVALID, "geometry_reduce: d2 and out are required");
+    if (!workspace || workspace_bytes < geometry_reduce_workspace_bytes(N) || misaligned(workspace, 8) || misaligned(out, 8))
+        return fail(C3DGS_E_INVALID, "geometry_reduce: workspace must hold c3dgs_geometry_reduce_workspace_bytes(N) bytes, 8-byte aligned");
+    C3DGS_TIMED_STAGE(ST_GEOMETRY_REDUCE, 0, (hipStream_t)stream,
+                      launch_geometry_reduce(N, d2, points, bounds, max_dist, T, thresholds, workspace, out, (hipStream_t)stream));
     return C3DGS_OK;
 }
 

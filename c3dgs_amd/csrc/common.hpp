@@ -547,6 +547,23 @@ int run_knn_sort(int P, const float* xyz, void* workspace, hipStream_t s);
 void launch_knn_bounds(int P, void* workspace, hipStream_t s);
 void launch_knn_query(int P, const void* workspace, float* out, hipStream_t s);
 void launch_knn_query_neighbours(int P, const void* workspace, int32_t* idx, float* d2, hipStream_t s);
+// nn_query.hip (nearest neighbour of external queries in the tree run_knn_sort + launch_knn_bounds left in `index`)
+size_t nn_query_workspace_bytes(int Q);
+int run_nn_query_sort(int P, const void* index, int Q, const float* queries, void* workspace, hipStream_t s);
+void launch_nn_query(int P, const void* index, int Q, const float* queries, bool sorted, const void* workspace, int32_t* idx, float* d2,
+                     uint32_t* leaves, hipStream_t s);
+// mesh_sample.hip (surface sampling): clear, count, scan -> the device words {total low, total high, flags}; then emit
+size_t mesh_sample_workspace_bytes(int F);
+hipError_t mesh_sample_clear(int F, void* ws, hipStream_t s);
+void launch_mesh_sample_count(int V, const float* vertices, int F, const int32_t* faces, float density, uint32_t seed, void* ws,
+                              hipStream_t s);
+const uint32_t* launch_mesh_sample_scan(int F, void* ws, hipStream_t s);
+void launch_mesh_sample_emit(int V, const float* vertices, int F, const int32_t* faces, uint32_t seed, const void* ws, uint32_t S,
+                             float* points, int32_t* face, hipStream_t s);
+// geometry_metrics.hip (count, sum of distances and counts below thresholds of one direction)
+size_t geometry_reduce_workspace_bytes(int64_t N);
+void launch_geometry_reduce(int64_t N, const float* d2, const float* points, const float* bounds, float max_dist, int T,
+                            const float* thresholds, void* workspace, double* out, hipStream_t s);
 // ray_fill.hip (initial densification): top-2 -> counts -> scan -> emit -> per-slot level sort; then the positions.
 // A request the workspace cannot serve comes back in `problem` (hipSuccess, nothing written).
 size_t ray_fill_plan_workspace_bytes(int P, long long rows);

@@ -28,20 +28,12 @@
 // non-zero; at zero the search stops as before, and the three coincident points found are reported in ascending index
 // order). The bound's exactness argument is untouched. The cost is the extra visits of equal-bound nodes, which only
 // exact ties produce (lattices, duplicated points), and three more registers per lane.
-#include "common.hpp"
+#include "knn_tree.hpp"
 #include <cfloat>
 #include <climits>
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace c3dgs {
-
-constexpr int KNN_LEAF = 32;             // points per leaf box: half a wave, reduced with lane shuffles
-constexpr int KNN_WINDOW = 3;            // sorted neighbours each side that seed the best 3
-
-struct KnnLayout {
-    int nleaf, npow, levels;             // leaves, leaves padded to a power of two, tree levels (root level = levels - 1)
-    size_t box, codes, codes_sorted, ids, ids_sorted, pts, nodes, temp, temp_bytes, total;
-};
 
 static size_t knn_sort_temp_bytes(size_t p)
 {
@@ -51,7 +43,7 @@ static size_t knn_sort_temp_bytes(size_t p)
     return temp < 256 ? 256 : temp;
 }
 
-static KnnLayout knn_layout(int P)
+KnnLayout knn_layout(int P)
 {
     KnnLayout L{};
     const size_t p = (size_t)(P > 0 ? P : 1);
@@ -74,9 +66,6 @@ static KnnLayout knn_layout(int P)
 }
 
 size_t knn_workspace_bytes(int P) { return knn_layout(P).total; }
-
-// first node of tree level l (level 0 = the npow leaf slots, then npow/2, ...): 2*npow - 2*npow / 2^l
-__device__ __forceinline__ int knn_level_offset(int two_npow, int l) { return two_npow - (two_npow >> l); }
 
 __global__ void __launch_bounds__(256)
 knn_bbox(int P, const float* __restrict__ xyz, uint32_t* __restrict__ box /*[6] ordered ints: min xyz, max xyz*/)
@@ -104,20 +93,7 @@ knn_bbox(int P, const float* __restrict__ xyz, uint32_t* __restrict__ box /*[6] 
         }
 }
 
-__device__ __forceinline__ uint64_t knn_split_by_3(uint32_t a)   // 21 bits -> every third bit of 63
-{
-    uint64_t x = a & 0x1FFFFFull;
-    x = (x | x << 32) & 0x1F00000000FFFFull;
-    x = (x | x << 16) & 0x1F0000FF0000FFull;
-    x = (x | x << 8) & 0x100F00F00F00F00Full;
-    x = (x | x << 4) & 0x10C30C30C30C30C3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
-}
-
-// Morton code of each point over the bounding box. Only the ORDER matters (it decides which points share a leaf), not
-// the exact quantisation: a zero-extent axis (planar, collinear or single-point clouds) or an extent that overflows fp32
-// quantises to 0 instead of producing NaN.
+// Morton code of each point over the bounding box (the quantisation is knn_tree.hpp's knn_axis_cell).
 __global__ void __launch_bounds__(256)
 knn_codes(int P, const float* __restrict__ xyz, const uint32_t* __restrict__ box, uint64_t* __restrict__ codes,
           uint32_t* __restrict__ ids)
@@ -126,13 +102,8 @@ knn_codes(int P, const float* __restrict__ xyz, const uint32_t* __restrict__ box
     if (i >= P) return;
     uint64_t code = 0;
 #pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float mn = ord2f(box[a]), ext = ord2f(box[3 + a]) - mn;
-        const float inv = (ext > 0.f && ext <= FLT_MAX) ? 2097151.0f / ext : 0.f;
-        float t = (xyz[3 * (size_t)i + a] - mn) * inv;
-        t = (t >= 0.f) ? fminf(t, 2097151.0f) : 0.f;            // also maps a NaN to 0
-        code |= knn_split_by_3((uint32_t)t) << a;
-    }
+    for (int a = 0; a < 3; a++)
+        code |= knn_split_by_3(knn_axis_cell(xyz[3 * (size_t)i + a], ord2f(box[a]), ord2f(box[3 + a]))) << a;
     codes[i] = code;
     ids[i] = (uint32_t)i;
 }
@@ -176,19 +147,6 @@ knn_node_bounds(int n, const float4* __restrict__ child, float4* __restrict__ pa
     const float4 blo = child[4 * (size_t)k + 2], bhi = child[4 * (size_t)k + 3];
     parent[2 * (size_t)k] = make_float4(fminf(alo.x, blo.x), fminf(alo.y, blo.y), fminf(alo.z, blo.z), 0.f);
     parent[2 * (size_t)k + 1] = make_float4(fmaxf(ahi.x, bhi.x), fmaxf(ahi.y, bhi.y), fmaxf(ahi.z, bhi.z), 0.f);
-}
-
-__device__ __forceinline__ float knn_d2(const float4 p, const float4 q)
-{
-    const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-    return dx * dx + dy * dy + dz * dz;
-}
-
-// lower bound of knn_d2(p, q) over every p in [lo, hi], with the same rounding steps (see the head of the file)
-__device__ __forceinline__ float knn_box_d2(const float4 lo, const float4 hi, const float4 q)
-{
-    const float4 c = make_float4(fminf(fmaxf(q.x, lo.x), hi.x), fminf(fmaxf(q.y, lo.y), hi.y), fminf(fmaxf(q.z, lo.z), hi.z), 0.f);
-    return knn_d2(c, q);
 }
 
 struct KnnBest {

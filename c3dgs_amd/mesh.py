@@ -178,3 +178,37 @@ def extract_mesh(gaussians, cameras, pipe, bg, voxel_size, sdf_trunc=None, bound
     if timings is not None:
         timings.update(spent, dims=dims)
     return vertices, colors, faces
+
+
+def sample_surface(vertices, faces, density, seed=0):
+    """-> (points [S, 3] f32, face [S] int32): points on the mesh `vertices` [V, 3], `faces` [F, 3] (int32) at `density` points per
+    unit area, what a DTU-style evaluation compares with the scanned cloud (csrc/mesh_sample.hip). A face of area a gets floor(a
+    density) samples plus one more with probability frac(a density), decided by a hash of (face, seed); the samples are uniform in
+    the triangle, ordered by face. A pure function of its arguments, bit for bit. Zero-area faces and faces with a non-finite vertex
+    get none. Raises for a vertex index outside [0, V), for a face with 2^24 or more samples and for more than 2^31 - 1 samples.
+    Three launches and one host read (the total). GPU tensors only."""
+    density = float(density)
+    if not (math.isfinite(density) and density > 0):
+        raise ValueError(f"sample_surface: density must be finite and positive, not {density}")
+    _check(vertices, None, "vertices")
+    if vertices.dim() != 2 or vertices.size(1) != 3:
+        raise RuntimeError(f"c3dgs_amd: vertices must have shape (V, 3), not {tuple(vertices.shape)}")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.size(1) != 3:
+        raise RuntimeError("c3dgs_amd: faces must be a tensor of shape (F, 3)")
+    dev = vertices.device
+    v = vertices.detach().contiguous()
+    f = _lib.gpu_tensor(faces.detach(), "faces", torch.int32)
+    if f.device != dev:
+        raise RuntimeError(f"c3dgs_amd: faces must be on the vertices' device {dev}")
+    V, F, seed = int(v.size(0)), int(f.size(0)), int(seed) & 0xFFFFFFFF
+    lib, total = _lib.lib(), C.c_uint64(0)
+    with torch.cuda.device(dev):
+        ws = _lib.workspace("mesh_sample", dev, int(lib.c3dgs_mesh_sample_workspace_bytes(F)))
+        _lib.check(lib.c3dgs_mesh_sample_count(V, _ptr(v), F, _ptr(f), density, seed, ws.data_ptr(), ws.numel(), C.byref(total),
+                                               _stream(dev)))
+        S = int(total.value)
+        points = torch.empty((S, 3), dtype=torch.float32, device=dev)
+        face = torch.empty(S, dtype=torch.int32, device=dev)
+        _lib.check(lib.c3dgs_mesh_sample_emit(V, _ptr(v), F, _ptr(f), seed, ws.data_ptr(), ws.numel(), S, _ptr(points), _ptr(face),
+                                              _stream(dev)))
+    return points, face

@@ -4,6 +4,9 @@
     ssim(img1, img2, window_size=11, size_average=True)  utils/loss_utils.py:33-63, on [C,H,W] and [N,C,H,W]
     image_metrics(img, gt)                               [N, 3] float64 rows {mse, mean ssim_map, mean |img - gt|}
     render_and_eval(gaussians, cameras, pipe, bg, ...)   compress.py:121-163
+    geometry_metrics(points, reference, thresholds=...)  accuracy / completeness / Chamfer / precision / recall / F-score
+    mesh_metrics(vertices, faces, reference, density)    the same for a mesh, sampled at `density` points per unit area
+    reference_spacing(reference)                         the sampling distance of a reference cloud
 
 One forward-only kernel pass (csrc/metrics.hip) yields MSE, SSIM and L1 of every image of a batch, with a deterministic
 two-kernel reduction. Nothing here carries a gradient: the differentiable SSIM / L1 are c3dgs_amd.loss.ssim / l1_loss /
@@ -127,3 +130,91 @@ def render_and_eval(gaussians, cameras, pipeline_params, background, out_dir=Non
             means.append(torch.stack(lpipss).mean())
         vals = torch.stack(means).tolist()          # the one device-to-host read of the pass
     return {"SSIM": vals[0], "PSNR": vals[1], "LPIPS": vals[2] if lpipss else None}
+
+
+# ---- geometry: accuracy / completeness / Chamfer as DTU reports them, precision / recall / F-score as Tanks and Temples does
+MAX_THRESHOLDS = 8            # C3DGS_GEOMETRY_MAX_THRESHOLDS
+
+
+def _reduce_direction(d2, points, bounds, max_dist, thresholds, out):
+    """one row {count, sum of d, counts below the thresholds} of `out` (float64, on the device) from one direction's distances"""
+    import ctypes as C
+    L = _lib.lib()
+    N, T = int(d2.numel()), len(thresholds)
+    ws = torch.empty(int(L.c3dgs_geometry_reduce_workspace_bytes(N)), dtype=torch.uint8, device=d2.device)
+    tau = (C.c_float * max(T, 1))(*thresholds)
+    box = None if bounds is None else (C.c_float * 6)(*bounds)
+    with torch.cuda.device(d2.device):
+        _lib.check(L.c3dgs_geometry_reduce(N, _lib.ptr(d2), None if bounds is None else _lib.ptr(points), box, float(max_dist), T, tau,
+                                           ws.data_ptr(), ws.numel(), out.data_ptr(), _stream(d2.device)))
+
+
+def _flat_bounds(bounds):
+    if bounds is None:
+        return None
+    lo, hi = bounds
+    flat = [float(v) for v in lo] + [float(v) for v in hi]
+    if len(flat) != 6:
+        raise ValueError("geometry_metrics: bounds must be (lo [3], hi [3])")
+    return flat
+
+
+def geometry_metrics(points, reference, thresholds=(), max_dist=float("inf"), bounds=None, points_sort=None):
+    """Distances between two point sets, [N,3] and [M,3] finite GPU tensors, by exact nearest-neighbour search in both directions
+    (knn.NearestIndex), reduced on the device; ONE host read of the two result rows. With d = sqrt(squared distance) in fp32:
+
+        accuracy        mean d from `points` to their nearest point of `reference`
+        completeness    mean d from `reference` to their nearest point of `points`
+        chamfer         (accuracy + completeness) / 2, DTU's convention
+        n_accuracy, n_completeness   how many distances entered each mean
+        precision[tau], recall[tau]  the fraction of those with d < tau, per threshold (at most 8)
+        fscore[tau]     2 P R / (P + R), and 0 when P + R == 0
+
+    An element enters a mean iff it has a neighbour, d <= `max_dist` and, with `bounds` = (lo [3], hi [3]), its OWN coordinates lie
+    in the box (each set is filtered by its own points). A mean over zero elements is NaN, and so are precision and recall then
+    (fscore is 0). Sums are fp64 and bitwise reproducible. `points_sort`: NearestIndex.query's `sort` for the search FROM `points`
+    (it changes the time, never the result)."""
+    from . import knn
+    taus = [float(t) for t in thresholds]
+    if len(taus) > MAX_THRESHOLDS:
+        raise ValueError(f"geometry_metrics: at most {MAX_THRESHOLDS} thresholds")
+    box = _flat_bounds(bounds)
+    ref_index, pts_index = knn.NearestIndex(reference), knn.NearestIndex(points)
+    if ref_index.device != pts_index.device:
+        raise RuntimeError("geometry_metrics: points and reference must be on one device")
+    rows = torch.empty((2, 2 + MAX_THRESHOLDS), dtype=torch.float64, device=ref_index.device)
+    _reduce_direction(ref_index.query(pts_index.points, sort=points_sort)[1], pts_index.points, box, max_dist, taus, rows[0])
+    _reduce_direction(pts_index.query(ref_index.points)[1], ref_index.points, box, max_dist, taus, rows[1])
+    acc, comp = rows[:, :2 + len(taus)].tolist()                 # the one device-to-host read
+    nan = float("nan")
+    out = {"accuracy": acc[1] / acc[0] if acc[0] else nan, "completeness": comp[1] / comp[0] if comp[0] else nan,
+           "n_accuracy": int(acc[0]), "n_completeness": int(comp[0]), "precision": {}, "recall": {}, "fscore": {}}
+    out["chamfer"] = 0.5 * (out["accuracy"] + out["completeness"])
+    for t, tau in enumerate(taus):
+        p = acc[2 + t] / acc[0] if acc[0] else nan
+        r = comp[2 + t] / comp[0] if comp[0] else nan
+        out["precision"][tau], out["recall"][tau] = p, r
+        out["fscore"][tau] = 2.0 * p * r / (p + r) if p + r > 0 else 0.0
+    return out
+
+
+def mesh_metrics(vertices, faces, reference, density, seed=0, thresholds=(), max_dist=float("inf"), bounds=None):
+    """geometry_metrics of mesh.sample_surface(vertices, faces, density, seed) against `reference`, plus "samples": the number of
+    sampled points. Two host reads: the sample count and the result rows."""
+    from . import knn, mesh
+    points, _ = mesh.sample_surface(vertices, faces, density, seed)
+    out = geometry_metrics(points, reference, thresholds=thresholds, max_dist=max_dist, bounds=bounds,
+                           points_sort=knn.SORT_FACE_ORDERED_QUERIES)
+    out["samples"] = int(points.size(0))
+    return out
+
+
+def reference_spacing(reference):
+    """sqrt of the median squared distance of a reference point to its nearest OTHER point (knn.knn3's first column): the
+    sampling distance of the cloud. tools/eval_mesh.py samples the mesh at 1 / spacing^2 points per unit area by default, the
+    cloud's own density on a surface; nobody has tuned that default. One host read."""
+    from . import knn
+    d2 = knn.knn3(reference)[1][:, 0]
+    if d2.numel() < 2:
+        raise ValueError("reference_spacing: at least two points are needed")
+    return float(torch.sqrt(d2.median()))

@@ -653,6 +653,65 @@ int c3dgs_knn_mean_dist2(int32_t P, const float* xyz /*[P,3]*/, float* out /*[P]
 int c3dgs_knn_neighbours(int32_t P, const float* xyz /*[P,3]*/, int32_t* idx /*[P,3]*/, float* d2 /*[P,3]*/, void* workspace,
                          void* stream);
 
+/* ---- geometry evaluation: exact nearest neighbour of external queries, surface sampling, and the reduction behind accuracy /
+ * completeness / Chamfer / F-score (csrc/nn_query.hip, csrc/mesh_sample.hip, csrc/geometry_metrics.hip; no reference counterpart).
+ * Every fp32 expression below is one IEEE operation per operator, in the order written (no contraction), so results are bits.
+ * Added without an ABI version bump.
+ *
+ * NEAREST NEIGHBOUR. c3dgs_nn_build sorts the P reference points and builds the box tree of the 3-NN search ("knn_sort",
+ * "knn_bounds") into `index`, c3dgs_nn_index_bytes(P) bytes, 256-byte aligned, content on entry irrelevant. Queries only read
+ * the index: it serves any number of c3dgs_nn_query calls until the caller overwrites it. xyz must be finite.
+ * c3dgs_nn_query: with d(q, j) = dx*dx + dy*dy + dz*dz, left to right, dx = x[j] - q.x (c3dgs_knn_mean_dist2's expression),
+ * (d2[i], idx[i]) is the lexicographically smallest pair (d, j) over all j: among equal distances the lowest index wins, at
+ * d == 0 as well. d may be +inf where the subtraction overflows: then every d is +inf and idx = 0. P == 0, or a query with a
+ * non-finite coordinate: idx = -1, d2 = FLT_MAX. Q == 0 is a no-op that touches no pointer. Exact: the bits of a brute force.
+ * sort_queries != 0: the queries are walked in Morton order ("nn_query_sort": keys and a pair sort in `workspace`) and the results
+ * scattered back; 0: in the caller's order. The results are the same. workspace: c3dgs_nn_query_workspace_bytes(Q) bytes,
+ * 256-byte aligned, content on entry irrelevant; only the sorted form with P > 0 uses it, otherwise it may be NULL. leaves (optional, [Q]): the number of leaves scanned for each query.
+ * Stage names: "nn_query_sort", "nn_query". C3DGS_E_INVALID before any device work: a negative count; for P > 0 a NULL xyz or
+ * index; for Q > 0 a NULL queries, idx or d2, and where it is used a NULL workspace; a misaligned index or workspace.
+ *
+ * SURFACE SAMPLING at `density` points per unit area. mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b;
+ * x ^= x >> 16 (uint32); base(f) = mix(mix(f) ^ seed); u24(x) = float(x >> 8) * 2^-24. Face f with corners a, b, c:
+ *   u = b - a, v = c - a;  cx = u.y v.z - u.z v.y, cy = u.z v.x - u.x v.z, cz = u.x v.y - u.y v.x;
+ *   area = 0.5 sqrt_rn((cx cx + cy cy) + cz cz);  t = area * density;  n_f = int(floor(t)) + (u24(base(f)) < t - floor(t) ? 1 : 0);
+ *   a non-finite t gives n_f = 0;
+ *   sample k < n_f: u1 = u24(mix(base(f) + 2k + 1)), u2 = u24(mix(base(f) + 2k + 2)); if u1 + u2 > 1: u1 = 1 - u1, u2 = 1 - u2;
+ *   p = (a + u1 (b - a)) + u2 (c - a) per component.
+ * c3dgs_mesh_sample_count: a 16-byte clear, two launches ("mesh_sample_count", "mesh_sample_scan") and ONE host read of the total and a flag
+ * word; the call synchronises the stream. *total = the sum of n_f. C3DGS_E_INVALID with a message after the read: a vertex index
+ * outside [0, V) (never dereferenced), a face with a finite t >= 2^24, a total above 2^31 - 1.
+ * c3dgs_mesh_sample_emit ("mesh_sample_emit", one lane per sample): points [S,3] and face [S] for the S the count returned, from
+ * the SAME workspace, untouched in between, and the same mesh, density and seed; ordered by face, then by k. It never stores past
+ * S. workspace: c3dgs_mesh_sample_workspace_bytes(F) bytes, 256-byte aligned, content on entry irrelevant. F == 0: *total = 0,
+ * nothing is launched; S == 0 launches nothing. C3DGS_E_INVALID before any device work: V or F < 0 (workspace_bytes: 0); S < 0 or
+ * above 2^31 - 1; a density that is not finite and positive; for F > 0 a NULL vertices, faces or total, a NULL, small or misaligned
+ * workspace; for S > 0 NULL points or face, or F == 0.
+ *
+ * REDUCTION of one direction's distances. Per element: d = sqrt_rn(d2) in fp32; counted iff d2 != FLT_MAX, d <= max_dist and,
+ * with `points` [N,3] and `bounds` (host, {lo x y z, hi x y z}; both or neither), lo <= p <= hi on every axis; below threshold t
+ * iff counted and d < thresholds[t] (host [T], T <= C3DGS_GEOMETRY_MAX_THRESHOLDS). out (device, 2 + T doubles): the count, the
+ * fp64 sum of d, the T counts. Two launches ("geometry_reduce"), per-workgroup fp64 partials added in index order: bitwise
+ * reproducible, no floating-point atomics. N == 0 gives zeros. workspace: c3dgs_geometry_reduce_workspace_bytes(N) bytes, 8-byte
+ * aligned, content on entry irrelevant. C3DGS_E_INVALID before any device work: N < 0; T outside [0, 8]; thresholds NULL with
+ * T > 0; NULL out; for N > 0 NULL d2, or points without bounds or the reverse; a NULL, small or misaligned workspace. */
+#define C3DGS_GEOMETRY_MAX_THRESHOLDS 8
+size_t c3dgs_nn_index_bytes(int32_t P);
+int c3dgs_nn_build(int32_t P, const float* xyz /*[P,3]*/, void* index, void* stream);
+size_t c3dgs_nn_query_workspace_bytes(int32_t Q);
+int c3dgs_nn_query(int32_t P, const void* index, int32_t Q, const float* queries /*[Q,3]*/, int32_t sort_queries,
+                   int32_t* idx /*[Q]*/, float* d2 /*[Q]*/, uint32_t* leaves /*[Q] | NULL*/, void* workspace, void* stream);
+size_t c3dgs_mesh_sample_workspace_bytes(int32_t F);
+int c3dgs_mesh_sample_count(int32_t V, const float* vertices /*[V,3]*/, int32_t F, const int32_t* faces /*[F,3]*/, float density,
+                            uint32_t seed, void* workspace, size_t workspace_bytes, uint64_t* total /*host*/, void* stream);
+int c3dgs_mesh_sample_emit(int32_t V, const float* vertices /*[V,3]*/, int32_t F, const int32_t* faces /*[F,3]*/, uint32_t seed,
+                           const void* workspace, size_t workspace_bytes, int64_t S, float* points /*[S,3]*/,
+                           int32_t* face /*[S]*/, void* stream);
+size_t c3dgs_geometry_reduce_workspace_bytes(int64_t N);
+int c3dgs_geometry_reduce(int64_t N, const float* d2 /*[N]*/, const float* points /*[N,3] | NULL*/,
+                          const float* bounds /*host [6] | NULL*/, float max_dist, int32_t T, const float* thresholds /*host [T]*/,
+                          void* workspace, size_t workspace_bytes, double* out /*device [2 + T]*/, void* stream);
+
 /* ---- fused Adam step (the optimizer.step() that closes the QAT inner loop, finetune.py:65-66; optimizer set-up
  * scene/gaussian_model.py:296-308: torch.optim.Adam(param groups, lr=0.0, eps=1e-15), no weight decay, no amsgrad).
  * ONE launch updates up to C3DGS_ADAM_MAX_TENSORS tensors with torch's _single_tensor_adam arithmetic; the caller passes
